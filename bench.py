@@ -19,6 +19,9 @@ Objects on the line besides the contract's fields:
                   the token-exact fp32 engine on the same workload; the reference's default (sampled) decode; batch 256 (the north-star HBM target: cross-attention
                   >= 50 % of 8 TB/s); BASELINE configs[3] (ViT-Base 12L/768d + 6L decoder, B=256: encoder >= 40 % of the
                   bf16 MFMA peak).
+These objects (and the live PMC child passes behind `traffic`) are measured with --full only.  A plain run sets up, settles and warms
+up, times --steps steps and prints the contract's fields; --dump-outputs DIR also writes the tokens of the last timed step as
+DIR/tokens.npy (float32), so that two builds can be compared output for output on identical inputs.
 """
 from __future__ import annotations
 
@@ -45,9 +48,14 @@ def parse():
     ap.add_argument("--width", type=int, default=672)
     ap.add_argument("--max-len", type=int, default=256)
     ap.add_argument("--dtype", default=os.environ.get("TEXOCR_BENCH_DTYPE", "bf16"), choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure: live PMC passes, roofline, the side measurements and the "
+                         "CPU baseline (the --no-* options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write the tokens of the last one as DIR/tokens.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="also run the WHOLE un-sampled reference-algorithm generate on the CPU (minutes): validates the sampled estimate")
+                    help="with --full: also run the WHOLE un-sampled reference-algorithm generate on the CPU (minutes): validates the sampled estimate")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the fp32 / batch-256 / config-4 side measurements")
     ap.add_argument("--no-live-pmc", action="store_true",
@@ -56,7 +64,26 @@ def parse():
     ap.add_argument("--model", default="default", choices=["default", "cfg4"],
                     help="cfg4 = BASELINE configs[3] (ViT-Base 12L/768d encoder + 6L/768d decoder) as the main workload: for profiling "
                          "runs; the headline metric is quoted on the default model")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:                                        # a plain run measures the headline figure only
+        a.no_cpu_baseline = a.no_roofline = a.no_extras = a.no_live_pmc = True
+    return a
+
+
+def dump_outputs(dirname, arrays, limit=64 << 20):
+    """Writes each array as dirname/<name>.npy in float32.  Beyond `limit` bytes in all, every array keeps a fixed, seeded sample
+    of its rows (the same rows from run to run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > limit:
+            keep = max(1, int(v.shape[0] * limit // total))
+            v = v[np.sort(np.random.Generator(np.random.PCG64(0)).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), v)
 
 
 LIVE_PMC = {}          # kind -> HBM bytes per launch measured in THIS run (live_pmc), read where the roofline objects are built
@@ -583,6 +610,8 @@ def main():
     assert out.shape == (a.batch * world, a.max_len)
 
     result = None
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"tokens": out.cpu().numpy()})      # token ids < 2^24: exact in float32
     if rank == 0:
         lat.sort()
         N = dims.n_tokens(a.height, a.width)

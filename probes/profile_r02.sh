@@ -4,8 +4,8 @@
 # and the PMC traffic passes for batch 64 and 256.  Outputs under gpurun_out/; the summaries are copied to profiles/ by hand.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-python3 bench.py > $O/r02_bench_default.json 2> $O/r02_bench_default.err
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 2 \
+python3 bench.py --full > $O/r02_bench_default.json 2> $O/r02_bench_default.err
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 10 --warmup 2 \
     --no-extras --no-cpu-baseline > $O/r02_bench_torchrun1.json 2> $O/r02_bench_torchrun1.err
 FL="--steps 4 --warmup 1 --settle-seconds 0 --no-extras --no-cpu-baseline --no-roofline"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r02_b64 -- python3 bench.py $FL > $O/prof_r02_b64.log 2>&1

@@ -7,8 +7,8 @@
 #  * PMC traffic (one counter per pass): the persistent launch at batch 64; lat_core and the K/V cross-attention launch at batch 256, one row range
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-python3 bench.py > $O/r06_bench_default.json 2> $O/r06_bench_default.err
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 2 \
+python3 bench.py --full > $O/r06_bench_default.json 2> $O/r06_bench_default.err
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 10 --warmup 2 \
     --no-extras --no-cpu-baseline > $O/r06_bench_torchrun1.json 2> $O/r06_bench_torchrun1.err
 FL="--steps 4 --warmup 1 --settle-seconds 0 --no-extras --no-cpu-baseline --no-roofline"
 prof() { tag=$1; shift; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r06_$tag -- python3 bench.py $FL "$@" > $O/prof_r06_$tag.log 2>&1;
