@@ -83,6 +83,32 @@ def test_cfg1_greedy_tokens_and_logits():
     np.testing.assert_allclose(v.numpy(), g["top5_vals"], atol=5e-5)
 
 
+def test_cfg1_float64_oracle_matches_reference():
+    """The float64 run of the oracle (tests/ref64.py) -- the reference of the shape-matrix GPU tests -- against the fixture captured
+    from the reference: tokens equal wherever the fixture's top-1/top-2 margin is >= 1e-4, logits within 1e-4 (the fixture is fp32:
+    what is left is its own rounding)."""
+    import ref64
+    meta, g = load_golden("cfg1_b4_224x224")
+    d, sd, img = model_of(meta)
+    s64 = ref64.sd64(synth.synth_state_dict(d, meta["weight_seed"]))
+    enc = ref64.encode(s64, img)
+    assert enc.dtype == torch.float64
+    np.testing.assert_allclose(enc[0].numpy(), g["enc0"], atol=1e-4)
+    toks, logits = ref64.generate(s64, enc, d.bos, d.eos, 256)
+    assert logits.dtype == torch.float64 and toks.shape == (4, 256)
+    sure = g["margin"] >= 1e-4
+    assert sure.mean() > 0.99
+    assert np.array_equal(toks.numpy()[sure], g["tokens"][sure])
+    np.testing.assert_allclose(logits[:2, :16].numpy(), g["logits_first16"], atol=1e-4)
+    np.testing.assert_allclose(logits[:2, -4:].numpy(), g["logits_last4"], atol=1e-4)
+    v = torch.gather(logits, 2, torch.from_numpy(g["top5_ids"].astype(np.int64)))
+    np.testing.assert_allclose(v.numpy(), g["top5_vals"], atol=1e-4)
+    # the fp32 oracle on the same prefix is within its own rounding of the float64 one (and the fixture tests above stay fp32)
+    tf = cpu_ref.decoder_net(sd, torch.cat([torch.full((4, 1), d.bos, dtype=torch.long), toks[:, :15]], 1), cpu_ref.encode(sd, img))
+    assert tf.dtype == torch.float32
+    assert float((tf.double() - logits[:, :16]).abs().max()) < 1e-4
+
+
 def test_cfg2_shape_encoder_and_decode():
     meta, g = load_golden("cfg2_b2_224x672")
     d, sd, img = model_of(meta)
