@@ -18,6 +18,17 @@
 #include <type_traits>
 #include <vector>
 
+namespace txo {
+static thread_local std::string g_err;
+static int fail(int code, const std::string& msg) { g_err = msg; return code; }
+}  // namespace txo
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t _e = (expr);                                                                         \
+        if (_e != hipSuccess)                                                                           \
+            return txo::fail(TXO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));             \
+    } while (0)
+
 #include "common.h"
 #include "conv.h"
 #include "dec_attn.h"
@@ -31,26 +42,12 @@
 #include "prefill.h"
 #include "rows.h"
 #include "step.h"
+#include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
+#include "lanes.h"
+#include "stamps.h"
 
 namespace txo {
 
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-// inside a bool lambda: records the failure (look_failed) and returns false
-#define HIP_TRY_B(expr)                                                                                 \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) { (void)fail(TXO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); look_failed = true; return false; } \
-    } while (0)
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return fail(TXO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                  \
-    } while (0)
-
-static const bool g_dbg = getenv("TXO_DEBUG_SYNC") != nullptr;
 static void dbg(hipStream_t s, const char* what, int l = -1) {
     if (!g_dbg) return;
     hipError_t e = hipStreamSynchronize(s);
@@ -106,6 +103,7 @@ struct EventPool {
 
 template <typename T>
 struct Engine : EngineBase {
+    Knobs knobs;                      // every TXO_* setting, read at creation (knobs.h)
     // ----- device weights -----
     std::vector<void*> allocs;
     struct AttnW { T* wqkv = nullptr; T* wq = nullptr; T* wo = nullptr; float* bo = nullptr;
@@ -128,7 +126,7 @@ struct Engine : EngineBase {
     // (tests/test_oracle_golden.py), so no choice of WHICH tensors are stored as bf16 gives a usable mode; fp32 here costs ~3 ms per 64
     // images and puts the bf16 engine's encoder output within 1-2 % of the fp32 reference.  TXO_BACKBONE_BF16=1: the bf16 backbone
     // (r02-r05; kernels checked against a CPU emulation of bf16 storage) for checkpoints known to tolerate it.
-    bool bk_fp32 = sizeof(T) == 2 && getenv("TXO_BACKBONE_BF16") == nullptr;
+    bool bk_fp32 = sizeof(T) == 2 && !knobs.backbone_bf16;
     float *enc_g = nullptr, *enc_b = nullptr, *encn_g = nullptr, *encn_b = nullptr, *enc_gb = nullptr;   // enc_gb: gamma then beta (GEMM epilogues)
     std::vector<AttnW> enc_attn; std::vector<MlpW> enc_mlp;
     float *tok_emb = nullptr, *pos_emb = nullptr, *dec_g = nullptr, *dec_b = nullptr, *decn_g = nullptr, *decn_b = nullptr, *dec_gb = nullptr;
@@ -143,76 +141,31 @@ struct Engine : EngineBase {
     T *dqt = nullptr, *dqp = nullptr, *dcl = nullptr;   // latent cross attention: q [B][inner], q' and c [B][heads*D] in the storage type
     int64_t* cur_tok = nullptr; int *eos_seen = nullptr, *done_flag = nullptr; StepState* st = nullptr;
     unsigned char* kmask = nullptr; bool kmask_on = false;   // padding mask over the decoded positions of a decode_step session (txo_decode_set_key_mask)
-    // ----- decode session -----
-    // A decode runs as 1..MAXL independent "lanes" (contiguous row ranges of the batch), each on its own HIP
-    // stream with its own step state, so the latency chains of one lane's small kernels overlap the other's.
-    // Every lane's step is a fixed launch sequence (the position lives on the device) -> captured once as a
-    // hipGraph and replayed per step.
-    static constexpr int MAXL = 4;
-    struct Lane {
-        int b0 = 0, nb = 0;
-        hipStream_t stream = nullptr;      // lane 0 runs on the caller's stream
-        hipStream_t own = nullptr;         // engine-owned stream for lanes > 0
-        // captured steps, by what they were built for: {b0, nb, N, eos, sB, sImg, form flags} (the cache strides sB / sImg and the row count are
-        // baked into a graph's launches).  Per-row stop replays a step per row count of the shrinking range (multiples of 16): a handful of
-        // entries per range, built once and kept across generates.  exec = the entry the current decode replays.
-        std::map<std::array<int, 7>, std::pair<hipGraph_t, hipGraphExec_t>> graphs;
-        hipGraphExec_t exec = nullptr;
-    };
-    Lane lanes[MAXL];
-    int n_lanes = 1, max_lanes = 2;
-    // Run-time knobs of generate() (development / test switches).  Read ONCE per engine, at creation; txo_engine_query(TXO_Q_RELOAD_KNOBS)
-    // reads them again (the Python binding does that when it sees the TXO_* environment change between two calls: tests flip
-    // TXO_PERSIST / TXO_LANES on a live engine).  Everything else in this struct's neighbourhood is read once, in the member initialisers.
-    struct RunKnobs {
-        int persist = -1, graph = -1, lanes = 0;        // -1 / 0 = unset
-        bool stamps = false, pstamps = false;
-        std::string stamps_file, pstamps_file;
-        int stagger_ticks = 0, inject_fail = 0;
-        bool has_stagger = false, has_inject = false;
-        void read() {
-            *this = RunKnobs{};
-            if (const char* e = getenv("TXO_PERSIST")) persist = atoi(e) != 0;
-            if (const char* e = getenv("TXO_GRAPH")) graph = atoi(e) != 0;
-            if (const char* e = getenv("TXO_LANES")) lanes = std::max(1, atoi(e));
-            if (const char* e = getenv("TXO_STAMPS")) { stamps = true; stamps_file = e; }
-            if (const char* e = getenv("TXO_PSTAMPS")) { pstamps = true; pstamps_file = e; }
-            if (const char* e = getenv("TXO_PS_STAGGER_US")) { has_stagger = true; stagger_ticks = (int)(atof(e) * 100.0); }
-            if (const char* e = getenv("TXO_PERSIST_INJECT_FAIL")) { has_inject = true; inject_fail = atoi(e); }
-        }
-    } knobs;
-    bool self_plain = getenv("TXO_SELF_FUSED") == nullptr;
-    // experiment knobs are read ONCE per engine (never on a launch path)
-    bool dec_wide_off = getenv("TXO_DEC_WIDE_OFF") != nullptr;
-    // narrow decoder, folded latent out-projection (K = heads * D): 32 x 32 blocks from wide_min_rows rows of a range on, 32 x 16 blocks from
-    // wide_mid_rows on, 16 x 16 blocks below
+    // ----- decode session: 1..MAXL row ranges (lanes.h); a range's step is a fixed launch sequence, captured once and replayed -----
+    static constexpr int MAXL = LaneSet::MAXL;
+    LaneSet lanes;
+    // narrow decoder, folded latent out-projection (K = heads * D): 32 x 16 blocks from wide_mid_rows rows of a range on, 16 x 16 blocks below.
+    // The 32 x 32 form (from wide_min_rows on: never, decode rows are < 65536) is KEPT: without its instantiation every later kernel of the code
+    // object moves, and the bf16 persistent launch (143 KB, over twice the instruction cache) measured 1.5 % slower in alternating runs.
     static constexpr int wide_min_rows = 100000;   // (257 until the tiled operands: at a beam search's 320 rows per range 32 x 16 is now ahead, 98.5 vs 100.5 ms)
     static constexpr int wide_mid_rows = 129;
-    // encoder GEMM outputs with non-temporal stores (gemm_big.h: store8; the epilogues keep the parameter).  probes/pp_store_policy.hip
-    // measured +22 % for a plain 256x256 store epilogue at K = 768 (1.85 GB of output per launch), but the encoder's own epilogues
-    // (GeGLU halves the columns, the fp32 stream is read-modify-write) run the same with either policy: 45.84 vs 45.77 ms per ViT-Base
-    // encode (probes/enc_nt.py) -- so the default stays the plain store.
-    int enc_nt(size_t) const { return 0; }
     // cross attention in latent form (lat_attn.h): scores / values against the raw encoder rows instead of projected K/V panels.
-    // latent_ok: the tile exists for this engine's width / storage type.  lat_mode (TXO_LATENT, read once): 1 = every decode runs with
+    // latent_ok: the tile exists for this engine's width / storage type.  knobs.lat_mode (TXO_LATENT): 1 = every decode runs with
     // launches in latent form, 0 = never, unset = where it measured faster (auto_latent).  use_latent: what the current session does.
     bool latent_ok = false, use_latent = false;
     int n_cus = 256;                  // compute units of this engine's device (init): one latent tile per CU is the grouping target
     // lat_self: this session's SELF attention also runs in latent form (the history is z, not k / v: a quarter of the bytes at config.yml
     // dims).  Only inside generate() / generate_beam() with launches in latent form: a session opened through txo_decode_begin may be
-    // prefilled or masked, which work on the K/V history.  OPT-IN (TXO_LATENT_SELF=1, read once per engine): measured on MI355X it
+    // prefilled or masked, which work on the K/V history.  OPT-IN (TXO_LATENT_SELF=1): measured on MI355X it
     // ties the K/V history at batch 256 (76.5 vs 76.7 ms per generate: the core is 9.8 us against 14.8 for the K/V kernel, averaged over
     // the 256 positions, but the folded output projection's K = heads*D costs 9.1 us against 4.8) and loses in beam search (121 vs 115 ms
     // at 5 x 128); what it saves is history capacity (a quarter).  profiles/r05_latent_self.txt.
     bool lat_self = false;
-    int lat_self_env = getenv("TXO_LATENT_SELF") ? atoi(getenv("TXO_LATENT_SELF")) : 0;
     bool lat_self_ok() const {
         // (the beam slot table of the tile covers 16 keys x its wave count x LA_PATH_TILES positions: the bf16 tile at width 256 runs on 4 waves)
         const int waves = (D <= 256 && !(lat_nw4 && D == 256)) ? 8 : 4;
-        return lat_self_env != 0 && zc != nullptr && !dec_self.empty() && dec_self[0].wqp != nullptr && Tmax <= 16 * waves * LA_PATH_TILES;
+        return knobs.lat_self_env != 0 && zc != nullptr && !dec_self.empty() && dec_self[0].wqp != nullptr && Tmax <= 16 * waves * LA_PATH_TILES;
     }
-    int lat_mode = getenv("TXO_LATENT") ? atoi(getenv("TXO_LATENT")) : -1;
-    int lat_g_env = getenv("TXO_LAT_G") ? atoi(getenv("TXO_LAT_G")) : 0;
     // bf16, width 256: the latent tile on FOUR waves (r05).  Same one tile per CU, half the waves to
     // merge and twice the keys per wave: the whole-batch launch at 256 rows 19.3 -> 17.9 us (rocprofv3), generate +2-3 % at 130-192 rows,
     // beam search 5 x 128 +5 %.  (Two such tiles per CU, 512 tiles of 4 heads at 256 rows, were slower: 22.2 us -- every row's encoder
@@ -220,40 +173,11 @@ struct Engine : EngineBase {
     // 8-wave tile's, within the same bound against the reference.
     static constexpr bool lat_nw4 = sizeof(T) == 2;
     bool ckv_valid = false;           // the projected cross K/V panels of this session exist (the prefill needs them; the latent form does not)
-    bool use_pp = getenv("TXO_GEMM_OLD") == nullptr;   // bf16: 256x256 LDS-DMA GEMM for the encoder-side projections
-    static constexpr int enc_walk = 1;   // encoder kernels walk the rows alternately up and down (encode())
-    int pp_tr = getenv("TXO_PP_TR") ? (atoi(getenv("TXO_PP_TR")) != 0) : -1;   // its epilogue form: 1 direct, 0 staged through LDS, unset = by epilogue (gemm_pp.h)
-    int pp_ct = getenv("TXO_PP_CT") ? atoi(getenv("TXO_PP_CT")) : 0;     // experiment: column tiles per band of the multi-band GEMMs (0 = by size, gemm_pp.h)
-    int pp_sb_mb = getenv("TXO_PP_SB_MB") ? atoi(getenv("TXO_PP_SB_MB")) : PP_SB_MB;   // ... its row super-blocks: MB of A per super-block, 0 = none (gemm_pp.h)
-    // Two row ranges need two streams whose launches really run side by side.  Which HIP streams do depends on how the runtime mapped them onto
-    // hardware queues -- on every stream the process created before (profiles/r06_b256_stream_pairs.txt: 66 / 72 / 80 / 110 ms per generate
-    // at batch 256 for the same engine, by the number of streams created earlier) -- so the pair is CHOSEN by measurement, once per engine,
-    // the first time two ranges are wanted: tune_lane_streams().  TXO_TUNE_LANES=0: off (range 0 on the caller's stream, as r02-r05).
-    int tune_lanes = getenv("TXO_TUNE_LANES") ? atoi(getenv("TXO_TUNE_LANES")) : 1;
-    bool lanes_tuned = false;
-    double tune_best_ms = 0, tune_worst_ms = 0;
-    int* flags_host = nullptr;        // pinned: done flags of the chunk being looked at (generate)
-    hipEvent_t ev_flags[MAXL] = {};
-    // per-row stop (step.h): batch row held by every slot of a row range, scratch of the compaction, {live rows, moves} per range;
-    // live_host (pinned): the ranges' finished-row counts on their way to the host, ev_live behind them
+    // per-row stop (step.h): batch row held by every slot of a row range, scratch of the compaction, {live rows, moves} per range
     int *row_map = nullptr, *row_map2 = nullptr, *cmoves = nullptr, *cinfo = nullptr; int64_t* cur_tok2 = nullptr;
-    int* live_host = nullptr; hipEvent_t ev_live[MAXL] = {};
-    bool stop_graph_on = getenv("TXO_STOP_GRAPH") ? atoi(getenv("TXO_STOP_GRAPH")) != 0 : true;
-    int stop_every = getenv("TXO_STOP_EVERY") ? std::max(1, atoi(getenv("TXO_STOP_EVERY"))) : 16;   // positions between two looks at the live-row counts
-    int stop_gain = getenv("TXO_STOP_GAIN") ? std::max(1, atoi(getenv("TXO_STOP_GAIN"))) : 16;      // rows a compaction must free (one 16-row tile)
     int last_compactions = 0;         // compactions of the last generate (TXO_Q_LAST_COMPACTIONS)
-    bool look_failed = false;
     int step_host_t = -1;             // position of the step being enqueued when the host knows it (see enqueue_step)
-    // TXO_STAMPS=<file>: diagnostic -- every decode launch of ONE step records per-block entry / mid / exit times
-    unsigned long long* stamp_buf = nullptr; int stamp_slot = -1; static constexpr int STAMP_BLOCKS = 2048, STAMP_KERNELS = 64;
-    std::vector<std::string> stamp_names;
-    unsigned long long* next_stamp(const char* name) {
-        if (stamp_slot < 0 || stamp_slot >= STAMP_KERNELS) return nullptr;
-        stamp_names.push_back(name);
-        return stamp_buf + (size_t)(stamp_slot++) * STAMP_BLOCKS * 3;
-    }
-    hipStream_t cap_stream = nullptr;      // graphs are captured here, never on the caller's stream
-    hipEvent_t ev_fork = nullptr, ev_join[MAXL] = {nullptr, nullptr, nullptr, nullptr};
+    Stamps stamps;                    // TXO_STAMPS / TXO_PSTAMPS diagnostics (stamps.h)
     int64_t* tok_buf = nullptr;            // [Bmax][Tmax] generated ids (engine-owned so graphs do not bake user pointers)
     int sB = 0, sN = 0, sImg = 0; bool session = false;   // decode rows, encoder tokens, images behind the cross K/V cache
     // persistent decode launch (persist.h): control block (device + pinned host copy), per-stage stamps of one position
@@ -277,17 +201,6 @@ struct Engine : EngineBase {
     int D, Ie, Id, Fe, Fd, V, Tmax, Nmax, Bmax;
 
     ~Engine() override {
-        for (auto& ln : lanes) {
-            for (auto& g : ln.graphs) { if (g.second.second) (void)hipGraphExecDestroy(g.second.second); if (g.second.first) (void)hipGraphDestroy(g.second.first); }
-            if (ln.own) (void)hipStreamDestroy(ln.own);
-        }
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        for (auto e : ev_join) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_flags) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_live) if (e) (void)hipEventDestroy(e);
-        if (flags_host) (void)hipHostFree(flags_host);
-        if (live_host) (void)hipHostFree(live_host);
         if (pctl_host) (void)hipHostFree(pctl_host);
         for (void* p : allocs) (void)hipFree(p);
     }
@@ -424,7 +337,7 @@ struct Engine : EngineBase {
             if (int r = upload_T(&w->wqkv, cat)) return r;
             // decoder self attention in latent form (r05): the same two folds, against the history of normalised block inputs
             // (opt-in, TXO_LATENT_SELF=1: without it neither the fold nor the z history exists)
-            if (G == 8 && latent_fold() && lat_self_env != 0) { if (int r = fold_latent(q, k, v, wo, inner, w, G)) return r; }
+            if (G == 8 && latent_fold() && knobs.lat_self_env != 0) { if (int r = fold_latent(q, k, v, wo, inner, w, G)) return r; }
         }
         if (int r = upload_T(&w->wo, interleave(wo->data, D, inner, G))) return r;
         if (G != 16) {                                        // decoder: the prefill runs these projections on the encoder-side GEMMs
@@ -599,7 +512,7 @@ struct Engine : EngineBase {
         if (!(t = get("decoder.net.to_logits.bias", {V}))) return TXO_E_STATE;
         if (int r = upload_f32(&blog, t->data)) return r;
         host.clear();
-        if (w_tiled_on) {    // tiled copies of every weight the decode-step projections read (dec_gemm.h: w_tiled)
+        if (knobs.w_tiled_on) {    // tiled copies of every weight the decode-step projections read (dec_gemm.h: w_tiled)
             HIP_TRY(hipDeviceSynchronize());
             const int H = c.dec_heads;
             for (int l = 0; l < c.dec_layers; ++l) {
@@ -617,7 +530,6 @@ struct Engine : EngineBase {
     }
 
     int init() {
-        knobs.read();
         arena = Arena{}; arena.measuring = true;
         if (int r = init_buffers()) return r;                 // pass 1: sizes only
         if (int r = arena_begin(arena.off)) return r;
@@ -626,17 +538,8 @@ struct Engine : EngineBase {
         // the self-attention cache starts as zeros: clamped loads may touch rows no step has written yet (fused self-attention
         // at t = 0 multiplies such a row by p = 0, which must not meet NaN/Inf bit patterns of recycled memory)
         HIP_TRY(hipMemset(skv, 0, sizeof(T) * (size_t)cfg.dec_layers * 2 * Bmax * Id * Tmax));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&flags_host), sizeof(int) * MAXL * Tmax, hipHostMallocDefault));
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pctl_host), sizeof(PersistCtl), hipHostMallocDefault));
-        max_lanes = MAXL;
-        for (int i = 1; i < max_lanes; ++i) HIP_TRY(hipStreamCreateWithFlags(&lanes[i].own, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        for (int i = 0; i < MAXL; ++i) HIP_TRY(hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming));
-        for (int i = 0; i < MAXL; ++i) HIP_TRY(hipEventCreateWithFlags(&ev_flags[i], hipEventDisableTiming));
-        for (int i = 0; i < MAXL; ++i) HIP_TRY(hipEventCreateWithFlags(&ev_live[i], hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&live_host), sizeof(int) * MAXL, hipHostMallocDefault));
-        return 0;
+        return lanes.init(Tmax);
     }
     int init_buffers() {
         const txo_config& c = cfg;
@@ -697,7 +600,7 @@ struct Engine : EngineBase {
         if (int r = dalloc(&dhid, (size_t)Bmax * Fmax)) return r;
         if (int r = dalloc(&dz, (size_t)Bmax * D)) return r;
         if (int r = dalloc(&dqt, (size_t)Bmax * Imax)) return r;
-        if (lat_self_env != 0) { if (int r = dalloc(&zc, (size_t)c.dec_layers * Bmax * Tmax * D)) return r; }   // z history of the opt-in latent self attention
+        if (knobs.lat_self_env != 0) { if (int r = dalloc(&zc, (size_t)c.dec_layers * Bmax * Tmax * D)) return r; }   // z history of the opt-in latent self attention
         if (int r = dalloc(&dqp, (size_t)Bmax * c.dec_heads * D)) return r;
         // (+ tile alignment of the row ranges' regions: range li starts at ceil16(b0) + 16 li and spans ceil16(nb) rows -- beam ranges are not
         // multiples of 16 -- so the last of MAXL ranges can end at Bmax + 30 + 16 (MAXL - 1))
@@ -740,7 +643,7 @@ struct Engine : EngineBase {
     template <class Epi>
     void gemm_plain(hipStream_t s, const T* A, const T* W, int M, int N, int K, Epi epi, int rev = 0) {
         if constexpr (sizeof(T) == 2) {
-            if (use_pp && gemm_pp_fits(M, N, K)) { launch_gemm_pp(s, A, W, M, N, K, epi, pp_tr, rev, pp_sb_mb, pp_ct); return; }
+            if (knobs.use_pp && gemm_pp_fits(M, N, K)) { launch_gemm_pp(s, A, W, M, N, K, epi, knobs.pp_tr, rev, knobs.pp_sb_mb, knobs.pp_ct); return; }
         }
         launch_gemm_big<T>(s, LoadPlain<T>{A, K}, W, M, N, K, epi);
     }
@@ -768,7 +671,6 @@ struct Engine : EngineBase {
     // a backbone GEMM in storage type TB.  fp32 backbone INSIDE the bf16 engine: fp32 operands split onto the bf16 matrix pipe
     // (gemm_split.h: ~2^-16 per product, 5x less matrix time than exact-f32 MFMA); everything else -- the fp32 parity engine first of all --
     // the exact kernel.  TXO_BACKBONE_EXACT=1 keeps the exact-f32 kernel in the bf16 engine too (A/B, tests).
-    bool bk_exact = getenv("TXO_BACKBONE_EXACT") != nullptr;
     // gn_hw > 0: the output is the input of a GroupNorm over images of gn_hw pixels -- the split kernel then leaves the norm's partial sums
     // behind (gemm_split.h: GnPart) and group_norm() skips its own pass over the tensor (gn_fused)
     bool gn_fused = false;
@@ -777,7 +679,7 @@ struct Engine : EngineBase {
     void bk_gemm(hipStream_t s, ALoad ld, const TB* w, int M, int N, int K, Epi epi, int gn_hw = 0) {
         gn_fused = false;
         if constexpr (sizeof(TB) == 4 && sizeof(T) == 2) {
-            if (!bk_exact && gemm_split_fits(K)) {
+            if (!knobs.bk_exact && gemm_split_fits(K)) {
                 GnPart gp{nullptr, 1, 1};
                 if (gn_hw > 0 && gn_tiles && gn_fusable(gn_hw, N)) { gp = GnPart{gn_tiles, gn_hw, N / 32}; gn_fused = true; }
                 launch_gemm_split(s, ld, w, M, N, K, epi, gp);
@@ -850,7 +752,7 @@ struct Engine : EngineBase {
         // Image chunks (enc_chunk_images): every row of the stack belongs to ONE image, so the stack may run over a few images at a time
         // through the SAME workspace rows -- a chunk whose intermediates (stream, z, q/k/v, attention output, FFN hidden) fit the 256 MB
         // Infinity Cache keeps every producer -> consumer hand-over on the die instead of through HBM.  Same bits as the whole batch.
-        const int bc = enc_chunk_images(B, N);
+        const int bc = enc_chunk_images(B);
         for (int b0 = 0; b0 < B; b0 += bc) {
             const int nb = std::min(bc, B - b0);
             if (int r = encode_images(img + (size_t)b0 * C * H * W, nb, C, H, W, enc_out + (size_t)b0 * N * D, s)) return r;
@@ -859,14 +761,8 @@ struct Engine : EngineBase {
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    // images per encoder chunk: TXO_ENC_CHUNK=n forces n (0 = whole batch); default by measured working set (profiles/r06_encoder_chunk_sweep.txt)
-    int enc_chunk_env = getenv("TXO_ENC_CHUNK") ? atoi(getenv("TXO_ENC_CHUNK")) : -1;
-    int enc_chunk_images(int B, int N) const {
-        if (enc_chunk_env == 0) return B;
-        if (enc_chunk_env > 0) return std::min(B, enc_chunk_env);
-        (void)N;
-        return B;
-    }
+    // images per encoder chunk: TXO_ENC_CHUNK=n forces n (0 = whole batch); default the whole batch (profiles/r06_encoder_chunk_sweep.txt)
+    int enc_chunk_images(int B) const { return knobs.enc_chunk_env > 0 ? std::min(B, knobs.enc_chunk_env) : B; }
     int encode_images(const float* img, int B, int C, int H, int W, float* enc_out, hipStream_t s) {
         const int h = H / 16, w = W / 16, hw = h * w, N = hw + 1;
         const int M = B * N, G = cfg.canvas_w / 16;
@@ -887,39 +783,39 @@ struct Engine : EngineBase {
             }
         }
         const size_t hs = (size_t)M * Ie;      // one of q/k/v, head-major [B*heads][N][64]
-        // Walk direction (perf mode, enc_walk): successive kernels of the stack walk the rows alternately upwards and downwards, so that each
+        // Walk direction (perf mode): successive kernels of the stack walk the rows alternately upwards and downwards, so that each
         // starts on the rows its producer wrote LAST -- still in the 256 MB Infinity Cache -- instead of on the ones it wrote first
         // (every intermediate here is 0.2-0.9 GB at batch 256: with all kernels walking upwards a consumer's first reads are the
         // producer's oldest lines).  Results do not depend on it (every kernel's rows are independent).
         bool down = false;                                    // direction of the NEXT kernel
-        auto dir = [&]() -> int { if (!enc_walk || sizeof(T) != 2) return 0; const bool d = down; down = !down; return d ? 1 : 0; };
+        auto dir = [&]() -> int { if (sizeof(T) != 2) return 0; const bool d = down; down = !down; return d ? 1 : 0; };
         for (int l = 0; l < cfg.enc_layers; ++l) {
             // The stream between two sub-layers is x = LN(y) (the residual) and z = LN(x) (the block input), attention.py:242-259.
             // x is never written: the row kernel leaves {mean, rstd} of LN(y) per row (rows.h MODE 3) and the next GEMM epilogue
             // rebuilds its residual from y -- in place, ey is both its residual source and its output -- with the same expression.
             const ResidLN res_x{ey, estats, enc_gb, D}, res_first{ex, nullptr, nullptr, D};
-            // outputs far beyond the caches are written non-temporally (they would evict the GEMM's own operand panels from L2)
-            const int nt_y = enc_nt((size_t)M * D * 4), nt_qkv = enc_nt((size_t)3 * M * Ie * sizeof(T)), nt_h = enc_nt((size_t)M * Fe * sizeof(T));
+            // (the epilogues store plainly: non-temporal stores, +22 % for a bare 256x256 store epilogue at K = 768 in probes/pp_store_policy.hip,
+            // run these epilogues the same -- 45.84 vs 45.77 ms per ViT-Base encode, probes/enc_nt.py)
             if (l == 0) launch_ln<0, T>(s, ex, nullptr, ez, enc_g, enc_b, M, dir());
             else launch_ln<3, T>(s, ey, estats, ez, enc_g, enc_b, M, dir());
             const dim3 agrid = ea_grid((N + EA_QBLK - 1) / EA_QBLK, B * cfg.enc_heads);   // XCD-aware block order (enc_attn.h: ea_block)
             const int nbh = B * cfg.enc_heads;
             if constexpr (sizeof(T) == 4) {
                 gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D,
-                                   EpiHeads<float>{eqkv, hs, Ie, cfg.enc_heads, N, nt_qkv});
+                                   EpiHeads<float>{eqkv, hs, Ie, cfg.enc_heads, N});
                 hipLaunchKernelGGL((enc_attn_kernel<T>), agrid, dim3(256), 0, s, eqkv, eqkv + hs, eqkv + 2 * hs, eao, N,
                                    cfg.enc_heads, nbh);
             } else {                                              // perf mode: bf16 q/k/v, bf16 MFMA attention
                 bf16* qb = reinterpret_cast<bf16*>(eqkv);
                 gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D,
-                                   EpiHeads<bf16>{qb, hs, Ie, cfg.enc_heads, N, nt_qkv}, dir());
+                                   EpiHeads<bf16>{qb, hs, Ie, cfg.enc_heads, N}, dir());
                 hipLaunchKernelGGL((enc_attn_bf16_v2_kernel<T>), agrid, dim3(256), 0, s, qb, qb + hs, qb + 2 * hs, eao, N, cfg.enc_heads, nbh, dir());
             }
             gemm_plain(s, eao, enc_attn[l].wo, M, 2 * D, Ie,
-                               EpiGluRes<sizeof(T) == 2>{ey, l == 0 ? res_first : res_x, enc_attn[l].bo, nt_y}, dir());
+                               EpiGluRes<sizeof(T) == 2>{ey, l == 0 ? res_first : res_x, enc_attn[l].bo}, dir());
             launch_ln<3, T>(s, ey, estats, ez, enc_g, enc_b, M, dir());
-            gemm_plain(s, ez, enc_mlp[l].w1, M, 2 * Fe, D, EpiGeglu<T>{ehid, enc_mlp[l].b1, Fe, nt_h}, dir());
-            gemm_plain(s, ehid, enc_mlp[l].w2, M, D, Fe, EpiBiasRes{ey, res_x, enc_mlp[l].b2, nt_y}, dir());
+            gemm_plain(s, ez, enc_mlp[l].w1, M, 2 * Fe, D, EpiGeglu<T>{ehid, enc_mlp[l].b1, Fe}, dir());
+            gemm_plain(s, ehid, enc_mlp[l].w2, M, D, Fe, EpiBiasRes{ey, res_x, enc_mlp[l].b2}, dir());
         }
         launch_ln<2, float>(s, ey, nullptr, enc_out, encn_g, encn_b, M, dir());
         return 0;
@@ -944,10 +840,10 @@ struct Engine : EngineBase {
         // A session opened through txo_decode_begin (project_kv) may be prefilled, and the multi-position forward works on the projected
         // K/V panels: such a session steps in the K/V form too (one-pass and stepwise logits of decoder.net() then come from the same
         // weights), unless TXO_LATENT=1 pins the latent form.  generate() / generate_beam() choose their form themselves.
-        use_latent = latent_ok && (lat_mode == 1 || (lat_mode < 0 && !project_kv && auto_latent(B)));
+        use_latent = latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && !project_kv && auto_latent(B)));
         lat_self = false;
         if (!use_latent && project_kv) ensure_ckv(s);
-        set_lanes(1, s);
+        lanes.split(sB, 1, s);
         reset_lanes(s, eos);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -962,95 +858,10 @@ struct Engine : EngineBase {
         ckv_valid = true;
     }
 
-    // Error exit of a decode loop that forked onto the lanes' own streams: kernels of the failed call may still be running there on this
-    // engine's buffers.  The caller's stream is made to wait for every lane, drained, and the engine goes back to one lane; the error
-    // code passes through.
-    int abandon_lanes(hipStream_t s, int rc) {
-        for (int i = 0; i < n_lanes; ++i) {
-            if (lanes[i].stream == s) continue;
-            if (hipEventRecord(ev_join[i], lanes[i].stream) == hipSuccess) (void)hipStreamWaitEvent(s, ev_join[i], 0);
-            else (void)hipStreamSynchronize(lanes[i].stream);
-        }
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-        set_lanes(1, s);
-        stamp_slot = -1;
-        return rc;
-    }
-    // Pick the two streams of a two-range decode: NCAND candidate streams, every pair timed on two chains of 64 launches that hold one wave per
-    // CU for 4 us each behind a gate.  Pairs that share a hardware queue take twice as long (0.68 against 0.34 ms: nothing in between) -- a decode
-    // on such a pair runs its ranges one after the other (110 ms per generate at batch 256 instead of 66) -- and the first pair that runs side
-    // by side becomes lanes[0].own / lanes[1].own.  ~15 ms, once per engine.  (What it does NOT remove: among pairs that do run side by side a
-    // generate still takes 66-78 ms by PROCESS, whatever the pair -- profiles/r06_b256_stream_pairs.txt; a trial of real decode positions
-    // per pair was built and predicts nothing.)
-    int tune_lane_streams() {
-        lanes_tuned = true;
-        constexpr int NCAND = 5, CHAIN = 64;
-        const bool verbose = getenv("TXO_TUNE_LANES_VERBOSE") != nullptr;
-        hipStream_t cand[NCAND] = {};
-        for (auto& c : cand) HIP_TRY(hipStreamCreateWithFlags(&c, hipStreamNonBlocking));
-        hipEvent_t e0 = nullptr, ea = nullptr, eb = nullptr;
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&ea)); HIP_TRY(hipEventCreate(&eb));
-        auto run_pair = [&](hipStream_t a, hipStream_t b) -> double {
-            double best = 1e30;
-            for (int rep = 0; rep < 2; ++rep) {
-                (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b);
-                hipLaunchKernelGGL(hold_kernel, dim3(1), dim3(64), 0, a, 100000);          // the gate: the host enqueues both chains behind it
-                (void)hipEventRecord(e0, a);
-                (void)hipStreamWaitEvent(b, e0, 0);
-                for (int i = 0; i < CHAIN; ++i) {
-                    hipLaunchKernelGGL(hold_kernel, dim3(n_cus), dim3(64), 0, a, 400);
-                    hipLaunchKernelGGL(hold_kernel, dim3(n_cus), dim3(64), 0, b, 400);
-                }
-                (void)hipEventRecord(ea, a); (void)hipEventRecord(eb, b);
-                (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b);
-                float ta = 0, tb = 0;
-                (void)hipEventElapsedTime(&ta, e0, ea); (void)hipEventElapsedTime(&tb, e0, eb);
-                best = std::min(best, (double)std::max(ta, tb));
-            }
-            return best;
-        };
-        (void)run_pair(cand[0], cand[1]);                                  // (code object load, clocks)
-        double tp[NCAND][NCAND] = {};
-        double bt = 1e30, wt = 0;
-        for (int i = 0; i < NCAND; ++i)
-            for (int j = i + 1; j < NCAND; ++j) { tp[i][j] = run_pair(cand[i], cand[j]); bt = std::min(bt, tp[i][j]); wt = std::max(wt, tp[i][j]); }
-        int bi = 0, bj = 1; double best = 1e30;
-        for (int i = 0; i < NCAND; ++i)
-            for (int j = i + 1; j < NCAND; ++j) {
-                if (tp[i][j] > 1.3 * bt) continue;                         // (one after the other)
-                if (verbose) fprintf(stderr, "[txo] streams (%d, %d): side-by-side test %.2f ms\n", i, j, tp[i][j]);
-                if (best > 1e29) { best = tp[i][j]; bi = i; bj = j; }      // the first pair that runs side by side
-            }
-        tune_best_ms = best; tune_worst_ms = wt;
-        if (lanes[0].own) (void)hipStreamDestroy(lanes[0].own);
-        if (lanes[1].own) (void)hipStreamDestroy(lanes[1].own);
-        lanes[0].own = cand[bi]; lanes[1].own = cand[bj];
-        for (int i = 0; i < NCAND; ++i) if (i != bi && i != bj) (void)hipStreamDestroy(cand[i]);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(ea); (void)hipEventDestroy(eb);
-        if (verbose) fprintf(stderr, "[txo] row-range streams: pair (%d, %d) of %d candidates (serialised pairs take %.2f ms)\n", bi, bj, NCAND, wt);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    // split the batch into n contiguous row ranges (multiples of 16 rows where possible)
-    void set_lanes(int n, hipStream_t s) {
-        const int tiles = (sB + 15) / 16;
-        if (n > tiles) n = tiles;
-        if (n < 1) n = 1;
-        n_lanes = n;
-        int row = 0;
-        for (int i = 0; i < n; ++i) {
-            const int tl = tiles / n + (i < tiles % n ? 1 : 0);
-            lanes[i].b0 = row;
-            lanes[i].nb = std::min(sB - row, tl * 16);
-            row += lanes[i].nb;
-            lanes[i].stream = i == 0 ? s : lanes[i].own;
-        }
-        if (n >= 2 && lanes[0].own) lanes[0].stream = lanes[0].own;
-    }
+    int abandon_lanes(hipStream_t s, int rc) { stamps.slot = -1; return lanes.abandon(s, sB, rc); }
     void reset_lanes(hipStream_t s, int eos) {
-        for (int i = 0; i < n_lanes; ++i) {
-            const Lane& ln = lanes[i];
+        for (int i = 0; i < lanes.n; ++i) {
+            const LaneSet::Lane& ln = lanes[i];
             const int n = ln.nb > Tmax ? ln.nb : Tmax;
             hipLaunchKernelGGL(reset_state_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st + i, cur_tok + ln.b0,
                                eos_seen + ln.b0, done_flag + (size_t)i * Tmax, ln.nb, Tmax, cfg.bos, eos);
@@ -1060,12 +871,11 @@ struct Engine : EngineBase {
 
     // tiled copies of the decode projections' weights for the launch path (dec_gemm.h: w_tiled), keyed by the row-major buffer
     std::map<const void*, T*> wtiled;
-    int w_tiled_on = getenv("TXO_W_TILED") ? atoi(getenv("TXO_W_TILED")) : 1;     // TXO_W_TILED=0: every projection reads the row-major buffers (A/B)
     // one allocation for all of them (the arenas' reason: few large mappings); `want` collects (buffer, N, K), make_tiled_all() builds
     struct TileReq { const T* w; int N, K; };
     std::vector<TileReq> tile_reqs;
     void want_tiled(const T* w, int N, int K) {
-        if (!w_tiled_on || !w || K % Elem<T>::KCHUNK) return;
+        if (!knobs.w_tiled_on || !w || K % Elem<T>::KCHUNK) return;
         for (auto& r : tile_reqs) if (r.w == w) return;
         tile_reqs.push_back({w, N, K});
     }
@@ -1091,7 +901,7 @@ struct Engine : EngineBase {
     }
     void use_tiled(DecGemmArgs<T>& a) const {
         a.w_tiled = 0;
-        if (!w_tiled_on) return;
+        if (!knobs.w_tiled_on) return;
         auto it = wtiled.find(a.W);
         if (it != wtiled.end()) { a.W = it->second; a.w_tiled = 1; }
     }
@@ -1108,7 +918,7 @@ struct Engine : EngineBase {
         const int bn = half ? 16 : DG_BN;
         const dim3 grid((a.N + bn - 1) / bn, (a.rows + DG_BM - 1) / DG_BM), blk(256);
         const size_t lds = dec_gemm_lds_bytes<T>(a.K, has_pro);
-        a.stamps = (grid.x * grid.y <= (unsigned)STAMP_BLOCKS) ? next_stamp(PRO == PRO_NONE ? (EPI == EPI_GLU_RES ? "gemm out-proj+GLU+res" : "gemm ffn-out+res") : (EPI == EPI_QKV ? "gemm LN+qkv" : (EPI == EPI_GEGLU ? "gemm LN+ffn-in+GeGLU" : (EPI == EPI_STORE_T ? "gemm LN+q' (latent)" : "gemm LN+logits")))) : nullptr;
+        a.stamps = (grid.x * grid.y <= (unsigned)Stamps::BLOCKS) ? stamps.next(PRO == PRO_NONE ? (EPI == EPI_GLU_RES ? "gemm out-proj+GLU+res" : "gemm ffn-out+res") : (EPI == EPI_QKV ? "gemm LN+qkv" : (EPI == EPI_GEGLU ? "gemm LN+ffn-in+GeGLU" : (EPI == EPI_STORE_T ? "gemm LN+q' (latent)" : "gemm LN+logits")))) : nullptr;
         // K known at compile time for the shapes of the reference configurations (straight-line code, exact register
         // arrays); any other K takes the run-time form (KW = 0)
         constexpr int KCH = Elem<T>::KCHUNK;
@@ -1144,7 +954,7 @@ struct Engine : EngineBase {
     bool launch_dec_gemm_wide(hipStream_t s, DecGemmArgs<T> a) {
         if constexpr (sizeof(T) != 2) { (void)s; (void)a; return false; }
         else {
-            if (a.rows < 128 || dec_wide_off) return false;
+            if (a.rows < 128 || knobs.dec_wide_off) return false;
             use_tiled(a);
             constexpr int KCH = Elem<T>::KCHUNK;
             const int kw = (a.K % (4 * KCH) == 0) ? a.K / (4 * KCH) : 0;
@@ -1179,7 +989,7 @@ struct Engine : EngineBase {
         int kv_div = 1; const short* path = nullptr;      // beam search: shared cross K/V, scattered self history
     };
     void launch_dec_attn(hipStream_t s, int li, const AttnOpt& o) {
-        const Lane& ln = lanes[li];
+        const auto& ln = lanes[li];
         const size_t r0 = ln.b0;
         DecAttnArgs<T> a{};
         a.y = dy + r0 * D; a.tok = cur_tok + r0; a.tok_emb = tok_emb; a.pos_emb = pos_emb; a.x_out = o.x_out;
@@ -1189,7 +999,7 @@ struct Engine : EngineBase {
         a.out = dao + r0 * Id; a.heads = cfg.dec_heads; a.lmax = o.lmax; a.len = o.len; a.t_ptr = &st[li].t; a.t_host = step_host_t;
         a.qin = dq + r0 * Id; a.kv_div = o.kv_div; a.path = o.path ? o.path + r0 * Tmax : nullptr; a.path_stride = Tmax;   // slots are range-local
         a.kmask = kmask + r0 * Tmax; a.kmask_stride = Tmax;
-        a.stamps = (ln.nb * cfg.dec_heads <= STAMP_BLOCKS) ? next_stamp(o.cross ? "attn cross" : "attn self") : nullptr;
+        a.stamps = (ln.nb * cfg.dec_heads <= Stamps::BLOCKS) ? stamps.next(o.cross ? "attn cross" : "attn self") : nullptr;
         const dim3 grid(ln.nb * cfg.dec_heads), blk(256);
         constexpr int NLS = sizeof(T) == 2 ? 8 : 16;       // self: 256 cached keys per pass
         constexpr int WBS = sizeof(T) == 2 ? 3 : 1;        // self: q,k,v weight rows requested together (bf16) or one by one
@@ -1236,7 +1046,7 @@ struct Engine : EngineBase {
     // re-reads of an image's encoder rows; more tiles = more CUs pulling).  A head's bits do not depend on it.
     int latent_group(int rows, int slots) const {
         const int H = cfg.dec_heads;
-        if (lat_g_env > 0) return std::min(std::min(H, LA_GMAX), lat_g_env);
+        if (knobs.lat_g_env > 0) return std::min(std::min(H, LA_GMAX), knobs.lat_g_env);
         for (int g = 2; g < std::min(H, LA_GMAX); g *= 2)
             if (rows * ((H + g - 1) / g) <= slots) return g;
         const int n = (H + LA_GMAX - 1) / LA_GMAX;            // as few tiles per row as the tile allows, evenly filled (12 heads: one tile of 12; 24: 12 + 12)
@@ -1254,12 +1064,11 @@ struct Engine : EngineBase {
     // enc_rows = Tmax, len = position + 1 (host value or *t_ptr), kv_div = 1, path = the beams' slot tables (or null).
     // The latent core's output c feeds the folded output projection as its A operand: written in that GEMM's tiled layout (dec_gemm.h: a_tiled)
     // when the core serves the CROSS attention with folded weights.  A lane's region starts on a 16-row tile boundary and lanes do not overlap.
-    int a_tiled_on = getenv("TXO_A_TILED") ? atoi(getenv("TXO_A_TILED")) : 1;
-    size_t c_base_row(int li) const { return ((lanes[li].b0 + 15) / 16) * 16 + (size_t)16 * li; }
-    bool c_tiled(int l, bool cross) const { return a_tiled_on && w_tiled_on && cross && dec_cross[l].wqp != nullptr && (D * (int)sizeof(T)) % 64 == 0; }
+    size_t c_base_row(int li) const { return ((lanes.lane[li].b0 + 15) / 16) * 16 + (size_t)16 * li; }
+    bool c_tiled(int l, bool cross) const { return knobs.a_tiled_on && knobs.w_tiled_on && cross && dec_cross[l].wqp != nullptr && (D * (int)sizeof(T)) % 64 == 0; }
     void launch_lat_core(hipStream_t s, int li, int kv_div, const T* enc, int len, int enc_rows, const int* t_ptr, const short* path,
                          const char* stamp_name, bool cross, int layer = 0) {
-        const Lane& ln = lanes[li];
+        const auto& ln = lanes[li];
         const size_t r0 = ln.b0;
         const int H = cfg.dec_heads, HD = H * D;
         LatCoreArgs<T> a{};
@@ -1268,14 +1077,14 @@ struct Engine : EngineBase {
         a.rows = ln.nb; a.heads = H; a.G = latent_group(sB, n_cus); a.ngrp = (H + a.G - 1) / a.G; a.len = len; a.kv_div = kv_div;
         a.enc_rows = enc_rows; a.t_ptr = t_ptr; a.path = path; a.path_stride = Tmax;
         int nimg = (ln.nb + kv_div - 1) / kv_div;
-        if (cross && kv_div > 1 && ln.nb % kv_div == 0 && lat_g_env == 0) {
+        if (cross && kv_div > 1 && ln.nb % kv_div == 0 && knobs.lat_g_env == 0) {
             // beam search: the k beams of an image read the SAME encoder rows, and their q' / c rows are contiguous ([rows][heads * D]) --
             // one image = ONE row of k * heads heads, LA_GMAX of them per tile (the MFMA tile has 16 head columns whether 8 or 16 are
             // used): 640 tiles of 8 heads become 384 of up to 16.  A head's bits do not depend on the grouping.
             a.rows = nimg; a.heads = H * kv_div; a.G = LA_GMAX; a.ngrp = (a.heads + LA_GMAX - 1) / LA_GMAX; a.kv_div = 1;
         }
         const int nblk = ((nimg + 7) / 8) * 8 * a.kv_div * a.ngrp;   // XCD-aware tile order (lat_core_kernel)
-        a.stamps = (nblk <= STAMP_BLOCKS) ? next_stamp(stamp_name) : nullptr;
+        a.stamps = (nblk <= Stamps::BLOCKS) ? stamps.next(stamp_name) : nullptr;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         const bool timed = cross && (prof || (prof_cross && (cross_seq++ & 3) == 0 && pool.used + 2 <= pool.ev.size()));
         if (timed) { e0 = pool.next(); e1 = pool.next(); }
@@ -1302,7 +1111,7 @@ struct Engine : EngineBase {
     // self attention of layer l in latent form (folded weights): [embedding / LN sandwich + q' = z M^T, z appended to the history] ->
     // [scores / values against the history of z]; the gated output projection (Wo' folded) follows in enqueue_step
     int launch_lat_self(hipStream_t s, int li, int l, const BeamCtx* bm, const DecGemmArgs<T>& base) {
-        const Lane& ln = lanes[li];
+        const auto& ln = lanes[li];
         const size_t r0 = ln.b0;
         const int HD = cfg.dec_heads * D;
         T* zl = zc + ((size_t)l * sB + r0) * Tmax * D;           // this lane's rows of layer l's history
@@ -1315,7 +1124,7 @@ struct Engine : EngineBase {
         return 0;
     }
     int launch_lat_cross(hipStream_t s, int li, int l, int kv_div, const DecGemmArgs<T>& base) {
-        const Lane& ln = lanes[li];
+        const auto& ln = lanes[li];
         const size_t r0 = ln.b0;
         const int H = cfg.dec_heads, HD = H * D;
         const bool fold = dec_cross[l].wqp != nullptr;
@@ -1348,7 +1157,7 @@ struct Engine : EngineBase {
     int enqueue_step(hipStream_t s, int li, int64_t* tokens_out, int out_stride, float* logits_out, int eos,
                      const BeamCtx* bm = nullptr, int host_t = -1) {
         step_host_t = host_t;
-        const Lane& ln = lanes[li];
+        const auto& ln = lanes[li];
         const int B = sB, N = sN, nb = ln.nb;
         const size_t r0 = ln.b0;
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1371,7 +1180,7 @@ struct Engine : EngineBase {
             } else {   // causal self attention
                 AttnOpt o; o.W = dec_self[l].wqkv; o.K = kc; o.V = vc; o.lmax = Tmax; o.x_out = lx;
                 if (bm) o.path = bm->path_cur;
-                if (self_plain || bm || kmask_on) {
+                if (knobs.self_plain || bm || kmask_on) {
                     // default: LN sandwich + QKV GEMM (weights read once per 16 rows; k/v appended to the cache by
                     // its epilogue), then the plain cached attention.  TXO_SELF_FUSED=1 folds the projection into
                     // the attention launch instead (same wall time at B=64; re-reads 96 KB of weights per image).
@@ -1452,52 +1261,12 @@ struct Engine : EngineBase {
         return 0;
     }
 
-    void dump_stamps(const char* file, hipStream_t s) {
-        const int nk = stamp_slot;
-        stamp_slot = -1;
-        std::vector<unsigned long long> h((size_t)nk * STAMP_BLOCKS * 3);
-        if (hipStreamSynchronize(s) != hipSuccess) return;
-        if (hipMemcpy(h.data(), stamp_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
-        FILE* f = fopen(file, "w");
-        if (!f) return;
-        unsigned long long t0 = ~0ull;
-        for (auto v : h) if (v && v < t0) t0 = v;
-        for (int k2 = 0; k2 < nk; ++k2) {
-            unsigned long long first = ~0ull, last_in = 0, mid_lo = ~0ull, mid_hi = 0, first_out = ~0ull, last = 0; int nb = 0;
-            for (int b = 0; b < STAMP_BLOCKS; ++b) {
-                const unsigned long long* d = &h[((size_t)k2 * STAMP_BLOCKS + b) * 3];
-                if (!d[0]) continue;
-                ++nb; first = std::min(first, d[0]); last_in = std::max(last_in, d[0]); mid_lo = std::min(mid_lo, d[1]); mid_hi = std::max(mid_hi, d[1]);
-                first_out = std::min(first_out, d[2]); last = std::max(last, d[2]);
-            }
-            fprintf(f, "%-24s blocks %4d | first entry %7.2f us, last entry %7.2f | operands/panel done %7.2f .. %7.2f | first exit %7.2f, last exit %7.2f\n",
-                    stamp_names[k2].c_str(), nb, (first - t0) / 100.0, (last_in - t0) / 100.0, (mid_lo - t0) / 100.0, (mid_hi - t0) / 100.0,
-                    (first_out - t0) / 100.0, (last - t0) / 100.0);
-        }
-        // TXO_STAMPS_RAW=<substring>: also one line per block of the launches whose name contains it (which CU / tile is the slow one)
-        if (const char* raw = getenv("TXO_STAMPS_RAW")) {
-            for (int k2 = 0; k2 < nk; ++k2) {
-                if (stamp_names[k2].find(raw) == std::string::npos) continue;
-                for (int b = 0; b < STAMP_BLOCKS; ++b) {
-                    const unsigned long long* d = &h[((size_t)k2 * STAMP_BLOCKS + b) * 3];
-                    if (d[0]) fprintf(f, "raw %d %-24s block %4d  %7.2f %7.2f %7.2f\n", k2, stamp_names[k2].c_str(), b, (d[0] - t0) / 100.0, (d[1] - t0) / 100.0, (d[2] - t0) / 100.0);
-                }
-            }
-        }
-        fclose(f);
-    }
-
     // capture lane li's step (tokens into the engine-owned tok_buf) as a graph, or reuse the cached one
     int lane_graph(int li, int eos) {
-        Lane& ln = lanes[li];
-        const std::array<int, 7> key = {ln.b0, ln.nb, sN, eos, sB, sImg, (int)use_latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode};
-        auto it = ln.graphs.find(key);
-        if (it != ln.graphs.end()) { ln.exec = it->second.second; return 0; }
-        if (ln.graphs.size() >= 64) {                              // (shapes keep changing: start over rather than grow without bound)
-            for (auto& g : ln.graphs) { (void)hipGraphExecDestroy(g.second.second); (void)hipGraphDestroy(g.second.first); }
-            ln.graphs.clear();
-        }
-        hipStream_t cs = cap_stream;
+        const auto& ln = lanes[li];
+        const LaneSet::GraphKey key = {ln.b0, ln.nb, sN, eos, sB, sImg, (int)use_latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode};
+        if (lanes.cached(li, key)) return 0;
+        hipStream_t cs = lanes.cap_stream;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         HIP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
         const int r = enqueue_step(cs, li, tok_buf, Tmax, nullptr, eos);
@@ -1505,8 +1274,7 @@ struct Engine : EngineBase {
         if (r) return r;
         if (e != hipSuccess) return fail(TXO_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
         HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        ln.graphs[key] = {graph, exec};
-        ln.exec = exec;
+        lanes.add(li, key, graph, exec);
         return 0;
     }
 
@@ -1515,7 +1283,7 @@ struct Engine : EngineBase {
         if (t < 0 || t >= Tmax)
             return fail(TXO_E_INVALID, "position outside the decoder's positional table (the reference would slide its "
                                        "window, decoder.py:99-100; a KV cache cannot reproduce that)");
-        if (n_lanes != 1) return fail(TXO_E_STATE, "decode_step needs a session started by txo_decode_begin");
+        if (lanes.n != 1) return fail(TXO_E_STATE, "decode_step needs a session started by txo_decode_begin");
         lanes[0].stream = s;
         if (tok_in) hipLaunchKernelGGL(copy_tokens_kernel, dim3((sB + 255) / 256), dim3(256), 0, s, cur_tok, tok_in, sB, V);
         hipLaunchKernelGGL(set_position_kernel, dim3(1), dim3(1), 0, s, st, t);
@@ -1543,7 +1311,7 @@ struct Engine : EngineBase {
     }
 
     int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) override {
-        if (n_lanes != 1) return fail(TXO_E_STATE, "decode_prefill needs a session started by txo_decode_begin");
+        if (lanes.n != 1) return fail(TXO_E_STATE, "decode_prefill needs a session started by txo_decode_begin");
         if (sImg != sB) return fail(TXO_E_STATE, "decode_prefill is not available inside a beam-search session");
         lanes[0].stream = s;
         return prefill(tokens, t, t, logits_out, nullptr, s);
@@ -1628,12 +1396,12 @@ struct Engine : EngineBase {
     bool persist_usable(int B) const {
         // sampling: the persistent kernel's sampler keeps a row in registers, 16 logits per lane (step.h: sample_row_regs)
         if (sample_mode && V > 64 * SR_PER) return false;
-        if (prof || prof_cross || g_dbg || knobs.stamps || knobs.graph >= 0 || knobs.lanes > 0) return false;
+        if (prof || prof_cross || g_dbg || knobs.run.stamps || knobs.run.graph >= 0 || knobs.run.lanes > 0) return false;
         if (cfg.dec_exp != 4 || cfg.dec_layers > PS_MAXLD) return false;
         const bool exists = (D == 256 && cfg.dec_heads == 8) || (D == 768 && cfg.dec_heads == 12 && sizeof(T) == 2);
         if (!exists) return false;
-        if (latent_ok && lat_mode == 1) return false;           // latent form forced: the persistent kernel reads projected K/V panels
-        if (knobs.persist >= 0) return knobs.persist != 0;
+        if (latent_ok && knobs.lat_mode == 1) return false;           // latent form forced: the persistent kernel reads projected K/V panels
+        if (knobs.run.persist >= 0) return knobs.run.persist != 0;
         if (persist_cooldown > 0) return false;                // it gave up twice in a row (not all 256 workgroups co-resident?): not tried for a while
         if (D != 256) return false;                            // the 768-wide variant is opt-in (TXO_PERSIST=1): not measured faster
         // bf16 beyond 128 images: launches with the cross attention in latent form (one row range, two from 224 rows on) are ahead of the
@@ -1675,7 +1443,7 @@ struct Engine : EngineBase {
         }
         pa.wlog = wlog;
         {   // the projections' weights as their tiled copies (all of them, or none)
-            bool all = w_tiled_on && wtiled.count(wlog);
+            bool all = knobs.w_tiled_on && wtiled.count(wlog);
             for (int l = 0; l < cfg.dec_layers && all; ++l)
                 all = wtiled.count(dec_self[l].wqkv) && wtiled.count(dec_self[l].wo) && wtiled.count(dec_cross[l].wo) && wtiled.count(dec_mlp[l].w1) && wtiled.count(dec_mlp[l].w2);
             pa.w_tiled = all ? 1 : 0;
@@ -1696,12 +1464,12 @@ struct Engine : EngineBase {
         pa.tokens_out = tokens_out; pa.out_stride = out_stride; pa.logits_out = logits_out;
         pa.sample = sample_mode; pa.sample_topk = sample_topk; pa.inv_temp = 1.0f / sample_temp; pa.seed = sample_seed;
         pa.ctl = pctl; pa.stamps = pstamps;
-        const char* stamp_file = knobs.pstamps ? knobs.pstamps_file.c_str() : nullptr;
+        const char* stamp_file = knobs.run.pstamps ? knobs.run.pstamps_file.c_str() : nullptr;
         pa.stamp_step = stamp_file ? std::min(max_len - 1, 200) : -1;
-        if (knobs.has_stagger) pa.stagger_ticks = knobs.stagger_ticks;
+        if (knobs.run.has_stagger) pa.stagger_ticks = knobs.run.stagger_ticks;
         pa.poll_sleep = 1;
         pa.poll_mode = 3;                           // default 3: scalar polls behind s_dcache_inv (persist.h: TeamSync::poll; -1.3 % per generate against vector polls)
-        if (knobs.has_inject) pa.inject_fail = knobs.inject_fail; // tests: the give-up / fall-back path
+        if (knobs.run.has_inject) pa.inject_fail = knobs.run.inject_fail; // tests: the give-up / fall-back path
         HIP_TRY(hipMemsetAsync(pctl, 0, sizeof(PersistCtl), s));
         if (stamp_file) HIP_TRY(hipMemsetAsync(pstamps, 0, sizeof(unsigned long long) * PS_TEAMS * PS_STAMP_RANKS * PS_MAX_STAGES * PS_STAMP_WORDS, s));
         if (D == 256) { if (int r = launch_persist<256, 8>(pa, s)) return r; }
@@ -1730,52 +1498,10 @@ struct Engine : EngineBase {
         // lets a team stop only at or beyond the batch's last first-eos position -- checked here, never assumed)
         for (int k = 0; k < nteams; ++k)
             if (c.steps_run[k] < steps) { g_err = "persistent decode: a team stopped before the batch's last position"; return TXO_E_STATE; }
-        if (stamp_file) dump_persist_stamps(stamp_file, nteams);
+        if (stamp_file) Stamps::dump_persist(stamp_file, pstamps, nteams, cfg.dec_layers);
         *n_steps = steps;
         return 0;
     }
-    void dump_persist_stamps(const char* file, int nteams) {
-        const int ns = 7 * cfg.dec_layers + 2;
-        std::vector<unsigned long long> h((size_t)PS_TEAMS * PS_STAMP_RANKS * PS_MAX_STAGES * PS_STAMP_WORDS);
-        if (hipMemcpy(h.data(), pstamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
-        FILE* f = fopen(file, "w");
-        if (!f) return;
-        static const char* names[7] = {"LN+qkv gemm", "self attention", "self out-proj+GLU+res", "cross attention (LN+q fused)",
-                                       "cross out-proj+GLU+res", "LN+ffn-in+GeGLU", "ffn-out+res"};
-        static const int ranks[PS_STAMP_RANKS] = {0, 10, 20, PS_TEAM_BLOCKS - 1};
-        fprintf(f, "# persistent decode launch, ONE decode position, workgroups of rank 0 / 10 / 20 / 31 of every team.  Per stage, us:\n"
-                   "#   poll  = polling the team counter for the previous stage's arrivals (weights / K panel already requested)\n"
-                   "#   work  = barrier + read the previous stage's rows (sc1) + compute + issue the stores\n"
-                   "#   drain = s_waitcnt vmcnt(0) of every wave + workgroup barrier\n"
-                   "#   pub   = the arrival atomic, issued -> returned\n"
-                   "#   end   = time of publication since the position's first stamp\n");
-        for (int k = 0; k < nteams; ++k)
-            for (int r = 0; r < PS_STAMP_RANKS; ++r) {
-                const unsigned long long* d = &h[((size_t)k * PS_STAMP_RANKS + r) * PS_MAX_STAGES * PS_STAMP_WORDS];
-                if (!d[2]) continue;
-                const unsigned long long t0 = d[2];
-                fprintf(f, "team %d rank %d: position span %.2f us\n", k, ranks[r], (d[(ns - 1) * PS_STAMP_WORDS + 4] - t0) / 100.0);
-                if (k > 1) continue;                           // the per-stage table for two teams is enough
-                for (int i = 0; i < ns; ++i) {
-                    const unsigned long long* e = d + i * PS_STAMP_WORDS;
-                    const char* nm = i < 7 * cfg.dec_layers ? names[i % 7] : (i == 7 * cfg.dec_layers ? "LNf+logits" : "argmax+append");
-                    fprintf(f, "  L%-2d %-30s poll %5.2f  work %5.2f  drain %5.2f  pub %5.2f | end %7.2f", i < 7 * cfg.dec_layers ? i / 7 : -1, nm,
-                            e[0] ? (e[1] - e[0]) / 100.0 : 0.0, e[1] ? (e[2] - e[1]) / 100.0 : 0.0, (e[3] - e[2]) / 100.0, (e[4] - e[3]) / 100.0,
-                            (e[4] - t0) / 100.0);
-                    const bool attn = i < 7 * cfg.dec_layers && (i % 7 == 1 || i % 7 == 3);
-                    if (e[5] && e[1] && !attn)   // GEMM tile of the workgroup's first group: rows read + MFMAs | K reduction | epilogue
-                        fprintf(f, " | tile: seen->mfma done %5.2f  reduce %5.2f  epilogue+stores %5.2f", (e[6] - e[1]) / 100.0, (e[7] - e[6]) / 100.0, (e[2] - e[7]) / 100.0);
-                    if (e[5] && e[1] && attn)    // attention tile of the workgroup's first group: wait end -> last pass's scores and PV done | reductions + store
-                        fprintf(f, " | tile: seen->panel consumed %5.2f  reduce+store %5.2f  (other group / barrier %5.2f)", ((long long)e[6] - (long long)e[1]) / 100.0,
-                                (e[7] - e[6]) / 100.0, ((long long)e[2] - (long long)e[7]) / 100.0);
-                    if (e[5] && e[0] && i > 0)   // before the poll: previous publication -> tile entry (stage set-up) -> poll begin (the tile's weight / bias / gamma requests)
-                        fprintf(f, " | pre: setup %5.2f  requests %5.2f", ((long long)e[5] - (long long)(e - PS_STAMP_WORDS)[4]) / 100.0, ((long long)e[0] - (long long)e[5]) / 100.0);
-                    fprintf(f, "\n");
-                }
-            }
-        fclose(f);
-    }
-
     // txo_generate / txo_generate_from_enc.  Per-row stop (stop_mode 1, a build extension: the reference has only the global break,
     // decoder.py:115-116): the decode below is the same loop with the same break -- rows are independent, so every row's tokens up to its first eos
     // are what the global-break run gives -- and every token BEHIND a row's first eos becomes cfg.pad (pad_after_eos_kernel); on the launch
@@ -1800,7 +1526,7 @@ struct Engine : EngineBase {
     bool row_stop = false;            // this generate compacts the live rows of its row ranges (launch path, stop_mode 1)
     // live rows of range li to its front; the range then launches `new_rows` rows (>= its live rows).  t1 = positions decoded so far.
     int compact_lane(int li, int new_rows, int t1, int eos) {
-        Lane& ln = lanes[li];
+        auto& ln = lanes[li];
         hipStream_t s = ln.stream;
         const size_t r0 = ln.b0;
         CompactArgs ca{ln.nb, new_rows, (int)r0, cur_tok + r0, eos_seen + r0, row_map + r0, cur_tok2 + r0, row_map2 + r0, cmoves + 2 * r0,
@@ -1860,7 +1586,7 @@ struct Engine : EngineBase {
                 persist_cooldown = 64; persist_strikes = 0;
                 fprintf(stderr, "[txo] persistent decode launch gave up twice in a row (%s): decoding with launches for the next 64 generates\n", g_err.c_str());
             }
-            set_lanes(1, s);
+            lanes.split(sB, 1, s);
             reset_lanes(s, eos);
         }
         // lanes: graphs + extra streams unless per-step logits were asked for or a debug/profiling mode is on
@@ -1869,16 +1595,16 @@ struct Engine : EngineBase {
         // single-stream launches (57.1 vs 58.0 / 58.2 ms) -- so both stay opt-in: TXO_GRAPH=1, TXO_LANES=n.
         // graph replay by default only for very small batches (B <= 4: there the host's enqueue rate bounds the step --
         // 34.2 vs 37.2 ms per generate at B = 1 -- from B = 8 on it is equal); TXO_GRAPH=1 / 0 forces it on / off
-        use_latent = latent_ok && (lat_mode == 1 || (lat_mode < 0 && auto_latent(B)));
+        use_latent = latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && auto_latent(B)));
         // per-row stop with live-row compaction: inside the positional table, tokens only (a finished row's logits would be unspecified)
-        row_stop = stop_mode == 1 && eos >= 0 && logits_out == nullptr && max_len <= Tmax && stop_every > 0 && !prof && !prof_cross;
+        row_stop = stop_mode == 1 && eos >= 0 && logits_out == nullptr && max_len <= Tmax && knobs.stop_every > 0 && !prof && !prof_cross;
         lat_self = use_latent && lat_self_ok() && !row_stop;      // (the z history is not moved by compact_lane)
         if (!use_latent) ensure_ckv(s);
-        const bool want_graph = knobs.graph >= 0 ? knobs.graph != 0 : B <= 4;
+        const bool want_graph = knobs.run.graph >= 0 ? knobs.run.graph != 0 : B <= 4;
         // per-row stop replays captured steps: as the ranges shrink a position's launches take less time than the host needs to enqueue them
         // (68 launches for two ranges: ~230 us per position on the host against 130 us on the device at 40 % of the rows), and a step
         // per row count (multiples of 16) is captured once and kept (lane_graph).  TXO_STOP_GRAPH=0: eager launches.
-        const bool stop_graph = row_stop && !sample_mode && stop_graph_on;
+        const bool stop_graph = row_stop && !sample_mode && knobs.stop_graph_on;
         const bool eager = logits_out != nullptr || g_dbg || sample_mode || !(want_graph || stop_graph);
         // two row ranges on two streams for a WIDE decoder at >= 256 rows (BASELINE cfg 4): one range's latency-bound projection launches
         // run beside the other's HBM-bound attention launches (816 -> 834 images/s; four ranges: 765).  Greedy and sampled alike: a draw is keyed
@@ -1889,50 +1615,27 @@ struct Engine : EngineBase {
         // in latent form the second range pays from ~224 rows on (160: 66.6 ms with one range vs 71.7 with two, 192: 70.6 vs 72.2, 256: 82.0 vs 77.9;
         // K/V form: two ranges from 129 on, 160: 70.9 vs 66.3)
         if (want == 2 && use_latent && D < 512 && B < 224) want = 1;
-        if (knobs.lanes > 0) want = std::min(knobs.lanes, max_lanes);
+        if (knobs.run.lanes > 0) want = std::min(knobs.run.lanes, MAXL);
         if (B < 32) want = 1;
-        if (want == 2 && tune_lanes && !lanes_tuned) { if (int r = tune_lane_streams()) return r; }
-        set_lanes(want, s);
-        last_ranges = n_lanes;
+        if (want == 2 && knobs.tune_lanes && !lanes.tuned) { if (int r = lanes.tune(n_cus, knobs.tune_verbose)) return r; }
+        lanes.split(sB, want, s);
+        last_ranges = lanes.n;
         reset_lanes(s, eos);
         bool use_graph = !eager && !prof && !prof_cross;   // event-carrying launches cannot be captured
-        if (use_graph) for (int i = 0; i < n_lanes; ++i) if (int r = lane_graph(i, eos)) return r;
-        if (n_lanes > 1) {
-            HIP_TRY(hipEventRecord(ev_fork, s));
-            for (int i = 0; i < n_lanes; ++i) if (lanes[i].stream != s) HIP_TRY(hipStreamWaitEvent(lanes[i].stream, ev_fork, 0));
-        }
+        if (use_graph) for (int i = 0; i < lanes.n; ++i) if (int r = lane_graph(i, eos)) return r;
+        if (int r = lanes.fork(s)) return r;
         int64_t* tdst = use_graph ? tok_buf : tokens_out;
         const int tstride = use_graph ? Tmax : max_len;               // rows of tokens_out are max_len apart (only n_pos positions are decoded here)
-        // GLOBAL eos break (decoder.py:115-116): the device records done_flag[t]; the host looks at the flags of every 32 steps.
-        // The look must not drain the stream: the flags of a chunk are copied to pinned memory behind the chunk, a few more
-        // steps are enqueued, and only then the host waits for that copy -- the GPU keeps running those steps meanwhile (a
-        // full stream sync at every chunk left it idle for the host's wake-up + re-enqueue time: 1.2 ms per 256 steps).  After
-        // a break at most AHEAD extra steps have run; their tokens lie beyond `steps` and are never returned.
-        const int CHUNK = 32, AHEAD = 4;
-        int* flags = flags_host;                                   // pinned, allocated in init()
-        int steps = n_pos;
-        bool broke = false;                                        // the GLOBAL eos break fired inside the positional table
-        look_failed = false;
-        int pend_lo = -1, pend_hi = -1;                            // chunk whose flags are in flight to the host
+        DonePoll poll{lanes, done_flag, Tmax, n_pos};              // GLOBAL eos break: poll.done = it fired inside the positional table
         int live_pend = -1;                                        // per-row stop: position behind which the ranges' finished-row counts were requested
-        auto look = [&]() -> bool {                                // wait for the pending chunk's flags; true = all rows done
-            for (int i = 0; i < n_lanes; ++i) HIP_TRY_B(hipEventSynchronize(ev_flags[i]));
-            for (int k = pend_lo; k <= pend_hi; ++k) {
-                bool all = true;
-                for (int i = 0; i < n_lanes; ++i) all = all && flags[(size_t)i * Tmax + k];
-                if (all) { steps = k + 1; broke = true; pend_lo = -1; return true; }
-            }
-            pend_lo = -1;
-            return false;
-        };
-        const char* stamp_file = knobs.stamps ? knobs.stamps_file.c_str() : nullptr;
-        if (stamp_file && !stamp_buf) { if (int r = dalloc(&stamp_buf, (size_t)STAMP_KERNELS * STAMP_BLOCKS * 3)) return r; }
+        const char* stamp_file = knobs.run.stamps ? knobs.run.stamps_file.c_str() : nullptr;
+        if (stamp_file && !stamps.buf) { if (int r = dalloc(&stamps.buf, (size_t)Stamps::KERNELS * Stamps::BLOCKS * 3)) return r; }
         const int stamp_step = stamp_file ? std::min(n_pos - 1, 200) : -1;
         auto decode_loop = [&]() -> int {
         for (int t = 0; t < n_pos; ++t) {
-            if (t == stamp_step) { HIP_TRY(hipMemsetAsync(stamp_buf, 0, sizeof(unsigned long long) * STAMP_KERNELS * STAMP_BLOCKS * 3, s)); stamp_slot = 0; stamp_names.clear(); }
-            else if (stamp_slot >= 0) dump_stamps(stamp_file, s);
-            for (int i = 0; i < n_lanes; ++i) {
+            if (t == stamp_step) { if (int r2 = stamps.begin(s)) return r2; }
+            else if (stamps.slot >= 0) stamps.dump(stamp_file, knobs.has_stamps_raw ? &knobs.stamps_raw : nullptr, s);
+            for (int i = 0; i < lanes.n; ++i) {
                 if (use_graph) HIP_TRY(hipGraphLaunch(lanes[i].exec, lanes[i].stream));
                 else if (int r2 = enqueue_step(lanes[i].stream, i, tdst, tstride, logits_out, eos, nullptr, t)) return r2;
             }
@@ -1940,56 +1643,43 @@ struct Engine : EngineBase {
             if (row_stop) {
                 // Live-row compaction.  The host only needs an UPPER bound of a range's live rows to size its launches, and live rows only
                 // decrease: the finished-row counter of a range is copied to pinned memory behind a step, AHEAD more steps are enqueued,
-                // and only then the host reads it (never draining the stream, like the done flags below).  compact_scan_kernel works on the
+                // and only then the host reads it (never draining the stream, like the done flags).  compact_scan_kernel works on the
                 // state of the moment it runs; slots between its live count and the host's bound are filler rows that count as finished.
-                if (live_pend >= 0 && t == live_pend + AHEAD) {
-                    for (int i = 0; i < n_lanes; ++i) HIP_TRY(hipEventSynchronize(ev_live[i]));
-                    for (int i = 0; i < n_lanes; ++i) {
-                        int bound = lanes[i].nb - live_host[i];
+                if (live_pend >= 0 && t == live_pend + DonePoll::AHEAD) {
+                    for (int i = 0; i < lanes.n; ++i) HIP_TRY(hipEventSynchronize(lanes.ev_live[i]));
+                    for (int i = 0; i < lanes.n; ++i) {
+                        int bound = lanes[i].nb - lanes.live_host[i];
                         if (use_graph) bound = std::min(lanes[i].nb, (bound + 15) & ~15);      // a captured step per multiple of 16 rows
-                        if (bound >= 1 && lanes[i].nb - bound >= stop_gain) {
+                        if (bound >= 1 && lanes[i].nb - bound >= knobs.stop_gain) {
                             if (int r2 = compact_lane(i, bound, t + 1, eos)) return r2;
                             if (use_graph) { if (int r2 = lane_graph(i, eos)) return r2; }
                         }
                     }
                     live_pend = -1;
                 }
-                if (live_pend < 0 && (t + 1) % stop_every == 0 && t + 1 + AHEAD < n_pos) {
-                    for (int i = 0; i < n_lanes; ++i) {
-                        HIP_TRY(hipMemcpyAsync(live_host + i, &st[i].rows_with_eos, sizeof(int), hipMemcpyDeviceToHost, lanes[i].stream));
-                        HIP_TRY(hipEventRecord(ev_live[i], lanes[i].stream));
+                if (live_pend < 0 && (t + 1) % knobs.stop_every == 0 && t + 1 + DonePoll::AHEAD < n_pos) {
+                    for (int i = 0; i < lanes.n; ++i) {
+                        HIP_TRY(hipMemcpyAsync(lanes.live_host + i, &st[i].rows_with_eos, sizeof(int), hipMemcpyDeviceToHost, lanes[i].stream));
+                        HIP_TRY(hipEventRecord(lanes.ev_live[i], lanes[i].stream));
                     }
                     live_pend = t;
                 }
             }
-            if (pend_lo >= 0 && (t == pend_hi + AHEAD || t + 1 == n_pos)) { if (look()) break; if (look_failed) return TXO_E_HIP; }
-            if ((t + 1) % CHUNK == 0 || t + 1 == n_pos) {
-                const int lo = (t / CHUNK) * CHUNK;
-                for (int i = 0; i < n_lanes; ++i) {
-                    HIP_TRY(hipMemcpyAsync(flags + (size_t)i * Tmax + lo, done_flag + (size_t)i * Tmax + lo,
-                                           sizeof(int) * (t + 1 - lo), hipMemcpyDeviceToHost, lanes[i].stream));
-                    HIP_TRY(hipEventRecord(ev_flags[i], lanes[i].stream));
-                }
-                pend_lo = lo; pend_hi = t;
-                if (t + 1 == n_pos) { (void)look(); if (look_failed) return TXO_E_HIP; }
-            }
+            if (int r2 = poll.after(t)) return r2;
+            if (poll.done) break;
         }
         return 0;
         };
         if (int r = decode_loop()) return abandon_lanes(s, r);
-        // join the lanes back into the caller's stream
-        for (int i = 0; i < n_lanes; ++i) {
-            if (lanes[i].stream == s) continue;
-            HIP_TRY(hipEventRecord(ev_join[i], lanes[i].stream));
-            HIP_TRY(hipStreamWaitEvent(s, ev_join[i], 0));
-        }
+        if (int r = lanes.join(s)) return r;
         if (use_graph)
             HIP_TRY(hipMemcpy2DAsync(tokens_out, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax,
                                      sizeof(int64_t) * n_pos, B, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
-        set_lanes(1, s);
-        if (!broke && max_len > n_pos) { if (int r = generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, &steps, s)) return r; }
+        lanes.split(sB, 1, s);
+        int steps = poll.steps;
+        if (!poll.done && max_len > n_pos) { if (int r = generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, &steps, s)) return r; }
         if (n_steps) *n_steps = steps;
         return 0;
     }
@@ -2000,7 +1690,7 @@ struct Engine : EngineBase {
     // forward of Tmax rows per image (prefill) + the single-position final LayerNorm / logits / token selection of the step path.
     // The GLOBAL eos test still looks at the whole output (:115), i.e. the per-row "seen" state carries over.
     int generate_window(int B, int n_pos, int max_len, int eos, int64_t* tokens_out, float* logits_out, int* steps, hipStream_t s) {
-        set_lanes(1, s);
+        lanes.split(sB, 1, s);
         lanes[0].stream = s;
         // the launch path's eos bookkeeping, rebuilt from the tokens decoded so far (a persistent launch keeps its own)
         HIP_TRY(hipMemsetAsync(st, 0, sizeof(StepState), s));
@@ -2015,9 +1705,9 @@ struct Engine : EngineBase {
             else hipLaunchKernelGGL(argmax_step_kernel, dim3(B), dim3(64), 0, s, sa);
             *steps = i + 1;
             if (eos >= 0) {                                       // slow path: one host look per token
-                HIP_TRY(hipMemcpyAsync(flags_host, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(lanes.flags_host, flag, sizeof(int), hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
-                if (flags_host[0]) break;
+                if (lanes.flags_host[0]) break;
             }
         }
         HIP_TRY(hipStreamSynchronize(s));
@@ -2038,92 +1728,47 @@ struct Engine : EngineBase {
             enc = eenc; N = 1 + (H / 16) * (W / 16);
         }
         if (int r = begin_session(enc, B, N, eos, s, false)) return r;
-        use_latent = latent_ok && (lat_mode == 1 || (lat_mode < 0 && auto_latent(rows)));
+        use_latent = latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && auto_latent(rows)));
         lat_self = use_latent && lat_self_ok();
         if (!use_latent) ensure_ckv(s);                               // cross K/V of the B images
         sB = rows; sImg = B;                                          // decode rows are (image, beam) slots
         last_persist = false;
-        set_lanes(1, s);
+        lanes.split(sB, 1, s);
         // Two row ranges on two streams from 256 rows on, as generate() does beyond 128 images: one range's latency-bound projection
         // launches run beside the other's HBM-bound attention launches.  A range is a whole number of IMAGES (beam_select_kernel ranks
         // an image's k beams together; self-attention slots are range-local); every range has its own step state and done flags.
         int want = (rows >= 256 && B >= 2 && !prof && !prof_cross && !g_dbg) ? 2 : 1;
-        if (knobs.lanes > 0) want = std::max(1, std::min(std::min(knobs.lanes, max_lanes), B));
-        if (want == 2 && tune_lanes && !lanes_tuned) { if (int r = tune_lane_streams()) { sB = B; return r; } }
-        if (want > 1) {
-            n_lanes = want;
-            int img0 = 0;
-            for (int i = 0; i < want; ++i) {
-                const int ni = B / want + (i < B % want ? 1 : 0);
-                lanes[i].b0 = img0 * beams; lanes[i].nb = ni * beams; lanes[i].stream = i == 0 ? s : lanes[i].own;
-                img0 += ni;
-            }
-            if (lanes[0].own) lanes[0].stream = lanes[0].own;          // (the measured pair: tune_lane_streams)
-        }
-        last_ranges = n_lanes;
+        if (knobs.run.lanes > 0) want = std::max(1, std::min(std::min(knobs.run.lanes, MAXL), B));
+        if (want == 2 && knobs.tune_lanes && !lanes.tuned) { if (int r = lanes.tune(n_cus, knobs.tune_verbose)) { sB = B; return r; } }
+        if (want > 1) lanes.split(rows, want, s, beams);
+        last_ranges = lanes.n;
         const int n = std::max(rows, Tmax);
         hipLaunchKernelGGL(beam_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st, cur_tok, bscore, bfin, done_flag, rows,
                            beams, Tmax, cfg.bos);
-        for (int i = 1; i < n_lanes; ++i)                             // the other ranges' step state and flags (no rows: they were reset above)
+        for (int i = 1; i < lanes.n; ++i)                             // the other ranges' step state and flags (no rows: they were reset above)
             hipLaunchKernelGGL(beam_reset_kernel, dim3((Tmax + 255) / 256), dim3(256), 0, s, st + i, cur_tok, bscore, bfin,
                                done_flag + (size_t)i * Tmax, 0, beams, Tmax, cfg.bos);
-        if (n_lanes > 1) {
-            HIP_TRY(hipEventRecord(ev_fork, s));
-            for (int i = 0; i < n_lanes; ++i) if (lanes[i].stream != s) HIP_TRY(hipStreamWaitEvent(lanes[i].stream, ev_fork, 0));
-        }
+        if (int r = lanes.fork(s)) return r;
         // same non-draining eos look as generate(): once every beam is finished further steps only repeat eos at no cost
-        // (beam_select_kernel), so the few steps enqueued ahead of the look change neither scores nor slots.  A range's flag stays
-        // set once set, so the batch is done at the first position at which every range's flag is set.
-        int* flags = flags_host;
-        int steps = max_len, cur = 0;
-        const int CHUNK = 32, AHEAD = 4;
-        int pend_lo = -1, pend_hi = -1;
-        bool stop = false, look_err = false;
-        auto look = [&]() {
-            for (int i = 0; i < n_lanes; ++i) if (hipEventSynchronize(ev_flags[i]) != hipSuccess) { look_err = true; return; }
-            for (int k2 = pend_lo; k2 <= pend_hi && !stop; ++k2) {
-                bool all = true;
-                for (int i = 0; i < n_lanes; ++i) all = all && flags[(size_t)i * Tmax + k2];
-                if (all) { steps = k2 + 1; stop = true; }
-            }
-            pend_lo = -1;
-        };
+        // (beam_select_kernel), so the few steps enqueued ahead of the look change neither scores nor slots.
+        DonePoll poll{lanes, done_flag, Tmax, max_len};
+        int cur = 0;
         auto beam_loop = [&]() -> int {
-        for (int t = 0; t < max_len && !stop; ++t) {
+        for (int t = 0; t < max_len; ++t) {
             BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1]};
-            for (int i = 0; i < n_lanes; ++i)
+            for (int i = 0; i < lanes.n; ++i)
                 if (int r2 = enqueue_step(lanes[i].stream, i, nullptr, 0, nullptr, eos, &bm, t)) return r2;
             cur ^= 1;
             if (eos < 0) continue;
-            const bool last = t + 1 == max_len;
-            if ((t + 1) % CHUNK == 0 || last) {
-                if (pend_lo >= 0) {                                   // (only when CHUNK <= AHEAD; kept for safety)
-                    look();
-                    if (look_err) return fail(TXO_E_HIP, "beam search: waiting for the done flags failed");
-                    if (stop) break;
-                }
-                const int lo = (t / CHUNK) * CHUNK;
-                for (int i = 0; i < n_lanes; ++i) {
-                    HIP_TRY(hipMemcpyAsync(flags + (size_t)i * Tmax + lo, done_flag + (size_t)i * Tmax + lo, sizeof(int) * (t + 1 - lo),
-                                           hipMemcpyDeviceToHost, lanes[i].stream));
-                    HIP_TRY(hipEventRecord(ev_flags[i], lanes[i].stream));
-                }
-                pend_lo = lo; pend_hi = t;
-            }
-            if (pend_lo >= 0 && (t == pend_hi + AHEAD || last)) {
-                look();
-                if (look_err) return fail(TXO_E_HIP, "beam search: waiting for the done flags failed");
-            }
+            if (int r2 = poll.after(t)) return r2;
+            if (poll.done) break;
         }
         return 0;
         };
         if (int r = beam_loop()) { sB = B; return abandon_lanes(s, r); }
-        for (int i = 0; i < n_lanes; ++i) {                           // join the ranges back into the caller's stream
-            if (lanes[i].stream == s) continue;
-            HIP_TRY(hipEventRecord(ev_join[i], lanes[i].stream));
-            HIP_TRY(hipStreamWaitEvent(s, ev_join[i], 0));
-        }
-        set_lanes(1, s);
+        if (int r = lanes.join(s)) return r;
+        const int steps = poll.steps;
+        lanes.split(sB, 1, s);
         // backtrack every beam into tok_buf rows, then hand out the best beam (slot 0: selection order is by score)
         hipLaunchKernelGGL(beam_backtrack_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, bparent, btok, Bmax, steps, rows,
                            tok_buf, Tmax);
@@ -2145,7 +1790,7 @@ struct Engine : EngineBase {
         else if (what == TXO_Q_PERSIST_FALLBACKS) *out = persist_fallbacks;
         else if (what == TXO_Q_LAST_ROW_RANGES) *out = last_persist ? 1 : last_ranges;
         else if (what == TXO_Q_LAST_LATENT) *out = (!last_persist && use_latent) ? 1 : 0;
-        else if (what == TXO_Q_RELOAD_KNOBS) { knobs.read(); *out = 0; }
+        else if (what == TXO_Q_RELOAD_KNOBS) { knobs.run.read(); *out = 0; }
         else if (what == TXO_Q_LAST_COMPACTIONS) *out = last_compactions;
         else return fail(TXO_E_INVALID, "unknown query");
         return 0;
