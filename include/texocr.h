@@ -136,7 +136,11 @@ int txo_generate_beam(txo_engine* e, const float* img_dev, int32_t B, int32_t C,
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits
  * (the reference uses int((1 - 0.9) * vocab) = 99 for vocab 1000), softmax(logits / temp), one multinomial draw,
  * from a counter-based RNG keyed by (`seed`; row of the batch, position): reproducible, independent of the decode path and of
- * how the engine splits the batch into row ranges; a different stream than torch.multinomial. */
+ * how the engine splits the batch into row ranges; a different stream than torch.multinomial.  The draw, exactly: Philox4x32-10 with
+ * counter (row, position, 0, 0) and key (seed low 32 bits, seed high 32 bits); u = ((c0 >> 8) + 0.5f) / 2^24 in float32; the kept
+ * set is the `topk` largest logits, ties at the k-th value kept lowest index first; the token is the first kept entry, in index
+ * order, at which the running sum of exp((logit - max) / temp) reaches u times their total (tests/sampler_ref.py restates it).
+ * mode 1 with a vocabulary beyond TXO_Q_SAMPLE_VOCAB_MAX: TXO_E_INVALID. */
 int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint64_t seed);
 
 /* Where a decode stops -- the eos handling of txo_generate / txo_generate_from_enc (AutoRegressiveDecoder.generate, decoder.py:97-118).
@@ -174,6 +178,8 @@ int txo_profile_read(txo_engine* e, int32_t kind, double* avg_ms, int64_t* count
 #define TXO_Q_RELOAD_KNOBS 4      /* not a question: re-read the TXO_* development knobs of generate() from the environment (the engine reads them once,
                                    * at creation; tests flip TXO_PERSIST / TXO_LANES on a live engine).  *out = 0 */
 #define TXO_Q_LAST_COMPACTIONS 5   /* live-row compactions of the last txo_generate* (TXO_STOP_ROW on the launch path; 0 otherwise) */
+#define TXO_Q_SAMPLE_VOCAB_MAX 6   /* the largest vocabulary txo_set_sampling accepts on this device: beyond 1024 entries the sampler stages a row
+                                    * in LDS (vocab * 4 bytes per workgroup) */
 int txo_engine_query(txo_engine* e, int32_t what, int64_t* out);
 
 const char* txo_last_error(void);

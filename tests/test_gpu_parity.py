@@ -570,8 +570,9 @@ def test_errors_and_state_dict_checks():
 
 def test_sampling_mode_support_reproducibility_and_distribution():
     """N2: the reference's sampler (top-k 99 -> softmax(/0.3) -> multinomial, decoder.py:104-108) on the device.
-    A different RNG stream than torch.multinomial, so parity is statistical: support, reproducibility, and a
-    chi-square test of 4096 first-step draws against the oracle's sampling distribution."""
+    A different RNG stream than torch.multinomial, so parity with the reference is statistical: support, reproducibility, and a
+    chi-square test of 4096 first-step draws against the oracle's sampling distribution -- the one link to torch.multinomial's law.
+    The draws themselves are pinned exactly, each against the documented rule, by tests/test_gpu_sampler.py."""
     cpu_ref = _oracle()
     d = Dims(canvas=224)
     d, sd, m = build(d, seed=0, max_batch=64)

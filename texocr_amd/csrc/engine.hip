@@ -75,6 +75,7 @@ struct EngineBase {
                               int eos, int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps,
                               hipStream_t s) = 0;
     int sample_mode = 0, sample_topk = 0; float sample_temp = 1.f; unsigned long long sample_seed = 0;
+    size_t sample_lds_max = 65536;              // dynamic LDS the LDS-form sampler may ask for (init: the device's per-workgroup limit)
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
     virtual int query(int what, int64_t* out) = 0;
     virtual int profile_enable(int on) = 0;
@@ -548,7 +549,16 @@ struct Engine : EngineBase {
         hybrid = c.embed == TXO_EMBED_HYBRID;
         {
             int dev = 0; hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n_cus = prop.multiProcessorCount;
+            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) {
+                if (prop.multiProcessorCount > 0) n_cus = prop.multiProcessorCount;
+                if (prop.sharedMemPerBlock > 0) sample_lds_max = prop.sharedMemPerBlock;
+            }
+            // the LDS-form sampler (step.h: sample_step_kernel<false>) stages a whole row, V * 4 bytes: beyond 64 KB it needs the opt-in,
+            // and a refusal leaves it at 64 KB.  A larger vocabulary is refused by txo_set_sampling, never a failed launch mid-decode
+            if (sample_lds_max > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_step_kernel<false>),
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sample_lds_max) != hipSuccess) {
+                (void)hipGetLastError(); sample_lds_max = 65536;
+            }
         }
         {
             bool exists = (D == 64 && la_supported<T, 64>()) || (D == 256 && la_supported<T, 256>()) || (D == 768 && la_supported<T, 768>());
@@ -1792,6 +1802,7 @@ struct Engine : EngineBase {
         else if (what == TXO_Q_LAST_LATENT) *out = (!last_persist && use_latent) ? 1 : 0;
         else if (what == TXO_Q_RELOAD_KNOBS) { knobs.run.read(); *out = 0; }
         else if (what == TXO_Q_LAST_COMPACTIONS) *out = last_compactions;
+        else if (what == TXO_Q_SAMPLE_VOCAB_MAX) *out = std::max<int64_t>(64 * SR_PER, (int64_t)(sample_lds_max / sizeof(float)));
         else return fail(TXO_E_INVALID, "unknown query");
         return 0;
     }
@@ -1929,6 +1940,10 @@ int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint
     if (!e) return fail(TXO_E_INVALID, "null engine");
     if (mode != 0 && mode != 1) return fail(TXO_E_INVALID, "sampling mode must be 0 (greedy) or 1 (top-k / temperature / multinomial)");
     if (mode == 1 && (topk < 1 || !(temp > 0.f))) return fail(TXO_E_INVALID, "sampling needs topk >= 1 and temp > 0");
+    const int V = e->impl->cfg.vocab;
+    if (mode == 1 && !sample_in_regs(V) && (size_t)V * sizeof(float) > e->impl->sample_lds_max)
+        return fail(TXO_E_INVALID, "sampling: the vocabulary does not fit the sampler's LDS (vocab * 4 bytes per workgroup: txo_engine_query "
+                                   "TXO_Q_SAMPLE_VOCAB_MAX)");
     e->impl->sample_mode = mode; e->impl->sample_topk = topk; e->impl->sample_temp = mode ? temp : 1.f; e->impl->sample_seed = seed;
     return 0;
 }

@@ -211,7 +211,8 @@ class HipEngine:
         """txo_engine_query: 0 = the last generate() ran as one persistent launch, 1 = persistent launches that fell back,
         2 = row ranges (streams) of the last launch-path decode, 3 = the last decode's cross attention ran in latent form,
         4 = (not a question) re-read the TXO_* development knobs of generate() from the environment, 5 = live-row compactions of the
-        last generate (stop='row' on the launch path)."""
+        last generate (stop='row' on the launch path), 6 = the largest vocabulary decode='sample' accepts on this device (set_sampling
+        raises ValueError beyond it)."""
         out = C.c_int64(0)
         _lib.check(self.lib.txo_engine_query(self.handle, int(what), C.byref(out)))
         return out.value
