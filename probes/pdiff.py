@@ -2,7 +2,7 @@
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from test_gpu_parity import Dims, build
+from gpu_harness import Dims, build
 for dtype in ("fp32", "bf16"):
     for B in (1, 5):
         d = Dims(canvas=224)

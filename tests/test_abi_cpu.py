@@ -27,6 +27,16 @@ def test_header_symbols_all_exported(lib):
     assert lib.txo_version().decode().startswith("texocr-amd")
 
 
+def test_query_codes_match_the_header():
+    """the Q_* names tests and model.py pass to txo_engine_query are the header's TXO_Q_* values, none missing on either side"""
+    from texocr_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "texocr.h")).read()
+    declared = {name: int(val) for name, val in re.findall(r"^#define\s+TXO_(Q_[A-Z_0-9]+)\s+(-?\d+)\b", hdr, re.M)}
+    assert declared, "no TXO_Q_* definitions parsed"
+    bound = {k: v for k, v in vars(_lib).items() if k.startswith("Q_")}
+    assert bound == declared, set(bound.items()) ^ set(declared.items())
+
+
 def _cfg(**over):
     from texocr_amd import _lib
     base = dict(canvas_h=224, canvas_w=224, embed=0, in_channels=3, embed_dim=256, enc_heads=8, enc_layers=4, dec_heads=8, dec_layers=4,

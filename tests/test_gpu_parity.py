@@ -1,6 +1,7 @@
 """GPU parity tests (run with -m gpu on an MI355X): the HIP path, called through the C ABI via the
 reference-shaped facades, against (a) golden vectors captured from the reference and (b) the CPU oracle on
-seeded inputs; plus size-independent properties at the BASELINE size.
+seeded inputs; plus size-independent properties at the BASELINE size.  The tools come from tests/gpu_harness.py;
+beam search has its own module, tests/test_gpu_beam.py.
 
 Tolerances (north_star): greedy token ids bit-exact, logits within 1e-3 in fp32 mode.  The fp32 assertions
 below are much tighter than 1e-3 (observed error ~5e-6; the reference's own step-vs-teacher-forced noise is
@@ -11,53 +12,13 @@ import pytest
 import torch
 
 from conftest import load_golden
+from gpu_harness import (assert_tokens_exact_up_to_margin, both_paths, build, fixture_rows_in_batch, images, knobs, on_path, oracle,
+                         teacher_forced_stepwise, top5_error, top5_error_and_top1_agreement)
 from texocr_amd import synth
+from texocr_amd._lib import Q_LAST_LATENT, Q_LAST_PERSISTENT, Q_LAST_ROW_RANGES, Q_PERSIST_FALLBACKS
 from texocr_amd.config import Dims
 
 pytestmark = pytest.mark.gpu
-
-
-def _oracle():
-    from oracle import cpu_ref
-    return cpu_ref
-
-
-def build(meta_or_dims, seed=None, dtype="fp32", max_batch=8, max_tokens=0, latent=None, sd=None, env=None):
-    """latent: None = the engine's default choice of the cross-attention form; 0 / 1 = the projected K/V panels / the raw encoder
-    rows (csrc/lat_attn.h) on every decode with launches (TXO_LATENT, read once when the engine is created).
-    env: further knobs the engine reads once at creation (TXO_LAT_G, TXO_LATENT_SELF, ...)."""
-    import os
-    from texocr_amd.model import model_from_dims
-    if isinstance(meta_or_dims, dict):
-        d, seed = Dims(**meta_or_dims["dims"]), meta_or_dims["weight_seed"]
-    else:
-        d = meta_or_dims
-    sd = sd if sd is not None else synth.synth_state_dict(d, seed)
-    knobs = dict(env or {})
-    if latent is not None:
-        knobs["TXO_LATENT"] = str(int(latent))
-    os.environ.update(knobs)
-    try:
-        m = model_from_dims(d, dtype=dtype, max_batch=max_batch, max_tokens=max_tokens)
-    finally:
-        for k in knobs:
-            os.environ.pop(k, None)
-    m.load_state_dict(sd)
-    return d, sd, m
-
-
-def images(meta):
-    return torch.from_numpy(synth.synth_images(*meta["image_shape"], seed=meta["image_seed"]))
-
-
-def assert_tokens_exact_up_to_margin(tok, ref_tok, ref_logits, thr=2e-5):
-    """tokens must be identical until (per row) the first step whose oracle top1-top2 margin < thr."""
-    top2 = ref_logits.topk(2, dim=-1).values
-    margin = (top2[..., 0] - top2[..., 1]).numpy()
-    for b in range(tok.shape[0]):
-        small = np.nonzero(margin[b] < thr)[0]
-        upto = int(small[0]) if small.size else tok.shape[1]
-        assert np.array_equal(tok[b, :upto], ref_tok[b, :upto]), (b, upto)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -115,7 +76,7 @@ def test_cfg2_shape_golden():
 
 
 @pytest.mark.parametrize("path", ["persistent", "launches"])
-def test_cfg2_benchmark_shape_golden_256_steps_inside_batch_64(path, monkeypatch):
+def test_cfg2_benchmark_shape_golden_256_steps_inside_batch_64(path):
     """The benchmark's own shape pinned to the reference for the WHOLE decode: 3x224x672 (589 keys: two cross-attention passes
     together with a self history beyond 128 positions), 256 greedy steps captured from the reference at B=2 -- decoded here as
     rows 41 and 6 of a 64-image batch (rows never interact; decoder.py:115 is the only cross-row operation) on the fp32 engine,
@@ -123,20 +84,14 @@ def test_cfg2_benchmark_shape_golden_256_steps_inside_batch_64(path, monkeypatch
     meta, g = load_golden("cfg2_b2_224x672_t256")
     assert float(g["margin"].min()) >= 1e-4 and g["tokens"].shape == (2, 256)
     d, sd, m = build(meta, max_batch=64, max_tokens=589)
-    gen = torch.Generator(device="cuda").manual_seed(21)
-    img = torch.rand((64, 3, 224, 672), generator=gen, device="cuda")
-    fix = images(meta).cuda()
-    img[41], img[6] = fix[0], fix[1]
+    img = fixture_rows_in_batch(meta, 64, (41, 6), seed=21)
     enc = m.encoder(img[[41, 6]].contiguous())
     np.testing.assert_allclose(enc[:, ::8].cpu().numpy(), g["enc_rows"], atol=5e-5)
-    monkeypatch.setenv("TXO_PERSIST", "1" if path == "persistent" else "0")
-    toks, logits = m.generate(img, 256, return_logits=True)
-    assert m._engine.query(0) == (1 if path == "persistent" else 0) and m._engine.query(1) == 0
+    toks, logits = on_path(m, path == "persistent", lambda: m.generate(img, 256, return_logits=True))
     assert toks.shape == (64, 256)
     assert np.array_equal(toks[[41, 6]].cpu().numpy(), g["tokens"])
     lg = logits[[41, 6]].cpu()
-    v = torch.gather(lg, 2, torch.from_numpy(g["top5_ids"].astype(np.int64)))
-    err = float((v - torch.from_numpy(g["top5_vals"])).abs().max())
+    err = top5_error(lg, g)
     print(f"cfg2 t256 ({path}): max |dlogit| over the reference's top-5 of all 2x256 steps {err:.2e}")
     assert err < 1e-3                                                                  # north_star bound
     np.testing.assert_allclose(lg[:, :8].numpy(), g["logits_first8"], atol=1e-4)
@@ -173,7 +128,6 @@ def test_sliding_window_matches_reference():
     """max_len > decoder.max_len: the reference slides its window (decoder.py:99-100).  The one-call C entry point (txo_generate)
     follows it -- the first max_length positions through the KV cache, every later token through one multi-position forward of
     its window (txo_decode_prefill's pass) -- on both decode paths, and so do the facades."""
-    import os
     meta, g = load_golden("sliding_window")
     d, sd, m = build(meta)
     img = images(meta).cuda()
@@ -182,12 +136,9 @@ def test_sliding_window_matches_reference():
     assert t.shape == (1, meta["max_len"])
     assert np.array_equal(t.cpu().numpy(), g["tokens"])
     # straight through the C entry point, with logits, persistent launch and launches
-    for mode in ("1", "0"):
-        os.environ["TXO_PERSIST"] = mode
-        try:
+    for mode in (1, 0):
+        with knobs(TXO_PERSIST=mode):
             tk, lg = m._engine.generate(img, meta["max_len"], d.eos, return_logits=True)
-        finally:
-            os.environ.pop("TXO_PERSIST")
         assert np.array_equal(tk.cpu().numpy(), g["tokens"]) and lg.shape == (1, meta["max_len"], d.vocab)
         assert bool((lg.argmax(-1) == tk).all())
     # the same through decoder.generate with explicit start tokens, and with a longer start prefix (general stepwise form)
@@ -209,7 +160,7 @@ def test_sliding_window_matches_reference():
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_prefill_equals_cached_steps_and_continues(dtype, monkeypatch):
+def test_prefill_equals_cached_steps_and_continues(dtype):
     """txo_decode_prefill: decoder.net() over a whole prefix in one causal pass.  Against t single-position cached steps of the
     same engine (fp32: < 2e-5, i.e. summation-order noise; bf16: bf16 noise), batch 5 x 40 positions at 224x224 and the benchmark
     width (589 keys); and the K/V cache it leaves behind continues with txo_decode_step exactly like the cache the steps built."""
@@ -222,9 +173,8 @@ def test_prefill_equals_cached_steps_and_continues(dtype, monkeypatch):
         enc = m.encoder(img)
         prefix = torch.cat([torch.full((5, 1), d.bos, dtype=torch.int64, device="cuda"), toks[:, :39]], 1)   # 40 positions
         lp = m.decoder.net(prefix, enc=enc)                                   # one pass
-        monkeypatch.setenv("TXO_NET_STEPWISE", "1")
-        ls = m.decoder.net(prefix, enc=enc)                                   # 40 cached steps
-        monkeypatch.delenv("TXO_NET_STEPWISE")
+        with knobs(TXO_NET_STEPWISE=1):
+            ls = m.decoder.net(prefix, enc=enc)                               # 40 cached steps
         err = float((lp - ls).abs().max())
         print(f"prefill vs steps ({dtype}, width {W}): max |dlogit| {err:.2e}")
         assert lp.shape == (5, 40, d.vocab)
@@ -238,7 +188,7 @@ def test_prefill_equals_cached_steps_and_continues(dtype, monkeypatch):
         assert float((l40 - step_logits[:, 40]).abs().max()) < (2e-5 if dtype == "fp32" else 0.08)
 
 
-def test_prefill_in_image_chunks_when_the_workspace_is_smaller_than_the_prefix_block(monkeypatch):
+def test_prefill_in_image_chunks_when_the_workspace_is_smaller_than_the_prefix_block():
     """The multi-position forward runs in the encoder's workspace (max_batch * max_tokens rows); a prefix block with more rows
     than that is processed in image chunks (here 4 images x 20 positions = 80 rows against 4 x 17 = 68: chunks of 3 + 1 images).
     Same logits as single-position steps, and as the reference's teacher-forced fixture for the first two images."""
@@ -254,15 +204,15 @@ def test_prefill_in_image_chunks_when_the_workspace_is_smaller_than_the_prefix_b
     prefix = torch.cat([torch.full((4, 1), d.bos, dtype=torch.long, device="cuda"), rows, extra], 1)
     assert prefix.shape == (4, 20)
     one = m.decoder.net(prefix, enc=enc)
-    monkeypatch.setenv("TXO_NET_STEPWISE", "1")
-    steps = m.decoder.net(prefix, enc=enc)
+    with knobs(TXO_NET_STEPWISE=1):
+        steps = m.decoder.net(prefix, enc=enc)
     assert one.shape == (4, 20, d.vocab)
     assert float((one - steps).abs().max()) < 2e-5
     np.testing.assert_allclose(one[:2, :16].cpu().numpy(), g["tf_logits"][:, :16], atol=3e-5)
     np.testing.assert_allclose(one[2:, :16].flip(0).cpu().numpy(), g["tf_logits"][:, :16], atol=3e-5)
 
 
-def test_prefill_net_is_an_order_of_magnitude_faster_than_steps(monkeypatch):
+def test_prefill_net_is_an_order_of_magnitude_faster_than_steps():
     """decoder.net() on 4 x 256 tokens: one multi-position pass against 256 single-position steps driven from Python (measured
     16x in fp32 at 197 encoder tokens, 50-90x at 589: profiles/r03_prefill_bench.txt).  Timing on a shared box is noisy: the best
     of three rounds is taken and the assertion is a loose 5x."""
@@ -286,8 +236,8 @@ def test_prefill_net_is_an_order_of_magnitude_faster_than_steps(monkeypatch):
             best = dt if best is None else min(best, dt)
         return best, out
     fast, a = clock(5)
-    monkeypatch.setenv("TXO_NET_STEPWISE", "1")
-    slow, b = clock(1)
+    with knobs(TXO_NET_STEPWISE=1):
+        slow, b = clock(1)
     print(f"decoder.net 4x256: one pass {fast * 1e3:.2f} ms, 256 steps {slow * 1e3:.2f} ms ({slow / fast:.1f}x)")
     assert float((a - b).abs().max()) < 5e-5
     assert slow / fast >= 5
@@ -317,7 +267,7 @@ def test_hybrid_resnet_embedder_golden():
 
 
 def test_hybrid_oracle_wider_image_and_bf16():
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     from texocr_amd.config import reference_config
     d = Dims.from_config(reference_config())
     d, sd, m = build(d, seed=9, max_batch=3, max_tokens=1 + 4 * 20)
@@ -358,7 +308,7 @@ def test_split_fp32_backbone_gemm_against_exact_f32():
     kernel (TXO_BACKBONE_EXACT=1) the 45-layer backbone + ViT output moves by far less than bf16 storage anywhere would (0.1-0.2), and
     stays within the 2 % of the fp32 reference that the mode promises."""
     from texocr_amd.config import reference_config
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims.from_config(reference_config())
     img = torch.from_numpy(synth.synth_images(3, 1, 64, 320, seed=31))
     _, sd, m_split = build(d, seed=9, dtype="bf16", max_batch=3, max_tokens=1 + 4 * 20)
@@ -413,7 +363,7 @@ def test_hybrid_default_factory_full_canvas_golden():
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B,H,W,seed", [(1, 224, 224, 5), (3, 64, 448, 6), (5, 224, 672, 7), (2, 16, 16, 8)])
 def test_oracle_parity_free_seeds(B, H, W, seed):
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=672)
     d, sd, m = build(d, seed=seed)
     img = torch.from_numpy(synth.synth_images(B, 3, H, W, seed=100 + seed))
@@ -433,7 +383,7 @@ def test_oracle_parity_free_seeds(B, H, W, seed):
 def test_net_equals_generate_cache_equals_recompute():
     """KV-cache == full-prefix recompute: the teacher-forced net() logits for the generated
     prefix equal the step logits of generate(), and both equal the oracle's recompute-mode decoder_net."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=224)
     d, sd, m = build(d, seed=3)
     img = torch.from_numpy(synth.synth_images(2, 3, 96, 128, seed=17))
@@ -448,7 +398,7 @@ def test_net_equals_generate_cache_equals_recompute():
 
 def test_vit_base_width_768():
     """BASELINE config 4 dims at reduced depth: 768-d / 12 heads (3-vector LayerNorm rows, K=768 GEMMs)."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=224, embed_dim=768, enc_heads=12, enc_layers=2, dec_heads=12, dec_layers=2)
     d, sd, m = build(d, seed=4, max_batch=2)
     img = torch.from_numpy(synth.synth_images(2, 3, 64, 224, seed=21))
@@ -475,10 +425,7 @@ def test_bf16_mode_logits_error_bounded():
     toks = torch.from_numpy(g["tokens"].astype(np.int64)).cuda()
     prefix = torch.cat([torch.full((4, 1), d.bos, dtype=torch.long, device="cuda"), toks[:, :-1]], 1)
     tf = m.decoder.net(prefix[:, :64], enc=enc).cpu()
-    ref_top = torch.from_numpy(g["top5_vals"][:, :64])
-    got_top = torch.gather(tf, 2, torch.from_numpy(g["top5_ids"][:, :64].astype(np.int64)))
-    err = float((got_top - ref_top).abs().max())
-    agree = float((tf.argmax(-1) == toks[:, :64].cpu()).float().mean())
+    err, agree = top5_error_and_top1_agreement(tf, toks[:, :64].cpu(), g, upto=64)
     print(f"cfg1 bf16 vs reference fixture, teacher-forced 4x64: max |dlogit| over the reference's top-5 {err:.4f}, top-1 agreement {agree:.4f}")
     # measured on MI355X: max |dlogit| ~0.04 on logits spanning about [-3, 3], agreement ~0.98 (disagreements sit on the
     # thinnest margins of this random-weight model: the fixture's smallest top-1/top-2 margin is 1e-4)
@@ -509,20 +456,11 @@ def test_full_size_batch_independence_and_determinism():
     assert torch.equal(t3, t1[perm])
     assert int(t1.min()) >= 0 and int(t1.max()) < d.vocab
     # opt-in execution modes must give the same tokens: hipGraph replay of the step, two concurrent lanes, fused self QKV
-    import os
     for env in ({"TXO_GRAPH": "1"}, {"TXO_GRAPH": "1", "TXO_LANES": "2"}, {"TXO_LANES": "4"}):
-        os.environ.update(env)
-        try:
+        with knobs(**env):
             assert torch.equal(m.generate(img, 256), t1), env
-        finally:
-            for k in env:
-                os.environ.pop(k)
     # the fused-QKV self-attention variant (read at engine creation) is a different kernel: same tokens up to thin margins
-    os.environ["TXO_SELF_FUSED"] = "1"
-    try:
-        _, _, mfu = build(d, seed=0, max_batch=8, max_tokens=589)
-    finally:
-        os.environ.pop("TXO_SELF_FUSED")
+    _, _, mfu = build(d, seed=0, max_batch=8, max_tokens=589, env={"TXO_SELF_FUSED": "1"})
     tf = mfu.generate(img[:8].contiguous(), 64)
     assert float((tf == t1[:8, :64]).float().mean()) > 0.98
     # bucketed variable-width input (BASELINE config 5's input shape): per-image rows equal the fixed-width result
@@ -573,7 +511,7 @@ def test_sampling_mode_support_reproducibility_and_distribution():
     A different RNG stream than torch.multinomial, so parity with the reference is statistical: support, reproducibility, and a
     chi-square test of 4096 first-step draws against the oracle's sampling distribution -- the one link to torch.multinomial's law.
     The draws themselves are pinned exactly, each against the documented rule, by tests/test_gpu_sampler.py."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=224)
     d, sd, m = build(d, seed=0, max_batch=64)
     img1 = torch.from_numpy(synth.synth_images(1, 3, 64, 64, seed=2))
@@ -650,7 +588,7 @@ def test_non_finite_input_policy():
     assert torch.isfinite(lg).all()
 
 
-def test_world1_rccl_collectives_really_run():
+def test_world1_rccl_collectives_really_run(monkeypatch):
     """One-rank "nccl" (= RCCL) group on the one GPU a test box has: every collective of texocr_amd/dist.py is ISSUED (force_collective) and
     checked to have gone through torch.distributed.all_gather_into_tensor with an output buffer that is not its input -- the token
     gather, the logits gather north_star names, and the bucketed beam-search gather of BASELINE configs[4].  No 1 -> 8 GPU curve exists
@@ -659,8 +597,8 @@ def test_world1_rccl_collectives_really_run():
     import torch.distributed as dist
     from texocr_amd import dist as tdist
     from texocr_amd.dist import sharded_generate, sharded_generate_bucketed
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", "29611")
+    monkeypatch.setenv("MASTER_ADDR", os.getenv("MASTER_ADDR", "127.0.0.1"))
+    monkeypatch.setenv("MASTER_PORT", os.getenv("MASTER_PORT", "29611"))
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     calls = []
     real = dist.all_gather_into_tensor
@@ -808,84 +746,10 @@ def test_custom_ops_and_module_state_dict():
     assert bool((m2.generate(img, 4) == 5).all())
 
 
-@pytest.mark.parametrize("latent", [None, 1], ids=["kv_form", "latent_form"])
-@pytest.mark.parametrize("vocab", [1000, 1100], ids=["rows_in_registers", "general_path"])
-def test_beam_search_extension(vocab, latent):
-    """BASELINE config 5 asks for beam search; the reference has none, so parity is anchored at
-    beams=1 == greedy, plus agreement with the oracle's independent CPU restatement of the same definition.
-    Both forms of beam_select_kernel (csrc/step.h): an image's k rows in registers up to 1024 entries, the general path beyond."""
-    cpu_ref = _oracle()
-    d = Dims(canvas=224, vocab=vocab)
-    # latent_form: the cross attention against the raw encoder rows, an image's k beams as ONE row of k * heads heads (16 per tile)
-    d, sd, m = build(d, seed=0, max_batch=12, latent=latent)
-    img = torch.from_numpy(synth.synth_images(3, 3, 64, 96, seed=41))
-    m.eos_token = None
-    greedy = m.generate(img.cuda(), 24)
-    assert torch.equal(m.generate(img.cuda(), 24, beam=1), greedy)
-    assert m._engine.query(3) == (1 if latent else 0)
-    sdt = cpu_ref.to_torch_sd(sd)
-    enc = cpu_ref.encode(sdt, img)
-    for k, eos in ((4, None), (3, int(greedy[0, 5]))):
-        m.eos_token = eos
-        toks, scores = m.generate(img.cuda(), 24, beam=k, return_beams=True)
-        ref_t, ref_s = cpu_ref.beam_search_cached(sdt, enc, d.bos, eos, 24, k)
-        assert toks.shape[:2] == (3, k) and toks.shape[2] == ref_t.shape[2]
-        np.testing.assert_allclose(scores.cpu().numpy(), ref_s.numpy(), atol=2e-3)
-        assert bool((scores[:, :-1] >= scores[:, 1:]).all())                  # best first
-        assert torch.equal(toks.cpu(), ref_t), (k, eos)
-        best = m.generate(img.cuda(), 24, beam=k)
-        assert torch.equal(best, toks[:, 0])
-        assert torch.equal(m.generate(img.cuda(), 24, beam=k), best)          # deterministic
-        # two row ranges on two streams (the default from 256 beam rows on): ranges are whole images, slots range-local -> the same bits
-        import os
-        os.environ["TXO_LANES"] = "2"
-        try:
-            toks2, scores2 = m.generate(img.cuda(), 24, beam=k, return_beams=True)
-            assert m._engine.query(2) == 2
-        finally:
-            os.environ.pop("TXO_LANES")
-        assert torch.equal(toks2, toks) and torch.equal(scores2, scores)
-    with pytest.raises(ValueError):
-        m.generate(img.cuda(), 24, beam=9)
-    with pytest.raises(ValueError):
-        m.generate(torch.rand(5, 3, 64, 96, device="cuda"), 24, beam=3)       # 15 rows > max_batch 12
-
-
-def test_beam_search_two_row_ranges_at_300_rows_bit_identical_to_one():
-    """From 256 beam rows on, beam search decodes two row ranges (whole images each) on two streams, in bf16 with the latent cross
-    attention whose tiles take up to 16 heads = two beams of an image: same tokens and scores as ONE range."""
-    import os
-    d = Dims(canvas=224, max_len=16)
-    _, _, m = build(d, seed=9, dtype="bf16", max_batch=300)
-    img = torch.from_numpy(synth.synth_images(60, 3, 32, 64, seed=17)).cuda()
-    m.eos_token = None
-    t2, s2 = m.generate(img, 12, beam=5, return_beams=True)
-    assert m._engine.query(2) == 2 and m._engine.query(3) == 1
-    os.environ["TXO_LANES"] = "1"
-    try:
-        t1, s1 = m.generate(img, 12, beam=5, return_beams=True)
-        assert m._engine.query(2) == 1
-    finally:
-        os.environ.pop("TXO_LANES")
-    assert torch.equal(t1, t2) and torch.equal(s1, s2)
-    # with an eos (the most frequent token of the best beams): finished beams repeat eos at no cost, the loop stops only when EVERY
-    # range's beams are finished -- same length, same beams, same scores on one range and on two
-    vals, counts = np.unique(t2[:, 0].cpu().numpy(), return_counts=True)
-    m.eos_token = int(vals[counts.argmax()])
-    e2 = m.generate(img, 12, beam=5, return_beams=True)
-    os.environ["TXO_LANES"] = "1"
-    try:
-        e1 = m.generate(img, 12, beam=5, return_beams=True)
-    finally:
-        os.environ.pop("TXO_LANES")
-    assert e1[0].shape == e2[0].shape and torch.equal(e1[0], e2[0]) and torch.equal(e1[1], e2[1])
-    assert not torch.equal(e2[0], t2[:, :, :e2[0].shape[2]]) or e2[0].shape[2] < 12      # the eos changed something
-
-
 def test_multipass_attention_panels():
     """Panels longer than one register pass: a full 448x448 canvas (N = 785 encoder tokens -> several cross-attention passes
     per launch in both storage types) and a positional table of 300 (> 256 cached self-attention keys -> two passes)."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=448, embed_dim=64, enc_heads=2, enc_layers=1, dec_heads=2, dec_layers=2, vocab=96, max_len=300,
              bos=94, eos=93, pad=95)
     d, sd, m = build(d, seed=11, max_batch=2)
@@ -906,12 +770,8 @@ def test_multipass_attention_panels():
     d2, sd2, mb = build(d, seed=11, dtype="bf16", max_batch=2)
     encb = mb.encoder(img.cuda())
     prefix = torch.cat([torch.full((2, 1), d.bos, dtype=torch.long, device="cuda"), toks[:, :-1]], 1)
-    import os
-    os.environ["TXO_NET_STEPWISE"] = "1"            # the single-position kernels' multi-pass panels are what this test is about
-    try:
+    with knobs(TXO_NET_STEPWISE=1):                 # the single-position kernels' multi-pass panels are what this test is about
         lb = mb.decoder.net(prefix[:, :280], enc=encb).cpu()
-    finally:
-        os.environ.pop("TXO_NET_STEPWISE")
     errb = float((lb - ref_l[:, :280]).abs().max())
     print(f"multi-pass panels, bf16 steps vs oracle (64-d toy, 280 positions): max |dlogit| {errb:.4f}")
     assert errb < 0.04                              # measured 0.025
@@ -921,7 +781,7 @@ def test_large_ragged_batch_rows_independent():
     """More decode rows than one launch round of 16-row tiles at the config.yml widths, ragged (130 rows: nine tiles, the
     last one with 2 rows): fp32 vs the oracle, and in both storage types the rows of the 130-row run must equal the same
     images decoded in 64-row runs bit for bit (a row's arithmetic never depends on the batch around it)."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=64, max_len=16)
     img = torch.from_numpy(synth.synth_images(130, 3, 32, 64, seed=77))
     d, sd, m = build(d, seed=21, max_batch=130)
@@ -939,7 +799,7 @@ def test_large_ragged_batch_rows_independent():
         mm.eos_token = None
         big_t, big_l = mm.generate(img.cuda(), 12, return_logits=True)
         small_t, small_l = mm.generate(img[:64].cuda(), 12, return_logits=True)
-        assert mm._engine.query(3) == latent
+        assert mm._engine.query(Q_LAST_LATENT) == latent
         assert torch.equal(big_t[:64], small_t), (dtype, latent)
         assert torch.equal(big_l[:64], small_l), (dtype, latent)
         tail_t, tail_l = mm.generate(img[66:].cuda(), 12, return_logits=True)      # rows 66..129 as a 64-row batch
@@ -953,9 +813,9 @@ def test_large_ragged_batch_rows_independent():
     _, _, md = build(d, seed=21, dtype="bf16", max_batch=130)
     md.eos_token = None
     big_t, big_l = md.generate(img.cuda(), 12, return_logits=True)
-    assert md._engine.query(0) == 0 and md._engine.query(3) == 1          # 130 rows: launches, latent form
+    assert md._engine.query(Q_LAST_PERSISTENT) == 0 and md._engine.query(Q_LAST_LATENT) == 1          # 130 rows: launches, latent form
     small_t, small_l = md.generate(img[:64].cuda(), 12, return_logits=True)
-    assert md._engine.query(3) == 0                                       # 64 rows: K/V form
+    assert md._engine.query(Q_LAST_LATENT) == 0                           # 64 rows: K/V form
     first = float((big_l[:64, 0] - small_l[:, 0]).abs().max())
     BOUND = 0.07                                                          # 1.5x the measurement (0.031 / 0.047)
     ref_sorted = ref_l.sort(-1, descending=True).values
@@ -974,7 +834,7 @@ def test_large_ragged_batch_rows_independent():
     assert first < BOUND and worst < BOUND
 
 
-def test_bf16_dma_gemm_bit_identical_to_register_staged(monkeypatch):
+def test_bf16_dma_gemm_bit_identical_to_register_staged():
     """The 256x256 LDS-DMA GEMM (gemm_pp.h) and the 128x128 register-staged GEMM (gemm_big.h) accumulate every output element in
     the same order, so the bf16 engine must give bit-identical encoder features and tokens with either (TXO_GEMM_OLD=1 forces
     the latter) -- and with either EPILOGUE form of the former: TXO_PP_TR=1 runs every epilogue straight from the transposed
@@ -983,13 +843,7 @@ def test_bf16_dma_gemm_bit_identical_to_register_staged(monkeypatch):
     every epilogue (heads scatter, GLU + residual, GeGLU, bias + residual, cross K/V store) are on the path; repeated to screen
     for timing-dependent races (the seam's early request / counted wait)."""
     def build_with(env, *a, **kw):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        try:
-            return build(*a, **kw)[2]
-        finally:
-            for k in env:
-                monkeypatch.delenv(k)
+        return build(*a, env=env, **kw)[2]
     forms = ({}, {"TXO_PP_TR": "1"}, {"TXO_PP_TR": "0"})
     d = Dims(canvas=672)
     img = torch.from_numpy(synth.synth_images(12, 3, 224, 672, seed=91)).cuda()
@@ -1026,20 +880,14 @@ def test_bf16_dma_gemm_bit_identical_to_register_staged(monkeypatch):
         assert torch.equal(h_new.encoder(imgh), ref_h), env
 
 
-def test_encoder_tile_walk_and_image_chunks_do_not_change_a_bit(monkeypatch):
+def test_encoder_tile_walk_and_image_chunks_do_not_change_a_bit():
     """r06: (a) the 256x256 GEMM's persistent tile walk runs its column bands inside ROW SUPER-BLOCKS (gemm_pp.h: `sbr`; the A operand of a
     super-block stays in the Infinity Cache across the bands) and (b) Engine::encode can push IMAGE CHUNKS through the stack one after the
     other (TXO_ENC_CHUNK, an experiment knob).  Neither may change a bit: a tile's arithmetic does not depend on when it is computed, and rows
     of different images never meet.  ViT-Base widths, 50 images = 116 row panels: super-blocks of 10 panels (eleven full, one of six), with
     the walk direction alternating; chunks of 16 and of 7 images (ragged last chunk)."""
     def build_with(env):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        try:
-            return build(d, seed=6, dtype="bf16", max_batch=50, max_tokens=589)[2]
-        finally:
-            for k in env:
-                monkeypatch.delenv(k)
+        return build(d, seed=6, dtype="bf16", max_batch=50, max_tokens=589, env=env)[2]
     d = Dims(canvas=672, embed_dim=768, enc_heads=12, enc_layers=2, dec_heads=12, dec_layers=1)
     img = torch.from_numpy(synth.synth_images(50, 3, 224, 672, seed=95)).cuda()
     ref = build_with({"TXO_PP_SB_MB": "0"}).encoder(img)                 # the r05 walk: every band over all row panels
@@ -1062,13 +910,9 @@ def test_wide_decoder_large_batch_ffn_path():
     tf, lf = mf.generate(img, 10, return_logits=True)
     prefix = torch.cat([torch.full((130, 1), d.bos, dtype=torch.long, device="cuda"), tf[:, :-1]], 1)
     enc_big = mb.encoder(img)
-    import os
-    os.environ["TXO_NET_STEPWISE"] = "1"            # single-position steps: the launch path's FFN-in routing is what this test is about
-    try:
+    with knobs(TXO_NET_STEPWISE=1):                 # single-position steps: the launch path's FFN-in routing is what this test is about
         lb_big = mb.decoder.net(prefix, enc=enc_big)                       # 130 rows: large-batch path
         lb_small = mb.decoder.net(prefix[:64], enc=enc_big[:64])          # 64 rows: 16-row kernel
-    finally:
-        os.environ.pop("TXO_NET_STEPWISE")
     e1, e2 = float((lb_big[:64] - lb_small).abs().max()), float((lb_big.float() - lf).abs().max())
     a1 = float((lb_big[:64].argmax(-1) == lb_small.argmax(-1)).float().mean())
     print(f"wide decoder FFN routes: 130-row vs 64-row bf16 max |dlogit| {e1:.4f} (top-1 agreement {a1:.4f}); bf16 vs fp32 {e2:.4f}")
@@ -1081,23 +925,15 @@ def test_folded_out_projection_on_32_row_blocks_bit_identical_to_16_row_blocks()
     """From 129 decode rows per range on (a beam search's rows), the latent form's folded output projection (K = heads * D = 2048) runs on
     32-row x 16-column blocks that share their weight fragments (dec_gemm_wide_kernel<EPI_GLU_RES, 16, 16, 2>): same K split, same reduction
     order, same epilogue as the 16-row tile -> the same bits.  520 rows on ONE row range against the engine with that routing off."""
-    import os
     d = Dims(canvas=224, max_len=16)
     img = torch.from_numpy(synth.synth_images(520, 3, 32, 64, seed=91)).cuda()
     outs = []
     for off in (False, True):
-        if off: os.environ["TXO_DEC_WIDE_OFF"] = "1"
-        try:
-            _, _, m = build(d, seed=5, dtype="bf16", max_batch=520)
-        finally:
-            os.environ.pop("TXO_DEC_WIDE_OFF", None)
+        _, _, m = build(d, seed=5, dtype="bf16", max_batch=520, env={"TXO_DEC_WIDE_OFF": "1"} if off else None)
         m.eos_token = None
-        os.environ["TXO_LANES"] = "1"
-        try:
+        with knobs(TXO_LANES=1):
             outs.append(m.generate(img, 12, return_logits=True))
-        finally:
-            os.environ.pop("TXO_LANES")
-        assert m._engine.query(0) == 0 and m._engine.query(3) == 1          # launches, latent form
+        assert m._engine.query(Q_LAST_PERSISTENT) == 0 and m._engine.query(Q_LAST_LATENT) == 1          # launches, latent form
         del m
     assert torch.equal(outs[0][0], outs[1][0])
     assert torch.equal(outs[0][1], outs[1][1])                                # logits bit for bit
@@ -1106,21 +942,6 @@ def test_folded_out_projection_on_32_row_blocks_bit_identical_to_16_row_blocks()
 # ------------------------------------------------------------------------------------------------
 # the decode loop as ONE persistent launch (csrc/persist.h) against the launch-per-stage path
 # ------------------------------------------------------------------------------------------------
-def _both_paths(m, img, max_len, **kw):
-    """generate() through the persistent launch (TXO_PERSIST=1) and through launches (TXO_PERSIST=0); asserts which path ran."""
-    import os
-    outs = []
-    for mode in ("1", "0"):
-        os.environ["TXO_PERSIST"] = mode
-        try:
-            outs.append(m.generate(img, max_len, **kw))
-            assert m._engine.query(0) == int(mode), f"TXO_PERSIST={mode}: the other decode path ran"
-        finally:
-            os.environ.pop("TXO_PERSIST")
-    assert m._engine.query(1) == 0, "a persistent launch fell back to launches"
-    return outs[0], outs[1]
-
-
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("B", [1, 5, 64, 100, 200])
 def test_persistent_decode_bit_identical_to_launches(dtype, B):
@@ -1131,7 +952,7 @@ def test_persistent_decode_bit_identical_to_launches(dtype, B):
     d, sd, m = build(d, seed=3, dtype=dtype, max_batch=B, latent=0)     # (beyond 128 rows bf16 launches default to the latent form)
     g = torch.Generator(device="cuda").manual_seed(77 + B)
     img = torch.rand((B, 3, 64, 224), generator=g, device="cuda")
-    (tp, lp), (tl, ll) = _both_paths(m, img, 40, return_logits=True)
+    (tp, lp), (tl, ll) = both_paths(m, img, 40, return_logits=True)
     assert tp.shape == (B, 40)
     assert torch.equal(tp, tl)
     assert torch.equal(lp, ll)
@@ -1145,7 +966,7 @@ def test_persistent_decode_bit_identical_to_launches_full_width(dtype):
     d, sd, m = build(d, seed=4, dtype=dtype, max_batch=24)
     g = torch.Generator(device="cuda").manual_seed(5)
     img = torch.rand((24, 3, 224, 672), generator=g, device="cuda")
-    (tp, lp), (tl, ll) = _both_paths(m, img, 12, return_logits=True)
+    (tp, lp), (tl, ll) = both_paths(m, img, 12, return_logits=True)
     assert tp.shape == (24, 12)
     assert torch.equal(tp, tl)
     assert torch.equal(lp, ll)
@@ -1163,11 +984,11 @@ def test_persistent_decode_samples_like_the_launch_path(dtype, B):
     g = torch.Generator(device="cuda").manual_seed(31 + B)
     img = torch.rand((B, 3, 64, 224), generator=g, device="cuda")
     kw = dict(temp=0.3, decode="sample", seed=11, return_logits=True)
-    (tp, lp), (tl, ll) = _both_paths(m, img, 40, **kw)
+    (tp, lp), (tl, ll) = both_paths(m, img, 40, **kw)
     assert tp.shape == (B, 40) and torch.equal(tp, tl) and torch.equal(lp, ll)
     greedy = m.generate(img, 40)
     assert not torch.equal(tp, greedy), "sampling at temperature 0.3 never left the arg-max path"
-    (t2, _), _ = _both_paths(m, img, 40, temp=0.3, decode="sample", seed=12, return_logits=True)
+    (t2, _), _ = both_paths(m, img, 40, temp=0.3, decode="sample", seed=12, return_logits=True)
     assert not torch.equal(t2, tp)
     # support: every drawn token is among the 99 largest logits of its step
     top = lp.topk(99, dim=-1).indices
@@ -1177,7 +998,7 @@ def test_persistent_decode_samples_like_the_launch_path(dtype, B):
     cands = [tok for tok in range(d.vocab) if (flat == tok).any(axis=1).all()]
     if cands:
         m.eos_token = cands[0]
-        a, b = _both_paths(m, img, 40, temp=0.3, decode="sample", seed=11)
+        a, b = both_paths(m, img, 40, temp=0.3, decode="sample", seed=11)
         assert torch.equal(a, b) and a.shape[1] <= 40
 
 
@@ -1195,11 +1016,11 @@ def test_sampler_row_request_forms_and_the_oracle_top_k(vocab):
     img = torch.rand((21, 3, 64, 224), generator=g, device="cuda")
     kw = dict(temp=0.7, decode="sample", seed=4, return_logits=True)
     if vocab <= 1024:
-        (tp, lp), (tl, ll) = _both_paths(m, img, 24, **kw)
+        (tp, lp), (tl, ll) = both_paths(m, img, 24, **kw)
         assert torch.equal(tp, tl) and torch.equal(lp, ll)
     else:                                                    # (the persistent launch's sampler keeps the row in registers: launches serve this one)
         tp, lp = m.generate(img, 24, **kw)
-        assert m._engine.query(0) == 0
+        assert m._engine.query(Q_LAST_PERSISTENT) == 0
         t2, l2 = m.generate(img, 24, **kw)
         assert torch.equal(tp, t2) and torch.equal(lp, l2)
     k = max(int((1 - 0.9) * vocab), 1)
@@ -1212,19 +1033,15 @@ def test_sampler_row_request_forms_and_the_oracle_top_k(vocab):
 def test_sampled_decode_draws_do_not_depend_on_the_row_ranges(dtype):
     """A draw is keyed by (seed; row of the BATCH, position): two row ranges on two streams (the default for bf16 beyond 223 images,
     sampled like greedy) sample the same tokens from the same logits as one range."""
-    import os
     d = Dims(canvas=224)
     d, sd, m = build(d, seed=3, dtype=dtype, max_batch=48)
     g = torch.Generator(device="cuda").manual_seed(77)
     img = torch.rand((48, 3, 64, 224), generator=g, device="cuda")
     outs = []
-    for lanes in ("1", "2"):
-        os.environ["TXO_LANES"] = lanes
-        try:
+    for lanes in (1, 2):
+        with knobs(TXO_LANES=lanes):
             outs.append(m.generate(img, 24, temp=0.3, decode="sample", seed=11, return_logits=True))
-            assert m._engine.query(0) == 0 and m._engine.query(2) == int(lanes)
-        finally:
-            os.environ.pop("TXO_LANES")
+            assert m._engine.query(Q_LAST_PERSISTENT) == 0 and m._engine.query(Q_LAST_ROW_RANGES) == lanes
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert not torch.equal(outs[0][0], m.generate(img, 24))              # and they are draws, not arg-maxes
 
@@ -1233,31 +1050,21 @@ def test_persistent_decode_gives_up_cleanly_and_launches_take_over():
     """The persistent launch waits on other workgroups with bounded spins; when a hand-off times out (or a team turns out to
     span two XCDs) every workgroup leaves, the engine reports it and redoes the decode with launches.  A test hook makes
     team 0 report a time-out at position 3: same tokens and logits as the launch path, one fallback counted."""
-    import os
     d = Dims(canvas=224)
     d, sd, m = build(d, seed=5, dtype="bf16", max_batch=16)
     g = torch.Generator(device="cuda").manual_seed(11)
     img = torch.rand((16, 3, 64, 224), generator=g, device="cuda")
-    os.environ["TXO_PERSIST"] = "0"
-    try:
+    with knobs(TXO_PERSIST=0):
         tl, ll = m.generate(img, 24, return_logits=True)
-    finally:
-        os.environ.pop("TXO_PERSIST")
-    before = m._engine.query(1)
-    os.environ["TXO_PERSIST"] = "1"; os.environ["TXO_PERSIST_INJECT_FAIL"] = "3"
-    try:
+    before = m._engine.query(Q_PERSIST_FALLBACKS)
+    with knobs(TXO_PERSIST=1, TXO_PERSIST_INJECT_FAIL=3):
         tp, lp = m.generate(img, 24, return_logits=True)
-    finally:
-        os.environ.pop("TXO_PERSIST"); os.environ.pop("TXO_PERSIST_INJECT_FAIL")
-    assert m._engine.query(1) == before + 1, "the injected time-out was not counted as a fallback"
-    assert m._engine.query(0) == 0, "the fallback decode must be the launch path"
+    assert m._engine.query(Q_PERSIST_FALLBACKS) == before + 1, "the injected time-out was not counted as a fallback"
+    assert m._engine.query(Q_LAST_PERSISTENT) == 0, "the fallback decode must be the launch path"
     assert torch.equal(tp, tl) and torch.equal(lp, ll)
-    os.environ["TXO_PERSIST"] = "1"
-    try:
+    with knobs(TXO_PERSIST=1):
         tp2, _ = m.generate(img, 24, return_logits=True)     # and the engine is usable afterwards, persistent again
-    finally:
-        os.environ.pop("TXO_PERSIST")
-    assert m._engine.query(0) == 1 and torch.equal(tp2, tl)
+    assert m._engine.query(Q_LAST_PERSISTENT) == 1 and torch.equal(tp2, tl)
 
 
 @pytest.mark.parametrize("held_cus,hold_ms", [(96, 80), (200, 80), (128, 1)])
@@ -1267,7 +1074,7 @@ def test_persistent_decode_under_real_cu_contention(held_cus, hold_ms):
     the resident workgroups give up, the launch ends as soon as the rest have started and seen the fail word, and launches take
     over beside the filler -- or for 1 ms, which the launch simply waits out.  Tokens and logits equal the undisturbed launch
     path's either way, nothing hangs, the fall-back is counted, and the engine goes back to the persistent launch afterwards."""
-    import os, time
+    import time
     import ctypes as C
     from texocr_amd import build as tb
     hooks = C.CDLL(tb.build_test_hooks(verbose=False))          # tests/hooks/hold_cus.hip: not part of the product library
@@ -1276,11 +1083,8 @@ def test_persistent_decode_under_real_cu_contention(held_cus, hold_ms):
     d, sd, m = build(d, seed=5, dtype="bf16", max_batch=32)
     g = torch.Generator(device="cuda").manual_seed(12)
     img = torch.rand((32, 3, 64, 224), generator=g, device="cuda")
-    os.environ["TXO_PERSIST"] = "0"
-    try:
+    with knobs(TXO_PERSIST=0):
         tl, ll = m.generate(img, 48, return_logits=True)
-    finally:
-        os.environ.pop("TXO_PERSIST")
     # the filler must run BESIDE the decode: two HIP streams that the runtime mapped onto one hardware queue run one after the other
     # (profiles/r06_b256_stream_pairs.txt) -- the filler would then simply finish first and nothing would be contended.  Take a side stream
     # that demonstrably runs side by side with the current one (a 3 ms one-CU hold on it must not delay a trivial launch here).
@@ -1300,9 +1104,8 @@ def test_persistent_decode_under_real_cu_contention(held_cus, hold_ms):
             break
     if side is None:
         pytest.skip("no side stream runs beside the current stream in this process")
-    before = m._engine.query(1)
-    os.environ["TXO_PERSIST"] = "1"
-    try:
+    before = m._engine.query(Q_PERSIST_FALLBACKS)
+    with knobs(TXO_PERSIST=1):
         torch.cuda.synchronize()
         assert hooks.txo_test_hold_cus(held_cus, 160 * 1024, hold_ms * 1000, C.c_void_p(side.cuda_stream)) == 0
         time.sleep(0.002)                                       # the filler is on its CUs before the decode launch is enqueued
@@ -1310,32 +1113,28 @@ def test_persistent_decode_under_real_cu_contention(held_cus, hold_ms):
         tp, lp = m.generate(img, 48, return_logits=True)
         dt = time.perf_counter() - t0
         side.synchronize()
-        fell_back = m._engine.query(1) - before
-        print(f"held {held_cus} CUs for {hold_ms} ms: generate took {dt * 1e3:.1f} ms, fall-backs {fell_back}, persistent={m._engine.query(0)}")
+        fell_back = m._engine.query(Q_PERSIST_FALLBACKS) - before
+        print(f"held {held_cus} CUs for {hold_ms} ms: generate took {dt * 1e3:.1f} ms, fall-backs {fell_back}, persistent={m._engine.query(Q_LAST_PERSISTENT)}")
         assert torch.equal(tp, tl) and torch.equal(lp, ll)
         assert dt < 0.5, "generate() must not hang on a busy GPU"
         if hold_ms >= 40:
-            assert fell_back == 1 and m._engine.query(0) == 0, "co-residency was impossible: the launch must have given up"
+            assert fell_back == 1 and m._engine.query(Q_LAST_PERSISTENT) == 0, "co-residency was impossible: the launch must have given up"
             assert dt < 0.060, "the give-up must not wait for the filler to finish"
         tp2, lp2 = m.generate(img, 48, return_logits=True)      # idle GPU again: persistent, same result
-        assert m._engine.query(0) == 1 and torch.equal(tp2, tl) and torch.equal(lp2, ll)
-    finally:
-        os.environ.pop("TXO_PERSIST")
+        assert m._engine.query(Q_LAST_PERSISTENT) == 1 and torch.equal(tp2, tl) and torch.equal(lp2, ll)
 
 
 def test_persistent_decode_global_eos_break():
     """Small vocabulary so that eos fires at different positions in different rows and teams: the persistent launch must
     return exactly the columns of the reference's GLOBAL break (decoder.py:115-116), like the launch path and the oracle."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=224, vocab=16, bos=14, eos=5, pad=15, max_len=256)
     d, sd, m = build(d, seed=11, max_batch=20)
     img = torch.from_numpy(synth.synth_images(20, 3, 32, 96, seed=5)).cuda()
     # pick as eos a token that every row emits, the last row as late as possible (rows and teams finish at different positions)
-    import os
-    os.environ["TXO_PERSIST"] = "1"
     m.eos_token = None
-    free = m.generate(img, 256).cpu().numpy()
-    os.environ.pop("TXO_PERSIST")
+    with knobs(TXO_PERSIST=1):
+        free = m.generate(img, 256).cpu().numpy()
     best = None
     for tok in range(d.vocab):
         hit = free == tok
@@ -1346,7 +1145,7 @@ def test_persistent_decode_global_eos_break():
     assert best is not None and best[1] > best[2] + 2, best
     eos = best[0]
     m.eos_token = eos
-    tp, tl = _both_paths(m, img, 256)
+    tp, tl = both_paths(m, img, 256)
     assert torch.equal(tp, tl)
     ref = cpu_ref.generate_cached(cpu_ref.to_torch_sd(sd), img.cpu(), d.bos, eos, 256)
     assert tp.shape[1] == best[1] + 1 and 1 < tp.shape[1] < 256, "the crafted case must break early"
@@ -1356,31 +1155,28 @@ def test_persistent_decode_global_eos_break():
     assert bool((tp == eos).any(dim=1).all()) and not bool((tp[:, :-1] == eos).any(dim=1).all())
     # eos_tok = None: never breaks
     m.eos_token = None
-    os.environ["TXO_PERSIST"] = "1"
-    try:
-        assert m.generate(img, 48).shape == (20, 48) and m._engine.query(0) == 1
-    finally:
-        os.environ.pop("TXO_PERSIST")
+    with knobs(TXO_PERSIST=1):
+        assert m.generate(img, 48).shape == (20, 48) and m._engine.query(Q_LAST_PERSISTENT) == 1
     # bos == eos: the BOS column already satisfies the test -> one step (decoder.py:115 looks at the whole output)
     d2 = Dims(canvas=224, vocab=16, bos=5, eos=5, pad=15, max_len=64)
     d2, sd2, m2 = build(d2, seed=11, max_batch=20)
-    t2p, t2l = _both_paths(m2, img, 64)
+    t2p, t2l = both_paths(m2, img, 64)
     assert t2p.shape == (20, 1) and torch.equal(t2p, t2l)
 
 
 @pytest.mark.parametrize("stagger_us", ["150", "600"])
-def test_persistent_eos_break_when_teams_drift_apart(stagger_us, monkeypatch):
+def test_persistent_eos_break_when_teams_drift_apart(stagger_us):
     """Teams of the persistent launch are not synchronised with each other.  Started 150 / 600 us apart (TXO_PS_STAGGER_US: several
     positions of drift between neighbouring teams, dozens between the first and the last) with a ragged batch, a team that has
     seen the chip-wide done mask must still decode up to the position at which the LAST row of the batch first produced eos:
     every returned column of every row equals the launch path's and the oracle's (no column left as allocated)."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=224, vocab=16, bos=14, eos=5, pad=15, max_len=256)
     d, sd, m = build(d, seed=11, max_batch=20)
     img = torch.from_numpy(synth.synth_images(20, 3, 32, 96, seed=5)).cuda()
     m.eos_token = None
-    monkeypatch.setenv("TXO_PERSIST", "0")
-    free = m.generate(img, 256).cpu().numpy()
+    with knobs(TXO_PERSIST=0):
+        free = m.generate(img, 256).cpu().numpy()
     # eos candidates: every row emits the token; take those whose LAST first-occurrence is in the first team (rows 0..2) or in the
     # last one (rows 18..19) -- with the stagger the last team is the furthest behind, the first the furthest ahead
     cands = []
@@ -1393,22 +1189,19 @@ def test_persistent_eos_break_when_teams_drift_apart(stagger_us, monkeypatch):
     assert cands
     for eos, last, row in cands[:4]:
         m.eos_token = eos
-        monkeypatch.setenv("TXO_PERSIST", "0")
-        tl = m.generate(img, 256)
-        monkeypatch.setenv("TXO_PERSIST", "1"); monkeypatch.setenv("TXO_PS_STAGGER_US", stagger_us)
-        monkeypatch.setenv("TXO_DEBUG_POISON", "1")                   # ops.py pre-fills the token block with -7: an undecoded column would show
-        for _ in range(3):
-            tp = m.generate(img, 256)
-            assert int(tp.min()) >= 0
-            assert m._engine.query(0) == 1 and m._engine.query(1) == 0
-            assert tp.shape == (20, last + 1), (eos, last, row, tuple(tp.shape))
-            assert torch.equal(tp, tl), (eos, last, row)
-        monkeypatch.delenv("TXO_PS_STAGGER_US"); monkeypatch.delenv("TXO_DEBUG_POISON")
+        with knobs(TXO_PERSIST=0):
+            tl = m.generate(img, 256)
+        with knobs(TXO_PS_STAGGER_US=stagger_us, TXO_DEBUG_POISON=1):     # ops.py pre-fills the token block with -7: an undecoded column would show
+            for _ in range(3):
+                tp = on_path(m, True, lambda: m.generate(img, 256))
+                assert int(tp.min()) >= 0
+                assert tp.shape == (20, last + 1), (eos, last, row, tuple(tp.shape))
+                assert torch.equal(tp, tl), (eos, last, row)
         assert np.array_equal(tp.cpu().numpy(), free[:, :last + 1])
     ref = cpu_ref.generate_cached(cpu_ref.to_torch_sd(sd), img.cpu(), d.bos, cands[0][0], 256)
     m.eos_token = cands[0][0]
-    monkeypatch.setenv("TXO_PERSIST", "1"); monkeypatch.setenv("TXO_PS_STAGGER_US", stagger_us)
-    assert np.array_equal(m.generate(img, 256).cpu().numpy(), ref.numpy())
+    with knobs(TXO_PERSIST=1, TXO_PS_STAGGER_US=stagger_us):
+        assert np.array_equal(m.generate(img, 256).cpu().numpy(), ref.numpy())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1474,20 +1267,12 @@ def test_cfg4_golden_64_steps_inside_batch_256():
     as rows 200 and 33 of a 256-image batch on the fp32 engine (tokens exact, logits within 1e-3)."""
     meta, g = load_golden("cfg4_b2_224x672_t64")
     assert float(g["margin"].min()) >= 1e-4 and g["tokens"].shape == (2, 64)
-    d = Dims(**meta["dims"])
-    sd = synth.synth_state_dict(d, meta["weight_seed"])
-    from texocr_amd.model import model_from_dims
-    gen = torch.Generator(device="cuda").manual_seed(9)
-    img = torch.rand((256, 3, 224, 672), generator=gen, device="cuda")
-    fix = images(meta).cuda()
-    img[200], img[33] = fix[0], fix[1]
-    m = model_from_dims(d, dtype="fp32", max_batch=256, max_tokens=589)
-    m.load_state_dict(sd)
+    d, sd, m = build(meta, max_batch=256, max_tokens=589)
+    img = fixture_rows_in_batch(meta, 256, (200, 33), seed=9)
     toks, logits = m.generate(img, 64, return_logits=True)
     assert np.array_equal(toks[[200, 33]].cpu().numpy(), g["tokens"])
     lg = logits[[200, 33]].cpu()
-    v = torch.gather(lg, 2, torch.from_numpy(g["top5_ids"].astype(np.int64)))
-    err = float((v - torch.from_numpy(g["top5_vals"])).abs().max())
+    err = top5_error(lg, g)
     print(f"cfg4 t64: max |dlogit| over the reference's top-5 of all 2x64 steps {err:.2e}")
     assert err < 1e-3
     np.testing.assert_allclose(lg[:, -4:].numpy(), g["logits_last4"], atol=2e-4)
@@ -1498,7 +1283,7 @@ def test_cfg5_full_size_beam5_bucketed():
     64, render_data.py:85-86), bucketed by exact size like BucketBatchSampler (dataset.py:281-326), beam search k=5
     (a build extension: the reference has none), max_len 256.  Anchors: the oracle's independent CPU beam search on a
     4-image subset (fp32), and the composition bucket -> shard -> beam -> gather used on a node."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     from texocr_amd.dist import generate_bucketed, sharded_generate_bucketed
     from texocr_amd.model import model_from_dims
     d = Dims(canvas=896)
@@ -1605,8 +1390,8 @@ def test_latent_cross_attention_matches_kv_form_fp32(shape):
         _, _, m = build(d, seed=2, dtype=dtype, max_batch=B, latent=latent)
         m.eos_token = None
         toks, logits = m.generate(img, T, return_logits=True)
-        assert m._engine.query(0) == (0 if latent else m._engine.query(0))       # forced latent form decodes with launches
-        assert m._engine.query(3) == latent
+        assert m._engine.query(Q_LAST_PERSISTENT) == (0 if latent else m._engine.query(Q_LAST_PERSISTENT))       # forced latent form decodes with launches
+        assert m._engine.query(Q_LAST_LATENT) == latent
         if latent:
             assert torch.equal(m.generate(img, T), toks)      # without logits: up to 4 images replay a captured graph of the same launches
         outs.append((toks.cpu(), logits.cpu()))
@@ -1626,33 +1411,17 @@ def test_latent_form_fp32_meets_the_reference_fixture_at_the_benchmark_shape():
     (fixture margin >= 1e-4), logits over the reference's top-5 of every step within 1e-3."""
     meta, g = load_golden("cfg2_b2_224x672_t256")
     d, sd, m = build(meta, max_batch=64, max_tokens=589, latent=1)
-    gen = torch.Generator(device="cuda").manual_seed(21)
-    img = torch.rand((64, 3, 224, 672), generator=gen, device="cuda")
-    fix = images(meta).cuda()
-    img[41], img[6] = fix[0], fix[1]
+    img = fixture_rows_in_batch(meta, 64, (41, 6), seed=21)
     toks, logits = m.generate(img, 256, return_logits=True)
-    assert m._engine.query(0) == 0
+    assert m._engine.query(Q_LAST_PERSISTENT) == 0
     assert np.array_equal(toks[[41, 6]].cpu().numpy(), g["tokens"])
-    v = torch.gather(logits[[41, 6]].cpu(), 2, torch.from_numpy(g["top5_ids"].astype(np.int64)))
-    err = float((v - torch.from_numpy(g["top5_vals"])).abs().max())
+    err = top5_error(logits[[41, 6]].cpu(), g)
     print(f"cfg2 t256, fp32 latent form: max |dlogit| over the reference's top-5 of all 2x256 steps {err:.2e}")
     assert err < 1e-3
 
 
-def _teacher_forced_stepwise(m, d, img, ref_tokens, monkeypatch):
-    """decoder.net() as single-position steps (TXO_NET_STEPWISE=1): the reference's tokens fed through the DECODE kernels of the
-    launch path (dec_gemm / dec_attn or lat_attn), every position's logits"""
-    toks = torch.from_numpy(ref_tokens.astype(np.int64)).cuda()
-    prefix = torch.cat([torch.full((toks.shape[0], 1), d.bos, dtype=torch.long, device="cuda"), toks[:, :-1]], 1)
-    monkeypatch.setenv("TXO_NET_STEPWISE", "1")
-    try:
-        return m.decoder.net(prefix, enc=m.encoder(img)).cpu(), toks.cpu()
-    finally:
-        monkeypatch.delenv("TXO_NET_STEPWISE")
-
-
 @pytest.mark.parametrize("form", ["kv", "latent"])
-def test_bf16_benchmark_shape_vs_reference_every_position(form, monkeypatch):
+def test_bf16_benchmark_shape_vs_reference_every_position(form):
     """The mode the headline number is quoted in against the reference at the benchmark's OWN shape: fixture
     cfg2_b2_224x672_t256 (3x224x672 = 589 keys, self history beyond 128 positions), the reference's 2 x 256 tokens teacher-forced
     through the bf16 engine's decode kernels, both forms of the cross attention: logits over the reference's top-5 of every
@@ -1660,10 +1429,8 @@ def test_bf16_benchmark_shape_vs_reference_every_position(form, monkeypatch):
     meta, g = load_golden("cfg2_b2_224x672_t256")
     d, sd, m = build(meta, dtype="bf16", max_batch=2, max_tokens=589, latent=(1 if form == "latent" else 0))
     img = images(meta).cuda()
-    tf, toks = _teacher_forced_stepwise(m, d, img, g["tokens"], monkeypatch)
-    got = torch.gather(tf, 2, torch.from_numpy(g["top5_ids"].astype(np.int64)))
-    err = float((got - torch.from_numpy(g["top5_vals"])).abs().max())
-    agree = float((tf.argmax(-1) == toks).float().mean())
+    tf, toks = teacher_forced_stepwise(m, d, img, g["tokens"])
+    err, agree = top5_error_and_top1_agreement(tf, toks, g)
     flips = (tf.argmax(-1) != toks).numpy()
     worst = float(g["margin"][flips].max()) if flips.any() else 0.0
     print(f"cfg2 t256 bf16 ({form} form) vs reference, teacher-forced 2x256: max |dlogit| over the reference's top-5 {err:.4f}, "
@@ -1674,19 +1441,14 @@ def test_bf16_benchmark_shape_vs_reference_every_position(form, monkeypatch):
 
 
 @pytest.mark.parametrize("path", ["persistent", "launches"])
-def test_bf16_benchmark_shape_free_running_inside_batch_64(path, monkeypatch):
+def test_bf16_benchmark_shape_free_running_inside_batch_64(path):
     """... and free-running on both decode paths (the persistent launch cannot be teacher-forced): the fixture images as rows 41 and
     6 of a 64-image bf16 batch follow the reference's tokens until the first position whose reference margin is thinner than the
     bf16 logit error, and the logits on that common prefix stay within the bound; both paths return the same tokens."""
     meta, g = load_golden("cfg2_b2_224x672_t256")
     d, sd, m = build(meta, dtype="bf16", max_batch=64, max_tokens=589, latent=0)
-    gen = torch.Generator(device="cuda").manual_seed(21)
-    img = torch.rand((64, 3, 224, 672), generator=gen, device="cuda")
-    fix = images(meta).cuda()
-    img[41], img[6] = fix[0], fix[1]
-    monkeypatch.setenv("TXO_PERSIST", "1" if path == "persistent" else "0")
-    toks, logits = m.generate(img, 256, return_logits=True)
-    assert m._engine.query(0) == (1 if path == "persistent" else 0) and m._engine.query(1) == 0
+    img = fixture_rows_in_batch(meta, 64, (41, 6), seed=21)
+    toks, logits = on_path(m, path == "persistent", lambda: m.generate(img, 256, return_logits=True))
     got_t, got_l = toks[[41, 6]].cpu().numpy(), logits[[41, 6]].cpu()
     worst_err, shortest = 0.0, 256
     for r in range(2):
@@ -1699,27 +1461,25 @@ def test_bf16_benchmark_shape_free_running_inside_batch_64(path, monkeypatch):
             assert float(g["margin"][r, k]) < 2 * 0.035, (r, k, float(g["margin"][r, k]))
     print(f"cfg2 t256 bf16 free-running ({path}) inside batch 64: common prefix >= {shortest} positions, max |dlogit| over the top-5 on it {worst_err:.4f}")
     assert worst_err < 0.035 and shortest >= 32                # measured 0.0208 on a common prefix of 53 positions
-    monkeypatch.setenv("TXO_PERSIST", "0" if path == "persistent" else "1")
-    assert torch.equal(m.generate(img, 256), toks)            # the other path: same tokens
+    with knobs(TXO_PERSIST=int(path != "persistent")):
+        assert torch.equal(m.generate(img, 256), toks)        # the other path: same tokens
 
 
 @pytest.mark.parametrize("form", ["kv", "latent"])
-def test_bf16_cfg4_vs_reference_64_positions(form, monkeypatch):
+def test_bf16_cfg4_vs_reference_64_positions(form):
     """ViT-Base + 6L decoder in bf16 against the reference's 2 x 64 tokens (fixture cfg4_b2_224x672_t64), teacher-forced through
     the decode kernels of the launch path, both forms (the 768-wide latent tile: 4 waves, one tile of encoder rows per wave)."""
     meta, g = load_golden("cfg4_b2_224x672_t64")
     d, sd, m = build(meta, dtype="bf16", max_batch=2, max_tokens=589, latent=(1 if form == "latent" else 0))
     img = images(meta).cuda()
-    tf, toks = _teacher_forced_stepwise(m, d, img, g["tokens"], monkeypatch)
-    got = torch.gather(tf, 2, torch.from_numpy(g["top5_ids"].astype(np.int64)))
-    err = float((got - torch.from_numpy(g["top5_vals"])).abs().max())
-    agree = float((tf.argmax(-1) == toks).float().mean())
+    tf, toks = teacher_forced_stepwise(m, d, img, g["tokens"])
+    err, agree = top5_error_and_top1_agreement(tf, toks, g)
     print(f"cfg4 t64 bf16 ({form} form) vs reference, teacher-forced 2x64: max |dlogit| over the reference's top-5 {err:.4f}, top-1 agreement {agree:.4f}")
     assert err < 0.039, err                                    # 1.5x the measurement (r04: 0.0258 / 0.0251, top-1 0.9844 both forms)
     assert agree > 0.976, agree
 
 
-def test_two_row_ranges_bit_identical_to_one(monkeypatch):
+def test_two_row_ranges_bit_identical_to_one():
     """The default decode beyond 128 images in bf16 (two row ranges on two streams, latent cross attention) against ONE range
     (TXO_LANES=1): rows never interact, so the tokens must be identical -- at batch 256, the benchmark's image size."""
     d = Dims(canvas=672)
@@ -1727,33 +1487,30 @@ def test_two_row_ranges_bit_identical_to_one(monkeypatch):
     gen = torch.Generator(device="cuda").manual_seed(9)
     img = torch.rand((256, 3, 224, 672), generator=gen, device="cuda")
     t2 = m.generate(img, 96)
-    assert m._engine.query(0) == 0
-    monkeypatch.setenv("TXO_LANES", "1")
-    t1 = m.generate(img, 96)
+    assert m._engine.query(Q_LAST_PERSISTENT) == 0
+    with knobs(TXO_LANES=1):
+        t1 = m.generate(img, 96)
     assert torch.equal(t1, t2)
 
 
-def test_fp32_fixture_on_two_row_ranges(monkeypatch):
+def test_fp32_fixture_on_two_row_ranges():
     """the fp32 reference-fixture run of the benchmark's shape (rows 41 and 6 of 64) with the batch decoded as TWO row ranges on
     two streams (TXO_LANES=2): tokens exact, logits within 1e-3"""
     meta, g = load_golden("cfg2_b2_224x672_t256")
     d, sd, m = build(meta, max_batch=64, max_tokens=589)
-    gen = torch.Generator(device="cuda").manual_seed(21)
-    img = torch.rand((64, 3, 224, 672), generator=gen, device="cuda")
-    fix = images(meta).cuda()
-    img[41], img[6] = fix[0], fix[1]
-    monkeypatch.setenv("TXO_LANES", "2")
-    toks = m.generate(img, 256)
-    assert m._engine.query(0) == 0
+    img = fixture_rows_in_batch(meta, 64, (41, 6), seed=21)
+    with knobs(TXO_LANES=2):
+        toks = m.generate(img, 256)
+    assert m._engine.query(Q_LAST_PERSISTENT) == 0
     assert np.array_equal(toks[[41, 6]].cpu().numpy(), g["tokens"])
 
 
 @pytest.mark.parametrize("path", ["persistent", "launches"])
-def test_eos_break_at_the_last_table_position_does_not_start_the_window(path, monkeypatch):
+def test_eos_break_at_the_last_table_position_does_not_start_the_window(path):
     """max_len > decoder.max_len AND the GLOBAL eos break (decoder.py:115-116) fires exactly at the table's last position: the
     reference returns max_length columns and never slides its window.  (steps == max_length alone cannot tell this case from
     'no break'; the engine carries the break out of both decode paths.)"""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     d = Dims(canvas=64, vocab=32, max_len=8, bos=30, eos=29, pad=31)     # config.yml widths (the persistent launch exists for them), an 8-entry table
     d, sd, m = build(d, seed=5, max_batch=3)
     sdt = cpu_ref.to_torch_sd(sd)
@@ -1773,15 +1530,15 @@ def test_eos_break_at_the_last_table_position_does_not_start_the_window(path, mo
     ref = cpu_ref.generate_recompute(sdt, img, d.bos, eos, 20)
     assert ref.shape == (3, 8)
     m.eos_token = eos
-    monkeypatch.setenv("TXO_PERSIST", "1" if path == "persistent" else "0")
-    out = m.generate(img.cuda(), 20)
-    assert m._engine.query(0) == (1 if path == "persistent" else 0)
-    assert out.shape == (3, 8), tuple(out.shape)
-    assert np.array_equal(out.cpu().numpy(), ref.numpy())
-    # and one position later the window does run: the reference's 9th column
-    m.eos_token = None
-    ref9 = cpu_ref.generate_recompute(sdt, img, d.bos, None, 9)
-    assert np.array_equal(m.generate(img.cuda(), 9).cpu().numpy(), ref9.numpy())
+    with knobs(TXO_PERSIST=int(path == "persistent")):
+        out = m.generate(img.cuda(), 20)
+        assert m._engine.query(Q_LAST_PERSISTENT) == (1 if path == "persistent" else 0)
+        assert out.shape == (3, 8), tuple(out.shape)
+        assert np.array_equal(out.cpu().numpy(), ref.numpy())
+        # and one position later the window does run: the reference's 9th column
+        m.eos_token = None
+        ref9 = cpu_ref.generate_recompute(sdt, img, d.bos, None, 9)
+        assert np.array_equal(m.generate(img.cuda(), 9).cpu().numpy(), ref9.numpy())
 
 
 def test_ragged_start_prefix_with_padding_mask_matches_reference():
@@ -1803,12 +1560,8 @@ def test_ragged_start_prefix_with_padding_mask_matches_reference():
     keep = torch.from_numpy(g["mask"])
     assert float((net - ref)[keep].abs().max()) < 1e-3
     assert bool(torch.isfinite(net).all())
-    import os
-    os.environ["TXO_NET_STEPWISE"] = "1"                               # the same call as single-position steps
-    try:
+    with knobs(TXO_NET_STEPWISE=1):                                    # the same call as single-position steps
         net_steps = m.decoder.net(start, mask=mask, enc=enc).cpu()
-    finally:
-        os.environ.pop("TXO_NET_STEPWISE")
     assert float((net_steps - ref)[keep].abs().max()) < 1e-3
     assert float((net_steps - net)[keep].abs().max()) < 2e-5
     # perf mode: the masked pass within bf16 noise of the reference at the positions that are not padding, finite everywhere
@@ -1838,7 +1591,7 @@ def test_latent_tile_head_group_size_does_not_change_a_heads_bits():
             _, _, m = build(d, seed=12, dtype=dtype, max_batch=40, latent=1, env={"TXO_LAT_G": g} if g else None)
             m.eos_token = None
             toks, logits = m.generate(img, 32, return_logits=True)
-            assert m._engine.query(3) == 1
+            assert m._engine.query(Q_LAST_LATENT) == 1
             beams = m.generate(img, 20, beam=5, return_beams=True)
             if ref is None:
                 ref = (toks, logits, beams)
@@ -1861,13 +1614,13 @@ def test_tiled_weights_and_whole_row_requests_do_not_change_a_bit():
         for env in (None, {"TXO_W_TILED": "0"}, {"TXO_A_TILED": "0"}):
             _, _, m = build(d, seed=5, dtype=dtype, max_batch=185, env=env)
             m.eos_token = None
-            (tp, lp), (tl, ll) = _both_paths(m, img[:7], 24, return_logits=True)
+            (tp, lp), (tl, ll) = both_paths(m, img[:7], 24, return_logits=True)
             assert torch.equal(tp, tl) and torch.equal(lp, ll)
             del m
             _, _, m = build(d, seed=5, dtype=dtype, max_batch=185, latent=1, env=env)
             m.eos_token = None
             lat = m.generate(img, 24, return_logits=True)
-            assert m._engine.query(3) == 1
+            assert m._engine.query(Q_LAST_LATENT) == 1
             beams = m.generate(img, 16, beam=5, return_beams=True)
             out = (tp, lp, lat[0], lat[1], beams[0], beams[1])
             if ref is None:
@@ -1885,12 +1638,9 @@ def test_bf16_benchmark_shape_free_running_inside_batch_256_default_path():
     prefix within the bound of the batch-64 test."""
     meta, g = load_golden("cfg2_b2_224x672_t256")
     d, sd, m = build(meta, dtype="bf16", max_batch=256, max_tokens=589)
-    gen = torch.Generator(device="cuda").manual_seed(23)
-    img = torch.rand((256, 3, 224, 672), generator=gen, device="cuda")
-    fix = images(meta).cuda()
-    img[200], img[33] = fix[0], fix[1]
+    img = fixture_rows_in_batch(meta, 256, (200, 33), seed=23)
     toks, logits = m.generate(img, 256, return_logits=True)
-    assert m._engine.query(0) == 0 and m._engine.query(3) == 1
+    assert m._engine.query(Q_LAST_PERSISTENT) == 0 and m._engine.query(Q_LAST_LATENT) == 1
     got_t, got_l = toks[[200, 33]].cpu().numpy(), logits[[200, 33]].cpu()
     worst_err, shortest = 0.0, 256
     for r in range(2):
@@ -1906,11 +1656,11 @@ def test_bf16_benchmark_shape_free_running_inside_batch_256_default_path():
     assert worst_err < 0.038 and shortest >= 32
     # without per-step logits the batch runs on two row ranges (the default): the same tokens
     t2 = m.generate(img, 256)
-    assert m._engine.query(2) == 2
+    assert m._engine.query(Q_LAST_ROW_RANGES) == 2
     assert torch.equal(t2, toks)
 
 
-def test_sampled_decode_at_256_rows_on_its_default_path(monkeypatch):
+def test_sampled_decode_at_256_rows_on_its_default_path():
     """decode='sample' beyond 223 images takes the greedy decode's path (launches in latent form, two row ranges): the draws must not
     depend on the ranges (one range vs two: bit-identical tokens), every drawn token lies inside the top-k support of the logits it
     was drawn from (k = int(0.1 * vocab) = 100 at 1000 entries... the reference keeps int((1 - 0.9) * V), utils.py:85-91), and the
@@ -1921,17 +1671,17 @@ def test_sampled_decode_at_256_rows_on_its_default_path(monkeypatch):
     gen = torch.Generator(device="cuda").manual_seed(31)
     img = torch.rand((256, 3, 224, 672), generator=gen, device="cuda")
     t2 = m.generate(img, 48, temp=0.3, decode="sample", seed=5)
-    assert m._engine.query(0) == 0 and m._engine.query(2) == 2 and m._engine.query(3) == 1
+    assert m._engine.query(Q_LAST_PERSISTENT) == 0 and m._engine.query(Q_LAST_ROW_RANGES) == 2 and m._engine.query(Q_LAST_LATENT) == 1
     assert torch.equal(m.generate(img, 48, temp=0.3, decode="sample", seed=5), t2)
-    monkeypatch.setenv("TXO_LANES", "1")
-    t1, l1 = m.generate(img, 48, temp=0.3, decode="sample", seed=5, return_logits=True)
-    assert m._engine.query(2) == 1
-    assert torch.equal(t1, t2)
-    k = int((1 - 0.9) * d.vocab)
-    kth = l1.topk(k, dim=-1).values[..., -1]
-    drawn = torch.gather(l1, 2, t1[..., None])[..., 0]
-    assert bool((drawn >= kth).all())                                     # support within the top-k of the step's logits
-    assert not torch.equal(t1, m.generate(img, 48))                       # draws, not arg-maxes
+    with knobs(TXO_LANES=1):
+        t1, l1 = m.generate(img, 48, temp=0.3, decode="sample", seed=5, return_logits=True)
+        assert m._engine.query(Q_LAST_ROW_RANGES) == 1
+        assert torch.equal(t1, t2)
+        k = int((1 - 0.9) * d.vocab)
+        kth = l1.topk(k, dim=-1).values[..., -1]
+        drawn = torch.gather(l1, 2, t1[..., None])[..., 0]
+        assert bool((drawn >= kth).all())                                 # support within the top-k of the step's logits
+        assert not torch.equal(t1, m.generate(img, 48))                   # draws, not arg-maxes
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
@@ -1940,7 +1690,7 @@ def test_latent_self_attention_history(dtype):
     (attention.py:114-127 with kv_input = x; folded q' and Wo' as in the cross attention).  fp32: logits within 2e-5 of the K/V history
     and the reference fixture of the benchmark's shape (256 greedy steps) token-exact in this form; bf16: within bf16 noise of the
     K/V history; beam search (per-beam slot tables through the latent core) against the oracle's beam search."""
-    cpu_ref = _oracle()
+    cpu_ref = oracle()
     env = {"TXO_LATENT_SELF": "1"}
     d = Dims(canvas=224)
     img = torch.from_numpy(synth.synth_images(6, 3, 64, 160, seed=71))
@@ -1967,14 +1717,10 @@ def test_latent_self_attention_history(dtype):
         del m_kv, m_z
         meta, g = load_golden("cfg2_b2_224x672_t256")
         _, _, m = build(meta, max_batch=16, max_tokens=589, latent=1, env=env)
-        gen = torch.Generator(device="cuda").manual_seed(21)
-        big = torch.rand((16, 3, 224, 672), generator=gen, device="cuda")
-        fix = images(meta).cuda()
-        big[11], big[2] = fix[0], fix[1]
+        big = fixture_rows_in_batch(meta, 16, (11, 2), seed=21)
         toks, logits = m.generate(big, 256, return_logits=True)
         assert np.array_equal(toks[[11, 2]].cpu().numpy(), g["tokens"])
-        v = torch.gather(logits[[11, 2]].cpu(), 2, torch.from_numpy(g["top5_ids"].astype(np.int64)))
-        assert float((v - torch.from_numpy(g["top5_vals"])).abs().max()) < 1e-3
+        assert top5_error(logits[[11, 2]].cpu(), g) < 1e-3
     else:
         # bf16 beam search in this form: the width-256 bf16 tile runs on FOUR waves, so its beam slot table covers 16 x 4 x 4 = 256
         # positions.  Inside that range the z history must reproduce the K/V history's beams (within bf16 noise: the same best first tokens);
@@ -1987,4 +1733,3 @@ def test_latent_self_attention_history(dtype):
         _, sd3, a = build(d300, seed=14, dtype="bf16", max_batch=30, latent=1)
         _, _, b = build(d300, seed=14, dtype="bf16", max_batch=30, latent=1, env=env)
         assert torch.equal(a.generate(img[:3].cuda(), 280, beam=4), b.generate(img[:3].cuda(), 280, beam=4))
-

@@ -20,15 +20,13 @@ import torch
 
 import ref64
 import sampler_ref as sr
-from test_gpu_parity import build, _both_paths
-from test_gpu_shapes import BF16_BOUND, CASES, _images
-from test_gpu_stop import STOP_ENV, Q_LAST_COMPACTIONS, Q_LAST_PERSISTENT, Q_LAST_RANGES, _first_eos, _stop_case, knobs
+from gpu_harness import BF16_BOUND, SHAPE_CASES, STOP_ENV, both_paths, build, first_eos, knobs, rgb_images, stop_case
 from texocr_amd import synth
+from texocr_amd._lib import Q_LAST_COMPACTIONS, Q_LAST_PERSISTENT, Q_LAST_ROW_RANGES, Q_SAMPLE_VOCAB_MAX
 from texocr_amd.config import Dims
 
 pytestmark = pytest.mark.gpu
 
-Q_SAMPLE_VOCAB_MAX = 6
 BAND = 2e-5                    # of the kept mass: float32 sums of up to a few thousand terms stay well inside it
 STEPS = 24
 ROWS = 21
@@ -38,7 +36,7 @@ TEMPS = (0.3, 1.0, 5.0)
 
 def _dims(vocab, base="calib256"):
     """config.yml decoder widths (the persistent launch exists for them), 1 encoder / 2 decoder layers, 128x128 canvas"""
-    return dataclasses.replace(CASES[base][0], vocab=vocab, bos=vocab - 2, eos=vocab - 3, pad=vocab - 1)
+    return dataclasses.replace(SHAPE_CASES[base][0], vocab=vocab, bos=vocab - 2, eos=vocab - 3, pad=vocab - 1)
 
 
 def _tiny(vocab, max_len):
@@ -124,11 +122,11 @@ def test_every_draw_on_each_sampler_form(vocab):
     sd = synth.synth_state_dict(d, 3)
     _, _, m = build(d, sd=sd, max_batch=ROWS)
     m.eos_token = None
-    img = _images(ROWS, 64, 64, 21)
+    img = rgb_images(ROWS, 64, 64, 21)
     x = img.cuda()
     kw = dict(temp=temp, decode="sample", seed=seed, return_logits=True)
     if vocab <= 1024 and vocab != 10:
-        (tp, lp), (tl, ll) = _both_paths(m, x, STEPS, **kw)
+        (tp, lp), (tl, ll) = both_paths(m, x, STEPS, **kw)
         runs = {"persistent": (tp, lp), "launches": (tl, ll)}
     else:
         with knobs(TXO_PERSIST=0):
@@ -149,7 +147,7 @@ def test_every_temperature_and_seed(vocab):
     d = _dims(vocab)
     _, _, m = build(d, seed=5, max_batch=ROWS)
     m.eos_token = None
-    x = _images(ROWS, 64, 64, 22).cuda()
+    x = rgb_images(ROWS, 64, 64, 22).cuda()
     for temp in TEMPS:
         for seed in SEEDS:
             t, lg = m.generate(x, STEPS, temp=temp, decode="sample", seed=seed, return_logits=True)
@@ -164,8 +162,8 @@ def test_bf16_both_paths():
     sd = synth.synth_state_dict(d, 3)
     _, _, m = build(d, sd=sd, dtype="bf16", max_batch=ROWS)
     m.eos_token = None
-    img = _images(ROWS, 64, 64, 23)
-    (tp, lp), (tl, ll) = _both_paths(m, img.cuda(), STEPS, temp=0.3, decode="sample", seed=2 ** 32 + 5, return_logits=True)
+    img = rgb_images(ROWS, 64, 64, 23)
+    (tp, lp), (tl, ll) = both_paths(m, img.cuda(), STEPS, temp=0.3, decode="sample", seed=2 ** 32 + 5, return_logits=True)
     _check_engine("bf16 persistent", tp, lp, 0.3, 2 ** 32 + 5)
     _check_engine("bf16 launches", tl, ll, 0.3, 2 ** 32 + 5)
     err = _feedback(sd, img, _bos(d, ROWS), tp, lp, d.max_len, BF16_BOUND["logits"])
@@ -201,10 +199,10 @@ def test_two_row_ranges_key_by_the_batch_row():
     d = _dims(1000)
     _, _, m = build(d, seed=3, dtype="bf16", max_batch=256)
     m.eos_token = None
-    x = _images(256, 16, 16, 24).cuda()
+    x = rgb_images(256, 16, 16, 24).cuda()
     with knobs(TXO_LANES=2):
         t, lg = m.generate(x, STEPS, temp=1.0, decode="sample", seed=7, return_logits=True)
-    assert m._engine.query(Q_LAST_PERSISTENT) == 0 and m._engine.query(Q_LAST_RANGES) == 2
+    assert m._engine.query(Q_LAST_PERSISTENT) == 0 and m._engine.query(Q_LAST_ROW_RANGES) == 2
     _check_engine("bf16 256 rows, two row ranges", t, lg, 1.0, 7)
 
 
@@ -212,19 +210,19 @@ def test_row_stop_compactions_key_by_the_batch_row():
     """stop='row' with a compaction every other position: a row that moves to another slot keeps its key.  The compacting decode
     returns no logits (a finished row's would be missing), so its tokens are predicted from the logits of the same decode with the
     global stop, up to each row's first eos."""
-    d, sd, img = _stop_case()
+    d, sd, img = stop_case()
     _, _, m = build(d, sd=sd, max_batch=40, env=STOP_ENV)
     x = img.cuda()
     seed, temp = 2 ** 32 + 5, 0.5
     with knobs(TXO_LANES=2):
         glob, lg = m.generate(x, d.max_len, temp=temp, decode="sample", seed=seed, return_logits=True)
         row = m.generate(x, d.max_len, temp=temp, decode="sample", seed=seed, stop="row")
-        assert m._engine.query(Q_LAST_RANGES) == 2 and m._engine.query(Q_LAST_COMPACTIONS) >= 2
+        assert m._engine.query(Q_LAST_ROW_RANGES) == 2 and m._engine.query(Q_LAST_COMPACTIONS) >= 2
     host = _check_engine("global stop, two ranges", glob, lg, temp, seed)
     g = glob.cpu().numpy()
     want = np.where(host.dist > BAND, host.token, g.reshape(-1)).reshape(g.shape)
     r = row.cpu().numpy()
-    first = _first_eos(r, d.eos)
+    first = first_eos(r, d.eos)
     assert len(set(first)) >= 4, first
     n = min(r.shape[1], g.shape[1])
     for b, f in enumerate(first):
@@ -238,7 +236,7 @@ def test_positions_beyond_256():
     sd = synth.synth_state_dict(d, 11)
     _, _, m = build(d, sd=sd, max_batch=2)
     m.eos_token = None
-    img = _images(2, 64, 64, 51)
+    img = rgb_images(2, 64, 64, 51)
     t, lg = m.generate(img.cuda(), 290, temp=1.0, decode="sample", seed=2 ** 64 - 1, return_logits=True)
     assert t.shape == (2, 290)
     _check_engine("290 positions", t, lg, 1.0, 2 ** 64 - 1)
@@ -252,7 +250,7 @@ def test_generate_window_beyond_the_table():
     sd = synth.synth_state_dict(d, 12)
     _, _, m = build(d, sd=sd, max_batch=4)
     m.eos_token = None
-    img = _images(4, 64, 64, 52)
+    img = rgb_images(4, 64, 64, 52)
     t, lg = m.generate(img.cuda(), 20, temp=1.0, decode="sample", seed=2 ** 32 + 5, return_logits=True)
     assert t.shape == (4, 20)
     for i in (0, 7, 8, 19):
@@ -269,7 +267,7 @@ def test_stepwise_loop_keys():
     d = _tiny(90, 8)
     sd = synth.synth_state_dict(d, 13)
     _, _, m = build(d, sd=sd, max_batch=4)
-    img = _images(4, 64, 64, 53)
+    img = rgb_images(4, 64, 64, 53)
     enc = m.encoder(img.cuda())
     seed, temp, L = 2 ** 32 + 5, 1.0, d.max_len
     rng = np.random.default_rng(0)
@@ -310,7 +308,7 @@ def test_the_index_order_tie_rule(vocab):
     w[~free] = 0
     b[~free] = 0
     sd["decoder.net.to_logits.weight"] = w
-    x = _images(ROWS, 64, 64, 25).cuda()
+    x = rgb_images(ROWS, 64, 64, 25).cuda()
     _, _, m0 = build(d, sd=dict(sd, **{"decoder.net.to_logits.bias": b}), max_batch=ROWS)
     m0.eos_token = None
     _, lg0 = m0.generate(x, STEPS, return_logits=True)
@@ -322,7 +320,7 @@ def test_the_index_order_tie_rule(vocab):
     m.eos_token = None
     kw = dict(temp=1.0, decode="sample", seed=7, return_logits=True)
     if vocab <= 1024:
-        (tp, lp), (tl, ll) = _both_paths(m, x, STEPS, **kw)
+        (tp, lp), (tl, ll) = both_paths(m, x, STEPS, **kw)
         runs = {"persistent": (tp, lp), "launches": (tl, ll)}
     else:
         tl, ll = m.generate(x, STEPS, **kw)
@@ -348,7 +346,7 @@ def test_sampling_refuses_a_vocabulary_beyond_the_lds_and_takes_the_largest_that
     vmax = m._engine.query(Q_SAMPLE_VOCAB_MAX)
     assert vmax >= 65536 // 4, vmax
     del m
-    x = _images(2, 64, 64, 54).cuda()
+    x = rgb_images(2, 64, 64, 54).cuda()
     _, _, m = build(_tiny(vmax + 1, 8), seed=1, max_batch=2)
     with pytest.raises(ValueError, match="LDS"):
         m._engine.set_sampling(True)

@@ -2,7 +2,7 @@
 
 validate() takes any width that is a multiple of 64 in [64, 768], any head count (dim_head is 64, so heads * 64 need not be the width)
 and any FFN width that is a multiple of 64; the LayerNorm and decoder-GEMM launches dispatch on the width and on K.  Each case below
-is chosen for a branch the rest of the suite never reaches (see CASES).  Small images on a 128x128 canvas keep the encoder cheap:
+is chosen for a branch the rest of the suite never reaches (gpu_harness.SHAPE_CASES).  Small images on a 128x128 canvas keep the encoder cheap:
 N = 65, 17, 16 and 2 encoder tokens (128x128, 64x64, 48x80, 16x16), 1, 17 and 2 rows, and in bf16 130 rows of 16x16 images (the
 >= 128-row paths).  Per case and storage type:
 - encoder rows, the teacher-forced prefix pass (decoder.net: the one-pass prefill where vocab % 8 == 0) and greedy generate with
@@ -17,38 +17,13 @@ import pytest
 import torch
 
 import ref64
-from test_gpu_parity import build, assert_tokens_exact_up_to_margin
-from test_gpu_stop import STOP_ENV, Q_LAST_PERSISTENT, Q_LAST_RANGES, Q_LAST_COMPACTIONS, _first_eos
+from gpu_harness import BF16_BOUND, SHAPE_CASES, STOP_ENV, assert_tokens_exact_up_to_margin, build, first_eos, rgb_images
 from texocr_amd import synth
-from texocr_amd.config import Dims
+from texocr_amd._lib import Q_LAST_COMPACTIONS, Q_LAST_LATENT, Q_LAST_PERSISTENT, Q_LAST_ROW_RANGES
 
 pytestmark = pytest.mark.gpu
 
-Q_LAST_LATENT = 3
 STEPS = 24
-
-
-def _dims(D, eh, dh, ee, de, vocab):
-    return Dims(canvas=128, in_channels=3, embed_dim=D, enc_heads=eh, enc_layers=1, dec_heads=dh, dec_layers=2, enc_exp=ee, dec_exp=de,
-                vocab=vocab, max_len=32, bos=vocab - 2, eos=vocab - 3, pad=vocab - 1)
-
-
-# name: (dims, what it reaches)
-CASES = {
-    "w64_h4": (_dims(64, 4, 4, 1, 1, 200), "inner 256 > D, GeGLU width 64, latent core at D = 64 with 4 heads"),
-    "w128": (_dims(128, 2, 2, 4, 4, 200), "ln_rows_generic_kernel; fp32 dec_gemm KW = 2 (K = 128); bf16 run-time K, one k-chunk per wave"),
-    "w192_h3": (_dims(192, 3, 3, 2, 1, 333), "bf16 K = 192: 6 k-chunks split 2/2/1/1 over the waves, A-swizzle mask 7; odd vocabulary"),
-    "w256_h3": (_dims(256, 5, 3, 1, 3, 1000), "latent at 256 with 3 decoder heads (bf16: the 4-wave tile); no persistent kernel; "
-                                              "out-projection K = 192"),
-    "w384_h6": (_dims(384, 6, 6, 4, 4, 1000), "ViT-Small-like; fp32 dec_gemm KW = 6 (K = 384), bf16 run-time K = 384; two row ranges "
-                                              "on the K/V form at 130 bf16 rows"),
-    "w512": (_dims(512, 8, 8, 4, 2, 1000), "ln_rows_kernel<., 2>; bf16 >= 128 rows: LayerNorm launch + GEMM for the FFN-in"),
-    "w704_h11": (_dims(704, 11, 11, 3, 3, 1000), "largest generic LayerNorm (11 float4 per lane); bf16 22 k-chunks"),
-    "w768_h20": (_dims(768, 20, 20, 1, 1, 1000), "heads > 16: two latent tiles per row, beam packing across tiles; dec_gemm_wide_kernel; "
-                                                 "no persistent kernel"),
-    "calib256": (_dims(256, 8, 8, 4, 4, 1000), "config.yml widths (persistent launch): calibrates the bf16 bounds"),
-    "calib768": (_dims(768, 12, 12, 4, 4, 1000), "ViT-Base widths: calibrates the bf16 bounds"),
-}
 
 
 def _has_latent(d, dtype):
@@ -60,18 +35,6 @@ def _has_latent(d, dtype):
 IMAGE_SETS = [(1, 128, 128), (17, 64, 64), (17, 48, 80), (2, 16, 16)]
 BF16_ROWS = (130, 16, 16)
 
-# bf16 against float64 (2 decoder layers, 24 steps, the IMAGE_SETS and BF16_ROWS above), max |d| measured on MI355X:
-#   calib256: encoder 0.0198, logits teacher forced 0.0371 / greedy 0.0323 (latent form 0.0322)
-#   calib768: encoder 0.0199, logits teacher forced 0.0314 / greedy 0.0299 (latent form 0.0327)
-# the new widths sit at encoder 0.019-0.024 and logits 0.030-0.041 (w64_h4 teacher forced); a wrong index gives 1-4
-BF16_CALIB = {"enc": 0.0199, "logits": 0.0371}
-BF16_BOUND = {k: 1.5 * v for k, v in BF16_CALIB.items()}
-
-
-def _images(b, h, w, seed):
-    return torch.from_numpy(synth.synth_images(b, 3, h, w, seed=seed))
-
-
 _REF = {}
 
 
@@ -82,9 +45,9 @@ def _ref(case, seed, shape, sd):
     if any(k[0] != case for k in _REF):
         _REF.clear()
     if key not in _REF:
-        d = CASES[case][0]
+        d = SHAPE_CASES[case][0]
         s64 = ref64.sd64(sd)
-        img = _images(*shape, seed)
+        img = rgb_images(*shape, seed)
         enc = ref64.encode(s64, img)
         toks, lg = ref64.generate(s64, enc, d.bos, None, STEPS)
         prefix = torch.cat([torch.full((shape[0], 1), d.bos, dtype=torch.long), toks[:, :-1]], 1)
@@ -123,15 +86,15 @@ def _sets(dtype):
 
 
 def _check_greedy(case, dtype, m, sd, latent, report):
-    d = CASES[case][0]
+    d = SHAPE_CASES[case][0]
     m.eos_token = None
     for i, shape in enumerate(_sets(dtype)):
         img, enc64, rtok, rlg, prefix, tf64 = _ref(case, 100 + i, shape, sd)
         x = img.cuda()
         tok, lg = m.generate(x, STEPS, return_logits=True)
-        got = {q: m._engine.query(q) for q in (Q_LAST_PERSISTENT, Q_LAST_RANGES, Q_LAST_LATENT)}
+        got = {q: m._engine.query(q) for q in (Q_LAST_PERSISTENT, Q_LAST_ROW_RANGES, Q_LAST_LATENT)}
         want_p = 0 if latent == 1 else _expect_persistent(d, dtype, shape[0])
-        want = {Q_LAST_PERSISTENT: want_p, Q_LAST_RANGES: 1 if want_p else _expect_ranges(d, dtype, shape[0], latent == 1),
+        want = {Q_LAST_PERSISTENT: want_p, Q_LAST_ROW_RANGES: 1 if want_p else _expect_ranges(d, dtype, shape[0], latent == 1),
                 Q_LAST_LATENT: int(latent == 1)}
         assert got == want, (case, dtype, shape, got, want)
         tok, lg = tok.cpu().numpy(), lg.cpu()
@@ -146,9 +109,9 @@ def _check_greedy(case, dtype, m, sd, latent, report):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case", list(SHAPE_CASES))
 def test_shape_matrix_against_float64(case, dtype):
-    d, what = CASES[case]
+    d, what = SHAPE_CASES[case]
     sd = synth.synth_state_dict(d, 3)
     mb = BF16_ROWS[0] if dtype == "bf16" else 17
     latent = 0 if _has_latent(d, dtype) else None
@@ -182,10 +145,10 @@ def test_shape_matrix_against_float64(case, dtype):
         assert agree >= 0.97, agree
 
 
-@pytest.mark.parametrize("case,dtype", [(c, t) for t in ("fp32", "bf16") for c, (d, _) in CASES.items() if _has_latent(d, t)])
+@pytest.mark.parametrize("case,dtype", [(c, t) for t in ("fp32", "bf16") for c, (d, _) in SHAPE_CASES.items() if _has_latent(d, t)])
 def test_shape_matrix_latent_form(case, dtype):
     """The same greedy decodes with the cross attention in latent form (csrc/lat_attn.h: against the raw encoder rows; TXO_LATENT=1)."""
-    d, what = CASES[case]
+    d, what = SHAPE_CASES[case]
     sd = synth.synth_state_dict(d, 3)
     mb = BF16_ROWS[0] if dtype == "bf16" else 17
     _, _, m = build(d, sd=sd, dtype=dtype, max_batch=mb, latent=1)
@@ -201,13 +164,13 @@ def test_shape_matrix_latent_form(case, dtype):
 
 @pytest.mark.parametrize("case", ["w256_h3", "w384_h6", "w768_h20"])
 def test_shape_matrix_beam_search_fp32(case):
-    """Beam search k = 3 against the oracle's restatement (test_gpu_parity.py: test_beam_search_extension), K/V form and, where it
+    """Beam search k = 3 against the oracle's restatement (test_gpu_beam.py: test_beam_search_extension), K/V form and, where it
     exists in fp32, latent form (an image's k beams are ONE row of k * heads heads: 9 at w256_h3).  Beams across several latent tiles:
     test_shape_matrix_beam_search_bf16_latent."""
-    d, what = CASES[case]
+    d, what = SHAPE_CASES[case]
     sd = synth.synth_state_dict(d, 3)
     s64 = ref64.sd64(sd)
-    img = _images(5, 64, 64, 7)
+    img = rgb_images(5, 64, 64, 7)
     enc64 = ref64.encode(s64, img)
     ref_t, ref_s = ref64.beam_search(s64, enc64, d.bos, None, STEPS, 3)
     for latent in ((0, 1) if _has_latent(d, "fp32") else (None,)):
@@ -232,10 +195,10 @@ def test_shape_matrix_beam_search_bf16_latent(case):
     (w768_h20: 60 heads, several tiles per row; calib768: 36).  Each returned beam's score against the float64 score of its own token
     path (teacher forced through the oracle): a slot or tile index that mixes beams gives a path whose score is not the engine's.
     Bound: 1.5x calib768's measured error."""
-    d, what = CASES[case]
+    d, what = SHAPE_CASES[case]
     sd = synth.synth_state_dict(d, 3)
     s64 = ref64.sd64(sd)
-    img = _images(5, 64, 64, 7)
+    img = rgb_images(5, 64, 64, 7)
     enc64 = ref64.encode(s64, img)
     _, _, m = build(d, sd=sd, dtype="bf16", max_batch=15, latent=1)
     m.eos_token = None
@@ -268,15 +231,15 @@ STOP_BIAS = {"w192_h3": 2.0, "w768_h20": 2.0}
 
 @pytest.mark.parametrize("case", list(STOP_BIAS))
 def test_shape_matrix_row_stop_compaction_fp32(case):
-    """stop='row' with a compaction every other position (test_gpu_stop.py: STOP_ENV): the float64 oracle's tokens bit for bit.  A
+    """stop='row' with a compaction every other position (gpu_harness.py: STOP_ENV): the float64 oracle's tokens bit for bit.  A
     compaction moves a row's K/V history (heads * Tmax * 64 per row): with 3 and 20 heads its stride is not the 8-head one."""
-    d, what = CASES[case]
+    d, what = SHAPE_CASES[case]
     sd = _stop_sd(d, STOP_BIAS[case])
-    img = _images(24, 64, 64, 11) * torch.linspace(0.2, 3.0, 24)[:, None, None, None]
+    img = rgb_images(24, 64, 64, 11) * torch.linspace(0.2, 3.0, 24)[:, None, None, None]
     s64 = ref64.sd64(sd)
     enc64 = ref64.encode(s64, img)
     want, lg = ref64.generate(s64, enc64, d.bos, d.eos, STEPS, stop="row", pad=d.pad)
-    first = _first_eos(want.numpy(), d.eos)
+    first = first_eos(want.numpy(), d.eos)
     assert len(set(first)) >= 6 and -1 in first and min(f for f in first if f >= 0) < 8, first   # the schedule the test is about
     _, _, m = build(d, sd=sd, max_batch=24, latent=0 if _has_latent(d, "fp32") else None, env=STOP_ENV)
     t = m.generate(img.cuda(), STEPS, stop="row")

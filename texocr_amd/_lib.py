@@ -15,6 +15,9 @@ LIB_PATH = os.environ.get("TXO_LIB_PATH") or os.path.join(_HERE, "libtexocr_hip.
 
 TXO_F32, TXO_BF16 = 0, 1
 TXO_E_INVALID, TXO_E_STATE, TXO_E_HIP = -1, -2, -3
+# txo_engine_query codes (include/texocr.h: TXO_Q_*; tests/test_abi_cpu.py holds the two lists together)
+(Q_LAST_PERSISTENT, Q_PERSIST_FALLBACKS, Q_LAST_ROW_RANGES, Q_LAST_LATENT, Q_RELOAD_KNOBS, Q_LAST_COMPACTIONS,
+ Q_SAMPLE_VOCAB_MAX) = 0, 1, 2, 3, 4, 5, 6
 
 
 class TxoConfig(C.Structure):

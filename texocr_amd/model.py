@@ -141,7 +141,7 @@ class HipEngine:
         # flip TXO_PERSIST / TXO_LANES on a live engine) it is told to read them again
         env = self._txo_env()
         if env != self._env_seen and self.handle:
-            self.query(4)                             # TXO_Q_RELOAD_KNOBS
+            self.query(_lib.Q_RELOAD_KNOBS)
             self._env_seen = env
 
     # ---- path (every call goes through a torch.ops.texocr operator) -------------------------------------------------
@@ -208,11 +208,12 @@ class HipEngine:
         _lib.check(self.lib.txo_set_stop_mode(self.handle, 1 if stop == "row" else 0))
 
     def query(self, what: int) -> int:
-        """txo_engine_query: 0 = the last generate() ran as one persistent launch, 1 = persistent launches that fell back,
-        2 = row ranges (streams) of the last launch-path decode, 3 = the last decode's cross attention ran in latent form,
-        4 = (not a question) re-read the TXO_* development knobs of generate() from the environment, 5 = live-row compactions of the
-        last generate (stop='row' on the launch path), 6 = the largest vocabulary decode='sample' accepts on this device (set_sampling
-        raises ValueError beyond it)."""
+        """txo_engine_query, `what` one of _lib.Q_*: LAST_PERSISTENT = the last generate() ran as one persistent launch,
+        PERSIST_FALLBACKS = persistent launches that fell back, LAST_ROW_RANGES = row ranges (streams) of the last launch-path decode,
+        LAST_LATENT = the last decode's cross attention ran in latent form, RELOAD_KNOBS = (not a question) re-read the TXO_*
+        development knobs of generate() from the environment, LAST_COMPACTIONS = live-row compactions of the last generate (stop='row'
+        on the launch path), SAMPLE_VOCAB_MAX = the largest vocabulary decode='sample' accepts on this device (set_sampling raises
+        ValueError beyond it)."""
         out = C.c_int64(0)
         _lib.check(self.lib.txo_engine_query(self.handle, int(what), C.byref(out)))
         return out.value
