@@ -84,6 +84,14 @@ def assert_tokens_exact_up_to_margin(tok, ref_tok, ref_logits, thr=2e-5):
         assert np.array_equal(tok[b, :upto], ref_tok[b, :upto]), (b, upto)
 
 
+def per_image_rel(enc, ref, scale=None):
+    """(B,) mean |enc - ref| over an image's tokens and columns / mean |scale| of that image (scale: ref unless given).  The hybrid tests
+    assert its MAXIMUM over a batch: a batch mean hides one image's wrong GroupNorm statistics behind a weight of 1 / B."""
+    enc, ref = torch.as_tensor(enc).double().cpu(), torch.as_tensor(ref).double().cpu()
+    scale = ref if scale is None else torch.as_tensor(scale).double().cpu()
+    return (enc - ref).abs().mean(dim=(1, 2)) / scale.abs().mean(dim=(1, 2))
+
+
 def top5_error(logits, g, upto=None):
     """max |logits - reference| over the reference's top-5 of every position (fixture arrays top5_ids / top5_vals; the first `upto`
     positions); logits (B, n, V) on the host"""

@@ -28,8 +28,9 @@ def img64(img: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def encode(sd, img: torch.Tensor, grid_w: Optional[int] = None) -> torch.Tensor:
-    return cpu_ref.encode(sd, img64(img), grid_w=grid_w)
+def encode(sd, img: torch.Tensor, grid_w: Optional[int] = None, backbone_q=None) -> torch.Tensor:
+    """backbone_q: a rounding applied wherever the hybrid backbone stores (cpu_ref.resnet_backbone); it has to keep the dtype it is given"""
+    return cpu_ref.encode(sd, img64(img), grid_w=grid_w, backbone_q=backbone_q)
 
 
 @torch.no_grad()

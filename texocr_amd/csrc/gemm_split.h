@@ -142,7 +142,8 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_split_kernel(ALoad aload, con
             s0 += in0 ? v : 0.f; q0 = in0 ? fmaf(v, v, q0) : q0;
             s1 += in1 ? v : 0.f; q1 = in1 ? fmaf(v, v, q1) : q1;
         }
-        // the cpg channels of a group are cpg adjacent lanes (cpg = 2 .. 32, a power of two)
+        // the cpg channels of a group are cpg adjacent lanes (gn_fusable: cpg = 1 .. 32, a power of two; the backbone has 2 .. 32, and with cpg = 1 the
+        // loop is empty and every lane writes its own group)
         for (int o = 1; o < gn.cpg; o <<= 1) {
             s0 += __shfl_xor(s0, o, 64); q0 += __shfl_xor(q0, o, 64); s1 += __shfl_xor(s1, o, 64); q1 += __shfl_xor(q1, o, 64);
         }
