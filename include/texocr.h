@@ -97,10 +97,29 @@ int txo_decode_step(txo_engine* e, const int64_t* tok_in_dev, int32_t t, float* 
  * (teacher-forced logits), and what the sliding window of AutoRegressiveDecoder.generate (decoder.py:99-100) costs per token. */
 int txo_decode_prefill(txo_engine* e, const int64_t* tokens_dev, int32_t t, float* logits_out_dev, void* stream);
 
+/* AutoRegressiveDecoder.forward (decoder.py:124-145) without autograd, on the session opened by txo_decode_begin.
+ * tokens_dev int64 [B][L], 2 <= L <= cfg.max_len + 1: columns 0..L-2 are fed (one causal multi-position pass, key mask of
+ * txo_decode_set_key_mask honoured), column p+1 is the target of position p.  Outputs, each [B][L-1], each may be NULL:
+ * logp_out (float) log_softmax(logits[b,p])[tokens[b,p+1]];  top1_out (int64) argmax of logits[b,p] (lowest index among equals);
+ * top1_logp_out (float) its log-probability.  The logits are formed tile by tile inside one kernel (texocr_amd/csrc/score.h) and
+ * never stored: no [B][L-1][vocab] buffer exists, and any vocabulary size is accepted (txo_decode_prefill's logits_out needs a
+ * multiple of 8).  Token ids outside [0, vocab) are forced into the table on both sides -- as inputs like txo_decode_step, and as
+ * TARGETS: the score returned is the clamped id's (the Python facade raises IndexError first).  Scores at padded positions, and
+ * at positions whose target is padding, are unspecified.  Side effect as txo_decode_prefill: self K/V rows 0..L-2 are filled.
+ * Asynchronous on `stream`; results are bit-reproducible run to run. */
+int txo_decode_score(txo_engine* e, const int64_t* tokens_dev, int32_t L, float* logp_out_dev, int64_t* top1_out_dev,
+                     float* top1_logp_out_dev, void* stream);
+
+/* OCRModel.forward's path (ocr_model.py:38-44) in one call: txo_encode + txo_decode_begin + txo_decode_set_key_mask(mask_dev, L) +
+ * txo_decode_score.  mask_dev uint8 [B][L] (0 = padding; its first L-1 columns are the fed positions) or NULL.  The key mask is
+ * cleared again before the call returns; the session stays open (txo_decode_step(e, tok, L-1, ...) continues behind it). */
+int txo_score(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t H, int32_t W, const int64_t* tokens_dev,
+              const uint8_t* mask_dev, int32_t L, float* logp_out_dev, int64_t* top1_out_dev, float* top1_logp_out_dev, void* stream);
+
 /* The `mask` argument of decoder.generate / decoder.net (model/decoder.py:95-101,112: a (B, T0) bool over the start tokens, padded
  * with True for every generated token; model/attention.py:130-155: energy filled with -FLT_MAX where query or key is masked).
  * mask_dev: uint8 [B][cols] on the device, 0 = padding; positions >= cols are not padding; NULL clears the mask.  Applies to the
- * txo_decode_step and txo_decode_prefill calls of the session opened by txo_decode_begin: a padded position is never attended by a
+ * txo_decode_step, txo_decode_prefill and txo_decode_score calls of the session opened by txo_decode_begin: a padded position is never attended by a
  * query that is not padding.  Rows of padded positions themselves are computed but unspecified (the reference softmaxes them
  * uniformly over all keys; nothing downstream reads them). */
 int txo_decode_set_key_mask(txo_engine* e, const uint8_t* mask_dev, int32_t cols, void* stream);

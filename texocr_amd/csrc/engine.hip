@@ -40,6 +40,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "lat_attn.h"
 #include "persist.h"
 #include "prefill.h"
+#include "score.h"
 #include "rows.h"
 #include "step.h"
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
@@ -68,6 +69,9 @@ struct EngineBase {
     virtual int decode_begin(const float* enc, int B, int N, int eos, hipStream_t s) = 0;
     virtual int decode_step(const int64_t* tok_in, int t, float* logits_out, int64_t* tok_out, hipStream_t s) = 0;
     virtual int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) = 0;
+    virtual int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
+    virtual int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
+                      int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
     virtual int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) = 0;
     virtual int generate(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
                          int64_t* tokens_out, int* n_steps, float* logits_out, hipStream_t s) = 0;
@@ -1327,9 +1331,37 @@ struct Engine : EngineBase {
         return prefill(tokens, t, t, logits_out, nullptr, s);
     }
 
+    // AutoRegressiveDecoder.forward without autograd (decoder.py:124-145): tokens [B][L]; columns 0..L-2 are fed through the
+    // multi-position forward, column p + 1 is the target of position p; per-position scores from the fused kernel of score.h
+    int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
+        if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
+        if (lanes.n != 1) return fail(TXO_E_STATE, "decode_score needs a session started by txo_decode_begin");
+        if (sImg != sB) return fail(TXO_E_STATE, "decode_score is not available inside a beam-search session");
+        lanes[0].stream = s;
+        const ScoreOut so{logp_out, top1_out, top1_logp_out};
+        return prefill(tokens, L, L - 1, nullptr, nullptr, s, &so);
+    }
+
+    // OCRModel.forward's path (ocr_model.py:38-44) in one call: encode into the engine's own buffer, open the session, mask, score
+    int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
+              int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
+        if (int r = encode(img, B, C, H, W, eenc, s)) return r;
+        if (int r = begin_session(eenc, B, 1 + (H / 16) * (W / 16), cfg.eos, s, true)) return r;
+        if (mask) {
+            const int n = sB * Tmax;
+            hipLaunchKernelGGL(set_key_mask_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, kmask, sB, L, L - 1, Tmax);
+            kmask_on = true;
+        }
+        const int rc = decode_score(tokens, L, logp_out, top1_out, top1_logp_out, s);
+        kmask_on = false;
+        return rc;
+    }
+
     // ---- multi-position decoder forward (prefill.h): Transformer.forward over t positions at once, filling the self K/V cache ----
     // tokens [B][tok_stride] (the first t of each row); logits_out [B][t][V] or null; last_logits [B][V] or null (final LN + logits of
-    // position t-1 only, on the single-position launch).  Runs in the encoder's workspace, image chunks of as many rows as fit.
+    // position t-1 only, on the single-position launch); score: per-position scores [B][t] against the targets tokens[b][p + 1]
+    // (tok_stride > t then) or null.  Runs in the encoder's workspace, image chunks of as many rows as fit.
+    struct ScoreOut { float* logp; int64_t* top1; float* top1_logp; };
     template <typename TO>
     void launch_attn_mq(hipStream_t s, bool causal, const T* q, const T* k, const T* v, TO* out, int nb, int nq, int nk, int kv_rows,
                         const unsigned char* km = nullptr) {
@@ -1338,10 +1370,11 @@ struct Engine : EngineBase {
         else if (causal) hipLaunchKernelGGL((attn_mq_kernel<T, TO, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
         else hipLaunchKernelGGL((attn_mq_kernel<T, TO, false>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
     }
-    int prefill(const int64_t* tokens, int tok_stride, int t, float* logits_out, float* last_logits, hipStream_t s) {
+    int prefill(const int64_t* tokens, int tok_stride, int t, float* logits_out, float* last_logits, hipStream_t s, const ScoreOut* score = nullptr) {
         if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (t < 1 || t > Tmax) return fail(TXO_E_INVALID, "prefill length outside the decoder's positional table");
-        if (V % 8) return fail(TXO_E_INVALID, "prefill needs a vocabulary size that is a multiple of 8");
+        // (only the logits GEMM's 8-wide store epilogue needs it: the scoring tail takes any vocabulary)
+        if (logits_out && V % 8) return fail(TXO_E_INVALID, "prefill needs a vocabulary size that is a multiple of 8");
         const size_t cap = (size_t)Bmax * Nmax;               // rows of the encoder workspace
         if ((size_t)t > cap) return fail(TXO_E_INVALID, "prefill: one prefix does not fit the engine's workspace (max_batch * max_tokens rows)");
         const int B = sB, N = sN, heads = cfg.dec_heads;
@@ -1381,6 +1414,15 @@ struct Engine : EngineBase {
             if (logits_out) {                                 // decoder.py:57-60 over every position
                 launch_ln<2, T>(s, ey, nullptr, ez, decn_g, decn_b, M);
                 gemm_plain(s, ez, wlog, M, V, D, EpiStore<float>{logits_out + (size_t)b0 * t * V, V, blog});
+            }
+            if (score && (score->logp || score->top1 || score->top1_logp)) {   // decoder.py:141-145 without the logits: score.h
+                launch_ln<2, T>(s, ey, nullptr, ez, decn_g, decn_b, M);
+                const int nw = score_waves<T>(D);
+                const size_t o = (size_t)b0 * t;
+                hipLaunchKernelGGL((score_rows_kernel<T>), dim3((M + nw * SC_ROWS - 1) / (nw * SC_ROWS)), dim3(64 * nw),
+                                   (size_t)nw * SC_ROWS * D * sizeof(T), s, ez, wlog, blog, tokens + (size_t)b0 * tok_stride, tok_stride, t, M, D, V,
+                                   score->logp ? score->logp + o : nullptr, score->top1 ? score->top1 + o : nullptr,
+                                   score->top1_logp ? score->top1_logp + o : nullptr);
             }
             if (last_logits) {                                // the last position only: the step path's final-LN + logits launch on gathered rows
                 hipLaunchKernelGGL(gather_last_rows_kernel, dim3((nb * D + 255) / 256), dim3(256), 0, s, ey, dy + (size_t)b0 * D, nb, t, D);
@@ -1910,6 +1952,19 @@ int txo_decode_step(txo_engine* e, const int64_t* tok_in, int32_t t, float* logi
 int txo_decode_prefill(txo_engine* e, const int64_t* tokens, int32_t t, float* logits_out, void* stream) {
     if (!e || !tokens) return fail(TXO_E_INVALID, "null argument");
     return e->impl->decode_prefill(tokens, t, logits_out, (hipStream_t)stream);
+}
+
+int txo_decode_score(txo_engine* e, const int64_t* tokens, int32_t L, float* logp_out, int64_t* top1_out, float* top1_logp_out, void* stream) {
+    if (!e || !tokens) return fail(TXO_E_INVALID, "null argument");
+    if (L < 2 || L > e->impl->cfg.max_len + 1) return fail(TXO_E_INVALID, "score: L must be in [2, max_len + 1]");
+    return e->impl->decode_score(tokens, L, logp_out, top1_out, top1_logp_out, (hipStream_t)stream);
+}
+
+int txo_score(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, const int64_t* tokens, const uint8_t* mask, int32_t L,
+              float* logp_out, int64_t* top1_out, float* top1_logp_out, void* stream) {
+    if (!e || !img || !tokens) return fail(TXO_E_INVALID, "null argument");
+    if (L < 2 || L > e->impl->cfg.max_len + 1) return fail(TXO_E_INVALID, "score: L must be in [2, max_len + 1]");
+    return e->impl->score(img, B, C, H, W, tokens, mask, L, logp_out, top1_out, top1_logp_out, (hipStream_t)stream);
 }
 
 int txo_decode_set_key_mask(txo_engine* e, const uint8_t* mask, int32_t cols, void* stream) {

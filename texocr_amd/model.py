@@ -32,7 +32,7 @@ import ctypes as C
 import math
 import os
 import re
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -161,6 +161,10 @@ class HipEngine:
         """All positions of a prefix in one pass (txo_decode_prefill); the K/V cache then holds rows 0..t-1."""
         logits = torch.ops.texocr.decode_prefill(tokens, self.id, bool(want_logits))
         return logits if want_logits else None
+
+    def decode_score(self, tokens: torch.Tensor):
+        """Teacher-forced scores of the current session (txo_decode_score): tokens (B, L) -> (logp, top1, top1_logp), each (B, L-1)."""
+        return torch.ops.texocr.decode_score(tokens, self.id)
 
     def decode_step(self, t: int, tok_in: Optional[torch.Tensor] = None, want_logits: bool = True):
         logits, nxt = torch.ops.texocr.decode_step(tok_in, self.id, int(t), int(self._B), bool(want_logits))
@@ -301,6 +305,32 @@ def _check_token_ids(tokens: torch.Tensor, vocab: int) -> None:
         raise IndexError(f"token id outside the vocabulary [0, {vocab})")
 
 
+class Score(NamedTuple):
+    """What AutoRegressiveDecoder.score / OCRModel.score return (position p of row b scores the target trg[b, p + 1]):
+    logp (B, L-1) log-probability of the target; top1 (B, L-1) arg-max of the logits; top1_logp (B, L-1) its log-probability;
+    valid (B, L-1) bool, both the fed token and its target are not padding; nll (B,) -sum of logp over valid; loss (0-dim) sum of
+    nll / number of valid positions; token_acc (0-dim) share of valid positions whose top1 is the target.  Values of logp / top1 /
+    top1_logp outside `valid` are unspecified."""
+    logp: torch.Tensor
+    top1: torch.Tensor
+    top1_logp: torch.Tensor
+    valid: torch.Tensor
+    nll: torch.Tensor
+    loss: torch.Tensor
+    token_acc: torch.Tensor
+
+
+def score_summary(logp: torch.Tensor, top1: torch.Tensor, top1_logp: torch.Tensor, trg: torch.Tensor, mask: torch.Tensor) -> Score:
+    """The arithmetic on top of the engine's three arrays (plain torch, any device): trg (B, L) tokens, mask (B, L) bool (False =
+    padding).  Sums run in float64 and come back as float32; with no valid position loss and token_acc are nan."""
+    mask = mask.to(device=logp.device, dtype=torch.bool)
+    valid = mask[:, :-1] & mask[:, 1:]
+    n = valid.sum()
+    nll64 = -(torch.where(valid, logp, torch.zeros_like(logp)).double().sum(dim=1))
+    hit = (top1 == trg[:, 1:].to(top1.device)) & valid
+    return Score(logp, top1, top1_logp, valid, nll64.float(), (nll64.sum() / n).float(), (hit.sum().double() / n).float())
+
+
 class Transformer(nn.Module):
     """model.decoder.net: (B,t) int64 tokens -> (B,t,V) logits over the whole prefix (decoder.py:41-67): ONE causal
     multi-position pass (txo_decode_prefill), which also leaves the K/V cache filled for the positions given."""
@@ -365,6 +395,36 @@ class AutoRegressiveDecoder(nn.Module):
     def forward(self, *a, **k):
         raise NotImplementedError("AutoRegressiveDecoder.forward is the training loss (decoder.py:124-145); this engine "
                                   "implements the generate() inference path only")
+
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None) -> Score:
+        """The quantity forward() trains on, for inference (decoder.py:124-145 without autograd): x (B, L) int64 target sequences
+        (bos first), x[:, :-1] is fed in one causal pass and x[:, 1:] are the targets.  mask (B, L) bool, False = padding (None: no
+        padding).  The logits are never materialised (csrc/score.h).  Unlike the reference's loss, `loss` averages over the valid
+        positions only (F.cross_entropy there has no ignore_index); without padding the two are the same number."""
+        if enc is None:
+            raise ValueError("Must provide enc (cross-attending decoder)")       # attention.py:232-233
+        if x.ndim != 2 or x.dtype != torch.int64 or not x.is_cuda:
+            raise ValueError("x must be an int64 GPU tensor of shape (B, L)")
+        if x.shape[1] < 2:
+            raise ValueError("x needs at least two columns (one fed token and its target)")
+        if x.shape[1] - 1 > self.max_len:
+            raise ValueError("sequence longer than decoder.max_len + 1")
+        if mask is not None and tuple(mask.shape) != tuple(x.shape):
+            raise ValueError("mask must have the shape of x")
+        eng = self._engine
+        _check_token_ids(x, eng.dims.vocab)
+        m = torch.ones_like(x, dtype=torch.bool) if mask is None else mask.to(device=x.device, dtype=torch.bool)
+        eng.decode_begin(enc)
+        padded = not bool(m.all())
+        if padded:
+            eng.set_key_mask(m[:, :-1])
+        try:
+            logp, top1, top1_logp = eng.decode_score(x)
+        finally:
+            if padded:
+                eng.set_key_mask(None)
+        return score_summary(logp, top1, top1_logp, x, m)
 
     @torch.no_grad()
     def generate(self, start_tokens: torch.Tensor, eos_tok: Optional[int], max_len: int, temp: float = 1.0,
@@ -567,6 +627,15 @@ class OCRModel(nn.Module):
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
                                      stop=stop, pad=self.trg_pad_idx)
+
+    @torch.no_grad()
+    def score(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:
+        """Teacher-forced scoring of trg (B, L) against the images src -- what forward(src, trg) computes (ocr_model.py:38-44),
+        without autograd and per token: see AutoRegressiveDecoder.score.  mask defaults to trg != trg_pad_idx (make_trg_mask).
+        The confidence of a generate() result: score(src, cat([bos], tokens))."""
+        if mask is None:
+            mask = trg != self.trg_pad_idx
+        return self.decoder.score(trg, mask=mask, enc=self.encoder(src))
 
     def forward(self, *a, **k):
         raise NotImplementedError("OCRModel.forward is the training loss (ocr_model.py:38-44); this engine "

@@ -9,6 +9,7 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::encode            VisionEncoder.forward                     model/encoder.py:128-152
   texocr::decode_begin      the ``enc=`` hand-over of decoder.generate model/decoder.py:56,103 (+ attention.py:125-126 once)
   texocr::decode_step       Transformer.forward, one position         model/decoder.py:41-67
+  texocr::decode_score      AutoRegressiveDecoder.forward, no autograd  model/decoder.py:124-145
   texocr::generate          OCRModel.generate                         model/ocr_model.py:46-66
   texocr::generate_from_enc AutoRegressiveDecoder.generate            model/decoder.py:77-122
   texocr::generate_beam     (build extension, BASELINE config 5)
@@ -185,6 +186,38 @@ def decode_prefill(tokens: torch.Tensor, engine: int, want_logits: bool) -> torc
 def _(tokens, engine, want_logits):
     d = _eng(engine).dims
     return tokens.new_empty((tokens.shape[0] if want_logits else 0, tokens.shape[1], d.vocab), dtype=torch.float32)
+
+
+@custom_op("texocr::decode_score", mutates_args=())
+def decode_score(tokens: torch.Tensor, engine: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Teacher-forced scores of the session opened by decode_begin (txo_decode_score): tokens (B, L) int64, columns 0..L-2 fed in one
+    causal pass, column p+1 the target of position p -> (logp (B, L-1) = log_softmax(logits)[target], top1 (B, L-1) = argmax of the
+    logits, top1_logp (B, L-1)).  No (B, L-1, V) tensor is made on the way; the K/V cache holds rows 0..L-2 afterwards."""
+    e = _eng(engine)
+    B = getattr(e, "_B", None)
+    if B is None:
+        raise RuntimeError("texocr::decode_score needs a session started by texocr::decode_begin")
+    if tokens.ndim != 2 or tokens.dtype != torch.int64 or not tokens.is_cuda or tokens.shape[0] != B:
+        raise ValueError("tokens must be an int64 GPU tensor of shape (B, L) matching the session started by texocr::decode_begin")
+    if tokens.device.index != e.device:
+        raise ValueError(f"tokens live on cuda:{tokens.device.index} but the engine was created on cuda:{e.device}")
+    L = int(tokens.shape[1])
+    if L < 2 or L - 1 > e.dims.max_len:
+        raise ValueError(f"tokens must have 2 <= L <= max_len + 1 = {e.dims.max_len + 1} columns, got {L}")
+    tokens = tokens.contiguous()
+    logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    top1 = torch.empty((B, L - 1), device=tokens.device, dtype=torch.int64)
+    top1_logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_decode_score(e.handle, tokens.data_ptr(), L, logp.data_ptr(), top1.data_ptr(), top1_logp.data_ptr(), _stream()))
+    return logp, top1, top1_logp
+
+
+@decode_score.register_fake
+def _(tokens, engine):
+    B, L = tokens.shape
+    return (tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1), dtype=torch.int64),
+            tokens.new_empty((B, L - 1), dtype=torch.float32))
 
 
 def _gen_outputs(src, e, max_len, want_logits):
