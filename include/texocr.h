@@ -151,6 +151,35 @@ int txo_generate_beam(txo_engine* e, const float* img_dev, int32_t B, int32_t C,
                       int32_t max_len, int32_t eos, int64_t* tokens_out_dev, float* scores_out_dev,
                       int64_t* all_tokens_out_dev, int32_t* n_steps_out, void* stream);
 
+/* ---- Ragged batches (a BUILD EXTENSION: the reference's callables take one (H, W) per batch) ------------------------------------
+ * B images of DIFFERENT sizes in one call.  The container img_dev is float32 [B][C][Hc][Wc]; image b sits in the top-left
+ * H_b x W_b corner of its slot, every side a positive multiple of 16, H_b <= min(Hc, canvas_h), W_b <= min(Wc, canvas_w).  Pixels
+ * outside that corner are NEVER READ (they may hold anything, NaN included).  Image b has n_b = 1 + (H_b/16)(W_b/16) encoder tokens;
+ * the slot stride is Ns = max_b n_b (<= max_tokens).  Everything returned for image b is what the fixed-shape call returns for image b
+ * passed on its own: its n_b encoder rows (position ids grid[:h_b, :w_b] of the canvas grid, encoder.py:136-143), its logits, its
+ * tokens.  Nothing in a padding row or a padding pixel reaches a valid row.  Sizes are HOST arrays (launch geometry depends on them);
+ * the engine copies them into its own device buffer (allocated at creation: no call allocates).
+ * Out of scope, each refused with TXO_E_INVALID and a message naming ragged batches: the hybrid front end; the latent cross-attention
+ * form forced by TXO_LATENT=1; the prefill, score and key-mask calls on a session opened by the ragged begin call; max_len >
+ * cfg.max_len.  Beam search and logits_out have no ragged entry point (the beam call takes one (H, W) and opens its own session).  The
+ * container's width Wc must be a multiple of 4 (rows are read in 16-byte pieces).  The persistent launch is not taken: a ragged
+ * generate runs one launch per stage (TXO_Q_LAST_PERSISTENT reads 0), and its session is closed when it returns.
+ *
+ * Encode: sizes_host int32 [B][2] = (H_b, W_b).  enc_out_dev float [B][Ns][D]: rows n_b..Ns-1 of slot b are written as zeros.
+ * *n_slot_out (HOST, may be NULL) receives Ns.  Asynchronous on `stream`. */
+int txo_encode_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
+                      float* enc_out_dev, int32_t* n_slot_out, void* stream);
+
+/* Open a decode session over a ragged encoder output enc_dev [B][Ns][D]: n_tokens_host int32 [B], 1 <= n_b <= Ns, the rows of slot b
+ * the cross attention may see.  txo_decode_step (its logits included) then works as on a fixed-shape session. */
+int txo_decode_begin_ragged(txo_engine* e, const float* enc_dev, int32_t B, int32_t Ns, const int32_t* n_tokens_host, void* stream);
+
+/* The loop of the fixed-shape generate call over a ragged batch: same eos rules (global break by default, TXO_STOP_ROW as set by
+ * txo_set_stop_mode), same token selection (txo_set_sampling; a draw is keyed by the row of the batch).  tokens_out_dev [B, max_len]
+ * int64, *n_steps_out (HOST) the valid columns; 1 <= max_len <= cfg.max_len.  Synchronises the stream before returning. */
+int txo_generate_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
+                        int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, void* stream);
+
 /* Token selection for the following decode steps / generate calls.  mode 0 (default): greedy argmax.  mode 1:
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits
  * (the reference uses int((1 - 0.9) * vocab) = 99 for vocab 1000), softmax(logits / temp), one multinomial draw,
@@ -199,6 +228,7 @@ int txo_profile_read(txo_engine* e, int32_t kind, double* avg_ms, int64_t* count
 #define TXO_Q_LAST_COMPACTIONS 5   /* live-row compactions of the last txo_generate* (TXO_STOP_ROW on the launch path; 0 otherwise) */
 #define TXO_Q_SAMPLE_VOCAB_MAX 6   /* the largest vocabulary txo_set_sampling accepts on this device: beyond 1024 entries the sampler stages a row
                                     * in LDS (vocab * 4 bytes per workgroup) */
+#define TXO_Q_LAST_RAGGED 7        /* 1 if the last generate decoded a ragged batch (per-image encoder token counts), 0 otherwise */
 int txo_engine_query(txo_engine* e, int32_t what, int64_t* out);
 
 const char* txo_last_error(void);

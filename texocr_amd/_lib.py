@@ -17,7 +17,7 @@ TXO_F32, TXO_BF16 = 0, 1
 TXO_E_INVALID, TXO_E_STATE, TXO_E_HIP = -1, -2, -3
 # txo_engine_query codes (include/texocr.h: TXO_Q_*; tests/test_abi_cpu.py holds the two lists together)
 (Q_LAST_PERSISTENT, Q_PERSIST_FALLBACKS, Q_LAST_ROW_RANGES, Q_LAST_LATENT, Q_RELOAD_KNOBS, Q_LAST_COMPACTIONS,
- Q_SAMPLE_VOCAB_MAX) = 0, 1, 2, 3, 4, 5, 6
+ Q_SAMPLE_VOCAB_MAX, Q_LAST_RAGGED) = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 class TxoConfig(C.Structure):
@@ -43,6 +43,9 @@ SYMBOLS = {
     "txo_generate": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
     "txo_generate_from_enc": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
     "txo_generate_beam": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I, _I64P, _FP, _I64P, C.POINTER(C.c_int32), _P]),
+    "txo_encode_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _FP, C.POINTER(C.c_int32), _P]),
+    "txo_decode_begin_ragged": (C.c_int, [_P, _FP, _I, _I, C.POINTER(C.c_int32), _P]),
+    "txo_generate_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _P]),
     "txo_set_sampling": (C.c_int, [_P, _I, _I, C.c_float, C.c_uint64]),
     "txo_set_stop_mode": (C.c_int, [_P, _I]),
     "txo_profile_enable": (C.c_int, [_P, _I]),

@@ -56,6 +56,11 @@ template <typename T> struct DecAttnArgs {
     // padding mask over the decoded positions (reference attention.py:130-155: energy filled with -FLT_MAX where the key is masked):
     // kmask[row * kmask_stride + position] == 0 -> that position is never attended by a later query (KMASK instantiations only)
     const unsigned char* kmask; int kmask_stride;
+    // ragged batches (RAGGED instantiations of the cross attention; texocr.h: txo_decode_begin_ragged): the panels keep ONE slot stride
+    // lmax = Ns and row r attends lens[r / kv_div] <= lmax keys.  The pass count follows the row's own length and every load behind it
+    // clamps to the row's last key (one cached line, no HBM bytes), its score masked: a short image costs fewer bytes and never sees a
+    // padding row.  The array is indexed by SLOT: compact_scan_kernel permutes it with the rows (step.h).
+    const int* lens;
 };
 
 template <typename T, int PER16>
@@ -122,7 +127,7 @@ template <bool BEAM> struct DecAttnLds {
 // counter (tid < 64 of the workgroup's first group: a poll's wait would also wait for that wave's own panel) requests it
 // BEFORE the wait.  valid = false: same barriers, clamped addresses, no stores.
 // pf(): called once this tile's own loads have been issued (persistent kernel: requests the next stage's weights there).
-template <typename T, int MODE, int APRO, int NL, int WB, bool NARROW, bool BEAM, bool COH, class Wait, class Pf = NoPf, bool KMASK = false>
+template <typename T, int MODE, int APRO, int NL, int WB, bool NARROW, bool BEAM, bool COH, class Wait, class Pf = NoPf, bool KMASK = false, bool RAGGED = false>
 __device__ __forceinline__ void dec_attn_tile(const DecAttnArgs<T>& a, int bh, int tid, DecAttnLds<BEAM>& L_, bool valid,
                                               bool poll_wave, Wait&& wait_prev, Pf&& pf = NoPf{}) {
     constexpr int PER16 = Elem<T>::PER16;
@@ -175,7 +180,8 @@ __device__ __forceinline__ void dec_attn_tile(const DecAttnArgs<T>& a, int bh, i
     int t = 0;
     if constexpr (MODE == ATT_SELF || APRO == APRO_EMBED) t = (COH || a.t_host >= 0) ? a.t_host : *a.t_ptr;
     // cached keys: fused self handles the new key t apart; plain self finds it in the cache already
-    const int L = MODE == ATT_CROSS ? a.len : (FUSED ? t : t + 1);
+    int L = MODE == ATT_CROSS ? a.len : (FUSED ? t : t + 1);
+    if constexpr (RAGGED && MODE == ATT_CROSS) L = min(max(a.lens[kvimg], 1), a.lmax);
     // valid = false (persistent kernel: a group without a tile keeps the workgroup's barriers): every panel address clamps
     // to row 0, one cache line per wave instead of the whole panel
     const int Lm1 = valid ? max(L - 1, 0) : 0;
@@ -476,6 +482,12 @@ template <typename T, int MODE, int APRO, int NL, int WB, bool NARROW, bool BEAM
 __global__ __launch_bounds__(256, 2) void dec_attn_kernel(DecAttnArgs<T> a) {
     __shared__ DecAttnLds<BEAM> lds;
     dec_attn_tile<T, MODE, APRO, NL, WB, NARROW, BEAM, false, NoWait, NoPf, KMASK>(a, blockIdx.x, threadIdx.x, lds, true, false, NoWait{});
+}
+// cross attention of a ragged session: row r attends a.lens[r / kv_div] keys of its panel
+template <typename T, int NL, bool NARROW>
+__global__ __launch_bounds__(256, 2) void dec_attn_ragged_kernel(DecAttnArgs<T> a) {
+    __shared__ DecAttnLds<false> lds;
+    dec_attn_tile<T, ATT_CROSS, APRO_LN2, NL, 1, NARROW, false, false, NoWait, NoPf, false, true>(a, blockIdx.x, threadIdx.x, lds, true, false, NoWait{});
 }
 
 }  // namespace txo

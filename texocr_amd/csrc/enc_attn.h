@@ -41,16 +41,42 @@ __device__ inline bool ea_block(int nq, int nbh, int& bh, int& qb, int rev = 0) 
 }
 inline dim3 ea_grid(int nq, int nbh) { return dim3(((nbh + 7) / 8) * 8 * nq); }
 
+// Ragged batches (RAGGED instantiations; texocr.h: txo_encode_ragged): the panels keep ONE slot stride N = Ns, and image b = bh / heads
+// has lens[b] <= N keys and queries.  The per-image count takes N's place in the tail mask, the clamps and the stage count -- key stages
+// wholly behind it are never run, a query block wholly behind it exits -- and the output rows lens[b]..N-1 of the slot are stored as
+// zeros (the row-wise kernels behind run over all B * Ns rows: padding rows stay finite, nothing of them reaches a valid row).
+// RAGGED = false is the code of the fixed-shape kernels, unchanged (n is N; lens is not read).
+// the wave's 32 output rows from q0w on, those below N, as zeros
 template <typename TO>
+__device__ inline void ea_store_zero_rows(TO* __restrict__ out, int b, int head, int heads, int N, int q0w, int lane) {
+    const int inner = heads * DH;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        const int idx = it * 64 + lane, qq = idx >> 4, piece = idx & 15;
+        const int qrow = q0w + qq;
+        if (qrow < N) {
+            TO* dst = out + ((size_t)(b * N + qrow)) * inner + head * DH + piece * 4;
+            if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(dst) = make_float4(0.f, 0.f, 0.f, 0.f);
+            else *reinterpret_cast<uint2*>(dst) = make_uint2(0u, 0u);
+        }
+    }
+}
+
+template <typename TO, bool RAGGED = false>
 __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__ Q, const float* __restrict__ Kg,
                                                        const float* __restrict__ Vg, TO* __restrict__ out, int N,
-                                                       int heads, int nbh) {
+                                                       int heads, int nbh, const int* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][EA_KSTAGE * 256];   // [buf][K|V]
     int bh, qblk;
     if (!ea_block((N + EA_QBLK - 1) / EA_QBLK, nbh, bh, qblk)) return;
     const int b = bh / heads, head = bh - b * heads;
     const int q0 = qblk * EA_QBLK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int n = N;                                               // keys = queries of this image
+    if constexpr (RAGGED) {
+        n = min(max(lens[b], 1), N);
+        if (q0 >= n) { ea_store_zero_rows<TO>(out, b, head, heads, N, q0 + wave * 32, lane); return; }
+    }
     const int lc = lane & 15, lg = lane >> 4;
     const float* Qb = Q + (size_t)bh * N * DH;
     const float* Kb = Kg + (size_t)bh * N * DH;
@@ -60,7 +86,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__
     u32x4 qf[2][4];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
-        const int qrow = min(q0 + wave * 32 + qt * 16 + lc, N - 1);
+        const int qrow = min(q0 + wave * 32 + qt * 16 + lc, n - 1);
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) {
             float4 t = *reinterpret_cast<const float4*>(Qb + (size_t)qrow * DH + kc * 16 + lg * 4);
@@ -82,7 +108,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + 256 * i, row = idx >> 4, piece = idx & 15;
-            const int key = min(s * EA_KSTAGE + row, N - 1);
+            const int key = min(s * EA_KSTAGE + row, n - 1);
             rk[i] = ld16(Kb + (size_t)key * DH + piece * 4);
             rv[i] = ld16(Vb + (size_t)key * DH + piece * 4);
         }
@@ -96,7 +122,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__
         }
     };
 
-    const int nstage = (N + EA_KSTAGE - 1) / EA_KSTAGE;
+    const int nstage = (n + EA_KSTAGE - 1) / EA_KSTAGE;
     load_stage(0);
     store_stage(0);
     __syncthreads();
@@ -121,14 +147,14 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__
                 sc[qt][kt] = a;
             }
         }
-        // keys past N only exist in the last stage
+        // keys past n only exist in the last stage
         const int kbase = s * EA_KSTAGE;
-        if (kbase + EA_KSTAGE > N) {
+        if (kbase + EA_KSTAGE > n) {
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (kbase + kt * 16 + lg * 4 + r >= N) { sc[0][kt][r] = -1e30f; sc[1][kt][r] = -1e30f; }
+                    if (kbase + kt * 16 + lg * 4 + r >= n) { sc[0][kt][r] = -1e30f; sc[1][kt][r] = -1e30f; }
         }
         // ---- online softmax (per query = per lane column; keys spread over regs and lane groups) ----
 #pragma unroll
@@ -189,7 +215,8 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__
         const int qrow = q0 + wave * 32 + qq;
         if (qrow < N) {
             const int c0 = (piece * 4) ^ ((qq & 7) << 2);
-            const float4 v4 = *reinterpret_cast<const float4*>(&tile[qq * 64 + c0]);
+            float4 v4 = *reinterpret_cast<const float4*>(&tile[qq * 64 + c0]);
+            if constexpr (RAGGED) { if (qrow >= n) v4 = make_float4(0.f, 0.f, 0.f, 0.f); }
             TO* dst = out + ((size_t)(b * N + qrow)) * inner + head * DH + piece * 4;
             if constexpr (sizeof(TO) == 4) {
                 *reinterpret_cast<float4*>(dst) = v4;
@@ -237,9 +264,10 @@ constexpr float EAB_GROW = 6.0f;      // base-2 units: P stays below 64 between 
 //     values that multiply V).
 // Per 64-key stage and wave: 36 MFMAs, 32 v_exp_f32, 16 packed conversions, ~16 three-input maxima.
 // q,k,v: bf16 head-major [B*heads][N][64].  Bound: MFMA bf16 / softmax VALU, about equal.
-template <typename TO>
+template <typename TO, bool RAGGED = false>
 __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kg,
-                                                               const bf16* __restrict__ Vg, TO* __restrict__ out, int N, int heads, int nbh, int rev) {
+                                                               const bf16* __restrict__ Vg, TO* __restrict__ out, int N, int heads, int nbh, int rev,
+                                                               const int* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][EA_KSTAGE * 128];   // [buf][K | V], 128-byte rows
     static_assert(sizeof(lds) >= 4 * 32 * 64 * 4, "epilogue tile must fit");
     typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -249,6 +277,11 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
     const int q0 = qblk * EA_QBLK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lc = lane & 15, lg = lane >> 4;
+    int n = N;                                               // keys = queries of this image (ragged batches: see enc_attn_kernel)
+    if constexpr (RAGGED) {
+        n = min(max(lens[b], 1), N);
+        if (q0 >= n) { ea_store_zero_rows<TO>(out, b, head, heads, N, q0 + wave * 32, lane); return; }
+    }
     const bf16* Qb = Q + (size_t)bh * N * DH;
     const bf16* Kb = Kg + (size_t)bh * N * DH;
     const bf16* Vb = Vg + (size_t)bh * N * DH;
@@ -257,7 +290,7 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
     u32x4 qf[2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
-        const int qrow = min(q0 + wave * 32 + qt * 16 + lc, N - 1);
+        const int qrow = min(q0 + wave * 32 + qt * 16 + lc, n - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const u32x4 raw = ld16_once(Qb + (size_t)qrow * DH + ks * 32 + lg * 8);
@@ -283,7 +316,7 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int idx = tid + 256 * i, row = idx >> 3, piece = idx & 7;
-            const int key = min(s * EA_KSTAGE + row, N - 1);
+            const int key = min(s * EA_KSTAGE + row, n - 1);
             rk[i] = ld16_once(Kb + (size_t)key * DH + piece * 8);
             rv[i] = ld16_once(Vb + (size_t)key * DH + piece * 8);
         }
@@ -304,11 +337,11 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
     for (int dt = 0; dt < 4; ++dt) vcol[dt] = ((2 * dt) ^ vx) << 4;
     const u32x4 ones = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
 
-    const int nstage = (N + EA_KSTAGE - 1) / EA_KSTAGE;
+    const int nstage = (n + EA_KSTAGE - 1) / EA_KSTAGE;
     // r05: the ragged ends.  N = 589 is 9 key stages of 64 + one of 13, and 4 query blocks of 128 + one of 77: the last stage runs only the
     // 16-key tiles / 32-key k-steps that hold a key (one of four / one of two), and a wave whose 32 queries all lie beyond N only stages
     // K / V and keeps the barriers.  Same arithmetic for every key and query that exists (a skipped tile contributed exact zeros).
-    const bool active = __builtin_amdgcn_readfirstlane(q0 + wave * 32) < N;
+    const bool active = __builtin_amdgcn_readfirstlane(q0 + wave * 32) < n;
     load_stage(0);
     store_stage(0);
     __syncthreads();
@@ -320,7 +353,7 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
         const unsigned char* Ks = lds[buf][0];
         const unsigned char* Vs = lds[buf][1];
         const int kbase = s * EA_KSTAGE;
-        const int nkt = LAST ? min(4, (N - kbase + 15) >> 4) : 4;      // 16-key tiles of this stage that hold a key (block-uniform)
+        const int nkt = LAST ? min(4, (n - kbase + 15) >> 4) : 4;      // 16-key tiles of this stage that hold a key (block-uniform)
 
         // ---- S^T - m for 64 keys x 32 queries: 16 MFMA, the running maximum as the initial accumulator ----
         f32x4 sc[2][4];
@@ -344,13 +377,13 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
                 sc[qt][kt] = a;
             }
         }
-        if (LAST && kbase + EA_KSTAGE > N) {
+        if (LAST && kbase + EA_KSTAGE > n) {
             asm volatile("; ragged last stage" ::: "memory");    // keep this a branch: if-converted it costs ~60 VALU ops in EVERY stage
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (kbase + kt * 16 + lg * 4 + r >= N) { sc[0][kt][r] = -1e30f; sc[1][kt][r] = -1e30f; }
+                    if (kbase + kt * 16 + lg * 4 + r >= n) { sc[0][kt][r] = -1e30f; sc[1][kt][r] = -1e30f; }
         }
         // ---- stage maximum relative to the running one; rescale only when some query's maximum grows ----
         float rel[2];
@@ -422,7 +455,10 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
     };
     for (int s = 0; s + 1 < nstage; ++s) stage(s, std::false_type{});
     stage(nstage - 1, std::true_type{});
-    if (!active) return;                                       // (behind the last barrier)
+    if (!active) {                                             // (behind the last barrier)
+        if constexpr (RAGGED) ea_store_zero_rows<TO>(out, b, head, heads, N, q0 + wave * 32, lane);
+        return;
+    }
 
     // ---- normalise, transpose through LDS (wave-private 32 x 64 f32 tile), store whole rows ----
     float* tile = reinterpret_cast<float*>(&lds[0][0][0]) + wave * (32 * 64);
@@ -443,7 +479,8 @@ __global__ __launch_bounds__(256) void enc_attn_bf16_v2_kernel(const bf16* __res
         const int qrow = q0 + wave * 32 + qq;
         if (qrow < N) {
             const int c0 = (piece * 4) ^ ((qq & 7) << 2);
-            const float4 v4 = *reinterpret_cast<const float4*>(&tile[qq * 64 + c0]);
+            float4 v4 = *reinterpret_cast<const float4*>(&tile[qq * 64 + c0]);
+            if constexpr (RAGGED) { if (qrow >= n) v4 = make_float4(0.f, 0.f, 0.f, 0.f); }
             TO* dst = out + ((size_t)(b * N + qrow)) * inner + head * DH + piece * 4;
             if constexpr (sizeof(TO) == 4) {
                 *reinterpret_cast<float4*>(dst) = v4;

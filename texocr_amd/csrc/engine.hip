@@ -67,6 +67,10 @@ struct EngineBase {
     virtual int finalize() = 0;
     virtual int encode(const float* img, int B, int C, int H, int W, float* enc_out, hipStream_t s) = 0;
     virtual int decode_begin(const float* enc, int B, int N, int eos, hipStream_t s) = 0;
+    virtual int encode_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, float* enc_out, int32_t* n_slot, hipStream_t s) = 0;
+    virtual int decode_begin_ragged(const float* enc, int B, int Ns, const int32_t* n_tokens, int eos, hipStream_t s) = 0;
+    virtual int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
+                                int* n_steps, hipStream_t s) = 0;
     virtual int decode_step(const int64_t* tok_in, int t, float* logits_out, int64_t* tok_out, hipStream_t s) = 0;
     virtual int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) = 0;
     virtual int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
@@ -181,6 +185,15 @@ struct Engine : EngineBase {
     // per-row stop (step.h): batch row held by every slot of a row range, scratch of the compaction, {live rows, moves} per range
     int *row_map = nullptr, *row_map2 = nullptr, *cmoves = nullptr, *cinfo = nullptr; int64_t* cur_tok2 = nullptr;
     int last_compactions = 0;         // compactions of the last generate (TXO_Q_LAST_COMPACTIONS)
+    // ragged batches (texocr.h: txo_encode_ragged ...): per-image sizes in engine-owned buffers.  rag_hw [Bmax][2] patch rows / columns and
+    // rag_ntok [Bmax] encoder tokens of the last ragged encode; slens [Bmax] cross-attention keys per decode SLOT of a ragged session
+    // (permuted with the rows by compact_lane), slens2 its scratch.  rag_host: pinned staging of the caller's host arrays, rag_ev: its last copy.
+    int *rag_hw = nullptr, *rag_ntok = nullptr, *slens = nullptr, *slens2 = nullptr;
+    int32_t* rag_host = nullptr; hipEvent_t rag_ev = nullptr; bool rag_ev_pending = false;
+    std::vector<int32_t> rag_stage;   // host scratch [3 Bmax] (sized at creation)
+    bool rag = false;                 // the open session is ragged
+    const int32_t* gen_sizes = nullptr; int gen_ns = 0;   // set by generate_ragged around generate()
+    bool last_ragged = false;         // TXO_Q_LAST_RAGGED
     int step_host_t = -1;             // position of the step being enqueued when the host knows it (see enqueue_step)
     Stamps stamps;                    // TXO_STAMPS / TXO_PSTAMPS diagnostics (stamps.h)
     int64_t* tok_buf = nullptr;            // [Bmax][Tmax] generated ids (engine-owned so graphs do not bake user pointers)
@@ -207,6 +220,8 @@ struct Engine : EngineBase {
 
     ~Engine() override {
         if (pctl_host) (void)hipHostFree(pctl_host);
+        if (rag_host) (void)hipHostFree(rag_host);
+        if (rag_ev) (void)hipEventDestroy(rag_ev);
         for (void* p : allocs) (void)hipFree(p);
     }
 
@@ -544,6 +559,9 @@ struct Engine : EngineBase {
         // at t = 0 multiplies such a row by p = 0, which must not meet NaN/Inf bit patterns of recycled memory)
         HIP_TRY(hipMemset(skv, 0, sizeof(T) * (size_t)cfg.dec_layers * 2 * Bmax * Id * Tmax));
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pctl_host), sizeof(PersistCtl), hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&rag_host), sizeof(int32_t) * 3 * (size_t)Bmax, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&rag_ev, hipEventDisableTiming));
+        rag_stage.assign((size_t)3 * Bmax, 0);
         return lanes.init(Tmax);
     }
     int init_buffers() {
@@ -625,6 +643,10 @@ struct Engine : EngineBase {
         if (int r = dalloc(&row_map, (size_t)Bmax)) return r;
         if (int r = dalloc(&row_map2, (size_t)Bmax)) return r;
         if (int r = dalloc(&cur_tok2, (size_t)Bmax)) return r;
+        if (int r = dalloc(&rag_hw, (size_t)2 * Bmax)) return r;
+        if (int r = dalloc(&rag_ntok, (size_t)Bmax)) return r;
+        if (int r = dalloc(&slens, (size_t)Bmax)) return r;
+        if (int r = dalloc(&slens2, (size_t)Bmax)) return r;
         if (int r = dalloc(&cmoves, (size_t)2 * Bmax)) return r;
         if (int r = dalloc(&cinfo, (size_t)2 * MAXL)) return r;
         if (int r = dalloc(&kmask, (size_t)Bmax * Tmax)) return r;
@@ -777,12 +799,17 @@ struct Engine : EngineBase {
     }
     // images per encoder chunk: TXO_ENC_CHUNK=n forces n (0 = whole batch); default the whole batch (profiles/r06_encoder_chunk_sweep.txt)
     int enc_chunk_images(int B) const { return knobs.enc_chunk_env > 0 ? std::min(B, knobs.enc_chunk_env) : B; }
-    int encode_images(const float* img, int B, int C, int H, int W, float* enc_out, hipStream_t s) {
-        const int h = H / 16, w = W / 16, hw = h * w, N = hw + 1;
+    // ragNs > 0: a ragged batch (H x W is then the CONTAINER's size, ragNs the slot stride; the sizes of images b0.. are in rag_hw / rag_ntok)
+    int encode_images(const float* img, int B, int C, int H, int W, float* enc_out, hipStream_t s, int ragNs = 0, int b0 = 0) {
+        const int h = H / 16, w = W / 16, hw = ragNs > 0 ? ragNs - 1 : h * w, N = hw + 1;
         const int M = B * N, G = cfg.canvas_w / 16;
+        const int* rhw = rag_hw + 2 * b0; const int* rtok = rag_ntok + b0;
 
         hipLaunchKernelGGL(cls_rows_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, ex, cls, pos, B, N, D);
-        if (!hybrid) {
+        if (ragNs > 0) {
+            launch_gemm_big<T>(s, LoadPatchRagged<T>{img, rhw, C, H, W, hw}, patch_w, B * hw, D, C * 256,
+                               EpiPatchRagged{ex, patch_b, pos, rhw, D, hw, G});
+        } else if (!hybrid) {
             launch_gemm_big<T>(s, LoadPatch<T>{img, C, H, W, hw, w}, patch_w, B * hw, D, C * 256,
                                EpiPatch{ex, patch_b, pos, D, hw, w, G});
         } else {
@@ -817,13 +844,22 @@ struct Engine : EngineBase {
             if constexpr (sizeof(T) == 4) {
                 gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D,
                                    EpiHeads<float>{eqkv, hs, Ie, cfg.enc_heads, N});
-                hipLaunchKernelGGL((enc_attn_kernel<T>), agrid, dim3(256), 0, s, eqkv, eqkv + hs, eqkv + 2 * hs, eao, N,
-                                   cfg.enc_heads, nbh);
+                if (ragNs > 0) {
+                    hipLaunchKernelGGL((enc_attn_kernel<T, true>), agrid, dim3(256), 0, s, eqkv, eqkv + hs, eqkv + 2 * hs, eao, N, cfg.enc_heads, nbh, rtok);
+                } else {
+                    hipLaunchKernelGGL((enc_attn_kernel<T>), agrid, dim3(256), 0, s, eqkv, eqkv + hs, eqkv + 2 * hs, eao, N, cfg.enc_heads, nbh,
+                                       (const int*)nullptr);
+                }
             } else {                                              // perf mode: bf16 q/k/v, bf16 MFMA attention
                 bf16* qb = reinterpret_cast<bf16*>(eqkv);
                 gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D,
                                    EpiHeads<bf16>{qb, hs, Ie, cfg.enc_heads, N}, dir());
-                hipLaunchKernelGGL((enc_attn_bf16_v2_kernel<T>), agrid, dim3(256), 0, s, qb, qb + hs, qb + 2 * hs, eao, N, cfg.enc_heads, nbh, dir());
+                if (ragNs > 0) {
+                    hipLaunchKernelGGL((enc_attn_bf16_v2_kernel<T, true>), agrid, dim3(256), 0, s, qb, qb + hs, qb + 2 * hs, eao, N, cfg.enc_heads, nbh, dir(), rtok);
+                } else {
+                    hipLaunchKernelGGL((enc_attn_bf16_v2_kernel<T>), agrid, dim3(256), 0, s, qb, qb + hs, qb + 2 * hs, eao, N, cfg.enc_heads, nbh, dir(),
+                                       (const int*)nullptr);
+                }
             }
             gemm_plain(s, eao, enc_attn[l].wo, M, 2 * D, Ie,
                                EpiGluRes<sizeof(T) == 2>{ey, l == 0 ? res_first : res_x, enc_attn[l].bo}, dir());
@@ -832,7 +868,102 @@ struct Engine : EngineBase {
             gemm_plain(s, ehid, enc_mlp[l].w2, M, D, Fe, EpiBiasRes{ey, res_x, enc_mlp[l].b2}, dir());
         }
         launch_ln<2, float>(s, ey, nullptr, enc_out, encn_g, encn_b, M, dir());
+        if (ragNs > 0) {                                      // the padding rows of every slot are returned as zeros
+            const size_t n4 = (size_t)M * (D / 4);
+            hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, enc_out, rtok, B, N, D / 4);
+        }
         return 0;
+    }
+
+    // ---- ragged batches (texocr.h) ------------------------------------------------------------------------------------------------
+    // host array -> engine-owned device buffer through the pinned staging area (its previous copy has left it first); no allocation
+    // (up to two destinations: the first n0 values go to dst0, the rest to dst1)
+    int upload_i32(const int32_t* src, int* dst0, int n0, int* dst1, int n1, hipStream_t s) {
+        if (rag_ev_pending) { HIP_TRY(hipEventSynchronize(rag_ev)); rag_ev_pending = false; }
+        memcpy(rag_host, src, sizeof(int32_t) * (n0 + n1));
+        HIP_TRY(hipMemcpyAsync(dst0, rag_host, sizeof(int32_t) * n0, hipMemcpyHostToDevice, s));
+        if (n1 > 0) HIP_TRY(hipMemcpyAsync(dst1, rag_host + n0, sizeof(int32_t) * n1, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(rag_ev, s));
+        rag_ev_pending = true;
+        return 0;
+    }
+    int ragged_refusals() {
+        if (!ready) return fail(TXO_E_STATE, "weights not finalized");
+        if (hybrid) return fail(TXO_E_INVALID, "ragged batches: the hybrid front end is not supported (GroupNorm statistics and SAME padding are per image extent)");
+        if (latent_ok && knobs.lat_mode == 1)
+            return fail(TXO_E_INVALID, "ragged batches: the latent cross-attention form (TXO_LATENT=1) is not supported; a ragged decode runs in the K/V form");
+        return 0;
+    }
+    // checks the sizes, leaves {h_b, w_b} in rag_hw and n_b in rag_ntok; *ns = the slot stride
+    int ragged_sizes(int B, int C, int Hc, int Wc, const int32_t* sizes, int* ns, hipStream_t s) {
+        if (int r = ragged_refusals()) return r;
+        if (!sizes) return fail(TXO_E_INVALID, "ragged batches: null sizes");
+        if (C != cfg.in_channels) return fail(TXO_E_INVALID, "image channel count does not match in_channels");
+        if (B < 1 || B > Bmax) return fail(TXO_E_INVALID, "ragged batches: batch exceeds engine max_batch");
+        if (Hc <= 0 || Wc <= 0) return fail(TXO_E_INVALID, "ragged batches: the container's height/width must be positive");
+        if (Wc % 4) return fail(TXO_E_INVALID, "ragged batches: the container's width must be a multiple of 4 (rows are read in 16-byte pieces)");
+        int Ns = 0;
+        std::vector<int32_t>& st = rag_stage;
+        for (int b = 0; b < B; ++b) {
+            const int H = sizes[2 * b], W = sizes[2 * b + 1];
+            if (H <= 0 || W <= 0 || H % 16 || W % 16)
+                return fail(TXO_E_INVALID, "ragged batches: image " + std::to_string(b) + " height/width must be positive multiples of 16");
+            if (H > Hc || W > Wc) return fail(TXO_E_INVALID, "ragged batches: image " + std::to_string(b) + " is larger than the container");
+            if (H > cfg.canvas_h || W > cfg.canvas_w)
+                return fail(TXO_E_INVALID, "ragged batches: image " + std::to_string(b) + " is larger than the position-embedding canvas");
+            st[2 * b] = H / 16; st[2 * b + 1] = W / 16; st[2 * Bmax + b] = 1 + (H / 16) * (W / 16);
+            Ns = std::max(Ns, st[2 * Bmax + b]);
+        }
+        if (Ns > Nmax) return fail(TXO_E_INVALID, "ragged batches: token count of the largest image exceeds engine max_tokens");
+        // one staged copy: [2 B] patch grids followed by [B] token counts
+        for (int b = 0; b < B; ++b) st[2 * B + b] = st[2 * Bmax + b];
+        if (int r = upload_i32(st.data(), rag_hw, 2 * B, rag_ntok, B, s)) return r;
+        *ns = Ns;
+        return 0;
+    }
+    int encode_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, float* enc_out, int32_t* n_slot, hipStream_t s) override {
+        int Ns = 0;
+        if (int r = ragged_sizes(B, C, Hc, Wc, sizes, &Ns, s)) return r;
+        if (n_slot) *n_slot = Ns;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (prof) { e0 = pool.next(); e1 = pool.next(); (void)hipEventRecord(e0, s); }
+        const int bc = enc_chunk_images(B);
+        for (int b0 = 0; b0 < B; b0 += bc) {
+            const int nb = std::min(bc, B - b0);
+            if (int r = encode_images(img + (size_t)b0 * C * Hc * Wc, nb, C, Hc, Wc, enc_out + (size_t)b0 * Ns * D, s, Ns, b0)) return r;
+        }
+        if (prof) { (void)hipEventRecord(e1, s); ev_enc.push_back({e0, e1}); }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    int decode_begin_ragged(const float* enc, int B, int Ns, const int32_t* n_tokens, int eos, hipStream_t s) override {
+        if (int r = ragged_refusals()) return r;
+        if (!n_tokens) return fail(TXO_E_INVALID, "ragged batches: null n_tokens");
+        if (B < 1 || B > Bmax) return fail(TXO_E_INVALID, "ragged batches: batch exceeds engine max_batch");
+        if (Ns < 1 || Ns > Nmax) return fail(TXO_E_INVALID, "ragged batches: slot stride exceeds engine max_tokens");
+        for (int b = 0; b < B; ++b)
+            if (n_tokens[b] < 1 || n_tokens[b] > Ns)
+                return fail(TXO_E_INVALID, "ragged batches: n_tokens[" + std::to_string(b) + "] must be in [1, Ns]");
+        if (int r = upload_i32(n_tokens, slens, B, nullptr, 0, s)) return r;
+        if (int r = begin_session(enc, B, Ns, eos, s, true)) return r;
+        rag = true;
+        return 0;
+    }
+    int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
+                        int* n_steps, hipStream_t s) override {
+        if (int r = ragged_refusals()) return r;
+        if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
+        if (max_len > Tmax)
+            return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length (the sliding window runs through the prefill, which has no ragged form)");
+        int Ns = 0;
+        if (int r = ragged_sizes(B, C, Hc, Wc, sizes, &Ns, s)) return r;
+        gen_sizes = sizes; gen_ns = Ns;
+        const int rc = generate(img, nullptr, B, C, Hc, Wc, 0, max_len, eos, tokens_out, n_steps, nullptr, s);
+        gen_sizes = nullptr;
+        // the session is closed: nothing ragged outlives the call (a fixed-shape call behind it, txo_score included, starts from scratch;
+        // stepping on a ragged batch goes through txo_decode_begin_ragged)
+        session = false; rag = false;
+        return rc;
     }
 
     // project_kv = false: generate() decides the form of the cross attention once it knows its decode path
@@ -848,6 +979,7 @@ struct Engine : EngineBase {
             hipLaunchKernelGGL((cast_rows_kernel<T>), dim3((n4 + 255) / 256), dim3(256), 0, s, enc, enc_t, n4);
         }
         sB = B; sN = N; sImg = B; session = true;
+        rag = false;                                          // (a ragged caller sets it behind this call)
         ckv_valid = false;
         kmask_on = false;
         // a session opened through the C entry point steps with launches: it takes the form generate()'s launches take at this batch size
@@ -1032,7 +1164,16 @@ struct Engine : EngineBase {
         } while (0)
 #define TXO_DA(MODE, APRO, NLV, WBV)                                                                          \
         do { if (narrow) TXO_DA1(MODE, APRO, NLV, WBV, true); else TXO_DA1(MODE, APRO, NLV, WBV, false); } while (0)
-        if (o.cross) TXO_DA(ATT_CROSS, APRO_LN2, DA_NL_CROSS, 1);
+#define TXO_DAR(NARROW)                                                                                             \
+        do {                                                                                                        \
+            if (timed) hipExtLaunchKernelGGL((dec_attn_ragged_kernel<T, DA_NL_CROSS, NARROW>), grid, blk, 0, s, e0, e1, 0, a); \
+            else hipLaunchKernelGGL((dec_attn_ragged_kernel<T, DA_NL_CROSS, NARROW>), grid, blk, 0, s, a);           \
+        } while (0)
+        if (o.cross && rag) {                                     // per-slot key counts (dec_attn.h: RAGGED)
+            a.lens = slens + kr0;
+            if (narrow) TXO_DAR(true); else TXO_DAR(false);
+        }
+        else if (o.cross) TXO_DA(ATT_CROSS, APRO_LN2, DA_NL_CROSS, 1);
         else if (o.apro == APRO_NONE && o.path) {
             if (narrow) hipLaunchKernelGGL((dec_attn_kernel<T, ATT_SELF, APRO_NONE, NLS, 1, true, true>), grid, blk, 0, s, a);
             else hipLaunchKernelGGL((dec_attn_kernel<T, ATT_SELF, APRO_NONE, NLS, 1, false, true>), grid, blk, 0, s, a);
@@ -1044,6 +1185,7 @@ struct Engine : EngineBase {
         else if (o.apro == APRO_NONE) TXO_DA(ATT_SELF, APRO_NONE, NLS, 1);
         else if (o.apro == APRO_EMBED) TXO_DA(ATT_SELF, APRO_EMBED, NLS, WBS);
         else TXO_DA(ATT_SELF, APRO_LN2, NLS, WBS);
+#undef TXO_DAR
 #undef TXO_DA
 #undef TXO_DA1
         if (timed) ev_cross.push_back({e0, e1});
@@ -1278,7 +1420,7 @@ struct Engine : EngineBase {
     // capture lane li's step (tokens into the engine-owned tok_buf) as a graph, or reuse the cached one
     int lane_graph(int li, int eos) {
         const auto& ln = lanes[li];
-        const LaneSet::GraphKey key = {ln.b0, ln.nb, sN, eos, sB, sImg, (int)use_latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode};
+        const LaneSet::GraphKey key = {ln.b0, ln.nb, sN, eos, sB, sImg, (int)use_latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)rag};
         if (lanes.cached(li, key)) return 0;
         hipStream_t cs = lanes.cap_stream;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -1315,6 +1457,7 @@ struct Engine : EngineBase {
     int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) override {
         if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (sImg != sB) return fail(TXO_E_STATE, "key masks are not available inside a beam-search session");
+        if (rag) return fail(TXO_E_INVALID, "txo_decode_set_key_mask: not available on a ragged batch session");
         if (!mask) { kmask_on = false; return 0; }
         if (cols < 1 || cols > Tmax) return fail(TXO_E_INVALID, "mask columns must be in [1, max_length]");
         const int n = sB * Tmax;
@@ -1327,6 +1470,7 @@ struct Engine : EngineBase {
     int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) override {
         if (lanes.n != 1) return fail(TXO_E_STATE, "decode_prefill needs a session started by txo_decode_begin");
         if (sImg != sB) return fail(TXO_E_STATE, "decode_prefill is not available inside a beam-search session");
+        if (session && rag) return fail(TXO_E_INVALID, "txo_decode_prefill: not available on a ragged batch session (the multi-position forward has no ragged form)");
         lanes[0].stream = s;
         return prefill(tokens, t, t, logits_out, nullptr, s);
     }
@@ -1337,6 +1481,7 @@ struct Engine : EngineBase {
         if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (lanes.n != 1) return fail(TXO_E_STATE, "decode_score needs a session started by txo_decode_begin");
         if (sImg != sB) return fail(TXO_E_STATE, "decode_score is not available inside a beam-search session");
+        if (rag) return fail(TXO_E_INVALID, "txo_decode_score: not available on a ragged batch session (the multi-position forward has no ragged form)");
         lanes[0].stream = s;
         const ScoreOut so{logp_out, top1_out, top1_logp_out};
         return prefill(tokens, L, L - 1, nullptr, nullptr, s, &so);
@@ -1345,6 +1490,8 @@ struct Engine : EngineBase {
     // OCRModel.forward's path (ocr_model.py:38-44) in one call: encode into the engine's own buffer, open the session, mask, score
     int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
               int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
+        if (session && rag)
+            return fail(TXO_E_INVALID, "txo_score: a ragged batch session is open and ragged batches have no scoring path (open a fixed-shape session first)");
         if (int r = encode(img, B, C, H, W, eenc, s)) return r;
         if (int r = begin_session(eenc, B, 1 + (H / 16) * (W / 16), cfg.eos, s, true)) return r;
         if (mask) {
@@ -1449,6 +1596,7 @@ struct Engine : EngineBase {
         // sampling: the persistent kernel's sampler keeps a row in registers, 16 logits per lane (step.h: sample_row_regs)
         if (sample_mode && V > 64 * SR_PER) return false;
         if (prof || prof_cross || g_dbg || knobs.run.stamps || knobs.run.graph >= 0 || knobs.run.lanes > 0) return false;
+        if (rag) return false;                                 // a ragged batch decodes with launches (persist.h has no per-row key count)
         if (cfg.dec_exp != 4 || cfg.dec_layers > PS_MAXLD) return false;
         const bool exists = (D == 256 && cfg.dec_heads == 8) || (D == 768 && cfg.dec_heads == 12 && sizeof(T) == 2);
         if (!exists) return false;
@@ -1562,6 +1710,7 @@ struct Engine : EngineBase {
                  int64_t* tokens_out, int* n_steps, float* logits_out, hipStream_t s) override {
         int steps = 0;
         row_stop = false; last_compactions = 0;
+        last_ragged = gen_sizes != nullptr;
         const int rc = generate_impl(img, enc, B, C, H, W, N, max_len, eos, tokens_out, &steps, logits_out, s);
         const bool compacted = last_compactions > 0;
         row_stop = false;
@@ -1582,7 +1731,7 @@ struct Engine : EngineBase {
         hipStream_t s = ln.stream;
         const size_t r0 = ln.b0;
         CompactArgs ca{ln.nb, new_rows, (int)r0, cur_tok + r0, eos_seen + r0, row_map + r0, cur_tok2 + r0, row_map2 + r0, cmoves + 2 * r0,
-                       cinfo + 2 * li, st + li, eos};
+                       cinfo + 2 * li, st + li, eos, rag ? slens + r0 : nullptr, slens2 + r0};   // (a ragged session's key counts move with the rows)
         hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, s, ca);
         const int heads = cfg.dec_heads;
         auto move = [&](void* base, size_t outer_stride, size_t inner_stride, size_t row_stride, int outer_n, int inner_n, size_t len_elems) {
@@ -1612,11 +1761,22 @@ struct Engine : EngineBase {
         if (max_len > Tmax && (V % 8 != 0 || (size_t)Tmax > (size_t)Bmax * Nmax))
             return fail(TXO_E_INVALID, "max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a vocabulary "
                                        "size that is a multiple of 8 and max_length <= max_batch * max_tokens (use decoder.generate's stepwise loop)");
-        if (img) {
+        const bool ragged = img && gen_sizes;                     // txo_generate_ragged: H x W is the container, the sizes are in rag_hw / rag_ntok
+        if (ragged) {
+            for (int b0 = 0, bc = enc_chunk_images(B); b0 < B; b0 += bc) {
+                const int nb = std::min(bc, B - b0);
+                if (int r = encode_images(img + (size_t)b0 * C * H * W, nb, C, H, W, eenc + (size_t)b0 * gen_ns * D, s, gen_ns, b0)) return r;
+            }
+            enc = eenc; N = gen_ns;
+        } else if (img) {
             if (int r = encode(img, B, C, H, W, eenc, s)) return r;
             enc = eenc; N = 1 + (H / 16) * (W / 16);
         }
         if (int r = begin_session(enc, B, N, eos, s, false)) return r;   // eos also decides whether the BOS column counts
+        if (ragged) {                                             // the session's key count per slot = the images' token counts
+            HIP_TRY(hipMemcpyAsync(slens, rag_ntok, sizeof(int) * B, hipMemcpyDeviceToDevice, s));
+            rag = true;
+        }
         last_persist = false;
         if (persist_cooldown > 0) --persist_cooldown;
         if (persist_usable(B)) {
@@ -1647,7 +1807,7 @@ struct Engine : EngineBase {
         // single-stream launches (57.1 vs 58.0 / 58.2 ms) -- so both stay opt-in: TXO_GRAPH=1, TXO_LANES=n.
         // graph replay by default only for very small batches (B <= 4: there the host's enqueue rate bounds the step --
         // 34.2 vs 37.2 ms per generate at B = 1 -- from B = 8 on it is equal); TXO_GRAPH=1 / 0 forces it on / off
-        use_latent = latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && auto_latent(B)));
+        use_latent = !rag && latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && auto_latent(B)));   // (ragged: K/V form)
         // per-row stop with live-row compaction: inside the positional table, tokens only (a finished row's logits would be unspecified)
         row_stop = stop_mode == 1 && eos >= 0 && logits_out == nullptr && max_len <= Tmax && knobs.stop_every > 0 && !prof && !prof_cross;
         lat_self = use_latent && lat_self_ok() && !row_stop;      // (the z history is not moved by compact_lane)
@@ -1844,6 +2004,7 @@ struct Engine : EngineBase {
         else if (what == TXO_Q_LAST_LATENT) *out = (!last_persist && use_latent) ? 1 : 0;
         else if (what == TXO_Q_RELOAD_KNOBS) { knobs.run.read(); *out = 0; }
         else if (what == TXO_Q_LAST_COMPACTIONS) *out = last_compactions;
+        else if (what == TXO_Q_LAST_RAGGED) *out = last_ragged ? 1 : 0;
         else if (what == TXO_Q_SAMPLE_VOCAB_MAX) *out = std::max<int64_t>(64 * SR_PER, (int64_t)(sample_lds_max / sizeof(float)));
         else return fail(TXO_E_INVALID, "unknown query");
         return 0;
@@ -1942,6 +2103,23 @@ int txo_encode(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H,
 int txo_decode_begin(txo_engine* e, const float* enc, int32_t B, int32_t N, void* stream) {
     if (!e || !enc) return fail(TXO_E_INVALID, "null argument");
     return e->impl->decode_begin(enc, B, N, e->impl->cfg.eos, (hipStream_t)stream);
+}
+
+int txo_encode_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, float* enc_out,
+                      int32_t* n_slot, void* stream) {
+    if (!e || !img || !sizes || !enc_out) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->encode_ragged(img, B, C, Hc, Wc, sizes, enc_out, n_slot, (hipStream_t)stream);
+}
+
+int txo_decode_begin_ragged(txo_engine* e, const float* enc, int32_t B, int32_t Ns, const int32_t* n_tokens, void* stream) {
+    if (!e || !enc || !n_tokens) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->decode_begin_ragged(enc, B, Ns, n_tokens, e->impl->cfg.eos, (hipStream_t)stream);
+}
+
+int txo_generate_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, int32_t max_len,
+                        int32_t eos, int64_t* tokens_out, int32_t* n_steps, void* stream) {
+    if (!e || !img || !sizes || !tokens_out) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->generate_ragged(img, B, C, Hc, Wc, sizes, max_len, eos, tokens_out, n_steps, (hipStream_t)stream);
 }
 
 int txo_decode_step(txo_engine* e, const int64_t* tok_in, int32_t t, float* logits_out, int64_t* tok_out, void* stream) {

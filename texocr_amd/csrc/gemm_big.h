@@ -45,6 +45,32 @@ template <typename T> struct LoadPatch {
     }
 };
 
+// Ragged batch (texocr.h: txo_encode_ragged): B images of different sizes in one container [B][C][Hc][Wc], image b in the top-left
+// corner.  GEMM row m = (b, p) with p < hwS = Ns - 1 patch slots per image; hw[2b], hw[2b+1] = the image's own patch rows / columns
+// (device array).  p = pr * w_b + pc for p < h_b * w_b, packed to the front of the slot; a slot behind it is a PADDING row: its A
+// fragment is zeros and nothing of the container is loaded for it (pixels outside an image's corner are never read).
+template <typename T> struct LoadPatchRagged {
+    const float* img; const int* hw; int C, Hc, Wc, hwS;
+    __device__ inline u32x4 operator()(int m, int k) const {
+        const int b = m / hwS, p = m - b * hwS;
+        const int2 d = *reinterpret_cast<const int2*>(hw + 2 * b);
+        if (p >= d.x * d.y) return u32x4{0u, 0u, 0u, 0u};
+        const int pr = p / d.y, pc = p - pr * d.y;
+        const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
+        const float* src = img + (((size_t)b * C + c) * Hc + pr * 16 + py) * Wc + pc * 16 + px;
+        if constexpr (sizeof(T) == 4) {
+            return ld16(src);
+        } else {
+            float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 4);
+            union { bf16 h[8]; u32x4 v; } u;
+            u.h[0] = __float2bfloat16(lo.x); u.h[1] = __float2bfloat16(lo.y); u.h[2] = __float2bfloat16(lo.z);
+            u.h[3] = __float2bfloat16(lo.w); u.h[4] = __float2bfloat16(hi.x); u.h[5] = __float2bfloat16(hi.y);
+            u.h[6] = __float2bfloat16(hi.z); u.h[7] = __float2bfloat16(hi.w);
+            return u.v;
+        }
+    }
+};
+
 // ---------------- epilogues ----------------------------------------------------------------------------------
 // The accumulator tile is staged through LDS and handed to the epilogue as 8 consecutive columns of one row
 // (plain: v[8] at columns n..n+7; paired: value v[8] and gate g[8] of outputs j..j+7), so every global access is a
@@ -220,6 +246,28 @@ struct EpiPatch {                                 // x[b][1+p][n..] = acc + bias
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += bb[e] + pp[e];
         store8<float>(x + ((size_t)b * (hw + 1) + 1 + p) * D + n, v);
+    }
+};
+
+// ragged batch (LoadPatchRagged): x[b][1 + p][n..] = acc + bias + pos[1 + pr*G + pc][n..] with (pr, pc) from the image's OWN grid
+// and the position id from the canvas grid (encoder.py:136-143: grid[:h_b, :w_b]); padding rows are stored as zeros
+struct EpiPatchRagged {
+    float* x; const float* bias; const float* pos; const int* hw; int D, hwS, G;
+    static constexpr bool PAIRED = false;
+    __device__ inline void operator()(int m, int n, float (&v)[8]) const {
+        const int b = m / hwS, p = m - b * hwS;
+        const int2 d = *reinterpret_cast<const int2*>(hw + 2 * b);
+        if (p < d.x * d.y) {
+            const int pr = p / d.y, pc = p - pr * d.y;
+            float bb[8], pp[8];
+            load8(bias + n, bb); load8(pos + (size_t)(1 + pr * G + pc) * D + n, pp);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += bb[e] + pp[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = 0.f;
+        }
+        store8<float>(x + ((size_t)b * (hwS + 1) + 1 + p) * D + n, v);
     }
 };
 

@@ -144,4 +144,13 @@ __global__ void cls_rows_kernel(float* __restrict__ x, const float* __restrict__
     x[(size_t)b * ntok * D + c] = cls[c] + pos[c];
 }
 
+
+// ragged batch (texocr.h: txo_encode_ragged): rows lens[b] .. Ns-1 of slot b of the encoder output [B][Ns][D] are written as zeros
+__global__ void zero_pad_rows_kernel(float* __restrict__ x, const int* __restrict__ lens, int B, int Ns, int D4) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * Ns * D4) return;
+    const int row = (int)(i / D4), b = row / Ns, p = row - b * Ns;
+    if (p >= lens[b]) reinterpret_cast<float4*>(x)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 }  // namespace txo

@@ -362,6 +362,7 @@ struct CompactArgs {
     int64_t* cur_tok2; int* row_map2;                         // scratch [rows]
     int* moves;                           // out: (src, dst) pairs of the live rows that change slot, ascending; info = {live rows, moves}
     int* info; StepState* st; int fill_tok;
+    int* lens; int* lens2;                // ragged session (else null): cross-attention key count per SLOT, permuted with the rows; scratch [rows]
 };
 // ONE workgroup.  Live rows keep their order, so dst <= src, and a live row moves iff a finished row precedes it: with F = the first
 // finished row (every row before it is live and stays), the live row that lands in slot dst > = F is entry dst - F of the move list.
@@ -384,6 +385,7 @@ __global__ __launch_bounds__(1024) void compact_scan_kernel(CompactArgs a) {
         const int dst = before + inc - live, F = s_first;     // F is final for every row up to this chunk's end
         if (live) {
             a.cur_tok2[dst] = a.cur_tok[r]; a.row_map2[dst] = a.row_map[r];
+            if (a.lens) a.lens2[dst] = a.lens[r];
             if (dst != r) { a.moves[2 * (dst - F)] = r; a.moves[2 * (dst - F) + 1] = dst; }
         }
         __syncthreads();
@@ -397,6 +399,7 @@ __global__ __launch_bounds__(1024) void compact_scan_kernel(CompactArgs a) {
         a.cur_tok[i] = lv ? a.cur_tok2[i] : (int64_t)a.fill_tok;
         a.row_map[i] = lv ? a.row_map2[i] : a.row0;
         a.eos_seen[i] = lv ? 0 : 1;
+        if (a.lens) a.lens[i] = lv ? a.lens2[i] : 1;          // (a filler row attends one key of whatever panel its slot holds: finite, never returned)
     }
     if (tid == 0) { a.info[0] = L; a.info[1] = L - F; a.st->rows_with_eos = a.new_rows - L; a.st->arrive = 0u; }
 }

@@ -184,6 +184,23 @@ class HipEngine:
         toks = toks[:, :n]
         return (toks, logits[:, :n]) if return_logits else toks
 
+    # ---- ragged batches (build extension): images of different sizes in one call; `images` is a sequence of (C, H_b, W_b) tensors ----
+    def encode_ragged(self, images):
+        """-> (enc (B, Ns, D) with zero rows behind each image's own token count, n_tokens (B,) int32 CPU)"""
+        self._ensure()
+        box, sizes = ops.pack_ragged(images)
+        return torch.ops.texocr.encode_ragged(box, sizes, self.id), ops.ragged_tokens(sizes)
+
+    def decode_begin_ragged(self, enc: torch.Tensor, n_tokens: torch.Tensor) -> None:
+        self._ensure()
+        torch.ops.texocr.decode_begin_ragged(enc, n_tokens, self.id)
+
+    def generate_ragged(self, images, max_len: int, eos: Optional[int]) -> torch.Tensor:
+        self._ensure()
+        box, sizes = ops.pack_ragged(images)
+        toks, n = torch.ops.texocr.generate_ragged(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
+        return toks[:, :int(n.item())]
+
     def generate_beam(self, img: torch.Tensor, beams: int, max_len: int, eos: Optional[int], return_beams: bool = False):
         """Beam search (build extension; the reference has none).  Returns the best beam's tokens (B, n), or with
         return_beams=True (tokens (B, beams, n), scores (B, beams)) sorted best first."""
@@ -217,7 +234,7 @@ class HipEngine:
         LAST_LATENT = the last decode's cross attention ran in latent form, RELOAD_KNOBS = (not a question) re-read the TXO_*
         development knobs of generate() from the environment, LAST_COMPACTIONS = live-row compactions of the last generate (stop='row'
         on the launch path), SAMPLE_VOCAB_MAX = the largest vocabulary decode='sample' accepts on this device (set_sampling raises
-        ValueError beyond it)."""
+        ValueError beyond it), LAST_RAGGED = the last generate decoded a ragged batch."""
         out = C.c_int64(0)
         _lib.check(self.lib.txo_engine_query(self.handle, int(what), C.byref(out)))
         return out.value
@@ -296,6 +313,11 @@ class VisionEncoder(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self._engine.encode(x)
+
+    def forward_ragged(self, images):
+        """Build extension: a sequence of (C, H_b, W_b) images of different sizes -> (enc (B, Ns, D), n_tokens (B,) int32 CPU).
+        enc[b, :n_tokens[b]] is forward(images[b][None])[0]; the rows behind it are zeros."""
+        return self._engine.encode_ragged(images)
 
 
 def _check_token_ids(tokens: torch.Tensor, vocab: int) -> None:
@@ -627,6 +649,31 @@ class OCRModel(nn.Module):
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
                                      stop=stop, pad=self.trg_pad_idx)
+
+    @torch.no_grad()
+    def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
+                        stop: str = "global") -> torch.Tensor:
+        """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
+        Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
+        is keyed by the row of the batch).  max_len <= decoder.max_len."""
+        if stop not in ("global", "row"):
+            raise ValueError("stop must be 'global' or 'row'")
+        if decode not in ("greedy", "sample"):
+            raise ValueError("decode must be 'greedy' or 'sample'")
+        eng = self._engine
+        if decode == "sample":
+            if seed is None:
+                seed = int(torch.randint(0, 2**62, (1,)).item())
+            eng.set_sampling(True, temp=temp, seed=seed)
+        if stop == "row":
+            eng.set_stop_mode("row")
+        try:
+            return eng.generate_ragged(images, max_len, self.eos_token)
+        finally:
+            if decode == "sample":
+                eng.set_sampling(False)
+            if stop == "row":
+                eng.set_stop_mode("global")
 
     @torch.no_grad()
     def score(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:

@@ -13,6 +13,9 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::generate          OCRModel.generate                         model/ocr_model.py:46-66
   texocr::generate_from_enc AutoRegressiveDecoder.generate            model/decoder.py:77-122
   texocr::generate_beam     (build extension, BASELINE config 5)
+  texocr::encode_ragged / decode_begin_ragged / generate_ragged
+                            (build extension) the same callables over a RAGGED batch: B images of different sizes in one
+                            container, every image computed as if it had been passed on its own (``pack_ragged`` builds the container)
 
 An engine is named by an integer id (operators take tensors and scalars only); ``register_engine`` hands one out.
 There is no CPU implementation: calling an operator on CPU tensors raises.
@@ -22,7 +25,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch.library import custom_op
@@ -302,3 +305,115 @@ def _(img, engine, beams, max_len, eos, want_all):
     B = img.shape[0]
     return (img.new_empty((B, max_len), dtype=torch.int64), img.new_empty((B, beams), dtype=torch.float32),
             img.new_empty((B * beams if want_all else 0, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"))
+
+
+# ---- ragged batches (build extension): images of different sizes in one call ---------------------------------------------------
+def pack_ragged(images: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """B images (C, H_b, W_b) -> (container (B, C, Hc, Wc) float32, sizes (B, 2) int32 CPU = (H_b, W_b)).  Image b sits in the
+    top-left corner of its slot; Hc / Wc are the largest height / width; the rest of the container is zero (the engine never reads
+    it).  Every side must be a positive multiple of 16; all images share C, the device and float32."""
+    if len(images) == 0:
+        raise ValueError("pack_ragged: no images")
+    first = images[0]
+    if first.ndim != 3:
+        raise ValueError("pack_ragged: every image must be (C, H, W)")
+    Cc = first.shape[0]
+    for i, im in enumerate(images):
+        if im.ndim != 3 or im.shape[0] != Cc:
+            raise ValueError(f"pack_ragged: image {i} must be ({Cc}, H, W), got {tuple(im.shape)}")
+        if im.dtype != torch.float32:
+            raise ValueError(f"pack_ragged: image {i} must be float32, got {im.dtype}")
+        if im.device != first.device:
+            raise ValueError(f"pack_ragged: image {i} lives on {im.device}, image 0 on {first.device}")
+        h, w = int(im.shape[1]), int(im.shape[2])
+        if h <= 0 or w <= 0 or h % 16 or w % 16:
+            raise ValueError(f"pack_ragged: image {i} is {h}x{w}; sides must be positive multiples of 16")
+    Hc, Wc = max(int(im.shape[1]) for im in images), max(int(im.shape[2]) for im in images)
+    box = torch.zeros((len(images), Cc, Hc, Wc), dtype=torch.float32, device=first.device)
+    for b, im in enumerate(images):
+        box[b, :, :im.shape[1], :im.shape[2]] = im
+    sizes = torch.tensor([[int(im.shape[1]), int(im.shape[2])] for im in images], dtype=torch.int32)
+    return box, sizes
+
+
+def _ragged_args(img: torch.Tensor, sizes: torch.Tensor, e):
+    if img.ndim != 4:
+        raise ValueError("expected a container of shape (B, C, Hc, Wc)")
+    img = _f32_dev(img, "container", e)
+    if sizes.is_cuda or sizes.dtype != torch.int32 or sizes.ndim != 2 or tuple(sizes.shape) != (img.shape[0], 2):
+        raise ValueError("sizes must be an int32 CPU tensor of shape (B, 2) = (H_b, W_b): launch geometry depends on them")
+    return img, sizes.contiguous()
+
+
+def _i32p(t: torch.Tensor):
+    return C.cast(t.data_ptr(), C.POINTER(C.c_int32))
+
+
+def ragged_tokens(sizes: torch.Tensor) -> torch.Tensor:
+    """(B, 2) image sizes -> (B,) int32 encoder tokens per image, 1 + (H_b / 16)(W_b / 16)"""
+    return (1 + (sizes[:, 0] // 16) * (sizes[:, 1] // 16)).to(torch.int32)
+
+
+@custom_op("texocr::encode_ragged", mutates_args=())
+def encode_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int) -> torch.Tensor:
+    """txo_encode_ragged: container (B, C, Hc, Wc) + sizes (B, 2) int32 CPU -> enc (B, Ns, D), Ns = the largest token count; rows
+    behind an image's own count are zeros."""
+    e = _eng(engine, ready=True)
+    img, sizes = _ragged_args(img, sizes, e)
+    B, Cc, Hc, Wc = img.shape
+    ns = int(ragged_tokens(sizes).max()) if B else 1
+    out = torch.empty((B, max(ns, 1), e.dims.embed_dim), device=img.device, dtype=torch.float32)
+    n = C.c_int32(0)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_encode_ragged(e.handle, img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), out.data_ptr(), C.byref(n), _stream()))
+    if n.value != out.shape[1]:
+        raise RuntimeError(f"texocr::encode_ragged: the engine's slot stride {n.value} is not the binding's {out.shape[1]}")
+    return out
+
+
+@encode_ragged.register_fake
+def _(img, sizes, engine):
+    d = _eng(engine).dims
+    ns = int(ragged_tokens(sizes).max())
+    return img.new_empty((img.shape[0], ns, d.embed_dim), dtype=torch.float32)
+
+
+@custom_op("texocr::decode_begin_ragged", mutates_args=())
+def decode_begin_ragged(enc: torch.Tensor, n_tokens: torch.Tensor, engine: int) -> None:
+    """txo_decode_begin_ragged: enc (B, Ns, D) as encode_ragged returns it, n_tokens (B,) int32 CPU = valid rows per image."""
+    e = _eng(engine, ready=True)
+    enc = _f32_dev(enc, "enc", e)
+    if enc.ndim != 3 or enc.shape[2] != e.dims.embed_dim:
+        raise ValueError(f"enc must be (B, Ns, {e.dims.embed_dim})")
+    if n_tokens.is_cuda or n_tokens.dtype != torch.int32 or tuple(n_tokens.shape) != (enc.shape[0],):
+        raise ValueError("n_tokens must be an int32 CPU tensor of shape (B,)")
+    n_tokens = n_tokens.contiguous()
+    e._enc_keepalive = enc
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_decode_begin_ragged(e.handle, enc.data_ptr(), enc.shape[0], enc.shape[1], _i32p(n_tokens), _stream()))
+    e._B = enc.shape[0]
+
+
+@decode_begin_ragged.register_fake
+def _(enc, n_tokens, engine):
+    return None
+
+
+@custom_op("texocr::generate_ragged", mutates_args=())
+def generate_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len: int, eos: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """txo_generate_ragged: (tokens (B, max_len) of which the first n are valid, n as an int64 CPU tensor of shape (1,))."""
+    e = _eng(engine, ready=True)
+    img, sizes = _ragged_args(img, sizes, e)
+    B, Cc, Hc, Wc = img.shape
+    toks, _ = _gen_outputs(img, e, max_len, False)
+    n = C.c_int32(0)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_generate_ragged(e.handle, img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), int(max_len), int(eos),
+                                             toks.data_ptr(), C.byref(n), _stream()))
+    e._B, e._enc_keepalive = B, img
+    return toks, torch.tensor([n.value], dtype=torch.int64)
+
+
+@generate_ragged.register_fake
+def _(img, sizes, engine, max_len, eos):
+    return img.new_empty((img.shape[0], max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu")

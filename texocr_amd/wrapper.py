@@ -12,7 +12,7 @@ Differences from the reference, all on the host side of the path:
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -53,12 +53,36 @@ class TeXOCRWrapper:
             self.model.load_state_dict(sd)
         self.dims: Dims = self.model._engine.dims
 
-    def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
-                 seed: Optional[int] = None) -> Tuple[list, str]:
+    def _tensor(self, img) -> torch.Tensor:
         x = preprocess_image(img, self.dims.patch)
         if self.dims.in_channels != 1:
             x = x.expand(self.dims.in_channels, -1, -1)
-        x = x[None].contiguous().cuda()
+        return x.contiguous()
+
+    def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
+              seed: Optional[int] = None) -> List[Tuple[list, str]]:
+        """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
+        Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
+        per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
+        window).  A sampled draw is keyed by (seed + chunk index, row of its chunk, position): with an explicit seed the result is
+        reproducible and no two images of the list share a stream of draws."""
+        eng = self.model._engine
+        max_len = min(int(max_len), self.dims.max_len)
+        out: List[Tuple[list, str]] = []
+        xs = [self._tensor(im).cuda() for im in imgs]
+        for c0 in range(0, len(xs), eng.max_batch):
+            chunk_seed = None if seed is None else int(seed) + c0 // eng.max_batch
+            toks = self.model.generate_ragged(xs[c0:c0 + eng.max_batch], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row")
+            for row in toks.tolist():
+                if self.model.eos_token in row:
+                    row = row[:row.index(self.model.eos_token) + 1]
+                row = row[:-1]                                                        # ocr_model.py:104 (drops the last token)
+                out.append((row, process_output(self.tokenizer.decode(row))))
+        return out
+
+    def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
+                 seed: Optional[int] = None) -> Tuple[list, str]:
+        x = self._tensor(img)[None].cuda()
         # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
         # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
         toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed)
