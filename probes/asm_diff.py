@@ -5,7 +5,8 @@ Build each side with the flags of probes/kstats.sh:
         texocr_amd/csrc/engine.hip -o before.s
 then: python probes/asm_diff.py before.s after.s
 Two builds of the same tree differ in the __hip_cuid_* symbol and, when templates are instantiated in another order, in the order of the
-functions and the numbers of their local labels: so every function is cut out on its own and its labels are renumbered before comparing.
+functions and the numbers of their local labels: so every function is cut out on its own and its labels are renumbered before comparing
+(and the padding in front of a label's comment, which depends on the number's width, is dropped).
 Prints the functions present on one side only and those whose text differs; exit status 1 if any body differs."""
 import re
 import shutil
@@ -21,7 +22,7 @@ def functions(path):
             name, body = m.group(1), []
         if name is None:
             continue
-        body.append(re.sub(r"(BB|\.Lfunc_end|\.Ltmp)\d+", r"\1", line))
+        body.append(re.sub(r"[ \t]+;", " ;", re.sub(r"(BB|\.Lfunc_end|\.Ltmp)\d+", r"\1", line)))
         if "; -- End function" in line:
             out[name], name = "".join(body), None
     return out

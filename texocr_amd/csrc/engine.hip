@@ -45,6 +45,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "step.h"
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
+#include "session.h"
 #include "stamps.h"
 
 namespace txo {
@@ -149,7 +150,7 @@ struct Engine : EngineBase {
     T* zc = nullptr;                  // self attention in latent form: history of normalised block inputs [Ld][B][Tmax][D] (lat_attn.h)
     T *dqt = nullptr, *dqp = nullptr, *dcl = nullptr;   // latent cross attention: q [B][inner], q' and c [B][heads*D] in the storage type
     int64_t* cur_tok = nullptr; int *eos_seen = nullptr, *done_flag = nullptr; StepState* st = nullptr;
-    unsigned char* kmask = nullptr; bool kmask_on = false;   // padding mask over the decoded positions of a decode_step session (txo_decode_set_key_mask)
+    unsigned char* kmask = nullptr;   // padding mask over the decoded positions of a decode_step session (txo_decode_set_key_mask)
     // ----- decode session: 1..MAXL row ranges (lanes.h); a range's step is a fixed launch sequence, captured once and replayed -----
     static constexpr int MAXL = LaneSet::MAXL;
     LaneSet lanes;
@@ -160,16 +161,15 @@ struct Engine : EngineBase {
     static constexpr int wide_mid_rows = 129;
     // cross attention in latent form (lat_attn.h): scores / values against the raw encoder rows instead of projected K/V panels.
     // latent_ok: the tile exists for this engine's width / storage type.  knobs.lat_mode (TXO_LATENT): 1 = every decode runs with
-    // launches in latent form, 0 = never, unset = where it measured faster (auto_latent).  use_latent: what the current session does.
-    bool latent_ok = false, use_latent = false;
+    // launches in latent form, 0 = never, unset = where it measured faster (auto_latent).  ses.latent: what the current session does.
+    bool latent_ok = false;
     int n_cus = 256;                  // compute units of this engine's device (init): one latent tile per CU is the grouping target
-    // lat_self: this session's SELF attention also runs in latent form (the history is z, not k / v: a quarter of the bytes at config.yml
+    // ses.lat_self: this session's SELF attention also runs in latent form (the history is z, not k / v: a quarter of the bytes at config.yml
     // dims).  Only inside generate() / generate_beam() with launches in latent form: a session opened through txo_decode_begin may be
     // prefilled or masked, which work on the K/V history.  OPT-IN (TXO_LATENT_SELF=1): measured on MI355X it
     // ties the K/V history at batch 256 (76.5 vs 76.7 ms per generate: the core is 9.8 us against 14.8 for the K/V kernel, averaged over
     // the 256 positions, but the folded output projection's K = heads*D costs 9.1 us against 4.8) and loses in beam search (121 vs 115 ms
     // at 5 x 128); what it saves is history capacity (a quarter).  profiles/r05_latent_self.txt.
-    bool lat_self = false;
     bool lat_self_ok() const {
         // (the beam slot table of the tile covers 16 keys x its wave count x LA_PATH_TILES positions: the bf16 tile at width 256 runs on 4 waves)
         const int waves = (D <= 256 && !(lat_nw4 && D == 256)) ? 8 : 4;
@@ -181,7 +181,6 @@ struct Engine : EngineBase {
     // rows cross the CU's L2 port twice.)  The wave count changes the order in which a row's key tiles are merged: low bits differ from the
     // 8-wave tile's, within the same bound against the reference.
     static constexpr bool lat_nw4 = sizeof(T) == 2;
-    bool ckv_valid = false;           // the projected cross K/V panels of this session exist (the prefill needs them; the latent form does not)
     // per-row stop (step.h): batch row held by every slot of a row range, scratch of the compaction, {live rows, moves} per range
     int *row_map = nullptr, *row_map2 = nullptr, *cmoves = nullptr, *cinfo = nullptr; int64_t* cur_tok2 = nullptr;
     int last_compactions = 0;         // compactions of the last generate (TXO_Q_LAST_COMPACTIONS)
@@ -191,13 +190,10 @@ struct Engine : EngineBase {
     int *rag_hw = nullptr, *rag_ntok = nullptr, *slens = nullptr, *slens2 = nullptr;
     int32_t* rag_host = nullptr; hipEvent_t rag_ev = nullptr; bool rag_ev_pending = false;
     std::vector<int32_t> rag_stage;   // host scratch [3 Bmax] (sized at creation)
-    bool rag = false;                 // the open session is ragged
-    const int32_t* gen_sizes = nullptr; int gen_ns = 0;   // set by generate_ragged around generate()
     bool last_ragged = false;         // TXO_Q_LAST_RAGGED
-    int step_host_t = -1;             // position of the step being enqueued when the host knows it (see enqueue_step)
     Stamps stamps;                    // TXO_STAMPS / TXO_PSTAMPS diagnostics (stamps.h)
     int64_t* tok_buf = nullptr;            // [Bmax][Tmax] generated ids (engine-owned so graphs do not bake user pointers)
-    int sB = 0, sN = 0, sImg = 0; bool session = false;   // decode rows, encoder tokens, images behind the cross K/V cache
+    Session ses;                           // the open decode session (session.h)
     // persistent decode launch (persist.h): control block (device + pinned host copy), per-stage stamps of one position
     PersistCtl* pctl = nullptr; PersistCtl* pctl_host = nullptr; unsigned long long* pstamps = nullptr;
     int persist_fallbacks = 0;                            // launches that gave up (placement / time-out) and were redone with launches
@@ -775,23 +771,38 @@ struct Engine : EngineBase {
         return 0;
     }
 
-    int encode(const float* img, int B, int C, int H, int W, float* enc_out, hipStream_t s) override {
+    // ---- what an encode is given (session.h: ImageBatch), checked.  The size checks of one image inside its Hc x Wc container: `who` names it
+    int check_image_size(const std::string& who, const char* is, int H, int W, int Hc, int Wc) {
+        if (H <= 0 || W <= 0 || H % 16 || W % 16) return fail(TXO_E_INVALID, who + " height/width must be positive multiples of 16");
+        if (H > Hc || W > Wc) return fail(TXO_E_INVALID, who + is + "larger than the container");
+        if (H > cfg.canvas_h || W > cfg.canvas_w) return fail(TXO_E_INVALID, who + is + "larger than the position-embedding canvas");
+        return 0;
+    }
+    int fixed_batch(int B, int C, int H, int W, ImageBatch* ib) {
         if (!ready) return fail(TXO_E_STATE, "weights not finalized");
         if (C != cfg.in_channels) return fail(TXO_E_INVALID, "image channel count does not match in_channels");
-        if (H <= 0 || W <= 0 || H % 16 || W % 16) return fail(TXO_E_INVALID, "image height/width must be positive multiples of 16");
-        if (H > cfg.canvas_h || W > cfg.canvas_w) return fail(TXO_E_INVALID, "image larger than the position-embedding canvas");
-        const int h = H / 16, w = W / 16, hw = h * w, N = hw + 1;
+        if (int r = check_image_size("image", " ", H, W, H, W)) return r;
+        const int N = 1 + (H / 16) * (W / 16);
         if (B < 1 || B > Bmax) return fail(TXO_E_INVALID, "batch exceeds engine max_batch");
         if (N > Nmax) return fail(TXO_E_INVALID, "token count exceeds engine max_tokens");
+        *ib = ImageBatch{B, C, H, W, N};
+        return 0;
+    }
+    int encode(const float* img, int B, int C, int H, int W, float* enc_out, hipStream_t s) override {
+        ImageBatch ib;
+        if (int r = fixed_batch(B, C, H, W, &ib)) return r;
+        return encode_batch(ib, img, enc_out, s);
+    }
+    int encode_batch(const ImageBatch& ib, const float* img, float* enc_out, hipStream_t s) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (prof) { e0 = pool.next(); e1 = pool.next(); (void)hipEventRecord(e0, s); }
         // Image chunks (enc_chunk_images): every row of the stack belongs to ONE image, so the stack may run over a few images at a time
         // through the SAME workspace rows -- a chunk whose intermediates (stream, z, q/k/v, attention output, FFN hidden) fit the 256 MB
         // Infinity Cache keeps every producer -> consumer hand-over on the die instead of through HBM.  Same bits as the whole batch.
-        const int bc = enc_chunk_images(B);
-        for (int b0 = 0; b0 < B; b0 += bc) {
-            const int nb = std::min(bc, B - b0);
-            if (int r = encode_images(img + (size_t)b0 * C * H * W, nb, C, H, W, enc_out + (size_t)b0 * N * D, s)) return r;
+        const int bc = enc_chunk_images(ib.B);
+        for (int b0 = 0; b0 < ib.B; b0 += bc) {
+            const int nb = std::min(bc, ib.B - b0);
+            if (int r = encode_images(ib.chunk(b0, nb), img + b0 * ib.pixels(), enc_out + (size_t)b0 * ib.N * D, s)) return r;
         }
         if (prof) { (void)hipEventRecord(e1, s); ev_enc.push_back({e0, e1}); }
         HIP_TRY(hipGetLastError());
@@ -799,20 +810,31 @@ struct Engine : EngineBase {
     }
     // images per encoder chunk: TXO_ENC_CHUNK=n forces n (0 = whole batch); default the whole batch (profiles/r06_encoder_chunk_sweep.txt)
     int enc_chunk_images(int B) const { return knobs.enc_chunk_env > 0 ? std::min(B, knobs.enc_chunk_env) : B; }
-    // ragNs > 0: a ragged batch (H x W is then the CONTAINER's size, ragNs the slot stride; the sizes of images b0.. are in rag_hw / rag_ntok)
-    int encode_images(const float* img, int B, int C, int H, int W, float* enc_out, hipStream_t s, int ragNs = 0, int b0 = 0) {
-        const int h = H / 16, w = W / 16, hw = ragNs > 0 ? ragNs - 1 : h * w, N = hw + 1;
+    // the RAGGED pairs of the encoder: the descriptor picks the instantiation, the arguments are spelled once
+    void launch_patch_embed(hipStream_t s, const ImageBatch& ib, const float* img) {
+        const int hw = ib.N - 1, w = ib.W / 16, G = cfg.canvas_w / 16;
+        const int* rhw = rag_hw + 2 * ib.first;
+        auto go = [&](auto load, auto epi) { launch_gemm_big<T>(s, load, patch_w, ib.B * hw, D, ib.C * 256, epi); };
+        if (ib.ragged) go(LoadPatchRagged<T>{img, rhw, ib.C, ib.H, ib.W, hw}, EpiPatchRagged{ex, patch_b, pos, rhw, D, hw, G});
+        else go(LoadPatch<T>{img, ib.C, ib.H, ib.W, hw, w}, EpiPatch{ex, patch_b, pos, D, hw, w, G});
+    }
+    const int* ragged_tokens(const ImageBatch& ib) const { return ib.ragged ? rag_ntok + ib.first : nullptr; }
+    void launch_enc_attn_f32(hipStream_t s, const ImageBatch& ib, dim3 grid, size_t hs) {
+        auto kern = ib.ragged ? enc_attn_kernel<T, true> : enc_attn_kernel<T, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, eqkv, eqkv + hs, eqkv + 2 * hs, eao, ib.N, cfg.enc_heads, ib.B * cfg.enc_heads, ragged_tokens(ib));
+    }
+    void launch_enc_attn_bf16(hipStream_t s, const ImageBatch& ib, dim3 grid, size_t hs, int rev) {
+        const bf16* qb = reinterpret_cast<const bf16*>(eqkv);
+        auto kern = ib.ragged ? enc_attn_bf16_v2_kernel<T, true> : enc_attn_bf16_v2_kernel<T, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, qb, qb + hs, qb + 2 * hs, eao, ib.N, cfg.enc_heads, ib.B * cfg.enc_heads, rev, ragged_tokens(ib));
+    }
+    int encode_images(const ImageBatch& ib, const float* img, float* enc_out, hipStream_t s) {
+        const int B = ib.B, H = ib.H, W = ib.W, N = ib.N, hw = N - 1, w = W / 16;
         const int M = B * N, G = cfg.canvas_w / 16;
-        const int* rhw = rag_hw + 2 * b0; const int* rtok = rag_ntok + b0;
 
         hipLaunchKernelGGL(cls_rows_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, ex, cls, pos, B, N, D);
-        if (ragNs > 0) {
-            launch_gemm_big<T>(s, LoadPatchRagged<T>{img, rhw, C, H, W, hw}, patch_w, B * hw, D, C * 256,
-                               EpiPatchRagged{ex, patch_b, pos, rhw, D, hw, G});
-        } else if (!hybrid) {
-            launch_gemm_big<T>(s, LoadPatch<T>{img, C, H, W, hw, w}, patch_w, B * hw, D, C * 256,
-                               EpiPatch{ex, patch_b, pos, D, hw, w, G});
-        } else {
+        if (!hybrid) launch_patch_embed(s, ib, img);              // (a ragged batch is refused on the hybrid front end)
+        else {
             if (bk_fp32) {
                 const float* feat = nullptr;
                 if (int r = backbone<float>(bk32, img, B, H, W, &feat, s)) return r;
@@ -840,26 +862,12 @@ struct Engine : EngineBase {
             if (l == 0) launch_ln<0, T>(s, ex, nullptr, ez, enc_g, enc_b, M, dir());
             else launch_ln<3, T>(s, ey, estats, ez, enc_g, enc_b, M, dir());
             const dim3 agrid = ea_grid((N + EA_QBLK - 1) / EA_QBLK, B * cfg.enc_heads);   // XCD-aware block order (enc_attn.h: ea_block)
-            const int nbh = B * cfg.enc_heads;
             if constexpr (sizeof(T) == 4) {
-                gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D,
-                                   EpiHeads<float>{eqkv, hs, Ie, cfg.enc_heads, N});
-                if (ragNs > 0) {
-                    hipLaunchKernelGGL((enc_attn_kernel<T, true>), agrid, dim3(256), 0, s, eqkv, eqkv + hs, eqkv + 2 * hs, eao, N, cfg.enc_heads, nbh, rtok);
-                } else {
-                    hipLaunchKernelGGL((enc_attn_kernel<T>), agrid, dim3(256), 0, s, eqkv, eqkv + hs, eqkv + 2 * hs, eao, N, cfg.enc_heads, nbh,
-                                       (const int*)nullptr);
-                }
+                gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D, EpiHeads<float>{eqkv, hs, Ie, cfg.enc_heads, N});
+                launch_enc_attn_f32(s, ib, agrid, hs);
             } else {                                              // perf mode: bf16 q/k/v, bf16 MFMA attention
-                bf16* qb = reinterpret_cast<bf16*>(eqkv);
-                gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D,
-                                   EpiHeads<bf16>{qb, hs, Ie, cfg.enc_heads, N}, dir());
-                if (ragNs > 0) {
-                    hipLaunchKernelGGL((enc_attn_bf16_v2_kernel<T, true>), agrid, dim3(256), 0, s, qb, qb + hs, qb + 2 * hs, eao, N, cfg.enc_heads, nbh, dir(), rtok);
-                } else {
-                    hipLaunchKernelGGL((enc_attn_bf16_v2_kernel<T>), agrid, dim3(256), 0, s, qb, qb + hs, qb + 2 * hs, eao, N, cfg.enc_heads, nbh, dir(),
-                                       (const int*)nullptr);
-                }
+                gemm_plain(s, ez, enc_attn[l].wqkv, M, 3 * Ie, D, EpiHeads<bf16>{reinterpret_cast<bf16*>(eqkv), hs, Ie, cfg.enc_heads, N}, dir());
+                launch_enc_attn_bf16(s, ib, agrid, hs, dir());
             }
             gemm_plain(s, eao, enc_attn[l].wo, M, 2 * D, Ie,
                                EpiGluRes<sizeof(T) == 2>{ey, l == 0 ? res_first : res_x, enc_attn[l].bo}, dir());
@@ -868,9 +876,9 @@ struct Engine : EngineBase {
             gemm_plain(s, ehid, enc_mlp[l].w2, M, D, Fe, EpiBiasRes{ey, res_x, enc_mlp[l].b2}, dir());
         }
         launch_ln<2, float>(s, ey, nullptr, enc_out, encn_g, encn_b, M, dir());
-        if (ragNs > 0) {                                      // the padding rows of every slot are returned as zeros
+        if (ib.ragged) {                                      // the padding rows of every slot are returned as zeros
             const size_t n4 = (size_t)M * (D / 4);
-            hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, enc_out, rtok, B, N, D / 4);
+            hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, enc_out, ragged_tokens(ib), B, N, D / 4);
         }
         return 0;
     }
@@ -894,8 +902,8 @@ struct Engine : EngineBase {
             return fail(TXO_E_INVALID, "ragged batches: the latent cross-attention form (TXO_LATENT=1) is not supported; a ragged decode runs in the K/V form");
         return 0;
     }
-    // checks the sizes, leaves {h_b, w_b} in rag_hw and n_b in rag_ntok; *ns = the slot stride
-    int ragged_sizes(int B, int C, int Hc, int Wc, const int32_t* sizes, int* ns, hipStream_t s) {
+    // the checked descriptor of a ragged batch; leaves {h_b, w_b} in rag_hw and n_b in rag_ntok
+    int ragged_batch(int B, int C, int Hc, int Wc, const int32_t* sizes, hipStream_t s, ImageBatch* ib) {
         if (int r = ragged_refusals()) return r;
         if (!sizes) return fail(TXO_E_INVALID, "ragged batches: null sizes");
         if (C != cfg.in_channels) return fail(TXO_E_INVALID, "image channel count does not match in_channels");
@@ -906,11 +914,7 @@ struct Engine : EngineBase {
         std::vector<int32_t>& st = rag_stage;
         for (int b = 0; b < B; ++b) {
             const int H = sizes[2 * b], W = sizes[2 * b + 1];
-            if (H <= 0 || W <= 0 || H % 16 || W % 16)
-                return fail(TXO_E_INVALID, "ragged batches: image " + std::to_string(b) + " height/width must be positive multiples of 16");
-            if (H > Hc || W > Wc) return fail(TXO_E_INVALID, "ragged batches: image " + std::to_string(b) + " is larger than the container");
-            if (H > cfg.canvas_h || W > cfg.canvas_w)
-                return fail(TXO_E_INVALID, "ragged batches: image " + std::to_string(b) + " is larger than the position-embedding canvas");
+            if (int r = check_image_size("ragged batches: image " + std::to_string(b), " is ", H, W, Hc, Wc)) return r;
             st[2 * b] = H / 16; st[2 * b + 1] = W / 16; st[2 * Bmax + b] = 1 + (H / 16) * (W / 16);
             Ns = std::max(Ns, st[2 * Bmax + b]);
         }
@@ -918,23 +922,14 @@ struct Engine : EngineBase {
         // one staged copy: [2 B] patch grids followed by [B] token counts
         for (int b = 0; b < B; ++b) st[2 * B + b] = st[2 * Bmax + b];
         if (int r = upload_i32(st.data(), rag_hw, 2 * B, rag_ntok, B, s)) return r;
-        *ns = Ns;
+        *ib = ImageBatch{B, C, Hc, Wc, Ns, true};
         return 0;
     }
     int encode_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, float* enc_out, int32_t* n_slot, hipStream_t s) override {
-        int Ns = 0;
-        if (int r = ragged_sizes(B, C, Hc, Wc, sizes, &Ns, s)) return r;
-        if (n_slot) *n_slot = Ns;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (prof) { e0 = pool.next(); e1 = pool.next(); (void)hipEventRecord(e0, s); }
-        const int bc = enc_chunk_images(B);
-        for (int b0 = 0; b0 < B; b0 += bc) {
-            const int nb = std::min(bc, B - b0);
-            if (int r = encode_images(img + (size_t)b0 * C * Hc * Wc, nb, C, Hc, Wc, enc_out + (size_t)b0 * Ns * D, s, Ns, b0)) return r;
-        }
-        if (prof) { (void)hipEventRecord(e1, s); ev_enc.push_back({e0, e1}); }
-        HIP_TRY(hipGetLastError());
-        return 0;
+        ImageBatch ib;
+        if (int r = ragged_batch(B, C, Hc, Wc, sizes, s, &ib)) return r;
+        if (n_slot) *n_slot = ib.N;
+        return encode_batch(ib, img, enc_out, s);
     }
     int decode_begin_ragged(const float* enc, int B, int Ns, const int32_t* n_tokens, int eos, hipStream_t s) override {
         if (int r = ragged_refusals()) return r;
@@ -944,10 +939,7 @@ struct Engine : EngineBase {
         for (int b = 0; b < B; ++b)
             if (n_tokens[b] < 1 || n_tokens[b] > Ns)
                 return fail(TXO_E_INVALID, "ragged batches: n_tokens[" + std::to_string(b) + "] must be in [1, Ns]");
-        if (int r = upload_i32(n_tokens, slens, B, nullptr, 0, s)) return r;
-        if (int r = begin_session(enc, B, Ns, eos, s, true)) return r;
-        rag = true;
-        return 0;
+        return begin_session(enc, B, Ns, eos, s, true, KeyCounts{nullptr, n_tokens});
     }
     int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
                         int* n_steps, hipStream_t s) override {
@@ -955,63 +947,59 @@ struct Engine : EngineBase {
         if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
         if (max_len > Tmax)
             return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length (the sliding window runs through the prefill, which has no ragged form)");
-        int Ns = 0;
-        if (int r = ragged_sizes(B, C, Hc, Wc, sizes, &Ns, s)) return r;
-        gen_sizes = sizes; gen_ns = Ns;
-        const int rc = generate(img, nullptr, B, C, Hc, Wc, 0, max_len, eos, tokens_out, n_steps, nullptr, s);
-        gen_sizes = nullptr;
-        // the session is closed: nothing ragged outlives the call (a fixed-shape call behind it, txo_score included, starts from scratch;
-        // stepping on a ragged batch goes through txo_decode_begin_ragged)
-        session = false; rag = false;
-        return rc;
+        ImageBatch ib;
+        if (int r = ragged_batch(B, C, Hc, Wc, sizes, s, &ib)) return r;
+        return generate_common(&ib, img, B, ib.N, max_len, eos, tokens_out, n_steps, nullptr, s);
     }
 
-    // project_kv = false: generate() decides the form of the cross attention once it knows its decode path
+    // Opens the decode session on enc [B][N][D] (session.h), complete: no caller patches a field in behind this call.  kc: a ragged session's
+    // key counts.  beams: decode rows per image.  project_kv: a session opened through txo_decode_begin or txo_score may be prefilled, and the
+    // multi-position forward works on the projected K/V panels: such a session steps in the K/V form too (one-pass and stepwise logits of
+    // decoder.net() then come from the same weights), unless TXO_LATENT=1 pins the latent form.  false: generate() / generate_beam() choose it.
     int decode_begin(const float* enc, int B, int N, int eos, hipStream_t s) override { return begin_session(enc, B, N, eos, s, true); }
-    int begin_session(const float* enc, int B, int N, int eos, hipStream_t s, bool project_kv) {
+    int begin_session(const float* enc, int B, int N, int eos, hipStream_t s, bool project_kv, KeyCounts kc = {}, int beams = 1) {
         if (!ready) return fail(TXO_E_STATE, "weights not finalized");
         if (B < 1 || B > Bmax) return fail(TXO_E_INVALID, "batch exceeds engine max_batch");
         if (N < 1 || N > Nmax) return fail(TXO_E_INVALID, "token count exceeds engine max_tokens");
-        const int M = B * N;
+        if (kc.host) { if (int r = upload_i32(kc.host, slens, B, nullptr, 0, s)) return r; }
+        if (kc.dev) HIP_TRY(hipMemcpyAsync(slens, kc.dev, sizeof(int) * B, hipMemcpyDeviceToDevice, s));
         {   // the session's copy of the encoder rows in the storage type: A operand of the K/V projection; in the latent form what
             // every cross-attention tile of every layer reads (the caller's buffer is not referenced after this call)
-            const size_t n4 = (size_t)M * D / 4;
+            const size_t n4 = (size_t)B * N * D / 4;
             hipLaunchKernelGGL((cast_rows_kernel<T>), dim3((n4 + 255) / 256), dim3(256), 0, s, enc, enc_t, n4);
         }
-        sB = B; sN = N; sImg = B; session = true;
-        rag = false;                                          // (a ragged caller sets it behind this call)
-        ckv_valid = false;
-        kmask_on = false;
-        // a session opened through the C entry point steps with launches: it takes the form generate()'s launches take at this batch size
-        // A session opened through txo_decode_begin (project_kv) may be prefilled, and the multi-position forward works on the projected
-        // K/V panels: such a session steps in the K/V form too (one-pass and stepwise logits of decoder.net() then come from the same
-        // weights), unless TXO_LATENT=1 pins the latent form.  generate() / generate_beam() choose their form themselves.
-        use_latent = latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && !project_kv && auto_latent(B)));
-        lat_self = false;
-        if (!use_latent && project_kv) ensure_ckv(s);
-        lanes.split(sB, 1, s);
+        ses = Session{B * beams, N, B, true, kc.dev || kc.host, project_kv && latent_ok && knobs.lat_mode == 1};
+        if (!ses.latent && project_kv) ensure_ckv(s);
+        lanes.split(ses.rows, 1, s);
         reset_lanes(s, eos);
         HIP_TRY(hipGetLastError());
         return 0;
+    }
+    // The form of a launch-path decode, chosen by generate() / generate_beam() once the decode path is known.
+    void choose_form(bool row_stop, hipStream_t s) {
+        ses.latent = !ses.ragged && latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && auto_latent(ses.rows)));   // (ragged: K/V form)
+        ses.row_stop = row_stop;
+        ses.lat_self = ses.latent && lat_self_ok() && !row_stop;      // (the z history is not moved by compact_lane)
+        if (!ses.latent) ensure_ckv(s);                               // cross K/V of the session's images
     }
 
     // K/V of every decoder layer's cross attention in one GEMM: W = [Ld][k|v][Id][D] (attention.py:125-126).  The K/V form's decode
     // steps and the multi-position prefill read these panels; a latent-form session projects them only if a prefill asks.
     void ensure_ckv(hipStream_t s) {
-        if (ckv_valid) return;
-        const int M = sImg * sN;
-        gemm_plain(s, enc_t, wckv, M, cfg.dec_layers * 2 * Id, D, EpiHeads<T>{ckv, (size_t)M * Id, Id, cfg.dec_heads, sN});
-        ckv_valid = true;
+        if (ses.ckv_valid) return;
+        const int M = ses.images * ses.keys;
+        gemm_plain(s, enc_t, wckv, M, cfg.dec_layers * 2 * Id, D, EpiHeads<T>{ckv, (size_t)M * Id, Id, cfg.dec_heads, ses.keys});
+        ses.ckv_valid = true;
     }
 
-    int abandon_lanes(hipStream_t s, int rc) { stamps.slot = -1; return lanes.abandon(s, sB, rc); }
+    int abandon_lanes(hipStream_t s, int rc) { stamps.slot = -1; return lanes.abandon(s, ses.images, rc); }
     void reset_lanes(hipStream_t s, int eos) {
         for (int i = 0; i < lanes.n; ++i) {
             const LaneSet::Lane& ln = lanes[i];
             const int n = ln.nb > Tmax ? ln.nb : Tmax;
             hipLaunchKernelGGL(reset_state_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st + i, cur_tok + ln.b0,
                                eos_seen + ln.b0, done_flag + (size_t)i * Tmax, ln.nb, Tmax, cfg.bos, eos);
-            if (row_stop) hipLaunchKernelGGL(iota_kernel, dim3((ln.nb + 255) / 256), dim3(256), 0, s, row_map + ln.b0, ln.nb, ln.b0);
+            if (ses.row_stop) hipLaunchKernelGGL(iota_kernel, dim3((ln.nb + 255) / 256), dim3(256), 0, s, row_map + ln.b0, ln.nb, ln.b0);
         }
     }
 
@@ -1132,7 +1120,7 @@ struct Engine : EngineBase {
         bool cross = false; int apro = APRO_LN2;
         const T* W = nullptr; T* K = nullptr; T* V = nullptr; int lmax = 0, len = 0;
         float* x_out = nullptr;
-        int kv_div = 1; const short* path = nullptr;      // beam search: shared cross K/V, scattered self history
+        int kv_div = 1; const short* path = nullptr; int t_host = -1;   // beam search: shared cross K/V, scattered self history;  t_host: the position when the host knows it (enqueue_step)
     };
     void launch_dec_attn(hipStream_t s, int li, const AttnOpt& o) {
         const auto& ln = lanes[li];
@@ -1142,7 +1130,7 @@ struct Engine : EngineBase {
         a.gamma = dec_g; a.beta = dec_b; a.D = D; a.W = o.W;
         const size_t kr0 = o.cross ? r0 / o.kv_div : r0;      // cross panels are per IMAGE (kv_div beams share one)
         a.K = o.K + kr0 * cfg.dec_heads * o.lmax * DH; a.V = o.V + kr0 * cfg.dec_heads * o.lmax * DH;
-        a.out = dao + r0 * Id; a.heads = cfg.dec_heads; a.lmax = o.lmax; a.len = o.len; a.t_ptr = &st[li].t; a.t_host = step_host_t;
+        a.out = dao + r0 * Id; a.heads = cfg.dec_heads; a.lmax = o.lmax; a.len = o.len; a.t_ptr = &st[li].t; a.t_host = o.t_host;
         a.qin = dq + r0 * Id; a.kv_div = o.kv_div; a.path = o.path ? o.path + r0 * Tmax : nullptr; a.path_stride = Tmax;   // slots are range-local
         a.kmask = kmask + r0 * Tmax; a.kmask_stride = Tmax;
         a.stamps = (ln.nb * cfg.dec_heads <= Stamps::BLOCKS) ? stamps.next(o.cross ? "attn cross" : "attn self") : nullptr;
@@ -1169,7 +1157,7 @@ struct Engine : EngineBase {
             if (timed) hipExtLaunchKernelGGL((dec_attn_ragged_kernel<T, DA_NL_CROSS, NARROW>), grid, blk, 0, s, e0, e1, 0, a); \
             else hipLaunchKernelGGL((dec_attn_ragged_kernel<T, DA_NL_CROSS, NARROW>), grid, blk, 0, s, a);           \
         } while (0)
-        if (o.cross && rag) {                                     // per-slot key counts (dec_attn.h: RAGGED)
+        if (o.cross && ses.ragged) {                                     // per-slot key counts (dec_attn.h: RAGGED)
             a.lens = slens + kr0;
             if (narrow) TXO_DAR(true); else TXO_DAR(false);
         }
@@ -1178,7 +1166,7 @@ struct Engine : EngineBase {
             if (narrow) hipLaunchKernelGGL((dec_attn_kernel<T, ATT_SELF, APRO_NONE, NLS, 1, true, true>), grid, blk, 0, s, a);
             else hipLaunchKernelGGL((dec_attn_kernel<T, ATT_SELF, APRO_NONE, NLS, 1, false, true>), grid, blk, 0, s, a);
         }
-        else if (o.apro == APRO_NONE && kmask_on) {               // padding mask over the decoded positions (txo_decode_set_key_mask)
+        else if (o.apro == APRO_NONE && ses.kmask_on) {               // padding mask over the decoded positions (txo_decode_set_key_mask)
             if (narrow) hipLaunchKernelGGL((dec_attn_kernel<T, ATT_SELF, APRO_NONE, NLS, 1, true, false, true>), grid, blk, 0, s, a);
             else hipLaunchKernelGGL((dec_attn_kernel<T, ATT_SELF, APRO_NONE, NLS, 1, false, false, true>), grid, blk, 0, s, a);
         }
@@ -1216,7 +1204,7 @@ struct Engine : EngineBase {
         hipLaunchKernelGGL((grp_gemm_kernel<T, KG>), dim3((N + 63) / 64, (rows + 15) / 16), dim3(256), 0, s, g);
     }
     // the latent core over lane li's rows: q' in dqp, c to dcl.  Cross attention: enc = the session's encoder rows of the lane's first image,
-    // len = sN, every beam of an image reads the same rows (kv_div).  Self attention: enc = the lane's rows of the z history of one layer,
+    // len = ses.keys, every beam of an image reads the same rows (kv_div).  Self attention: enc = the lane's rows of the z history of one layer,
     // enc_rows = Tmax, len = position + 1 (host value or *t_ptr), kv_div = 1, path = the beams' slot tables (or null).
     // The latent core's output c feeds the folded output projection as its A operand: written in that GEMM's tiled layout (dec_gemm.h: a_tiled)
     // when the core serves the CROSS attention with folded weights.  A lane's region starts on a 16-row tile boundary and lanes do not overlap.
@@ -1230,7 +1218,7 @@ struct Engine : EngineBase {
         LatCoreArgs<T> a{};
         a.qp = dqp + r0 * HD; a.c = dcl + r0 * HD; a.enc = enc;
         if (c_tiled(layer, cross)) { a.c = dcl + c_base_row(li) * HD; a.c_hpr = H; }
-        a.rows = ln.nb; a.heads = H; a.G = latent_group(sB, n_cus); a.ngrp = (H + a.G - 1) / a.G; a.len = len; a.kv_div = kv_div;
+        a.rows = ln.nb; a.heads = H; a.G = latent_group(ses.rows, n_cus); a.ngrp = (H + a.G - 1) / a.G; a.len = len; a.kv_div = kv_div;
         a.enc_rows = enc_rows; a.t_ptr = t_ptr; a.path = path; a.path_stride = Tmax;
         int nimg = (ln.nb + kv_div - 1) / kv_div;
         if (cross && kv_div > 1 && ln.nb % kv_div == 0 && knobs.lat_g_env == 0) {
@@ -1266,16 +1254,16 @@ struct Engine : EngineBase {
     }
     // self attention of layer l in latent form (folded weights): [embedding / LN sandwich + q' = z M^T, z appended to the history] ->
     // [scores / values against the history of z]; the gated output projection (Wo' folded) follows in enqueue_step
-    int launch_lat_self(hipStream_t s, int li, int l, const BeamCtx* bm, const DecGemmArgs<T>& base) {
+    int launch_lat_self(hipStream_t s, int li, int l, const BeamCtx* bm, const DecGemmArgs<T>& base, int t_host) {
         const auto& ln = lanes[li];
         const size_t r0 = ln.b0;
         const int HD = cfg.dec_heads * D;
-        T* zl = zc + ((size_t)l * sB + r0) * Tmax * D;           // this lane's rows of layer l's history
+        T* zl = zc + ((size_t)l * ses.rows + r0) * Tmax * D;           // this lane's rows of layer l's history
         DecGemmArgs<T> a = base; a.N = HD; a.K = D; a.W = dec_self[l].wqp; a.y = dy + r0 * D; a.x_out = dx + r0 * D;
         a.tok = cur_tok + r0; a.tok_emb = tok_emb; a.pos_emb = pos_emb;
         a.h_out = dqp + r0 * HD; a.F = HD; a.z_cache = zl;
         if (int r = (l == 0 ? launch_dec_gemm<PRO_EMBED, EPI_STORE_T>(s, a) : launch_dec_gemm<PRO_LN2, EPI_STORE_T>(s, a))) return r;
-        launch_lat_core(s, li, 1, zl, step_host_t + 1, Tmax, step_host_t >= 0 ? nullptr : &st[li].t, bm ? bm->path_cur + r0 * Tmax : nullptr,
+        launch_lat_core(s, li, 1, zl, t_host + 1, Tmax, t_host >= 0 ? nullptr : &st[li].t, bm ? bm->path_cur + r0 * Tmax : nullptr,
                         "attn self (latent core)", false);
         return 0;
     }
@@ -1298,7 +1286,7 @@ struct Engine : EngineBase {
             launch_grp_gemm<DH>(s, dqt + r0 * Id, Id, dec_cross[l].wkT, dqp + r0 * HD, HD, ln.nb, HD, D);
         }
         // 3. c_h = softmax_n(q'_h . enc[n]) enc
-        launch_lat_core(s, li, kv_div, enc_t + (r0 / kv_div) * (size_t)sN * D, sN, 0, nullptr, nullptr, "attn cross (latent core)", true, l);
+        launch_lat_core(s, li, kv_div, enc_t + (r0 / kv_div) * (size_t)ses.keys * D, ses.keys, 0, nullptr, nullptr, "attn cross (latent core)", true, l);
         if (fold) return 0;                                       // 4+5: the gated output projection takes c directly (K = heads*D, Wo' folded at load)
         // 4. o_h = c_h Wv_h^T ; 'b h n d -> b n (h d)'
         if (D == 64) launch_grp_gemm<64>(s, dcl + r0 * HD, HD, dec_cross[l].wv, dao + r0 * Id, Id, ln.nb, Id, DH);
@@ -1312,9 +1300,8 @@ struct Engine : EngineBase {
     // device-side counter instead, which is what lets ONE captured graph serve every step
     int enqueue_step(hipStream_t s, int li, int64_t* tokens_out, int out_stride, float* logits_out, int eos,
                      const BeamCtx* bm = nullptr, int host_t = -1) {
-        step_host_t = host_t;
         const auto& ln = lanes[li];
-        const int B = sB, N = sN, nb = ln.nb;
+        const int B = ses.rows, N = ses.keys, nb = ln.nb;
         const size_t r0 = ln.b0;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (prof) { e0 = pool.next(); e1 = pool.next(); (void)hipEventRecord(e0, s); }
@@ -1323,20 +1310,20 @@ struct Engine : EngineBase {
         base.inner = Id; base.heads = cfg.dec_heads; base.tmax = Tmax;
         float* lx = dx + r0 * D; float* ly = dy + r0 * D; T* lao = dao + r0 * Id; T* lhid = dhid + r0 * Fd;
         float* llog = dlogits + r0 * V;
-        const size_t self_stride = (size_t)B * Id * Tmax, cross_stride = (size_t)sImg * N * Id;
+        const size_t self_stride = (size_t)B * Id * Tmax, cross_stride = (size_t)ses.images * N * Id;
         for (int l = 0; l < cfg.dec_layers; ++l) {
             T* kc = skv + (size_t)(2 * l) * self_stride; T* vc = skv + (size_t)(2 * l + 1) * self_stride;
-            if (lat_self) {   // causal self attention against the history of normalised block inputs (lat_attn.h)
-                if (int r = launch_lat_self(s, li, l, bm, base)) return r;
+            if (ses.lat_self) {   // causal self attention against the history of normalised block inputs (lat_attn.h)
+                if (int r = launch_lat_self(s, li, l, bm, base, host_t)) return r;
                 dbg(s, "self attn (latent)", l);
                 DecGemmArgs<T> g = base; g.N = 2 * D; g.K = cfg.dec_heads * D; g.W = dec_self[l].wo_f; g.bias = dec_self[l].bo;
                 g.A = dcl + r0 * cfg.dec_heads * D; g.resid = lx; g.y_out = ly;
                 if (!launch_dec_gemm_wide<EPI_GLU_RES>(s, g)) { if (int r = launch_dec_gemm<PRO_NONE, EPI_GLU_RES>(s, g)) return r; }
                 dbg(s, "self out", l);
             } else {   // causal self attention
-                AttnOpt o; o.W = dec_self[l].wqkv; o.K = kc; o.V = vc; o.lmax = Tmax; o.x_out = lx;
+                AttnOpt o; o.W = dec_self[l].wqkv; o.K = kc; o.V = vc; o.lmax = Tmax; o.x_out = lx; o.t_host = host_t;
                 if (bm) o.path = bm->path_cur;
-                if (knobs.self_plain || bm || kmask_on) {
+                if (knobs.self_plain || bm || ses.kmask_on) {
                     // default: LN sandwich + QKV GEMM (weights read once per 16 rows; k/v appended to the cache by
                     // its epilogue), then the plain cached attention.  TXO_SELF_FUSED=1 folds the projection into
                     // the attention launch instead (same wall time at B=64; re-reads 96 KB of weights per image).
@@ -1359,11 +1346,11 @@ struct Engine : EngineBase {
                 dbg(s, "self out", l);
             }
             {   // cross attention (LN sandwich + q projection fused in): against the raw encoder rows (latent form) or over the cached projections
-                const bool fold = use_latent && dec_cross[l].wqp != nullptr;
-                if (use_latent) { if (int r = launch_lat_cross(s, li, l, bm ? bm->k : 1, base)) return r; }
+                const bool fold = ses.latent && dec_cross[l].wqp != nullptr;
+                if (ses.latent) { if (int r = launch_lat_cross(s, li, l, bm ? bm->k : 1, base)) return r; }
                 else {
                 AttnOpt o; o.cross = true; o.W = dec_cross[l].wq; o.K = ckv + (size_t)(2 * l) * cross_stride;
-                o.V = ckv + (size_t)(2 * l + 1) * cross_stride; o.lmax = N; o.len = N; o.x_out = lx;
+                o.V = ckv + (size_t)(2 * l + 1) * cross_stride; o.lmax = N; o.len = N; o.x_out = lx; o.t_host = host_t;
                 if (bm) o.kv_div = bm->k;
                 launch_dec_attn(s, li, o);
                 }
@@ -1405,7 +1392,7 @@ struct Engine : EngineBase {
         StepArgs sa{llog, V, nb, cur_tok + r0, tokens_out ? tokens_out + r0 * out_stride : nullptr, out_stride,
                     logits_out ? logits_out + r0 * (size_t)out_stride * V : nullptr, st + li, eos_seen + r0,
                     done_flag + (size_t)li * Tmax, eos, sample_topk, 1.0f / sample_temp, sample_seed, (int)r0,
-                    row_stop ? 1 : 0, row_stop ? row_map + r0 : nullptr};
+                    ses.row_stop ? 1 : 0, ses.row_stop ? row_map + r0 : nullptr};
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
@@ -1420,7 +1407,7 @@ struct Engine : EngineBase {
     // capture lane li's step (tokens into the engine-owned tok_buf) as a graph, or reuse the cached one
     int lane_graph(int li, int eos) {
         const auto& ln = lanes[li];
-        const LaneSet::GraphKey key = {ln.b0, ln.nb, sN, eos, sB, sImg, (int)use_latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)rag};
+        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode);
         if (lanes.cached(li, key)) return 0;
         hipStream_t cs = lanes.cap_stream;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -1435,17 +1422,17 @@ struct Engine : EngineBase {
     }
 
     int decode_step(const int64_t* tok_in, int t, float* logits_out, int64_t* tok_out, hipStream_t s) override {
-        if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
+        if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (t < 0 || t >= Tmax)
             return fail(TXO_E_INVALID, "position outside the decoder's positional table (the reference would slide its "
                                        "window, decoder.py:99-100; a KV cache cannot reproduce that)");
         if (lanes.n != 1) return fail(TXO_E_STATE, "decode_step needs a session started by txo_decode_begin");
         lanes[0].stream = s;
-        if (tok_in) hipLaunchKernelGGL(copy_tokens_kernel, dim3((sB + 255) / 256), dim3(256), 0, s, cur_tok, tok_in, sB, V);
+        if (tok_in) hipLaunchKernelGGL(copy_tokens_kernel, dim3((ses.rows + 255) / 256), dim3(256), 0, s, cur_tok, tok_in, ses.rows, V);
         hipLaunchKernelGGL(set_position_kernel, dim3(1), dim3(1), 0, s, st, t);
         if (int r = enqueue_step(s, 0, nullptr, 0, nullptr, -1, nullptr, t)) return r;
-        if (logits_out) HIP_TRY(hipMemcpyAsync(logits_out, dlogits, sizeof(float) * sB * V, hipMemcpyDeviceToDevice, s));
-        if (tok_out) HIP_TRY(hipMemcpyAsync(tok_out, cur_tok, sizeof(int64_t) * sB, hipMemcpyDeviceToDevice, s));
+        if (logits_out) HIP_TRY(hipMemcpyAsync(logits_out, dlogits, sizeof(float) * ses.rows * V, hipMemcpyDeviceToDevice, s));
+        if (tok_out) HIP_TRY(hipMemcpyAsync(tok_out, cur_tok, sizeof(int64_t) * ses.rows, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -1455,22 +1442,22 @@ struct Engine : EngineBase {
     // the causal self attention (energy filled with -FLT_MAX).  Rows of padded positions are computed but unspecified (the reference
     // softmaxes them uniformly over all keys, future ones included; nothing reads them).  Applies to txo_decode_step of this session.
     int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) override {
-        if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
-        if (sImg != sB) return fail(TXO_E_STATE, "key masks are not available inside a beam-search session");
-        if (rag) return fail(TXO_E_INVALID, "txo_decode_set_key_mask: not available on a ragged batch session");
-        if (!mask) { kmask_on = false; return 0; }
+        if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
+        if (ses.images != ses.rows) return fail(TXO_E_STATE, "key masks are not available inside a beam-search session");
+        if (ses.ragged) return fail(TXO_E_INVALID, "txo_decode_set_key_mask: not available on a ragged batch session");
+        if (!mask) { ses.kmask_on = false; return 0; }
         if (cols < 1 || cols > Tmax) return fail(TXO_E_INVALID, "mask columns must be in [1, max_length]");
-        const int n = sB * Tmax;
-        hipLaunchKernelGGL(set_key_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, kmask, sB, cols, Tmax);
-        kmask_on = true;
+        const int n = ses.rows * Tmax;
+        hipLaunchKernelGGL(set_key_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, kmask, ses.rows, cols, Tmax);
+        ses.kmask_on = true;
         HIP_TRY(hipGetLastError());
         return 0;
     }
 
     int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) override {
         if (lanes.n != 1) return fail(TXO_E_STATE, "decode_prefill needs a session started by txo_decode_begin");
-        if (sImg != sB) return fail(TXO_E_STATE, "decode_prefill is not available inside a beam-search session");
-        if (session && rag) return fail(TXO_E_INVALID, "txo_decode_prefill: not available on a ragged batch session (the multi-position forward has no ragged form)");
+        if (ses.images != ses.rows) return fail(TXO_E_STATE, "decode_prefill is not available inside a beam-search session");
+        if (ses.open && ses.ragged) return fail(TXO_E_INVALID, "txo_decode_prefill: not available on a ragged batch session (the multi-position forward has no ragged form)");
         lanes[0].stream = s;
         return prefill(tokens, t, t, logits_out, nullptr, s);
     }
@@ -1478,10 +1465,10 @@ struct Engine : EngineBase {
     // AutoRegressiveDecoder.forward without autograd (decoder.py:124-145): tokens [B][L]; columns 0..L-2 are fed through the
     // multi-position forward, column p + 1 is the target of position p; per-position scores from the fused kernel of score.h
     int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
-        if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
+        if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (lanes.n != 1) return fail(TXO_E_STATE, "decode_score needs a session started by txo_decode_begin");
-        if (sImg != sB) return fail(TXO_E_STATE, "decode_score is not available inside a beam-search session");
-        if (rag) return fail(TXO_E_INVALID, "txo_decode_score: not available on a ragged batch session (the multi-position forward has no ragged form)");
+        if (ses.images != ses.rows) return fail(TXO_E_STATE, "decode_score is not available inside a beam-search session");
+        if (ses.ragged) return fail(TXO_E_INVALID, "txo_decode_score: not available on a ragged batch session (the multi-position forward has no ragged form)");
         lanes[0].stream = s;
         const ScoreOut so{logp_out, top1_out, top1_logp_out};
         return prefill(tokens, L, L - 1, nullptr, nullptr, s, &so);
@@ -1490,17 +1477,17 @@ struct Engine : EngineBase {
     // OCRModel.forward's path (ocr_model.py:38-44) in one call: encode into the engine's own buffer, open the session, mask, score
     int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
               int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
-        if (session && rag)
+        if (ses.open && ses.ragged)
             return fail(TXO_E_INVALID, "txo_score: a ragged batch session is open and ragged batches have no scoring path (open a fixed-shape session first)");
         if (int r = encode(img, B, C, H, W, eenc, s)) return r;
         if (int r = begin_session(eenc, B, 1 + (H / 16) * (W / 16), cfg.eos, s, true)) return r;
         if (mask) {
-            const int n = sB * Tmax;
-            hipLaunchKernelGGL(set_key_mask_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, kmask, sB, L, L - 1, Tmax);
-            kmask_on = true;
+            const int n = ses.rows * Tmax;
+            hipLaunchKernelGGL(set_key_mask_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, kmask, ses.rows, L, L - 1, Tmax);
+            ses.kmask_on = true;
         }
         const int rc = decode_score(tokens, L, logp_out, top1_out, top1_logp_out, s);
-        kmask_on = false;
+        ses.kmask_on = false;
         return rc;
     }
 
@@ -1518,16 +1505,16 @@ struct Engine : EngineBase {
         else hipLaunchKernelGGL((attn_mq_kernel<T, TO, false>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
     }
     int prefill(const int64_t* tokens, int tok_stride, int t, float* logits_out, float* last_logits, hipStream_t s, const ScoreOut* score = nullptr) {
-        if (!session) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
+        if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (t < 1 || t > Tmax) return fail(TXO_E_INVALID, "prefill length outside the decoder's positional table");
         // (only the logits GEMM's 8-wide store epilogue needs it: the scoring tail takes any vocabulary)
         if (logits_out && V % 8) return fail(TXO_E_INVALID, "prefill needs a vocabulary size that is a multiple of 8");
         const size_t cap = (size_t)Bmax * Nmax;               // rows of the encoder workspace
         if ((size_t)t > cap) return fail(TXO_E_INVALID, "prefill: one prefix does not fit the engine's workspace (max_batch * max_tokens rows)");
-        const int B = sB, N = sN, heads = cfg.dec_heads;
+        const int B = ses.rows, N = ses.keys, heads = cfg.dec_heads;
         ensure_ckv(s);
         const int bc = (int)std::min<size_t>(B, cap / t);     // images per chunk
-        const size_t self_stride = (size_t)B * Id * Tmax, cross_stride = (size_t)sImg * N * Id;
+        const size_t self_stride = (size_t)B * Id * Tmax, cross_stride = (size_t)ses.images * N * Id;
         T* qbuf = reinterpret_cast<T*>(eqkv);
         for (int b0 = 0; b0 < B; b0 += bc) {
             const int nb = std::min(bc, B - b0), M = nb * t;
@@ -1544,13 +1531,13 @@ struct Engine : EngineBase {
                 T* kc = skv + (size_t)(2 * l) * self_stride + (size_t)b0 * heads * Tmax * DH;
                 T* vc = skv + (size_t)(2 * l + 1) * self_stride + (size_t)b0 * heads * Tmax * DH;
                 gemm_plain(s, ez, dec_self[l].wqkv, M, 3 * Id, D, EpiHeadsKV<T>{qbuf, kc, vc, Id, heads, t, Tmax});
-                launch_attn_mq<T>(s, true, qbuf, kc, vc, eao, nb, t, t, Tmax, kmask_on ? kmask + (size_t)b0 * Tmax : nullptr);   // (padding mask of the session, if any)
+                launch_attn_mq<T>(s, true, qbuf, kc, vc, eao, nb, t, t, Tmax, ses.kmask_on ? kmask + (size_t)b0 * Tmax : nullptr);   // (padding mask of the session, if any)
                 gemm_plain(s, eao, dec_self[l].wo16, M, 2 * D, Id, EpiGluRes<sizeof(T) == 2>{ey, l == 0 ? res_first : res_x, dec_self[l].bo16});
-                // cross attention over the cached encoder projections (attention.py:114-126: k, v from the raw encoder output)
+                // cross attention over the cached encoder projections (attention.py:114-126); one row per image: no prefill in a beam session
                 launch_ln<3, T>(s, ey, estats, ez, dec_g, dec_b, M);
                 gemm_plain(s, ez, dec_cross[l].wq, M, Id, D, EpiHeads<T>{qbuf, 0, Id, heads, t});
-                const T* ck = ckv + (size_t)(2 * l) * cross_stride + (size_t)(b0 / std::max(1, sB / sImg)) * heads * N * DH;
-                const T* cv = ckv + (size_t)(2 * l + 1) * cross_stride + (size_t)(b0 / std::max(1, sB / sImg)) * heads * N * DH;
+                const T* ck = ckv + (size_t)(2 * l) * cross_stride + (size_t)b0 * heads * N * DH;
+                const T* cv = ckv + (size_t)(2 * l + 1) * cross_stride + (size_t)b0 * heads * N * DH;
                 launch_attn_mq<T>(s, false, qbuf, ck, cv, eao, nb, t, N, N);
                 gemm_plain(s, eao, dec_cross[l].wo16, M, 2 * D, Id, EpiGluRes<sizeof(T) == 2>{ey, res_x, dec_cross[l].bo16});
                 // GeGLU feed-forward
@@ -1579,7 +1566,6 @@ struct Engine : EngineBase {
             DecGemmArgs<T> f{};
             f.rows = B; f.D = D; f.inner = Id; f.heads = heads; f.tmax = Tmax; f.t_host = t - 1; f.t_ptr = &st[0].t;
             f.N = V; f.K = D; f.W = wlog; f.bias = blog; f.logits = last_logits; f.y = dy; f.gamma = decn_g; f.beta = decn_b;
-            step_host_t = t - 1;
             if (int r = launch_dec_gemm<PRO_LNF, EPI_LOGITS>(s, f)) return r;
         }
         HIP_TRY(hipGetLastError());
@@ -1596,7 +1582,7 @@ struct Engine : EngineBase {
         // sampling: the persistent kernel's sampler keeps a row in registers, 16 logits per lane (step.h: sample_row_regs)
         if (sample_mode && V > 64 * SR_PER) return false;
         if (prof || prof_cross || g_dbg || knobs.run.stamps || knobs.run.graph >= 0 || knobs.run.lanes > 0) return false;
-        if (rag) return false;                                 // a ragged batch decodes with launches (persist.h has no per-row key count)
+        if (ses.ragged) return false;                                 // a ragged batch decodes with launches (persist.h has no per-row key count)
         if (cfg.dec_exp != 4 || cfg.dec_layers > PS_MAXLD) return false;
         const bool exists = (D == 256 && cfg.dec_heads == 8) || (D == 768 && cfg.dec_heads == 12 && sizeof(T) == 2);
         if (!exists) return false;
@@ -1660,7 +1646,7 @@ struct Engine : EngineBase {
         pa.blog = blog;
         pa.dx = dx; pa.dy = dy; pa.dq = dq; pa.dlogits = dlogits; pa.dao = dao; pa.dhid = dhid;
         pa.cur_tok = cur_tok; pa.eos_seen = eos_seen; pa.skv = skv; pa.ckv = ckv;
-        pa.self_stride = (size_t)sB * Id * Tmax; pa.cross_stride = (size_t)sImg * N * Id;
+        pa.self_stride = (size_t)ses.rows * Id * Tmax; pa.cross_stride = (size_t)ses.images * N * Id;
         pa.tokens_out = tokens_out; pa.out_stride = out_stride; pa.logits_out = logits_out;
         pa.sample = sample_mode; pa.sample_topk = sample_topk; pa.inv_temp = 1.0f / sample_temp; pa.seed = sample_seed;
         pa.ctl = pctl; pa.stamps = pstamps;
@@ -1708,15 +1694,27 @@ struct Engine : EngineBase {
     // path the finished rows also stop costing work (compact_lane).
     int generate(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
                  int64_t* tokens_out, int* n_steps, float* logits_out, hipStream_t s) override {
-        int steps = 0;
-        row_stop = false; last_compactions = 0;
-        last_ragged = gen_sizes != nullptr;
-        const int rc = generate_impl(img, enc, B, C, H, W, N, max_len, eos, tokens_out, &steps, logits_out, s);
-        const bool compacted = last_compactions > 0;
-        row_stop = false;
+        last_compactions = 0; last_ragged = false;                // (results of THIS call, also when it is refused)
+        if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
+        // the window's multi-position forward (generate_window) has two preconditions: refuse BEFORE decoding anything
+        if (max_len > Tmax && (V % 8 != 0 || (size_t)Tmax > (size_t)Bmax * Nmax))
+            return fail(TXO_E_INVALID, "max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a vocabulary "
+                                       "size that is a multiple of 8 and max_length <= max_batch * max_tokens (use decoder.generate's stepwise loop)");
+        ImageBatch ib;
+        if (img) if (int r = fixed_batch(B, C, H, W, &ib)) return r;
+        return generate_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, max_len, eos, tokens_out, n_steps, logits_out, s);
+    }
+    // the common body of generate() / generate_ragged(): `ib` and its images, or (ib null) the caller's encoder rows src [B][N][D]
+    int generate_common(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* n_steps,
+                        float* logits_out, hipStream_t s) {
+        int steps = 0; last_compactions = 0;
+        last_ragged = ib && ib->ragged;
+        const int rc = generate_impl(ib, src, B, N, max_len, eos, tokens_out, &steps, logits_out, s);
+        ses.row_stop = false;                                     // the decode is over (a txo_decode_step behind it steps every row)
+        if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
         if (n_steps) *n_steps = steps;
-        if (compacted) session = false;                           // the session's rows are no longer the batch's: a new decode must begin
+        if (last_compactions > 0) ses.open = false;               // the session's rows are no longer the batch's: a new decode must begin
         if (stop_mode == 1 && eos >= 0 && steps > 0) {
             hipLaunchKernelGGL(pad_after_eos_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tokens_out, max_len, steps, B, eos, cfg.bos, cfg.pad);
             HIP_TRY(hipStreamSynchronize(s));
@@ -1724,14 +1722,13 @@ struct Engine : EngineBase {
         }
         return 0;
     }
-    bool row_stop = false;            // this generate compacts the live rows of its row ranges (launch path, stop_mode 1)
     // live rows of range li to its front; the range then launches `new_rows` rows (>= its live rows).  t1 = positions decoded so far.
     int compact_lane(int li, int new_rows, int t1, int eos) {
         auto& ln = lanes[li];
         hipStream_t s = ln.stream;
         const size_t r0 = ln.b0;
         CompactArgs ca{ln.nb, new_rows, (int)r0, cur_tok + r0, eos_seen + r0, row_map + r0, cur_tok2 + r0, row_map2 + r0, cmoves + 2 * r0,
-                       cinfo + 2 * li, st + li, eos, rag ? slens + r0 : nullptr, slens2 + r0};   // (a ragged session's key counts move with the rows)
+                       cinfo + 2 * li, st + li, eos, ses.ragged ? slens + r0 : nullptr, slens2 + r0};   // (a ragged session's key counts move with the rows)
         hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, s, ca);
         const int heads = cfg.dec_heads;
         auto move = [&](void* base, size_t outer_stride, size_t inner_stride, size_t row_stride, int outer_n, int inner_n, size_t len_elems) {
@@ -1741,55 +1738,34 @@ struct Engine : EngineBase {
             hipLaunchKernelGGL(move_rows_kernel, dim3((ma.len16 + 255) / 256, outer_n * inner_n), dim3(256), 0, s, ma);
         };
         // self-attention history [Ld][2][rows*heads][Tmax][64]: positions 0 .. t1-1 of every head of every moved row
-        move(skv + r0 * heads * Tmax * DH, (size_t)sB * Id * Tmax, (size_t)Tmax * DH, (size_t)heads * Tmax * DH, 2 * cfg.dec_layers, heads, (size_t)t1 * DH);
+        move(skv + r0 * heads * Tmax * DH, (size_t)ses.rows * Id * Tmax, (size_t)Tmax * DH, (size_t)heads * Tmax * DH, 2 * cfg.dec_layers, heads, (size_t)t1 * DH);
         // the cross attention's operand: the session's encoder rows (latent form) or the projected K/V panels [Ld][2][rows*heads][N][64]
-        if (use_latent) move(enc_t + r0 * sN * D, 0, 0, (size_t)sN * D, 1, 1, (size_t)sN * D);
-        else move(ckv + r0 * sN * Id, (size_t)sImg * sN * Id, 0, (size_t)sN * Id, 2 * cfg.dec_layers, 1, (size_t)sN * Id);
+        if (ses.latent) move(enc_t + r0 * ses.keys * D, 0, 0, (size_t)ses.keys * D, 1, 1, (size_t)ses.keys * D);
+        else move(ckv + r0 * ses.keys * Id, (size_t)ses.images * ses.keys * Id, 0, (size_t)ses.keys * Id, 2 * cfg.dec_layers, 1, (size_t)ses.keys * Id);
         ln.nb = new_rows;
         ++last_compactions;
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    int generate_impl(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
-                 int64_t* tokens_out, int* n_steps, float* logits_out, hipStream_t s) {
-        if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
+    int generate_impl(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* steps,
+                      float* logits_out, hipStream_t s) {
         // max_len > decoder.max_len: the reference slides its window (decoder.py:99-100).  The first Tmax positions decode with the
         // KV cache as always (n_pos of them; rows of the outputs are max_len apart); every further token re-runs its window of the
         // last Tmax tokens, positions re-indexed from 0, through ONE multi-position forward (prefill) -- generate_window below.
         const int n_pos = std::min(max_len, Tmax);
-        // the window's multi-position forward has two preconditions: refuse BEFORE decoding anything
-        if (max_len > Tmax && (V % 8 != 0 || (size_t)Tmax > (size_t)Bmax * Nmax))
-            return fail(TXO_E_INVALID, "max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a vocabulary "
-                                       "size that is a multiple of 8 and max_length <= max_batch * max_tokens (use decoder.generate's stepwise loop)");
-        const bool ragged = img && gen_sizes;                     // txo_generate_ragged: H x W is the container, the sizes are in rag_hw / rag_ntok
-        if (ragged) {
-            for (int b0 = 0, bc = enc_chunk_images(B); b0 < B; b0 += bc) {
-                const int nb = std::min(bc, B - b0);
-                if (int r = encode_images(img + (size_t)b0 * C * H * W, nb, C, H, W, eenc + (size_t)b0 * gen_ns * D, s, gen_ns, b0)) return r;
-            }
-            enc = eenc; N = gen_ns;
-        } else if (img) {
-            if (int r = encode(img, B, C, H, W, eenc, s)) return r;
-            enc = eenc; N = 1 + (H / 16) * (W / 16);
-        }
-        if (int r = begin_session(enc, B, N, eos, s, false)) return r;   // eos also decides whether the BOS column counts
-        if (ragged) {                                             // the session's key count per slot = the images' token counts
-            HIP_TRY(hipMemcpyAsync(slens, rag_ntok, sizeof(int) * B, hipMemcpyDeviceToDevice, s));
-            rag = true;
-        }
+        if (ib) { if (int r = encode_batch(*ib, src, eenc, s)) return r; src = eenc; }
+        // (eos also decides whether the BOS column counts; a ragged session's key count per slot = the images' token counts)
+        if (int r = begin_session(src, B, N, eos, s, false, KeyCounts{ib && ib->ragged ? rag_ntok : nullptr})) return r;
         last_persist = false;
         if (persist_cooldown > 0) --persist_cooldown;
         if (persist_usable(B)) {
-            int steps = 0;
-            use_latent = false; lat_self = false;
-            ensure_ckv(s);
+            ensure_ckv(s);                                        // (the persistent launch reads projected K/V panels: the session stays in the K/V form)
             bool broke = false;
-            const int pr = generate_persist(B, N, n_pos, max_len, eos, tokens_out, logits_out, &steps, &broke, s);
+            const int pr = generate_persist(B, N, n_pos, max_len, eos, tokens_out, logits_out, steps, &broke, s);
             if (pr == 0) {
                 last_persist = true; persist_strikes = 0;
                 // (an eos break exactly at position n_pos - 1 also leaves steps == n_pos: the window must not start then)
-                if (!broke && max_len > n_pos) { if (int r = generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, &steps, s)) return r; }
-                if (n_steps) *n_steps = steps;
+                if (!broke && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, steps, s);
                 return 0;
             }
             if (pr != TXO_E_STATE) return pr;
@@ -1798,7 +1774,7 @@ struct Engine : EngineBase {
                 persist_cooldown = 64; persist_strikes = 0;
                 fprintf(stderr, "[txo] persistent decode launch gave up twice in a row (%s): decoding with launches for the next 64 generates\n", g_err.c_str());
             }
-            lanes.split(sB, 1, s);
+            lanes.split(ses.rows, 1, s);
             reset_lanes(s, eos);
         }
         // lanes: graphs + extra streams unless per-step logits were asked for or a debug/profiling mode is on
@@ -1807,16 +1783,13 @@ struct Engine : EngineBase {
         // single-stream launches (57.1 vs 58.0 / 58.2 ms) -- so both stay opt-in: TXO_GRAPH=1, TXO_LANES=n.
         // graph replay by default only for very small batches (B <= 4: there the host's enqueue rate bounds the step --
         // 34.2 vs 37.2 ms per generate at B = 1 -- from B = 8 on it is equal); TXO_GRAPH=1 / 0 forces it on / off
-        use_latent = !rag && latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && auto_latent(B)));   // (ragged: K/V form)
         // per-row stop with live-row compaction: inside the positional table, tokens only (a finished row's logits would be unspecified)
-        row_stop = stop_mode == 1 && eos >= 0 && logits_out == nullptr && max_len <= Tmax && knobs.stop_every > 0 && !prof && !prof_cross;
-        lat_self = use_latent && lat_self_ok() && !row_stop;      // (the z history is not moved by compact_lane)
-        if (!use_latent) ensure_ckv(s);
+        choose_form(stop_mode == 1 && eos >= 0 && logits_out == nullptr && max_len <= Tmax && knobs.stop_every > 0 && !prof && !prof_cross, s);
         const bool want_graph = knobs.run.graph >= 0 ? knobs.run.graph != 0 : B <= 4;
         // per-row stop replays captured steps: as the ranges shrink a position's launches take less time than the host needs to enqueue them
         // (68 launches for two ranges: ~230 us per position on the host against 130 us on the device at 40 % of the rows), and a step
         // per row count (multiples of 16) is captured once and kept (lane_graph).  TXO_STOP_GRAPH=0: eager launches.
-        const bool stop_graph = row_stop && !sample_mode && knobs.stop_graph_on;
+        const bool stop_graph = ses.row_stop && !sample_mode && knobs.stop_graph_on;
         const bool eager = logits_out != nullptr || g_dbg || sample_mode || !(want_graph || stop_graph);
         // two row ranges on two streams for a WIDE decoder at >= 256 rows (BASELINE cfg 4): one range's latency-bound projection launches
         // run beside the other's HBM-bound attention launches (816 -> 834 images/s; four ranges: 765).  Greedy and sampled alike: a draw is keyed
@@ -1826,11 +1799,11 @@ struct Engine : EngineBase {
                     ((D >= 512 && B >= 256) || (D < 512 && B > PERSIST_MAX_BF16_GREEDY))) ? 2 : 1;
         // in latent form the second range pays from ~224 rows on (160: 66.6 ms with one range vs 71.7 with two, 192: 70.6 vs 72.2, 256: 82.0 vs 77.9;
         // K/V form: two ranges from 129 on, 160: 70.9 vs 66.3)
-        if (want == 2 && use_latent && D < 512 && B < 224) want = 1;
+        if (want == 2 && ses.latent && D < 512 && B < 224) want = 1;
         if (knobs.run.lanes > 0) want = std::min(knobs.run.lanes, MAXL);
         if (B < 32) want = 1;
         if (want == 2 && knobs.tune_lanes && !lanes.tuned) { if (int r = lanes.tune(n_cus, knobs.tune_verbose)) return r; }
-        lanes.split(sB, want, s);
+        lanes.split(ses.rows, want, s);
         last_ranges = lanes.n;
         reset_lanes(s, eos);
         bool use_graph = !eager && !prof && !prof_cross;   // event-carrying launches cannot be captured
@@ -1852,7 +1825,7 @@ struct Engine : EngineBase {
                 else if (int r2 = enqueue_step(lanes[i].stream, i, tdst, tstride, logits_out, eos, nullptr, t)) return r2;
             }
             if (eos < 0) continue;
-            if (row_stop) {
+            if (ses.row_stop) {
                 // Live-row compaction.  The host only needs an UPPER bound of a range's live rows to size its launches, and live rows only
                 // decrease: the finished-row counter of a range is copied to pinned memory behind a step, AHEAD more steps are enqueued,
                 // and only then the host reads it (never draining the stream, like the done flags).  compact_scan_kernel works on the
@@ -1889,10 +1862,9 @@ struct Engine : EngineBase {
                                      sizeof(int64_t) * n_pos, B, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
-        lanes.split(sB, 1, s);
-        int steps = poll.steps;
-        if (!poll.done && max_len > n_pos) { if (int r = generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, &steps, s)) return r; }
-        if (n_steps) *n_steps = steps;
+        lanes.split(ses.rows, 1, s);
+        *steps = poll.steps;
+        if (!poll.done && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, steps, s);
         return 0;
     }
 
@@ -1902,7 +1874,7 @@ struct Engine : EngineBase {
     // forward of Tmax rows per image (prefill) + the single-position final LayerNorm / logits / token selection of the step path.
     // The GLOBAL eos test still looks at the whole output (:115), i.e. the per-row "seen" state carries over.
     int generate_window(int B, int n_pos, int max_len, int eos, int64_t* tokens_out, float* logits_out, int* steps, hipStream_t s) {
-        lanes.split(sB, 1, s);
+        lanes.split(ses.rows, 1, s);
         lanes[0].stream = s;
         // the launch path's eos bookkeeping, rebuilt from the tokens decoded so far (a persistent launch keeps its own)
         HIP_TRY(hipMemsetAsync(st, 0, sizeof(StepState), s));
@@ -1939,19 +1911,17 @@ struct Engine : EngineBase {
             if (int r = encode(img, B, C, H, W, eenc, s)) return r;
             enc = eenc; N = 1 + (H / 16) * (W / 16);
         }
-        if (int r = begin_session(enc, B, N, eos, s, false)) return r;
-        use_latent = latent_ok && (knobs.lat_mode == 1 || (knobs.lat_mode < 0 && auto_latent(rows)));
-        lat_self = use_latent && lat_self_ok();
-        if (!use_latent) ensure_ckv(s);                               // cross K/V of the B images
-        sB = rows; sImg = B;                                          // decode rows are (image, beam) slots
+        // decode rows are (image, beam) slots for the length of this call: whatever way it ends, the session it leaves has one row per image
+        struct Rows { Session& ses; ~Rows() { ses.rows = ses.images; } } restore{ses};
+        if (int r = begin_session(enc, B, N, eos, s, false, {}, beams)) return r;
+        choose_form(false, s);
         last_persist = false;
-        lanes.split(sB, 1, s);
         // Two row ranges on two streams from 256 rows on, as generate() does beyond 128 images: one range's latency-bound projection
         // launches run beside the other's HBM-bound attention launches.  A range is a whole number of IMAGES (beam_select_kernel ranks
         // an image's k beams together; self-attention slots are range-local); every range has its own step state and done flags.
         int want = (rows >= 256 && B >= 2 && !prof && !prof_cross && !g_dbg) ? 2 : 1;
         if (knobs.run.lanes > 0) want = std::max(1, std::min(std::min(knobs.run.lanes, MAXL), B));
-        if (want == 2 && knobs.tune_lanes && !lanes.tuned) { if (int r = lanes.tune(n_cus, knobs.tune_verbose)) { sB = B; return r; } }
+        if (want == 2 && knobs.tune_lanes && !lanes.tuned) { if (int r = lanes.tune(n_cus, knobs.tune_verbose)) return r; }
         if (want > 1) lanes.split(rows, want, s, beams);
         last_ranges = lanes.n;
         const int n = std::max(rows, Tmax);
@@ -1977,10 +1947,10 @@ struct Engine : EngineBase {
         }
         return 0;
         };
-        if (int r = beam_loop()) { sB = B; return abandon_lanes(s, r); }
+        if (int r = beam_loop()) return abandon_lanes(s, r);
         if (int r = lanes.join(s)) return r;
         const int steps = poll.steps;
-        lanes.split(sB, 1, s);
+        lanes.split(rows, 1, s);
         // backtrack every beam into tok_buf rows, then hand out the best beam (slot 0: selection order is by score)
         hipLaunchKernelGGL(beam_backtrack_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, bparent, btok, Bmax, steps, rows,
                            tok_buf, Tmax);
@@ -1992,7 +1962,6 @@ struct Engine : EngineBase {
         if (scores_out) HIP_TRY(hipMemcpyAsync(scores_out, bscore, sizeof(float) * rows, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
-        sB = B;
         if (n_steps) *n_steps = steps;
         return 0;
     }
@@ -2001,7 +1970,7 @@ struct Engine : EngineBase {
         if (what == TXO_Q_LAST_PERSISTENT) *out = last_persist ? 1 : 0;
         else if (what == TXO_Q_PERSIST_FALLBACKS) *out = persist_fallbacks;
         else if (what == TXO_Q_LAST_ROW_RANGES) *out = last_persist ? 1 : last_ranges;
-        else if (what == TXO_Q_LAST_LATENT) *out = (!last_persist && use_latent) ? 1 : 0;
+        else if (what == TXO_Q_LAST_LATENT) *out = (!last_persist && ses.latent) ? 1 : 0;
         else if (what == TXO_Q_RELOAD_KNOBS) { knobs.run.read(); *out = 0; }
         else if (what == TXO_Q_LAST_COMPACTIONS) *out = last_compactions;
         else if (what == TXO_Q_LAST_RAGGED) *out = last_ragged ? 1 : 0;

@@ -8,8 +8,8 @@ namespace txo {
 
 struct LaneSet {
     static constexpr int MAXL = 4;
-    // captured steps, by what they were built for: {b0, nb, N, eos, sB, sImg, form flags} (the cache strides sB / sImg and the row count are
-    // baked into a graph's launches).  Per-row stop replays a step per row count of the shrinking range (multiples of 16): a handful of
+    // captured steps, by what they were built for: built in ONE place, Session::graph_key (session.h: the range, eos, and every field of the
+    // session a step's launches depend on).  Per-row stop replays a step per row count of the shrinking range (multiples of 16): a handful of
     // entries per range, built once and kept across generates.  exec = the entry the current decode replays.
     using GraphKey = std::array<int, 7>;
     struct Lane {

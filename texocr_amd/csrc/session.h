@@ -1,0 +1,31 @@
+// Session, the open decode session, and ImageBatch, what an encode is given, as values.  Host code, included by engine.hip only (after lanes.h).
+#pragma once
+
+namespace txo {
+// One decode session.  Engine::begin_session assigns a freshly constructed one, so nothing survives a new session by omission; behind it
+// only the transitions of a running decode write a field (Engine::ensure_ckv, the key-mask calls, choose_form and the ends of generate).
+struct Session {
+    int rows = 0, keys = 0, images = 0;   // decode rows, encoder tokens per image (ragged: the slot stride), images behind the cross K/V cache
+    bool open = false, ragged = false;    // ragged: per-slot key counts (Engine::slens)
+    bool latent = false;                  // the cross attention runs in latent form (lat_attn.h) ...
+    bool lat_self = false;                // ... and the self attention too (the history is z, not k / v)
+    bool ckv_valid = false;               // the projected cross K/V panels exist (the prefill needs them; the latent form does not)
+    bool kmask_on = false;                // padding mask over the decoded positions (txo_decode_set_key_mask)
+    bool row_stop = false;                // this generate compacts the live rows of its row ranges (launch path, stop_mode 1)
+    // what a captured step was built for (lanes.h): every field a step's launches depend on (strides and row count are baked into them)
+    LaneSet::GraphKey graph_key(const LaneSet::Lane& ln, int eos, int sample_mode) const {
+        return {ln.b0, ln.nb, keys, eos, rows, images, (int)latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)ragged};
+    }
+};
+struct KeyCounts { const int* dev = nullptr; const int32_t* host = nullptr; };   // a ragged session's key count per image: a device array or the caller's host array (staged)
+
+// What an encode is given: B images of C x H x W, N tokens each.  A ragged batch: H x W is the CONTAINER, N the slot stride of the encoder's
+// rows, and the sizes of image b are in Engine::rag_hw / rag_ntok at first + b.  Built by Engine::fixed_batch / ragged_batch, which check it.
+struct ImageBatch {
+    int B = 0, C = 0, H = 0, W = 0, N = 0;
+    bool ragged = false; int first = 0;
+    size_t pixels() const { return (size_t)C * H * W; }   // of one image (slot)
+    ImageBatch chunk(int b0, int nb) const { ImageBatch c = *this; c.first = first + b0; c.B = nb; return c; }
+};
+
+}  // namespace txo
