@@ -123,13 +123,12 @@ template <bool BEAM> struct DecAttnLds {
 };
 
 // One (image, head) pair `bh` by 256 threads (tid 0..255).  COH / wait_prev: see dec_gemm.h (persistent kernel); KV_EARLY:
-// the K panel does not depend on the previous stage (cross attention), so every wave except the one that polls the team
-// counter (tid < 64 of the workgroup's first group: a poll's wait would also wait for that wave's own panel) requests it
-// BEFORE the wait.  valid = false: same barriers, clamped addresses, no stores.
-// pf(): called once this tile's own loads have been issued (persistent kernel: requests the next stage's weights there).
-template <typename T, int MODE, int APRO, int NL, int WB, bool NARROW, bool BEAM, bool COH, class Wait, class Pf = NoPf, bool KMASK = false, bool RAGGED = false>
+// the K panel does not depend on the previous stage (cross attention), so every wave requests it BEFORE the wait (the wait
+// polls through the scalar data path and does not queue behind the panel: persist.h, TeamSync).
+// valid = false: same barriers, clamped addresses, no stores.
+template <typename T, int MODE, int APRO, int NL, int WB, bool NARROW, bool BEAM, bool COH, class Wait, bool KMASK = false, bool RAGGED = false>
 __device__ __forceinline__ void dec_attn_tile(const DecAttnArgs<T>& a, int bh, int tid, DecAttnLds<BEAM>& L_, bool valid,
-                                              bool poll_wave, Wait&& wait_prev, Pf&& pf = NoPf{}) {
+                                              Wait&& wait_prev) {
     constexpr int PER16 = Elem<T>::PER16;
     constexpr int LPR = DH / PER16;          // lanes per 64-element row: 16 (f32) / 8 (bf16)
     constexpr int KPI = 64 / LPR;            // keys per wave-instruction: 4 / 8
@@ -205,7 +204,7 @@ __device__ __forceinline__ void dec_attn_tile(const DecAttnArgs<T>& a, int bh, i
     // is read with the default policy (measured: self-attention launch 6.2 -> 5.4 us)
     // the self-attention cache is read with plain loads also in the persistent kernel: a row is final once its position's
     // hand-off has passed, and no CU reads it earlier (clamps below), so no L1 can hold an older copy of its lines
-    auto ld_kv = [](const T* p) -> u32x4 { if constexpr (MODE == ATT_SELF && !(COH && TXO_PS_W_NT)) return ld16(p); else return ld16_stream(p); };
+    auto ld_kv = [](const T* p) -> u32x4 { if constexpr (MODE == ATT_SELF) return ld16(p); else return ld16_stream(p); };
     int clamp_row = Lm1;
     auto issue_k = [&](int base) {
 #pragma unroll
@@ -217,20 +216,16 @@ __device__ __forceinline__ void dec_attn_tile(const DecAttnArgs<T>& a, int bh, i
     };
     [[maybe_unused]] u32x4 kt = {0u, 0u, 0u, 0u}, vt = {0u, 0u, 0u, 0u};
     if constexpr (KV_EARLY) {
-        if (!poll_wave) issue_k(0);
+        issue_k(0);
         wait_prev();
-        if (poll_wave) issue_k(0);
     } else if constexpr (HIST_EARLY) {
-        const bool early = t > 0 && !poll_wave;                // the polling wave's wait would wait for its own panel too
+        const bool early = t > 0;
         clamp_row = valid ? max(t - 1, 0) : 0;
         if (early) issue_k(0);
         wait_prev();
         if (!early) {
-            if (t > 0) issue_k(0);
-            else {
 #pragma unroll
-                for (int u = 0; u < NL; ++u) { rk[u] = kt; rv[u] = kt; }   // t = 0: no history; zeros (finite) under masked keys
-            }
+            for (int u = 0; u < NL; ++u) { rk[u] = kt; rv[u] = kt; }   // t = 0: no history; zeros (finite) under masked keys
         }
         kt = ld16(Kb + (size_t)t * DH + sub * PER16);
         vt = ld16(Vb + (size_t)t * DH + sub * PER16);
@@ -357,8 +352,6 @@ __device__ __forceinline__ void dec_attn_tile(const DecAttnArgs<T>& a, int bh, i
     for (int e = 0; e < PER16; ++e)
         qv[e] = (FUSED ? qkv[0][sub * PER16 + e] : ldc_f32<COH>(a.qin + (size_t)img * inner + head * DH + sub * PER16 + e)) * ATTN_SCALE;
 
-    pf();
-
     // ---- 4. passes over the panel (one pass when len <= NL*KPB) ----
     float m_run = (MODE == ATT_SELF && FUSED) ? s_new : -3.0e38f, l_run = 0.f;
     float acc[PER16];
@@ -481,13 +474,13 @@ __device__ __forceinline__ void dec_attn_idle(int L, Wait&& wait_prev) {
 template <typename T, int MODE, int APRO, int NL, int WB, bool NARROW, bool BEAM = false, bool KMASK = false>
 __global__ __launch_bounds__(256, 2) void dec_attn_kernel(DecAttnArgs<T> a) {
     __shared__ DecAttnLds<BEAM> lds;
-    dec_attn_tile<T, MODE, APRO, NL, WB, NARROW, BEAM, false, NoWait, NoPf, KMASK>(a, blockIdx.x, threadIdx.x, lds, true, false, NoWait{});
+    dec_attn_tile<T, MODE, APRO, NL, WB, NARROW, BEAM, false, NoWait, KMASK>(a, blockIdx.x, threadIdx.x, lds, true, NoWait{});
 }
 // cross attention of a ragged session: row r attends a.lens[r / kv_div] keys of its panel
 template <typename T, int NL, bool NARROW>
 __global__ __launch_bounds__(256, 2) void dec_attn_ragged_kernel(DecAttnArgs<T> a) {
     __shared__ DecAttnLds<false> lds;
-    dec_attn_tile<T, ATT_CROSS, APRO_LN2, NL, 1, NARROW, false, false, NoWait, NoPf, false, true>(a, blockIdx.x, threadIdx.x, lds, true, false, NoWait{});
+    dec_attn_tile<T, ATT_CROSS, APRO_LN2, NL, 1, NARROW, false, false, NoWait, false, true>(a, blockIdx.x, threadIdx.x, lds, true, NoWait{});
 }
 
 }  // namespace txo

@@ -75,18 +75,9 @@ template <bool COH> __device__ inline float4 ldc_f4(const float* p) {
 // kernel (the launch boundary is the dependency); the persistent kernel waits for its team's arrival counter here
 struct NoWait { __device__ inline void operator()() const {} };
 
-struct NoPf { __device__ inline void operator()() const {} };
-
-// Weight fragments of one tile (one wave's share, K fixed at compile time: KW 64-byte chunks per wave) can be requested one
-// stage ahead by the persistent kernel (dec_gemm_prefetch) into ONE small register buffer shared by all stages:
+// Weight fragments of one tile (one wave's share, K fixed at compile time: KW 64-byte chunks per wave) can be requested ahead of
+// the tile by the persistent kernel (dec_gemm_prefetch: the FFN-out fragments it keeps parked in LDS) into a small register buffer:
 // layout w0[0..KW) then (32-column tiles) w1[0..KW).
-// experiment build (-DTXO_PS_W_NT=1): inside the persistent kernel the decoder weights (18 MB per position and XCD, far beyond its 4 MiB
-// L2) are requested non-temporally, so that the stream does not push the latent cross attention's encoder rows (2.4 MB per XCD,
-// re-read by every layer) out of that L2
-#ifndef TXO_PS_W_NT
-#define TXO_PS_W_NT 0
-#endif
-template <bool COH> __device__ inline u32x4 ld16_w(const void* p) { if constexpr (COH && TXO_PS_W_NT) return ld16_stream(p); else return ld16(p); }
 constexpr int wfrag_regs(int KW, int BN) { return KW * (BN == 32 ? 2 : 1); }
 constexpr int WBUF_REGS = 8;
 struct WBuf { u32x4 r[WBUF_REGS]; };
@@ -186,12 +177,11 @@ __device__ __forceinline__ void dec_gemm_prefetch(WBuf& f, const T* W, int N, in
     }
 }
 
-// pre: the tile's weight fragments if they were requested earlier (persistent kernel), else null; pf(): called once the
-// tile's own activation loads have been issued -- the persistent kernel requests the NEXT stage's weights there (vector
-// memory returns in order, so anything requested before the activations would delay them)
-template <typename T, int PRO, int EPI, int KW, int BN, bool COH, bool HASPRE, class Wait, class Pf>
-__device__ __forceinline__ void dec_gemm_tile_pf(const DecGemmArgs<T>& a, int bx, int by, int tid, unsigned char* smem, bool valid,
-                                                 Wait&& wait_prev, const WBuf& pre, Pf&& pf) {
+// HASPRE: the tile's weight fragments are in `pre` already (persistent kernel: the FFN-out tile whose fragments stay parked in
+// LDS); otherwise the tile requests them itself and `pre` is not read (dec_gemm_tile below)
+template <typename T, int PRO, int EPI, int KW, int BN, bool COH, bool HASPRE, class Wait>
+__device__ __forceinline__ void dec_gemm_tile_pre(const DecGemmArgs<T>& a, int bx, int by, int tid, unsigned char* smem, bool valid,
+                                                  Wait&& wait_prev, const WBuf& pre) {
     // value/gate-paired epilogues (GLU, GeGLU) run on ONE 16-column tile whose weight rows are interleaved by 8
     // (8 value rows, then their 8 gate rows): lane lr < 8 holds the value, lane lr + 8 the gate of output n0/2 + lr
     constexpr bool PAIRED = EPI == EPI_GLU_RES || EPI == EPI_GEGLU;
@@ -246,7 +236,7 @@ __device__ __forceinline__ void dec_gemm_tile_pf(const DecGemmArgs<T>& a, int bx
 #pragma unroll
         for (int c = 0; c < GROUP; ++c) if (g0 + c < my_nch) {
             const int kc = wave + 4 * (g0 + c);
-            fw0[c] = ld16_w<COH>(w0 + (size_t)kc * wstep); if constexpr (TWO) fw1[c] = ld16_w<COH>(w1 + (size_t)kc * wstep);
+            fw0[c] = ld16(w0 + (size_t)kc * wstep); if constexpr (TWO) fw1[c] = ld16(w1 + (size_t)kc * wstep);
         }
     };
     auto load_a_global = [&](int g0) {
@@ -293,7 +283,7 @@ __device__ __forceinline__ void dec_gemm_tile_pf(const DecGemmArgs<T>& a, int bx
     }
     int t = 0;
     if constexpr (PRO == PRO_EMBED || EPI == EPI_QKV || (EPI == EPI_STORE_T && PRO != PRO_NONE)) t = a.t_host >= 0 ? a.t_host : *a.t_ptr;
-    if constexpr (PRO == PRO_NONE) { load_a_global(0); pf(); }
+    if constexpr (PRO == PRO_NONE) load_a_global(0);
     // keep every fragment load ahead of the first MFMA: with K fixed this is one basic block and the machine
     // scheduler would otherwise interleave loads and MFMAs four at a time (serialising the memory latency)
     __builtin_amdgcn_sched_barrier(0);
@@ -319,7 +309,6 @@ __device__ __forceinline__ void dec_gemm_tile_pf(const DecGemmArgs<T>& a, int bx
             for (int i = 0; i < NVMAX; ++i) if (i < nv)
                 v[i] = ldc_f4_at<COH>(a.y, (size_t)m * K + i * 64 + sub * 4);
         }
-        pf();
         if constexpr (PRO == PRO_LN2) ln16<NVMAX, sizeof(T) == 2>(v, nv, g, b, inv_d);
         if constexpr (PRO == PRO_EMBED || PRO == PRO_LN2) {
             if (bx == 0 && valid && m0 + r < rows) {
@@ -418,7 +407,7 @@ __device__ __forceinline__ void dec_gemm_tile_pf(const DecGemmArgs<T>& a, int bx
     }
 }
 
-// A group WITHOUT a tile in a round of the persistent kernel: the workgroup barriers of dec_gemm_tile_pf and nothing else (no
+// A group WITHOUT a tile in a round of the persistent kernel: the workgroup barriers of dec_gemm_tile and nothing else (no
 // dummy tile on clamped addresses: its 16 KB of weight requests would sit in the CU's vector-memory pipeline in front of the
 // other group's)
 template <int PRO, class Wait>
@@ -428,11 +417,12 @@ __device__ __forceinline__ void dec_gemm_idle(Wait&& wait_prev) {
     __syncthreads();                                          // partial sums written
 }
 
+// the tile without fragments requested earlier: every launch-per-stage kernel and every other stage of the persistent kernel
 template <typename T, int PRO, int EPI, int KW, int BN, bool COH, class Wait>
 __device__ __forceinline__ void dec_gemm_tile(const DecGemmArgs<T>& a, int bx, int by, int tid, unsigned char* smem, bool valid,
                                               Wait&& wait_prev) {
     const WBuf none{};
-    dec_gemm_tile_pf<T, PRO, EPI, KW, BN, COH, false>(a, bx, by, tid, smem, valid, wait_prev, none, NoPf{});
+    dec_gemm_tile_pre<T, PRO, EPI, KW, BN, COH, false>(a, bx, by, tid, smem, valid, wait_prev, none);
 }
 
 template <typename T, int PRO, int EPI, int KW, int BN = DG_BN>
@@ -443,7 +433,7 @@ void dec_gemm_kernel(DecGemmArgs<T> a) {
 }
 
 // ---- >= 128 rows of a wide decoder (launch path only) ---------------------------------------------------------------------------
-// dec_gemm_tile_pf's PRO_NONE form with RT row tiles of 16 per block that SHARE the block's weight fragments: 16-row blocks
+// dec_gemm_tile's PRO_NONE form with RT row tiles of 16 per block that SHARE the block's weight fragments: 16-row blocks
 // re-read every weight slice rows/16 times from L2 (74 MB per out-projection at 256 rows x 768), which is what bounds those
 // launches; 64-row blocks read a quarter of that.  Same K split over the four waves, same reduction order, same epilogue
 // arithmetic as the 16-row tile -> a row's bits do not depend on which of the two kernels computed it.  A separate function on
@@ -470,7 +460,7 @@ __device__ __forceinline__ void dec_gemm_wide_tile(const DecGemmArgs<T>& a, int 
     const T* w0 = a.W + (size_t)min(na, a.N - 1) * K + lg * PER16;
     const T* w1 = a.W + (size_t)min(nb, a.N - 1) * K + lg * PER16;
     int wstep = KCH;
-    if (a.w_tiled) {                                          // (dec_gemm_tile_pf)
+    if (a.w_tiled) {                                          // (dec_gemm_tile)
         const int nt = (a.N + 15) >> 4;
         w0 = a.W + ((size_t)min(na >> 4, nt - 1) * (K / KCH) * 16 + lr) * KCH + lg * PER16;
         w1 = a.W + ((size_t)min(nb >> 4, nt - 1) * (K / KCH) * 16 + lr) * KCH + lg * PER16;
@@ -506,7 +496,7 @@ __device__ __forceinline__ void dec_gemm_wide_tile(const DecGemmArgs<T>& a, int 
     }
     int t = 0;
     if constexpr (EPI == EPI_QKV) t = a.t_host >= 0 ? a.t_host : *a.t_ptr;
-    __builtin_amdgcn_sched_barrier(0);                        // every fragment load ahead of the first MFMA (see dec_gemm_tile_pf)
+    __builtin_amdgcn_sched_barrier(0);                        // every fragment load ahead of the first MFMA (see dec_gemm_tile)
     f32x4 acc0[RT], acc1[RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) { acc0[rt] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[rt] = f32x4{0.f, 0.f, 0.f, 0.f}; }

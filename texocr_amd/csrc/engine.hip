@@ -1653,8 +1653,6 @@ struct Engine : EngineBase {
         const char* stamp_file = knobs.run.pstamps ? knobs.run.pstamps_file.c_str() : nullptr;
         pa.stamp_step = stamp_file ? std::min(max_len - 1, 200) : -1;
         if (knobs.run.has_stagger) pa.stagger_ticks = knobs.run.stagger_ticks;
-        pa.poll_sleep = 1;
-        pa.poll_mode = 3;                           // default 3: scalar polls behind s_dcache_inv (persist.h: TeamSync::poll; -1.3 % per generate against vector polls)
         if (knobs.run.has_inject) pa.inject_fail = knobs.run.inject_fail; // tests: the give-up / fall-back path
         HIP_TRY(hipMemsetAsync(pctl, 0, sizeof(PersistCtl), s));
         if (stamp_file) HIP_TRY(hipMemsetAsync(pstamps, 0, sizeof(unsigned long long) * PS_TEAMS * PS_STAMP_RANKS * PS_MAX_STAGES * PS_STAMP_WORDS, s));

@@ -20,13 +20,17 @@
 //
 // Hand-off (one per stage, all-to-all inside the team): every storing wave drains its stores (s_waitcnt vmcnt(0)),
 // workgroup barrier, ONE plain store of the stage number into the workgroup's word of the team's flag line; a consumer
-// polls that line from one wave (scalar loads behind s_dcache_inv by default, or sc1 vector loads: TeamSync), workgroup barrier, then
-// reads the rows with sc1 loads (never from its CU's L1, which other CUs' stores do not refresh; the XCD's L2 -- the coherence point
-// of its 32 CUs -- serves them).  Stores are plain (they stay
-// in that L2).  This is valid only while producer and consumer share an XCD: each workgroup ORs its XCC id into a
-// per-team mask, and after the first hand-off every workgroup checks that its team's mask has ONE bit; otherwise the
-// launch gives up (ctl.fail) and the engine decodes with launches.  All spins are bounded (4 ms of the real-time counter, fail bit 0;
-// the fail word is read with every scalar poll, so one team's give-up ends every team within a hand-off).
+// polls that line from one wave through the SCALAR data path (TeamSync), workgroup barrier, then reads the rows with sc1
+// loads (never from its CU's L1, which other CUs' stores do not refresh; the XCD's L2 -- the coherence point of its 32 CUs --
+// serves them).  Scalar polls are counted by lgkmcnt and stay out of the wave's vector-memory queue, which returns in order:
+// that is what lets EVERY wave request its weights, its cross K panel and its self-attention history BEFORE the wait
+// without the poll's data arriving behind them.  Stores are plain (they stay in that L2).  This is valid only while producer
+// and consumer share an XCD: each workgroup ORs its XCC id into a per-team mask, and after the first hand-off every
+// workgroup checks that its team's mask has ONE bit; otherwise the launch gives up (ctl.fail) and the engine decodes with
+// launches.  All spins are bounded (4 ms of the real-time counter, fail bit 0; the fail word is read with every poll, so one
+// team's give-up ends every team within a hand-off).
+// Measured and removed (DESIGN_HISTORY.md, "Removed from the persistent kernel"): vector and glc polls, several polls in
+// flight, weights requested one stage ahead into registers, non-temporal weight loads.
 //
 // GLOBAL eos break: a row handler counts first occurrences of eos per team; a team whose rows all contain eos sets its
 // bit in a chip-wide mask (memory-side atomic).  Teams are not synchronised with each other, so once the mask is full a team
@@ -39,10 +43,6 @@
 #include "dec_gemm.h"
 #include "step.h"
 
-// build-time experiment switches (probes/ab_libs.sh): weights requested one stage ahead into registers
-#ifndef TXO_PS_AHEAD
-#define TXO_PS_AHEAD false
-#endif
 // per-tile stamps of the attention stages in the TXO_PSTAMPS dump (diagnostic build: -DTXO_PS_ATTN_STAMPS=true)
 #ifndef TXO_PS_ATTN_STAMPS
 #define TXO_PS_ATTN_STAMPS false
@@ -83,11 +83,8 @@ template <typename T> struct PersistArgs {
     T *skv, *ckv; size_t self_stride, cross_stride;           // per (layer, k|v) plane
     int64_t* tokens_out; int out_stride; float* logits_out;
     PersistCtl* ctl;
-    int poll_sleep;                                           // TeamSync: 64-clock sleeps between two polls of the flag line
     int w_tiled;                                              // the projections' weights (wqkv, wo_s, wo_c, w1, w2, wlog) are the TILED copies (dec_gemm.h); wq_c stays row-major (dec_attn.h reads it)
     int sample; int sample_topk; float inv_temp; unsigned long long seed;   // sample != 0: the reference's sampler ends a position (step.h: sample_row) instead of the arg-max
-    int early_mask;                                           // bit 0 / 1: the POLLING wave also requests its self-attention history / its cross K panel before the wait (its poll then returns behind them)
-    int poll_mode;                                            // TeamSync::poll: 0 vector sc1 loads, 1 scalar glc loads, 2 the same behind s_dcache_inv, 3 (default) s_dcache_inv + plain scalar loads
     int inject_fail;                                          // test hook: position at which team 0 reports a hand-off time-out (0 = never)
     int stagger_ticks;                                        // experiment: team k starts k * this many 10-ns ticks late (desynchronises the teams' HBM phases)
     unsigned long long* stamps; int stamp_step;               // diagnostic: [team][PS_STAMP_RANKS][stage][5] ticks at that position (ranks 0, 10, 20, 31)
@@ -95,9 +92,12 @@ template <typename T> struct PersistArgs {
 
 // The team's arrival flags, seen from one workgroup.  Every workgroup owns ONE word of its team's 128-byte flag line and stores
 // the number of the stage it has finished there (a plain store: it lands in the XCD's L2 like the stage's rows, and it is issued
-// only after every wave's row stores have been acknowledged).  A consumer's first wave reads the whole line with one sc1 load per
-// poll (lane r reads workgroup r's word) until every word has reached the stage it waits for.  No atomic is involved: an
-// agent-scope atomic add executes at the memory side, ~0.5-1 us away, and cost more than the stage's arithmetic
+// only after every wave's row stores have been acknowledged).  A consumer's first wave reads the whole line and the launch's
+// fail word per poll until every word has reached the stage it waits for: s_dcache_inv, then ordinary SCALAR loads, which miss
+// the just-invalidated scalar cache and read the XCD's L2, where the producers' plain stores are.  The scalar path keeps the
+// poll out of the wave's vector-memory queue (vector loads return in order: behind a vector poll, a panel or weights requested
+// before the wait would have to land first), so every wave requests early.  No atomic is involved: an agent-scope atomic add
+// executes at the memory side, ~0.5-1 us away, and cost more than the stage's arithmetic
 // (profiles/r02_persist_v4_stamps.txt: "pub").
 typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
 __device__ inline unsigned min8(const u32x8& v) {
@@ -111,16 +111,7 @@ struct TeamSync {
     unsigned* flags;                                          // this team's line: PS_TEAM_BLOCKS words
     int rank; unsigned epoch;                                 // stages this workgroup has finished
     unsigned* fail; int* lds_dead; bool armed, dead;
-    int poll_sleep;                                           // s_sleep(1) units (64 clocks) between two polls
-    // poll: 0 = one vector load of the line per poll (sc1: served by the XCD's L2); 3 (default) = s_dcache_inv + ordinary SCALAR
-    // loads (they miss the just-invalidated scalar cache and read the XCD's L2, where the producers' plain stores are); 1 / 2 =
-    // scalar loads with glc (correct, but every poll then sees a flag 5-17 us late: profiles/r03_decode_floor_experiments.txt).
-    // The scalar path keeps the poll out of the wave's vector-memory queue: vector loads return in order, so a wave that polls
-    // with vector loads cannot request its K/V panel or weights BEFORE the wait without the poll's data arriving behind them --
-    // with scalar polls EVERY wave requests early (-1.3 ... 1.9 % per generate).
-    int poll;
     unsigned long long* stp;                                  // diagnostic: 5 ticks per stage (wait begin / end, drain begin / end, published)
-    __device__ inline bool early_all() const { return poll != 0; }
     __device__ inline void operator()() {                     // wait until every workgroup of the team has finished the previous stage
         if (!armed) return;
         armed = false;
@@ -129,54 +120,24 @@ struct TeamSync {
             const int lane = threadIdx.x;
             unsigned spins = 0;
             const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-            if (poll != 0) {
-                // the whole 128-byte line + the launch's fail word per poll, through the scalar data path (lgkmcnt, not vmcnt)
-                for (;;) {
-                    u32x8 f0, f1, f2, f3; unsigned fl;
-                    if (poll == 3) {                          // invalidate the scalar cache, then ordinary scalar loads (they miss it and read the L2)
-                        asm volatile("s_dcache_inv\n\t"
-                                     "s_load_dwordx8 %0, %5, 0x0\n\t"
-                                     "s_load_dwordx8 %1, %5, 0x20\n\t"
-                                     "s_load_dwordx8 %2, %5, 0x40\n\t"
-                                     "s_load_dwordx8 %3, %5, 0x60\n\t"
-                                     "s_load_dword %4, %6, 0x0\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=&s"(f0), "=&s"(f1), "=&s"(f2), "=&s"(f3), "=&s"(fl) : "s"(flags), "s"(fail) : "memory");
-                    } else {
-                    if (poll == 2) asm volatile("s_dcache_inv" ::: "memory");
-                    asm volatile("s_load_dwordx8 %0, %5, 0x0 glc\n\t"
-                                 "s_load_dwordx8 %1, %5, 0x20 glc\n\t"
-                                 "s_load_dwordx8 %2, %5, 0x40 glc\n\t"
-                                 "s_load_dwordx8 %3, %5, 0x60 glc\n\t"
-                                 "s_load_dword %4, %6, 0x0 glc\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=&s"(f0), "=&s"(f1), "=&s"(f2), "=&s"(f3), "=&s"(fl) : "s"(flags), "s"(fail) : "memory");
-                    }
-                    const unsigned behind = min(min(min8(f0), min8(f1)), min(min8(f2), min8(f3)));
-                    if (behind >= epoch) break;
-                    // give up when another workgroup has (every hand-off sees the fail word) or after PS_GIVE_UP_TICKS
-                    if (fl != 0u || ((++spins & 63u) == 0u && __builtin_amdgcn_s_memrealtime() - t_begin > (epoch <= 2u ? PS_GIVE_UP_FIRST_TICKS : PS_GIVE_UP_TICKS))) {
-                        if (lane == 0) { atomicOr(fail, 1u); *lds_dead = 1; }
-                        break;
-                    }
-                    for (int i = 0; i < poll_sleep; ++i) __builtin_amdgcn_s_sleep(1);
+            for (;;) {                                    // the whole 128-byte line + the fail word through the scalar data path (lgkmcnt, not vmcnt)
+                u32x8 f0, f1, f2, f3; unsigned fl;
+                asm volatile("s_dcache_inv\n\t"
+                             "s_load_dwordx8 %0, %5, 0x0\n\t"
+                             "s_load_dwordx8 %1, %5, 0x20\n\t"
+                             "s_load_dwordx8 %2, %5, 0x40\n\t"
+                             "s_load_dwordx8 %3, %5, 0x60\n\t"
+                             "s_load_dword %4, %6, 0x0\n\t"
+                             "s_waitcnt lgkmcnt(0)"
+                             : "=&s"(f0), "=&s"(f1), "=&s"(f2), "=&s"(f3), "=&s"(fl) : "s"(flags), "s"(fail) : "memory");
+                const unsigned behind = min(min(min8(f0), min8(f1)), min(min8(f2), min8(f3)));
+                if (behind >= epoch) break;
+                // give up when another workgroup has (every hand-off sees the fail word) or after PS_GIVE_UP_TICKS
+                if (fl != 0u || ((++spins & 63u) == 0u && __builtin_amdgcn_s_memrealtime() - t_begin > (epoch <= 2u ? PS_GIVE_UP_FIRST_TICKS : PS_GIVE_UP_TICKS))) {
+                    if (lane == 0) { atomicOr(fail, 1u); *lds_dead = 1; }
+                    break;
                 }
-            } else {
-                // ONE poll in flight.  (Four, a quarter of a round trip apart, to see the last arrival sooner: 37.2 vs 36.5 ms per
-                // generate -- the extra reads of the line queue in front of the arrivals' stores at its L2 channel.)
-                for (;;) {
-                    const unsigned v = lane < PS_TEAM_BLOCKS ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : epoch;
-                    if (__builtin_amdgcn_ballot_w64(v < epoch) == 0ull) break;
-                    for (int i = 0; i < poll_sleep; ++i) __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 255u) == 0u) {             // give up after PS_GIVE_UP_TICKS or when another workgroup has
-                        if (__builtin_amdgcn_s_memrealtime() - t_begin > (epoch <= 2u ? PS_GIVE_UP_FIRST_TICKS : PS_GIVE_UP_TICKS) ||
-                            __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                            if (lane == 0) { atomicOr(fail, 1u); *lds_dead = 1; }
-                            break;
-                        }
-                    }
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_sleep(1);
             }
             if (stp && threadIdx.x == 0) stp[1] = __builtin_amdgcn_s_memrealtime();
         }
@@ -263,7 +224,7 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
         while (__builtin_amdgcn_s_memrealtime() - t0 < until) __builtin_amdgcn_s_sleep(8);
     }
     __syncthreads();
-    TeamSync ts{&ctl->flags[team][0], rank, 0u, &ctl->fail, lds_dead, false, false, a.poll_sleep, a.poll_mode, nullptr};
+    TeamSync ts{&ctl->flags[team][0], rank, 0u, &ctl->fail, lds_dead, false, false, nullptr};
     bool placement_checked = false;
 
     // LayerNorm parameters -> LDS once: {gamma, beta} of the stack's shared norm, then of the final norm
@@ -279,27 +240,13 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
     gb.rows = nr; gb.gamma = a.gamma; gb.beta = a.beta; gb.t_ptr = nullptr; gb.D = D; gb.inner = ID; gb.heads = HEADS; gb.tmax = a.Tmax;
     float* lx = a.dx + (size_t)r0 * D; float* ly = a.dy + (size_t)r0 * D; float* lq = a.dq + (size_t)r0 * ID;
     T* lao = a.dao + (size_t)r0 * ID; T* lhid = a.dhid + (size_t)r0 * F; float* llog = a.dlogits + (size_t)r0 * a.V;
-    const bool poll_wave = threadIdx.x < 64 && !ts.early_all();   // a wave that polls with VECTOR loads requests its panel behind the wait
     const int srank = rank == 0 ? 0 : (rank == 10 ? 1 : (rank == 20 ? 2 : (rank == PS_TEAM_BLOCKS - 1 ? 3 : -1)));
     unsigned long long* stamp_base = (a.stamps && srank >= 0 && threadIdx.x == 0)
         ? a.stamps + ((size_t)team * PS_STAMP_RANKS + srank) * PS_MAX_STAGES * PS_STAMP_WORDS : nullptr;
 
-    // the tile column this group takes in round 0 of a GEMM stage with `ncol` column tiles (what PS_GEMM computes)
-    auto bx0 = [&](int ncol) { const int nt = ncol * nrt; return (sa < nt ? sa : nt - 1) % ncol; };
-    auto has0 = [&](int ncol) { return rank < ncol * nrt; };            // this workgroup runs a tile in round 0
     constexpr int KWP = ps_kw_pro<T>(D), KWI = ps_kw_half<T>(ID), KWF = ps_kw_half<T>(F);
     constexpr int NC_QKV = (3 * ID + 31) / 32, NC_O = 2 * D / 16, NC_F1 = 2 * F / 32, NC_F2 = D / 16;
     const int nc_log = (a.V + 31) / 32;
-    // ONE register buffer for the weight fragments requested a stage ahead (<= 8 x 16 bytes per lane; stages whose tile needs
-    // more request their weights themselves, as the launch path does)
-    // PS_AHEAD: request a stage's weights one stage ahead into `wbuf`.  Measured (profiles/r02_persist_*): the 32 extra live
-    // registers push the attention stages (already at the 256-VGPR limit of an 8-wave workgroup) into scratch, and the
-    // arrival's vmcnt(0) drain waits for the early request anyway (vector memory returns in order) -- slower, so off.
-    constexpr bool PS_AHEAD = TXO_PS_AHEAD;
-    constexpr bool PF_P = PS_AHEAD && KWP > 0 && wfrag_regs(KWP, 32) <= WBUF_REGS, PF_I = PS_AHEAD && KWI > 0 && wfrag_regs(KWI, 16) <= WBUF_REGS,
-                   PF_F = PS_AHEAD && KWF > 0 && wfrag_regs(KWF, 16) <= WBUF_REGS;
-    WBuf wbuf;
-    if constexpr (PF_P) dec_gemm_prefetch<T, KWP, 32>(wbuf, a.L[0].wqkv, 3 * ID, bx0(NC_QKV), tid, has0(NC_QKV), a.w_tiled);
 
     // FFN-out (K = 4D: the longest weight rows of the step, 32 KB per tile) waited ~1.7 us per stage for its fragments to come
     // from the Infinity Cache (profiles/r02_persist_v6_stamps.txt: "reduce").  Its 16 tiles per layer are therefore pinned to
@@ -335,10 +282,8 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
         }
         int stage = 0;
         ts.stp = (stamp_base && t == a.stamp_step) ? stamp_base : nullptr;
-        // one GEMM stage: tiles (bx, by) dealt over the team's groups; a workgroup with no tile only synchronises.
-        // PRE: the first round's weight fragments when an earlier stage requested them (else nullptr); PF: what this stage
-        // requests for a later one once its own loads are out
-#define PS_GEMM(PRO, EPI, KW, BN, ARGS, NCOL, PRE, PF)                                                                  \
+        // one GEMM stage: tiles (bx, by) dealt over the team's groups; a workgroup with no tile only synchronises
+#define PS_GEMM(PRO, EPI, KW, BN, ARGS, NCOL)                                                                           \
         do {                                                                                                            \
             const int ncol_ = (NCOL), nt_ = ncol_ * nrt;                                                                \
             for (int base_ = 0; base_ < nt_; base_ += NSB) {                                                            \
@@ -349,17 +294,17 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                     else if (base_ == 0) {                                                                              \
                         auto args_ = ARGS;                                                                              \
                         args_.stamps = (ts.stp && grp == 0) ? ts.stp + 5 - 3 * tile_ : nullptr;   /* tile stamps land at stp[5..7] */ \
-                        dec_gemm_tile_pf<T, PRO, EPI, KW, BN, true, PRE>(args_, tile_ % ncol_, tile_ / ncol_, tid, smem, true, ts, wbuf, PF); \
+                        dec_gemm_tile<T, PRO, EPI, KW, BN, true>(args_, tile_ % ncol_, tile_ / ncol_, tid, smem, true, ts); \
                     }                                                                                                   \
                     else dec_gemm_tile<T, PRO, EPI, KW, BN, true>(ARGS, tile_ % ncol_, tile_ / ncol_, tid, smem, true, ts); \
-                } else if (base_ == 0) { ts(); PF(); }                                                                  \
+                } else if (base_ == 0) ts();                                                                            \
             }                                                                                                           \
             ts();                                                                                                       \
             ts.arrive();                                                                                                \
             ++stage;                                                                                                    \
         } while (0)
         // LK: keys of the panel (a group without a tile mirrors the tile's barriers)
-#define PS_ATTN(MODE, APRO, NLV, ARGS, PF, LK)                                                                          \
+#define PS_ATTN(MODE, APRO, NLV, ARGS, LK)                                                                              \
         do {                                                                                                            \
             const int np_ = nr * HEADS;                                                                                 \
             for (int base_ = 0; base_ < np_; base_ += NSB) {                                                            \
@@ -371,11 +316,11 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                         auto args_ = ARGS;                                                                              \
                         args_.stamps = (PS_ATTN_STAMPS && ts.stp && grp == 0) ? ts.stp + 5 - 3 * p_ : nullptr;   /* tile stamps land at stp[5..7] */ \
                         dec_attn_tile<T, MODE, APRO, NLV, 1, false, false, true>(args_, p_, tid,                       \
-                            *reinterpret_cast<DecAttnLds<false>*>(smem), true, poll_wave && !((a.early_mask >> (MODE == ATT_SELF ? 0 : 1)) & 1), ts, PF); \
+                            *reinterpret_cast<DecAttnLds<false>*>(smem), true, ts); \
                     }                                                                                                   \
                     else dec_attn_tile<T, MODE, APRO, NLV, 1, false, false, true>(ARGS, p_, tid,          \
-                        *reinterpret_cast<DecAttnLds<false>*>(smem), true, poll_wave && !((a.early_mask >> (MODE == ATT_SELF ? 0 : 1)) & 1), ts); \
-                } else if (base_ == 0) { ts(); PF(); }                                                                  \
+                        *reinterpret_cast<DecAttnLds<false>*>(smem), true, ts); \
+                } else if (base_ == 0) ts();                                                                            \
             }                                                                                                           \
             ts();                                                                                                       \
             ts.arrive();                                                                                                \
@@ -386,22 +331,11 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
             const PersistLayer<T>& W = a.L[l];
             T* kc = a.skv + (size_t)(2 * l) * a.self_stride + (size_t)r0 * HEADS * a.Tmax * DH;
             T* vc = a.skv + (size_t)(2 * l + 1) * a.self_stride + (size_t)r0 * HEADS * a.Tmax * DH;
-            auto pf_os = [&]() { if constexpr (PF_I) dec_gemm_prefetch<T, KWI, 16>(wbuf, W.wo_s, 2 * D, bx0(NC_O), tid, has0(NC_O), a.w_tiled); };
-            auto pf_oc = [&]() { if constexpr (PF_I) dec_gemm_prefetch<T, KWI, 16>(wbuf, W.wo_c, 2 * D, bx0(NC_O), tid, has0(NC_O), a.w_tiled); };
-            auto pf_f1 = [&]() { if constexpr (PF_P) dec_gemm_prefetch<T, KWP, 32>(wbuf, W.w1, 2 * F, bx0(NC_F1), tid, has0(NC_F1), a.w_tiled); };
-            auto pf_f2 = [&]() { if constexpr (PF_F) dec_gemm_prefetch<T, KWF, 16>(wbuf, W.w2, D, bx0(NC_F2), tid, has0(NC_F2), a.w_tiled); };
-            auto pf_next = [&]() {                            // behind the layer's last stage: next layer's q,k,v or the logits
-                if constexpr (PF_P) {
-                    if (l + 1 < a.Ld) dec_gemm_prefetch<T, KWP, 32>(wbuf, a.L[l + 1].wqkv, 3 * ID, bx0(NC_QKV), tid, has0(NC_QKV), a.w_tiled);
-                    else dec_gemm_prefetch<T, KWP, 32>(wbuf, a.wlog, a.V, bx0(nc_log), tid, has0(nc_log), a.w_tiled);
-                }
-            };
-            auto none = []() {};
             {   // LN sandwich (or token + position embedding) + q,k,v projection; k,v appended to the cache (attention.py:124-127)
                 DecGemmArgs<T> g = gb; g.N = 3 * ID; g.K = D; g.W = W.wqkv; g.y = ly; g.x_out = lx;
                 g.tok = a.cur_tok + r0; g.tok_emb = a.tok_emb; g.pos_emb = a.pos_emb; g.q_out = lq; g.k_cache = kc; g.v_cache = vc;
-                if (l == 0) PS_GEMM(PRO_EMBED, EPI_QKV, KWP, 32, g, NC_QKV, PF_P, none);
-                else PS_GEMM(PRO_LN2, EPI_QKV, KWP, 32, g, NC_QKV, PF_P, none);
+                if (l == 0) PS_GEMM(PRO_EMBED, EPI_QKV, KWP, 32, g, NC_QKV);
+                else PS_GEMM(PRO_LN2, EPI_QKV, KWP, 32, g, NC_QKV);
             }
             if (!placement_checked) {                         // every workgroup of the team has ORed its XCC id in by now
                 placement_checked = true;
@@ -419,11 +353,11 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
             at.y = ly; at.x_out = lx; at.out = lao; at.qin = lq; at.tok = a.cur_tok + r0; at.tok_emb = a.tok_emb; at.pos_emb = a.pos_emb;
             {   // causal self attention over the cache (attention.py:148-173, one query)
                 DecAttnArgs<T> s = at; s.W = W.wqkv; s.K = kc; s.V = vc; s.lmax = a.Tmax; s.len = 0;
-                PS_ATTN(ATT_SELF, APRO_NONE, (sizeof(T) == 2 ? 8 : 16), s, pf_os, t + 1);
+                PS_ATTN(ATT_SELF, APRO_NONE, (sizeof(T) == 2 ? 8 : 16), s, t + 1);
             }
             {   // gated output projection + residual (attention.py:96-99,180)
                 DecGemmArgs<T> g = gb; g.N = 2 * D; g.K = ID; g.W = W.wo_s; g.bias = W.bo_s; g.A = lao; g.resid = lx; g.y_out = ly;
-                PS_GEMM(PRO_NONE, EPI_GLU_RES, KWI, 16, g, NC_O, PF_I, none);
+                PS_GEMM(PRO_NONE, EPI_GLU_RES, KWI, 16, g, NC_O);
             }
             if (ts.dead) break;
             {   // cross attention over the cached encoder projections, LN sandwich + q projection fused in front
@@ -431,23 +365,23 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                 s.K = a.ckv + (size_t)(2 * l) * a.cross_stride + (size_t)r0 * HEADS * a.N * DH;
                 s.V = a.ckv + (size_t)(2 * l + 1) * a.cross_stride + (size_t)r0 * HEADS * a.N * DH;
                 s.lmax = a.N; s.len = a.N;
-                PS_ATTN(ATT_CROSS, APRO_LN2, DA_NL_CROSS, s, pf_oc, a.N);
+                PS_ATTN(ATT_CROSS, APRO_LN2, DA_NL_CROSS, s, a.N);
             }
             {
                 DecGemmArgs<T> g = gb; g.N = 2 * D; g.K = ID; g.W = W.wo_c; g.bias = W.bo_c; g.A = lao; g.resid = lx; g.y_out = ly;
-                PS_GEMM(PRO_NONE, EPI_GLU_RES, KWI, 16, g, NC_O, PF_I, pf_f1);
+                PS_GEMM(PRO_NONE, EPI_GLU_RES, KWI, 16, g, NC_O);
             }
             if (ts.dead) break;
             {   // GeGLU feed-forward (attention.py:9-17,41-67)
                 DecGemmArgs<T> g = gb; g.N = 2 * F; g.K = D; g.W = W.w1; g.bias = W.b1; g.y = ly; g.x_out = lx; g.h_out = lhid; g.F = F;
-                PS_GEMM(PRO_LN2, EPI_GEGLU, KWP, 32, g, NC_F1, PF_P, pf_f2);
+                PS_GEMM(PRO_LN2, EPI_GEGLU, KWP, 32, g, NC_F1);
                 DecGemmArgs<T> h = gb; h.N = D; h.K = F; h.W = W.w2; h.bias = W.b2; h.A = lhid; h.resid = lx; h.y_out = ly;
                 bool w2_done = false;
                 if constexpr (W2_LDS_OK) {
                     if (w2_lds) {                              // block-uniform
                         w2_done = true;
                         if ((rank >> 4) != (l & 1)) {              // this workgroup owns no tile of the layer
-                            ts(); pf_next();
+                            ts();
                         } else if (w2_layer != l) {                // the other group's layer: keep the barriers
                             for (int by = 0; by < nrt; ++by) {
                                 if (by > 0) __syncthreads();
@@ -461,8 +395,7 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                                 if (by > 0) __syncthreads();
                                 auto args_ = h;
                                 args_.stamps = (ts.stp && by == 0) ? ts.stp + 5 - 3 * w2_tile : nullptr;
-                                if (by == 0) dec_gemm_tile_pf<T, PRO_NONE, EPI_BIAS_RES, KWF, 16, true, true>(args_, w2_tile, by, tid, smem, true, ts, wb, pf_next);
-                                else dec_gemm_tile_pf<T, PRO_NONE, EPI_BIAS_RES, KWF, 16, true, true>(args_, w2_tile, by, tid, smem, true, ts, wb, none);
+                                dec_gemm_tile_pre<T, PRO_NONE, EPI_BIAS_RES, KWF, 16, true, true>(args_, w2_tile, by, tid, smem, true, ts, wb);
                             }
                         }
                         ts();
@@ -470,18 +403,15 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                         ++stage;
                     }
                 }
-                if (!w2_done) PS_GEMM(PRO_NONE, EPI_BIAS_RES, KWF, 16, h, NC_F2, PF_F, pf_next);
+                if (!w2_done) PS_GEMM(PRO_NONE, EPI_BIAS_RES, KWF, 16, h, NC_F2);
             }
             if (ts.dead) break;
         }
         if (ts.dead) break;
-        auto pf_step = [&]() {                                // behind the logits: the next position's first q,k,v projection
-            if constexpr (PF_P) dec_gemm_prefetch<T, KWP, 32>(wbuf, a.L[0].wqkv, 3 * ID, bx0(NC_QKV), tid, has0(NC_QKV), a.w_tiled);
-        };
         {   // final LayerNorm + logits of this position (decoder.py:57-60)
             DecGemmArgs<T> g = gb; g.N = a.V; g.K = D; g.W = a.wlog; g.bias = a.blog; g.logits = llog; g.y = ly;
             g.gamma = a.gamma_f; g.beta = a.beta_f; g.ln_lds = ln_lds_addr + 2 * D * (unsigned)sizeof(float);
-            PS_GEMM(PRO_LNF, EPI_LOGITS, KWP, 32, g, nc_log, PF_P, pf_step);
+            PS_GEMM(PRO_LNF, EPI_LOGITS, KWP, 32, g, nc_log);
         }
         {   // greedy token, append, eos bookkeeping (decoder.py:103-116): one wave per row, rows dealt over the team's workgroups
             ts();
