@@ -134,3 +134,47 @@ def test_replayed_graphs_fixed_ragged_fixed_equal_eager():
         assert m._engine.query(Q_LAST_PERSISTENT) == 0
     for name, g, w in zip(("fixed", "ragged", "fixed again"), got, (want_fixed, want_ragged, want_fixed)):
         assert torch.equal(g, w), f"replayed step graph, {name}: differs from eager launches"
+
+
+# ---- the binding's record of the session (texocr_amd/ops.py: Session) against the engine's --------------------------------------------
+def _tiny_model():
+    d = STOP_DIMS
+    _, _, m = build(d, sd=synth.synth_state_dict(d, 7), max_batch=8)
+    return d, m, m._engine
+
+
+def test_beam_search_leaves_the_bindings_row_count_equal_to_the_engines():
+    """decode_begin on 2 images, a beam search on 3: the engine is left with an open session of one row per image (engine.hip, struct
+    Rows in generate_beam), so a decode_step behind it writes 3 rows of logits and tokens -- the binding must size them for 3, not 2"""
+    d, m, eng = _tiny_model()
+    x2, x3 = rgb_images(2, 32, 48, seed=9).cuda(), rgb_images(3, 32, 48, seed=10).cuda()
+    eng.decode_begin(m.encoder(x2))
+    m.generate(x3, 8, beam=2)
+    bos = torch.full((3,), d.bos, dtype=torch.int64, device="cuda")
+    logits, tok = eng.decode_step(0, bos)
+    torch.cuda.synchronize()
+    assert logits.shape == (3, d.vocab) and tok.shape == (3,)
+    assert int(tok.min()) >= 0 and int(tok.max()) < d.vocab
+    with pytest.raises(ValueError, match="batch does not match"):
+        torch.ops.texocr.decode_step(bos[:2].contiguous(), eng.id, 0, 2, True)
+
+
+def test_ragged_generate_closes_the_bindings_session_too():
+    """behind generate_ragged the engine has no session; the binding knows, and refuses the session's operators itself"""
+    d, m, eng = _tiny_model()
+    m.generate_ragged(_sized_images([(32, 48), (16, 64)], 70), 8)
+    nxt = torch.empty((2,), dtype=torch.int64, device="cuda")
+    with torch.cuda.device(eng.device):                                    # the engine's own word on it, and a known last error
+        assert eng.lib.txo_decode_step(eng.handle, None, 0, None, nxt.data_ptr(), None) == _lib.TXO_E_STATE
+    said = eng.lib.txo_last_error()
+    assert said == b"txo_decode_begin has not been called"
+    bos = torch.full((2,), d.bos, dtype=torch.int64, device="cuda")
+    mask = torch.ones((2, 4), dtype=torch.bool, device="cuda")
+    mask[0, 3] = False
+    for call in (lambda: eng.decode_step(0, bos), lambda: eng.decode_prefill(bos[:, None].contiguous()), lambda: eng.set_key_mask(mask)):
+        with pytest.raises(RuntimeError, match="needs a session started by"):
+            call()
+    assert eng.lib.txo_last_error() == said                                # none of the three reached the engine
+    eng.decode_begin(m.encoder(rgb_images(2, 32, 48, seed=9).cuda()))
+    logits, tok = eng.decode_step(0, bos)
+    assert logits.shape == (2, d.vocab) and bool(torch.isfinite(logits).all()) and tok.shape == (2,)

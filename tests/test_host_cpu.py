@@ -360,3 +360,167 @@ def test_bench_step_composition_gloo_world2():
                 assert np.array_equal(got[r][k], want), (eos, k, r, got[r][k].shape, want.shape)
         if eos == common[0]:
             assert got[0][0].shape[1] < 24, "the crafted eos must break early"
+
+
+# ------------------------------------------------------------------------------------------------
+# the binding's mode scopes (model.py) and session record (ops.py) on stubs: no library, no GPU
+# ------------------------------------------------------------------------------------------------
+def _recording_engine(refuse_row_stop=False):
+    """a HipEngine that was never created: its three switches only write down what they were asked"""
+    from texocr_amd.model import HipEngine
+    calls = []
+
+    class Recorder(HipEngine):
+        def set_sampling(self, on, temp=1.0, seed=0, threshold=0.9):
+            calls.append(("sampling", temp, seed) if on else ("sampling", "off"))
+
+        def set_stop_mode(self, stop):
+            calls.append(("stop", stop))
+            if refuse_row_stop and stop == "row":
+                raise RuntimeError("refused")
+
+        def set_key_mask(self, mask):
+            calls.append(("mask", None if mask is None else mask.tolist()))
+
+    return Recorder.__new__(Recorder), calls
+
+
+def test_modes_scope_switches_on_and_puts_back_on_every_exit():
+    eng, calls = _recording_engine()
+    both = [("sampling", 0.3, 7), ("stop", "row"), "body", ("sampling", "off"), ("stop", "global")]
+    with eng.modes(sample=(0.3, 7), stop="row") as sample:
+        calls.append("body")
+    assert sample == (0.3, 7) and calls == both
+    calls.clear()
+    with pytest.raises(KeyError):
+        with eng.modes(sample=(0.3, 7), stop="row"):
+            calls.append("body")
+            raise KeyError("from the body")
+    assert calls == both
+    calls.clear()
+    with eng.modes(sample=(0.5, None), decode="sample") as sample:         # no seed: one is drawn
+        pass
+    assert isinstance(sample[1], int) and calls == [("sampling", 0.5, sample[1]), ("sampling", "off")]
+    calls.clear()
+    with eng.modes(sample=(0.5, 3), decode="greedy") as sample:            # decode decides, as in generate(temp=..., decode='greedy')
+        pass
+    with eng.modes():
+        pass
+    assert sample is None and calls == []
+    # the second switch refuses on the way in: the first is put back and the error is the caller's
+    eng, calls = _recording_engine(refuse_row_stop=True)
+    with pytest.raises(RuntimeError, match="refused"):
+        with eng.modes(sample=(0.3, 7), stop="row"):
+            calls.append("body")
+    assert calls == [("sampling", 0.3, 7), ("stop", "row"), ("sampling", "off"), ("stop", "global")]
+
+
+def test_modes_scope_validates_before_it_switches():
+    eng, calls = _recording_engine()
+    with pytest.raises(ValueError, match="stop must be 'global' or 'row'"):
+        with eng.modes(sample=(0.3, 7), stop="rows"):
+            calls.append("body")
+    with pytest.raises(ValueError, match="decode must be 'greedy' or 'sample'"):
+        with eng.modes(sample=(0.3, 7), stop="row", decode="beam"):
+            calls.append("body")
+    assert calls == []
+
+
+def test_key_mask_scope():
+    eng, calls = _recording_engine()
+    for mask in (None, torch.ones((2, 3), dtype=torch.bool)):
+        with eng.key_mask(mask) as on:
+            calls.append("body")
+        assert not on
+    assert calls == ["body", "body"]
+    calls.clear()
+    mask = torch.tensor([[True, True, False], [True, True, True]])
+    want = [("mask", mask.tolist()), "body", ("mask", None)]
+    with eng.key_mask(mask) as on:
+        calls.append("body")
+    assert on and calls == want
+    calls.clear()
+    with pytest.raises(KeyError):
+        with eng.key_mask(mask):
+            calls.append("body")
+            raise KeyError("from the body")
+    assert calls == want
+
+
+class _EntryPoints:
+    """stands for libtexocr_hip.so: every txo_* entry point writes down its name and returns the code set for it"""
+
+    def __init__(self):
+        self.calls, self.rc = [], {}
+
+    def __getattr__(self, name):
+        def fn(handle, *args):
+            self.calls.append(name)
+            return self.rc.get(name, 0)
+        return fn
+
+
+def test_session_record_follows_the_engine(monkeypatch):
+    """ops.py's record of the open session behind every entry point that changes the engine's: the real operators on CPU tensors,
+    with the device checks, the stream and the library taken out"""
+    import contextlib
+    from texocr_amd import _lib, ops
+    from texocr_amd.model import HipEngine
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(f"texocr engine error {rc}")
+
+    monkeypatch.setattr(_lib, "check", check)
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    monkeypatch.setattr(ops, "_f32_dev", lambda t, name, eng: t.contiguous())
+    monkeypatch.setattr(torch.cuda, "device", lambda index: contextlib.nullcontext())
+    d = Dims(**_BENCH_DIMS)
+
+    class Engine:
+        dims, device, handle = d, 0, None
+    e = Engine()
+    e.lib = lib = _EntryPoints()
+    eid = ops.register_engine(e)
+    t = torch.ops.texocr
+    tok = torch.zeros((2, 3), dtype=torch.int64)
+    needs = "needs a session started by texocr::decode_begin"
+    for op, call in (("decode_step", lambda: t.decode_step(None, eid, 0, 2, True)), ("decode_prefill", lambda: t.decode_prefill(tok, eid, True)),
+                     ("decode_score", lambda: t.decode_score(tok, eid)), ("decode_set_key_mask", lambda: t.decode_set_key_mask(None, eid)),
+                     ("decode_set_key_mask", lambda: t.decode_set_key_mask(tok > 0, eid))):
+        with pytest.raises(RuntimeError, match=f"texocr::{op} {needs}"):
+            call()
+    never_created = HipEngine.__new__(HipEngine)
+    with pytest.raises(RuntimeError, match=f"texocr::decode_step {needs}"):
+        never_created.decode_step(0)
+    assert lib.calls == []                                             # refused before any entry point
+
+    enc = torch.zeros((2, 7, d.embed_dim))
+    t.decode_begin(enc, eid)
+    assert e.session.rows == 2 and e.session.src.data_ptr() == enc.data_ptr() and e.session.mask is None
+    with pytest.raises(ValueError, match="batch does not match"):
+        t.decode_step(None, eid, 0, 3, True)
+    img = torch.zeros((4, 3, 32, 48))
+    t.generate_beam(img, eid, 2, 8, -1, False)
+    assert e.session.rows == 4                                         # images, not images * beams
+    t.generate(img[:3], eid, 8, -1, False)
+    assert e.session.rows == 3
+    t.generate_from_enc(enc, eid, 8, -1, False)
+    assert e.session.rows == 2
+    box, sizes = ops.pack_ragged([torch.zeros((3, 32, 48)), torch.zeros((3, 16, 32))])
+    t.decode_begin_ragged(enc, ops.ragged_tokens(sizes), eid)
+    assert e.session.rows == 2
+    t.generate_ragged(box, sizes, eid, 8, -1)
+    assert e.session is None
+    # a failing call: one that leaves the engine's session alone leaves the record, one that changes it closes the record
+    t.decode_begin(enc, eid)
+    lib.rc = {"txo_encode": _lib.TXO_E_STATE, "txo_generate": _lib.TXO_E_STATE}
+    with pytest.raises(RuntimeError):
+        t.encode(img, eid)
+    assert e.session.rows == 2
+    with pytest.raises(RuntimeError):
+        t.generate(img, eid, 8, -1, False)
+    assert e.session is None
+    assert lib.calls == ["txo_decode_begin", "txo_generate_beam", "txo_generate", "txo_generate_from_enc", "txo_decode_begin_ragged",
+                         "txo_generate_ragged", "txo_decode_begin", "txo_encode", "txo_generate"]
+    ops.unregister_engine(eid)

@@ -28,11 +28,12 @@ There is no CPU path: tensors must live on the GPU and the HIP library must be b
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
 import re
-from typing import Dict, NamedTuple, Optional
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -51,6 +52,13 @@ _LN_ALIAS = re.compile(r"\.layers\.(\d+)\.0\.(weight|bias)$")
 def _is_ln_alias(key: str) -> bool:
     m = _LN_ALIAS.search(key)
     return bool(m) and int(m.group(1)) > 0
+
+
+def _check_modes(stop: str, decode: str = "greedy") -> None:
+    if stop not in ("global", "row"):
+        raise ValueError("stop must be 'global' or 'row'")
+    if decode not in ("greedy", "sample"):
+        raise ValueError("decode must be 'greedy' or 'sample'")
 
 
 class HipEngine:
@@ -167,7 +175,8 @@ class HipEngine:
         return torch.ops.texocr.decode_score(tokens, self.id)
 
     def decode_step(self, t: int, tok_in: Optional[torch.Tensor] = None, want_logits: bool = True):
-        logits, nxt = torch.ops.texocr.decode_step(tok_in, self.id, int(t), int(self._B), bool(want_logits))
+        batch = ops.session(self, "decode_step").rows
+        logits, nxt = torch.ops.texocr.decode_step(tok_in, self.id, int(t), batch, bool(want_logits))
         return (logits if want_logits else None), nxt
 
     def generate(self, img: Optional[torch.Tensor], max_len: int, eos: Optional[int], enc: Optional[torch.Tensor] = None,
@@ -223,10 +232,44 @@ class HipEngine:
         """'global': the reference's loop (decoder.py:115-116: rows keep producing tokens after their eos, one break when every row
         contains it).  'row' (build extension): a row is finished at its first eos -- later tokens are the pad id -- and finished rows
         stop costing work on the launch path (txo_set_stop_mode)."""
-        if stop not in ("global", "row"):
-            raise ValueError("stop must be 'global' or 'row'")
+        _check_modes(stop)
         self._ensure()
         _lib.check(self.lib.txo_set_stop_mode(self.handle, 1 if stop == "row" else 0))
+
+    @contextlib.contextmanager
+    def modes(self, sample: Optional[Tuple[float, Optional[int]]] = None, stop: str = "global", decode: Optional[str] = None):
+        """The engine's two global switches around the calls of one generate: sampling with sample = (temp, seed) -- a seed of None is
+        drawn from torch's generator; decode='greedy' overrides it -- and per-row stop.  Nothing else in this module turns either on,
+        and both are off again behind every exit.  Yields (temp, seed) as set, or None."""
+        _check_modes(stop, decode or "greedy")
+        if decode == "greedy":
+            sample = None
+        if sample is not None and sample[1] is None:
+            sample = (sample[0], int(torch.randint(0, 2**62, (1,)).item()))
+        try:
+            if sample is not None:
+                self.set_sampling(True, temp=sample[0], seed=sample[1])
+            if stop == "row":
+                self.set_stop_mode("row")
+            yield sample
+        finally:
+            if sample is not None:
+                self.set_sampling(False)
+            if stop == "row":
+                self.set_stop_mode("global")
+
+    @contextlib.contextmanager
+    def key_mask(self, mask: Optional[torch.Tensor]):
+        """set_key_mask(mask) around the steps of the current session, cleared behind every exit; None or no padding at all: nothing.
+        Yields whether a mask was set."""
+        on = mask is not None and not bool(mask.all())
+        if on:
+            self.set_key_mask(mask)
+        try:
+            yield on
+        finally:
+            if on:
+                self.set_key_mask(None)
 
     def query(self, what: int) -> int:
         """txo_engine_query, `what` one of _lib.Q_*: LAST_PERSISTENT = the last generate() ran as one persistent launch,
@@ -320,6 +363,16 @@ class VisionEncoder(nn.Module):
         return self._engine.encode_ragged(images)
 
 
+def _need_enc(enc) -> None:
+    if enc is None:
+        raise ValueError("Must provide enc (cross-attending decoder)")       # attention.py:232-233
+
+
+def _check_x(x: torch.Tensor, shape: str) -> None:
+    if x.ndim != 2 or x.dtype != torch.int64 or not x.is_cuda:
+        raise ValueError(f"x must be an int64 GPU tensor of shape {shape}")
+
+
 def _check_token_ids(tokens: torch.Tensor, vocab: int) -> None:
     """The reference's nn.Embedding raises IndexError for an id outside the table (decoder.py:51); so does this facade (the C ABI
     forces such ids into the table instead: it cannot raise from the device)."""
@@ -366,39 +419,29 @@ class Transformer(nn.Module):
     def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None, **kw):
         if kw:
             raise ValueError(f"unsupported arguments for the inference path: {sorted(kw)}")
-        if enc is None:
-            raise ValueError("Must provide enc (cross-attending decoder)")       # attention.py:232-233
+        _need_enc(enc)
         padded = mask is not None and not bool(mask.all())
         if padded and tuple(mask.shape) != tuple(x.shape):
             raise ValueError("mask must have the shape of x")
-        if x.ndim != 2 or x.dtype != torch.int64 or not x.is_cuda:
-            raise ValueError("x must be an int64 GPU tensor of shape (B, t)")
+        _check_x(x, "(B, t)")
         if x.shape[1] > self.max_len:
             raise ValueError("prefix longer than decoder.max_len")
         eng = self._engine
         _check_token_ids(x, eng.dims.vocab)
         eng.decode_begin(enc)
+        # the one-pass prefill (csrc/prefill.h, with or without a key mask) needs a vocabulary that is a multiple of 8 and a prefix that
+        # fits the engine's workspace (max_batch * max_tokens rows); anything else takes the single-position steps
         one_pass = eng.dims.vocab % 8 == 0 and x.shape[1] <= eng.max_batch * eng.max_tokens and os.environ.get("TXO_NET_STEPWISE") is None
-        if padded:
-            # attention.py:130-155: a padded position is never attended by a query that is not padding.  Logits AT padded positions are
-            # unspecified here (the reference softmaxes such a row uniformly over all keys, future ones included; nothing reads it)
-            eng.set_key_mask(mask.to(x.device))
-            try:
-                if one_pass:
-                    return eng.decode_prefill(x)              # one causal multi-position pass with the key mask (csrc/prefill.h)
-                out = torch.empty((x.shape[0], x.shape[1], eng.dims.vocab), device=x.device, dtype=torch.float32)
-                xt = x.t().contiguous()
-                for t in range(x.shape[1]):
-                    out[:, t] = eng.decode_step(t, xt[t])[0]
-                return out
-            finally:
-                eng.set_key_mask(None)
-        # the one-pass prefill needs a vocabulary that is a multiple of 8 and a prefix that fits the engine's workspace
-        # (max_batch * max_tokens rows); anything else takes the single-position steps
-        if one_pass:
-            return eng.decode_prefill(x)
+        # attention.py:130-155: a padded position is never attended by a query that is not padding.  Logits AT padded positions are
+        # unspecified here (the reference softmaxes such a row uniformly over all keys, future ones included; nothing reads it)
+        with eng.key_mask(mask.to(x.device) if padded else None):
+            return eng.decode_prefill(x) if one_pass else self._net_stepwise(x)
+
+    def _net_stepwise(self, x: torch.Tensor) -> torch.Tensor:
+        """fallback (odd vocabulary sizes; tests): one cached step per position"""
+        eng = self._engine
         out = torch.empty((x.shape[0], x.shape[1], eng.dims.vocab), device=x.device, dtype=torch.float32)
-        xt = x.t().contiguous()                                   # fallback (odd vocabulary sizes; tests): one cached step per position
+        xt = x.t().contiguous()
         for t in range(x.shape[1]):
             out[:, t] = eng.decode_step(t, xt[t])[0]
         return out
@@ -412,7 +455,6 @@ class AutoRegressiveDecoder(nn.Module):
         self._engine = engine
         self.net = Transformer(engine, _shared)
         self.max_len = self.net.max_len
-        self._resample = None
 
     def forward(self, *a, **k):
         raise NotImplementedError("AutoRegressiveDecoder.forward is the training loss (decoder.py:124-145); this engine "
@@ -424,10 +466,8 @@ class AutoRegressiveDecoder(nn.Module):
         (bos first), x[:, :-1] is fed in one causal pass and x[:, 1:] are the targets.  mask (B, L) bool, False = padding (None: no
         padding).  The logits are never materialised (csrc/score.h).  Unlike the reference's loss, `loss` averages over the valid
         positions only (F.cross_entropy there has no ignore_index); without padding the two are the same number."""
-        if enc is None:
-            raise ValueError("Must provide enc (cross-attending decoder)")       # attention.py:232-233
-        if x.ndim != 2 or x.dtype != torch.int64 or not x.is_cuda:
-            raise ValueError("x must be an int64 GPU tensor of shape (B, L)")
+        _need_enc(enc)
+        _check_x(x, "(B, L)")
         if x.shape[1] < 2:
             raise ValueError("x needs at least two columns (one fed token and its target)")
         if x.shape[1] - 1 > self.max_len:
@@ -438,14 +478,8 @@ class AutoRegressiveDecoder(nn.Module):
         _check_token_ids(x, eng.dims.vocab)
         m = torch.ones_like(x, dtype=torch.bool) if mask is None else mask.to(device=x.device, dtype=torch.bool)
         eng.decode_begin(enc)
-        padded = not bool(m.all())
-        if padded:
-            eng.set_key_mask(m[:, :-1])
-        try:
+        with eng.key_mask(m[:, :-1]):                              # (the last column is a target only, never a key)
             logp, top1, top1_logp = eng.decode_score(x)
-        finally:
-            if padded:
-                eng.set_key_mask(None)
         return score_summary(logp, top1, top1_logp, x, m)
 
     @torch.no_grad()
@@ -457,51 +491,35 @@ class AutoRegressiveDecoder(nn.Module):
         return_logits = bool(kwargs.pop("return_logits", False))   # build extension: also the logits every token was picked from
         stop = kwargs.pop("stop", "global")                        # build extension: 'row' = per-row stop, pad behind a row's first eos
         pad = kwargs.pop("pad", None)
-        if stop not in ("global", "row"):
-            raise ValueError("stop must be 'global' or 'row'")
         if kwargs:
             raise ValueError(f"unsupported arguments: {sorted(kwargs)}")
-        if enc is None:
-            raise ValueError("Must provide enc (cross-attending decoder)")
+        _need_enc(enc)
         if mask is not None and mask.ndim == 1:
             mask = mask[None, :]
         padded = mask is not None and not bool(mask.all())
         if padded and tuple(mask.shape) != tuple(start_tokens.shape if start_tokens.ndim == 2 else start_tokens[None, :].shape):
             raise ValueError("mask must have the shape of start_tokens")
-        if decode not in ("greedy", "sample"):
-            raise ValueError("decode must be 'greedy' or 'sample'")
         squeeze = start_tokens.ndim == 1
         st = start_tokens[None, :] if squeeze else start_tokens                  # decoder.py:88
         B, T0 = st.shape
         eng = self._engine
         _check_token_ids(st, eng.dims.vocab)
-        self._resample = None
-        if decode == "sample":
-            if seed is None:
-                seed = generator.initial_seed() if generator is not None else int(torch.randint(0, 2**62, (1,)).item())
-            eng.set_sampling(True, temp=temp, seed=seed)
-            self._resample = (temp, seed)
-        if stop == "row":
-            eng.set_stop_mode("row")
-        try:
+        if seed is None and generator is not None:
+            seed = generator.initial_seed()
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode) as sample:
             # beyond the positional table the engine slides the window with its multi-position forward, which needs a vocabulary
             # that is a multiple of 8 and a table that fits its workspace -- else the general stepwise loop below
             window_ok = max_len <= self.max_len or (eng.dims.vocab % 8 == 0 and self.max_len <= eng.max_batch * eng.max_tokens)
             if padded:
                 if return_logits:
                     raise ValueError("return_logits is not available with a padding mask")
-                out = self._generate_stepwise(st, eos_tok, max_len, enc, mask=mask)
+                out = self._generate_stepwise(st, eos_tok, max_len, enc, sample, mask=mask)
             elif T0 == 1 and bool((st == eng.dims.bos).all()) and (window_ok or return_logits):
                 out = eng.generate(None, max_len, eos_tok, enc=enc, return_logits=return_logits)
             elif return_logits:
                 raise ValueError("return_logits needs a BOS start inside the positional table (max_len <= decoder.max_len)")
             else:
-                out = self._generate_stepwise(st, eos_tok, max_len, enc)
-        finally:
-            if decode == "sample":
-                eng.set_sampling(False)
-            if stop == "row":
-                eng.set_stop_mode("global")
+                out = self._generate_stepwise(st, eos_tok, max_len, enc, sample)
         if stop == "row" and eos_tok is not None:
             # (the engine's own generate has padded already; the stepwise loop -- arbitrary start prefix, padding mask -- and the
             # return_logits form are padded here: the same rule, tokens behind a row's first eos, start tokens included in the test as
@@ -515,7 +533,7 @@ class AutoRegressiveDecoder(nn.Module):
             return (out[0].squeeze(0), out[1].squeeze(0)) if squeeze else out
         return out.squeeze(0) if squeeze else out
 
-    def _generate_stepwise(self, st, eos_tok, max_len, enc, mask=None):
+    def _generate_stepwise(self, st, eos_tok, max_len, enc, sample, mask=None):
         """General form (arbitrary start prefix, any max_len): one engine step per position with the reference's per-step
         host-side eos check (decoder.py:115-116); the engine picks the token (argmax or its sampler).
 
@@ -531,35 +549,32 @@ class AutoRegressiveDecoder(nn.Module):
         output = st
         # decoder.py:95-101,112: the mask covers the start tokens, every generated token extends it with True, and it slides with the window
         m = None if mask is None else mask.to(device=enc.device, dtype=torch.bool)
-        if m is not None:
-            eng.set_key_mask(m[:, -L:])
         valid = 0                                                  # positions of the CURRENT window held by the cache
-        for i in range(max_len):
-            window = output[:, -L:]                                # decoder.py:99-100
-            n = window.shape[1]
-            if output.shape[1] > L:
-                valid = 0                                          # every position shifted: nothing cached is reusable
-                if m is not None:
-                    eng.set_key_mask(m[:, -L:])
-            wt = window.t().contiguous()
-            if n - 1 - valid > 1 and eng.dims.vocab % 8 == 0 and n - 1 <= eng.max_batch * eng.max_tokens:   # (with or without a padding mask)
-                eng.decode_prefill(window[:, :n - 1].contiguous(), want_logits=False)   # positions 0..n-2 in one pass
-            else:
-                for p in range(valid, n - 1):
-                    eng.decode_step(p, wt[p], want_logits=False)
-            if self._resample is not None and output.shape[1] > L:
-                # the device sampler draws from a counter RNG keyed by (seed, row, position); once the window slides the
-                # position stays at L - 1, so the seed advances with the token index instead
-                eng.set_sampling(True, temp=self._resample[0], seed=self._resample[1] + i)
-            _, tok = eng.decode_step(n - 1, wt[n - 1], want_logits=False)
-            valid = n
-            output = torch.cat((output, tok[:, None]), dim=-1)
-            if m is not None:
-                m = torch.nn.functional.pad(m, (0, 1), value=True)
-            if eos_tok is not None and bool((output == eos_tok).any(dim=1).all()):
-                break
-        if m is not None:
-            eng.set_key_mask(None)
+        with eng.key_mask(None if m is None else m[:, -L:]) as masked:
+            for i in range(max_len):
+                window = output[:, -L:]                            # decoder.py:99-100
+                n = window.shape[1]
+                if output.shape[1] > L:
+                    valid = 0                                      # every position shifted: nothing cached is reusable
+                    if masked:
+                        eng.set_key_mask(m[:, -L:])
+                wt = window.t().contiguous()
+                if n - 1 - valid > 1 and eng.dims.vocab % 8 == 0 and n - 1 <= eng.max_batch * eng.max_tokens:   # (with or without a padding mask)
+                    eng.decode_prefill(window[:, :n - 1].contiguous(), want_logits=False)   # positions 0..n-2 in one pass
+                else:
+                    for p in range(valid, n - 1):
+                        eng.decode_step(p, wt[p], want_logits=False)
+                if sample is not None and output.shape[1] > L:
+                    # the device sampler draws from a counter RNG keyed by (seed, row, position); once the window slides the
+                    # position stays at L - 1, so the seed advances with the token index instead (inside the caller's modes() scope)
+                    eng.set_sampling(True, temp=sample[0], seed=sample[1] + i)
+                _, tok = eng.decode_step(n - 1, wt[n - 1], want_logits=False)
+                valid = n
+                output = torch.cat((output, tok[:, None]), dim=-1)
+                if masked:
+                    m = torch.nn.functional.pad(m, (0, 1), value=True)
+                if eos_tok is not None and bool((output == eos_tok).any(dim=1).all()):
+                    break
         return output[:, T0:]
 
 
@@ -628,22 +643,16 @@ class OCRModel(nn.Module):
     def generate(self, src: torch.Tensor, max_len: int, temp: float = 0.3, *, decode: str = "greedy",
                  generator: Optional[torch.Generator] = None, seed: Optional[int] = None, return_logits: bool = False,
                  beam: int = 0, return_beams: bool = False, stop: str = "global"):
-        if stop not in ("global", "row"):
-            raise ValueError("stop must be 'global' or 'row'")
+        _check_modes(stop)
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
             if max_len > self.decoder.max_len:
                 raise ValueError(f"beam search needs max_len <= decoder.max_len ({self.decoder.max_len})")
             return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
         if decode == "greedy" and self.bos_token == self._engine.dims.bos:
             # (max_len > decoder.max_len: txo_generate slides the window like the reference, decoder.py:99-100)
-            if stop == "row":
-                # (with return_logits the engine does not compact -- a finished row's logits would be missing -- and only pads)
-                self._engine.set_stop_mode("row")
-                try:
-                    return self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits)
-                finally:
-                    self._engine.set_stop_mode("global")
-            return self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits)
+            # (stop='row' with return_logits: the engine does not compact -- a finished row's logits would be missing -- and only pads)
+            with self._engine.modes(stop=stop):
+                return self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits)
         enc = self.encoder(src)
         start = torch.full((src.shape[0], 1), self.bos_token, dtype=torch.int64, device=src.device)   # ocr_model.py:57
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
@@ -656,24 +665,8 @@ class OCRModel(nn.Module):
         """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
         is keyed by the row of the batch).  max_len <= decoder.max_len."""
-        if stop not in ("global", "row"):
-            raise ValueError("stop must be 'global' or 'row'")
-        if decode not in ("greedy", "sample"):
-            raise ValueError("decode must be 'greedy' or 'sample'")
-        eng = self._engine
-        if decode == "sample":
-            if seed is None:
-                seed = int(torch.randint(0, 2**62, (1,)).item())
-            eng.set_sampling(True, temp=temp, seed=seed)
-        if stop == "row":
-            eng.set_stop_mode("row")
-        try:
-            return eng.generate_ragged(images, max_len, self.eos_token)
-        finally:
-            if decode == "sample":
-                eng.set_sampling(False)
-            if stop == "row":
-                eng.set_stop_mode("global")
+        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode):
+            return self._engine.generate_ragged(images, max_len, self.eos_token)
 
     @torch.no_grad()
     def score(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:

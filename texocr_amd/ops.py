@@ -25,6 +25,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
+from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -73,22 +74,79 @@ def _f32_dev(t: torch.Tensor, name: str, eng) -> torch.Tensor:
     return t.contiguous()
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+def _i64_dev(t: torch.Tensor, name: str, eng, rows: int, ndim: int, shape: str) -> torch.Tensor:
+    """token ids: `rows` rows, `ndim` dimensions; `shape` is how the message names them"""
+    if t.dtype != torch.int64 or not t.is_cuda or t.ndim != ndim or t.shape[0] != rows:
+        raise ValueError(f"{name} must be an int64 GPU tensor of shape {shape}")
+    if t.device.index != eng.device:
+        raise ValueError(f"{name} live{'' if name.endswith('s') else 's'} on cuda:{t.device.index} but the engine was created on cuda:{eng.device}")
+    return t.contiguous()
+
+
+def _img_arg(img: torch.Tensor, eng) -> torch.Tensor:
+    if img.ndim != 4:
+        raise ValueError("expected an image batch of shape (B, C, H, W)")
+    img = _f32_dev(img, "src", eng)
+    eng.dims.check_image(*img.shape[1:])
+    return img
+
+
+def _enc_arg(enc: torch.Tensor, eng, n: str = "N") -> torch.Tensor:
+    enc = _f32_dev(enc, "enc", eng)
+    if enc.ndim != 3 or enc.shape[2] != eng.dims.embed_dim:
+        raise ValueError(f"enc must be (B, {n}, {eng.dims.embed_dim})")
+    return enc
+
+
+# ---- the decode session, as far as the binding has to know it ------------------------------------------------------------------
+@dataclass
+class Session:
+    rows: int                               # rows of a decode_step / decode_prefill / decode_score / key mask
+    src: torch.Tensor                       # what the session was opened on: kept alive while the engine may read it
+    mask: Optional[torch.Tensor] = None     # the uint8 key mask handed to the engine, kept alive likewise
+
+
+def _open(e, rows: int, src: torch.Tensor) -> None:
+    """The one writer of ``e.session``, behind every entry point that leaves the engine with an open session (_call).  Invariant: whenever the
+    engine's session is open, the record's ``rows`` equals the engine's ``ses.rows`` -- the operators size their outputs by it and the
+    engine writes ``ses.rows`` rows into them.  Not the converse: the engine also closes a session on its own (a stop='row' generate
+    that compacted) while the record stays; it then refuses the next step (TXO_E_STATE) before it writes anything."""
+    e.session = Session(int(rows), src)
+
+
+def _close(e) -> None:
+    """no session is known to be open: behind generate_ragged (the engine closes its own) and behind a failed call that would have changed it"""
+    e.session = None
+
+
+def session(e, op: str) -> Session:
+    """The record of the open session, for the operators (and HipEngine.decode_step) that work on one."""
+    s = getattr(e, "session", None)
+    if s is None:
+        raise RuntimeError(f"texocr::{op} needs a session started by texocr::decode_begin")
+    return s
+
+
+def _call(e, fn: str, *args, leaves: Optional[tuple] = None) -> None:
+    """ONE entry point ``fn(handle, *args, stream)`` on the engine's device and torch's current stream; raises what _lib.check raises.
+    leaves: the engine's session behind an entry point that opens, replaces or closes it -- (rows, src): this one, open; (): none.
+    If such a call fails the engine's state is not known here and the record stays closed: the engine will say what it holds."""
+    if leaves is not None:
+        _close(e)
+    with torch.cuda.device(e.device):
+        _lib.check(getattr(e.lib, fn)(e.handle, *args, _stream()))
+    if leaves:
+        _open(e, *leaves)
 
 
 # ---------------------------------------------------------------------------------------------------------------
 @custom_op("texocr::encode", mutates_args=())
 def encode(img: torch.Tensor, engine: int) -> torch.Tensor:
     e = _eng(engine, ready=True)
-    if img.ndim != 4:
-        raise ValueError("expected an image batch of shape (B, C, H, W)")
-    img = _f32_dev(img, "src", e)
+    img = _img_arg(img, e)
     B, Cc, H, W = img.shape
-    e.dims.check_image(Cc, H, W)
     out = torch.empty((B, e.dims.n_tokens(H, W), e.dims.embed_dim), device=img.device, dtype=torch.float32)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_encode(e.handle, img.data_ptr(), B, Cc, H, W, out.data_ptr(), _stream()))
+    _call(e, "txo_encode", img.data_ptr(), B, Cc, H, W, out.data_ptr())
     return out
 
 
@@ -102,18 +160,8 @@ def _(img, engine):
 @custom_op("texocr::decode_begin", mutates_args=())
 def decode_begin(enc: torch.Tensor, engine: int) -> None:
     e = _eng(engine, ready=True)
-    enc = _f32_dev(enc, "enc", e)
-    if enc.ndim != 3 or enc.shape[2] != e.dims.embed_dim:
-        raise ValueError(f"enc must be (B, N, {e.dims.embed_dim})")
-    e._enc_keepalive = enc
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_decode_begin(e.handle, enc.data_ptr(), enc.shape[0], enc.shape[1], _stream()))
-    e._B = enc.shape[0]
-
-
-@decode_begin.register_fake
-def _(enc, engine):
-    return None
+    enc = _enc_arg(enc, e)
+    _call(e, "txo_decode_begin", enc.data_ptr(), enc.shape[0], enc.shape[1], leaves=(enc.shape[0], enc))
 
 
 @custom_op("texocr::decode_set_key_mask", mutates_args=())
@@ -121,41 +169,29 @@ def decode_set_key_mask(mask: Optional[torch.Tensor], engine: int) -> None:
     """The `mask` argument of decoder.generate / decoder.net (decoder.py:95-101; attention.py:130-155) for the decode_step calls of
     the current session: (B, cols) bool, False = padding (never attended by later queries); None clears it."""
     e = _eng(engine)
-    B = getattr(e, "_B", None)
-    with torch.cuda.device(e.device):
-        if mask is None:
-            _lib.check(e.lib.txo_decode_set_key_mask(e.handle, None, 0, _stream()))
-            return
-        if mask.ndim != 2 or mask.shape[0] != B or not mask.is_cuda:
-            raise ValueError("mask must be a GPU tensor of shape (B, cols) matching the session started by texocr::decode_begin")
-        m8 = mask.to(torch.uint8).contiguous()
-        e._mask_keepalive = m8
-        _lib.check(e.lib.txo_decode_set_key_mask(e.handle, m8.data_ptr(), int(m8.shape[1]), _stream()))
-
-
-@decode_set_key_mask.register_fake
-def _(mask, engine):
-    return None
+    ses = session(e, "decode_set_key_mask")
+    if mask is None:
+        _call(e, "txo_decode_set_key_mask", None, 0)
+        return
+    if mask.ndim != 2 or mask.shape[0] != ses.rows or not mask.is_cuda:
+        raise ValueError("mask must be a GPU tensor of shape (B, cols) matching the session started by texocr::decode_begin")
+    ses.mask = mask.to(torch.uint8).contiguous()
+    _call(e, "txo_decode_set_key_mask", ses.mask.data_ptr(), int(ses.mask.shape[1]))
 
 
 @custom_op("texocr::decode_step", mutates_args=())
 def decode_step(tok_in: Optional[torch.Tensor], engine: int, t: int, batch: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     """One position: returns (logits (B, V) -- (0, V) when want_logits is false --, argmax token (B,))."""
     e = _eng(engine)
-    if batch != getattr(e, "_B", None):
+    if batch != session(e, "decode_step").rows:
         raise ValueError("batch does not match the decode session started by texocr::decode_begin")
     dev = torch.device("cuda", e.device)
     if tok_in is not None:
-        if tok_in.dtype != torch.int64 or not tok_in.is_cuda or tuple(tok_in.shape) != (batch,):
-            raise ValueError("tok_in must be an int64 GPU tensor of shape (B,)")
-        if tok_in.device.index != e.device:
-            raise ValueError(f"tok_in lives on cuda:{tok_in.device.index} but the engine was created on cuda:{e.device}")
-        tok_in = tok_in.contiguous()
+        tok_in = _i64_dev(tok_in, "tok_in", e, batch, 1, "(B,)")
     logits = torch.empty((batch if want_logits else 0, e.dims.vocab), device=dev, dtype=torch.float32)
     nxt = torch.empty((batch,), device=dev, dtype=torch.int64)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_decode_step(e.handle, _ptr(tok_in), int(t), logits.data_ptr() if want_logits else None,
-                                         nxt.data_ptr(), _stream()))
+    _call(e, "txo_decode_step", None if tok_in is None else tok_in.data_ptr(), int(t), logits.data_ptr() if want_logits else None,
+          nxt.data_ptr())
     return logits, nxt
 
 
@@ -172,16 +208,11 @@ def decode_prefill(tokens: torch.Tensor, engine: int, want_logits: bool) -> torc
     """Transformer.forward over a whole prefix in one pass (decoder.py:41-67): tokens (B, t) int64 at positions 0..t-1 ->
     logits (B, t, V) (or (0, t, V)); fills the self-attention K/V cache rows 0..t-1 of the session opened by decode_begin."""
     e = _eng(engine)
-    B = getattr(e, "_B", None)
-    if tokens.ndim != 2 or tokens.dtype != torch.int64 or not tokens.is_cuda or tokens.shape[0] != B:
-        raise ValueError("tokens must be an int64 GPU tensor of shape (B, t) matching the session started by texocr::decode_begin")
-    if tokens.device.index != e.device:
-        raise ValueError(f"tokens live on cuda:{tokens.device.index} but the engine was created on cuda:{e.device}")
-    tokens = tokens.contiguous()
+    B = session(e, "decode_prefill").rows
+    tokens = _i64_dev(tokens, "tokens", e, B, 2, "(B, t) matching the session started by texocr::decode_begin")
     t = tokens.shape[1]
     logits = torch.empty((B if want_logits else 0, t, e.dims.vocab), device=tokens.device, dtype=torch.float32)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_decode_prefill(e.handle, tokens.data_ptr(), int(t), logits.data_ptr() if want_logits else None, _stream()))
+    _call(e, "txo_decode_prefill", tokens.data_ptr(), int(t), logits.data_ptr() if want_logits else None)
     return logits
 
 
@@ -197,22 +228,15 @@ def decode_score(tokens: torch.Tensor, engine: int) -> Tuple[torch.Tensor, torch
     causal pass, column p+1 the target of position p -> (logp (B, L-1) = log_softmax(logits)[target], top1 (B, L-1) = argmax of the
     logits, top1_logp (B, L-1)).  No (B, L-1, V) tensor is made on the way; the K/V cache holds rows 0..L-2 afterwards."""
     e = _eng(engine)
-    B = getattr(e, "_B", None)
-    if B is None:
-        raise RuntimeError("texocr::decode_score needs a session started by texocr::decode_begin")
-    if tokens.ndim != 2 or tokens.dtype != torch.int64 or not tokens.is_cuda or tokens.shape[0] != B:
-        raise ValueError("tokens must be an int64 GPU tensor of shape (B, L) matching the session started by texocr::decode_begin")
-    if tokens.device.index != e.device:
-        raise ValueError(f"tokens live on cuda:{tokens.device.index} but the engine was created on cuda:{e.device}")
+    B = session(e, "decode_score").rows
+    tokens = _i64_dev(tokens, "tokens", e, B, 2, "(B, L) matching the session started by texocr::decode_begin")
     L = int(tokens.shape[1])
     if L < 2 or L - 1 > e.dims.max_len:
         raise ValueError(f"tokens must have 2 <= L <= max_len + 1 = {e.dims.max_len + 1} columns, got {L}")
-    tokens = tokens.contiguous()
     logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
     top1 = torch.empty((B, L - 1), device=tokens.device, dtype=torch.int64)
     top1_logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_decode_score(e.handle, tokens.data_ptr(), L, logp.data_ptr(), top1.data_ptr(), top1_logp.data_ptr(), _stream()))
+    _call(e, "txo_decode_score", tokens.data_ptr(), L, logp.data_ptr(), top1.data_ptr(), top1_logp.data_ptr())
     return logp, top1, top1_logp
 
 
@@ -237,49 +261,33 @@ def generate(img: torch.Tensor, engine: int, max_len: int, eos: int, want_logits
     """Greedy OCRModel.generate: (tokens (B, max_len) of which the first n are valid, n as an int64 CPU tensor of shape (1,),
     logits (B, max_len, V) or (0, max_len, V)).  eos < 0: no eos test (eos_tok=None)."""
     e = _eng(engine, ready=True)
-    if img.ndim != 4:
-        raise ValueError("expected an image batch of shape (B, C, H, W)")
-    img = _f32_dev(img, "src", e)
+    img = _img_arg(img, e)
     B, Cc, H, W = img.shape
-    e.dims.check_image(Cc, H, W)
     toks, logits = _gen_outputs(img, e, max_len, want_logits)
     n = C.c_int32(0)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_generate(e.handle, img.data_ptr(), B, Cc, H, W, int(max_len), int(eos), toks.data_ptr(), C.byref(n),
-                                      logits.data_ptr() if want_logits else None, _stream()))
-    e._B, e._enc_keepalive = B, img
+    _call(e, "txo_generate", img.data_ptr(), B, Cc, H, W, int(max_len), int(eos), toks.data_ptr(), C.byref(n),
+          logits.data_ptr() if want_logits else None, leaves=(B, img))
     return toks, torch.tensor([n.value], dtype=torch.int64), logits
-
-
-@generate.register_fake
-def _(img, engine, max_len, eos, want_logits):
-    d = _eng(engine).dims
-    B = img.shape[0]
-    return (img.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
-            img.new_empty((B if want_logits else 0, max_len, d.vocab), dtype=torch.float32))
 
 
 @custom_op("texocr::generate_from_enc", mutates_args=())
 def generate_from_enc(enc: torch.Tensor, engine: int, max_len: int, eos: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     e = _eng(engine, ready=True)
-    enc = _f32_dev(enc, "enc", e)
-    if enc.ndim != 3 or enc.shape[2] != e.dims.embed_dim:
-        raise ValueError(f"enc must be (B, N, {e.dims.embed_dim})")
+    enc = _enc_arg(enc, e)
     toks, logits = _gen_outputs(enc, e, max_len, want_logits)
     n = C.c_int32(0)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_generate_from_enc(e.handle, enc.data_ptr(), enc.shape[0], enc.shape[1], int(max_len), int(eos),
-                                               toks.data_ptr(), C.byref(n), logits.data_ptr() if want_logits else None, _stream()))
-    e._B, e._enc_keepalive = enc.shape[0], enc
+    _call(e, "txo_generate_from_enc", enc.data_ptr(), enc.shape[0], enc.shape[1], int(max_len), int(eos), toks.data_ptr(), C.byref(n),
+          logits.data_ptr() if want_logits else None, leaves=(enc.shape[0], enc))
     return toks, torch.tensor([n.value], dtype=torch.int64), logits
 
 
+@generate.register_fake
 @generate_from_enc.register_fake
-def _(enc, engine, max_len, eos, want_logits):
+def _(src, engine, max_len, eos, want_logits):
     d = _eng(engine).dims
-    B = enc.shape[0]
-    return (enc.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
-            enc.new_empty((B if want_logits else 0, max_len, d.vocab), dtype=torch.float32))
+    B = src.shape[0]
+    return (src.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
+            src.new_empty((B if want_logits else 0, max_len, d.vocab), dtype=torch.float32))
 
 
 @custom_op("texocr::generate_beam", mutates_args=())
@@ -287,16 +295,14 @@ def generate_beam(img: torch.Tensor, engine: int, beams: int, max_len: int, eos:
     """Beam search (build extension): (best tokens (B, max_len), scores (B, beams), all beams (B*beams, max_len) or (0, max_len),
     n as an int64 CPU tensor)."""
     e = _eng(engine, ready=True)
-    img = _f32_dev(img, "src", e)
+    img = _img_arg(img, e)
     B, Cc, H, W = img.shape
-    e.dims.check_image(Cc, H, W)
     toks = torch.empty((B, max_len), device=img.device, dtype=torch.int64)
     scores = torch.empty((B, beams), device=img.device, dtype=torch.float32)
     allt = torch.empty((B * beams if want_all else 0, max_len), device=img.device, dtype=torch.int64)
     n = C.c_int32(0)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_generate_beam(e.handle, img.data_ptr(), B, Cc, H, W, int(beams), int(max_len), int(eos), toks.data_ptr(),
-                                           scores.data_ptr(), allt.data_ptr() if want_all else None, C.byref(n), _stream()))
+    _call(e, "txo_generate_beam", img.data_ptr(), B, Cc, H, W, int(beams), int(max_len), int(eos), toks.data_ptr(), scores.data_ptr(),
+          allt.data_ptr() if want_all else None, C.byref(n), leaves=(B, img))   # one row per IMAGE (engine.hip: struct Rows in generate_beam)
     return toks, scores, allt, torch.tensor([n.value], dtype=torch.int64)
 
 
@@ -364,8 +370,7 @@ def encode_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int) -> torch.
     ns = int(ragged_tokens(sizes).max()) if B else 1
     out = torch.empty((B, max(ns, 1), e.dims.embed_dim), device=img.device, dtype=torch.float32)
     n = C.c_int32(0)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_encode_ragged(e.handle, img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), out.data_ptr(), C.byref(n), _stream()))
+    _call(e, "txo_encode_ragged", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), out.data_ptr(), C.byref(n))
     if n.value != out.shape[1]:
         raise RuntimeError(f"texocr::encode_ragged: the engine's slot stride {n.value} is not the binding's {out.shape[1]}")
     return out
@@ -382,20 +387,17 @@ def _(img, sizes, engine):
 def decode_begin_ragged(enc: torch.Tensor, n_tokens: torch.Tensor, engine: int) -> None:
     """txo_decode_begin_ragged: enc (B, Ns, D) as encode_ragged returns it, n_tokens (B,) int32 CPU = valid rows per image."""
     e = _eng(engine, ready=True)
-    enc = _f32_dev(enc, "enc", e)
-    if enc.ndim != 3 or enc.shape[2] != e.dims.embed_dim:
-        raise ValueError(f"enc must be (B, Ns, {e.dims.embed_dim})")
+    enc = _enc_arg(enc, e, "Ns")
     if n_tokens.is_cuda or n_tokens.dtype != torch.int32 or tuple(n_tokens.shape) != (enc.shape[0],):
         raise ValueError("n_tokens must be an int32 CPU tensor of shape (B,)")
     n_tokens = n_tokens.contiguous()
-    e._enc_keepalive = enc
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_decode_begin_ragged(e.handle, enc.data_ptr(), enc.shape[0], enc.shape[1], _i32p(n_tokens), _stream()))
-    e._B = enc.shape[0]
+    _call(e, "txo_decode_begin_ragged", enc.data_ptr(), enc.shape[0], enc.shape[1], _i32p(n_tokens), leaves=(enc.shape[0], enc))
 
 
+@decode_begin.register_fake
 @decode_begin_ragged.register_fake
-def _(enc, n_tokens, engine):
+@decode_set_key_mask.register_fake
+def _(*args):
     return None
 
 
@@ -407,10 +409,8 @@ def generate_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len
     B, Cc, Hc, Wc = img.shape
     toks, _ = _gen_outputs(img, e, max_len, False)
     n = C.c_int32(0)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.txo_generate_ragged(e.handle, img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), int(max_len), int(eos),
-                                             toks.data_ptr(), C.byref(n), _stream()))
-    e._B, e._enc_keepalive = B, img
+    _call(e, "txo_generate_ragged", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), int(max_len), int(eos), toks.data_ptr(), C.byref(n),
+          leaves=())                            # nothing ragged outlives the call (engine.hip: generate_common)
     return toks, torch.tensor([n.value], dtype=torch.int64)
 
 
