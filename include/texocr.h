@@ -229,6 +229,8 @@ int txo_profile_read(txo_engine* e, int32_t kind, double* avg_ms, int64_t* count
 #define TXO_Q_SAMPLE_VOCAB_MAX 6   /* the largest vocabulary txo_set_sampling accepts on this device: beyond 1024 entries the sampler stages a row
                                     * in LDS (vocab * 4 bytes per workgroup) */
 #define TXO_Q_LAST_RAGGED 7        /* 1 if the last generate decoded a ragged batch (per-image encoder token counts), 0 otherwise */
+#define TXO_Q_LAST_LATENT_SELF 8   /* 1 if the last generate's SELF attention ran in latent form too (TXO_LATENT_SELF=1: the history is z, not k / v);
+                                    * 0 where the engine declined it (no latent form, per-row stop, a positional table beyond the beam slot table) */
 int txo_engine_query(txo_engine* e, int32_t what, int64_t* out);
 
 const char* txo_last_error(void);

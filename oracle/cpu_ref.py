@@ -399,7 +399,8 @@ def sample_probs(logits: torch.Tensor, temp: float) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------
-# beam search -- NOT in the reference: parity is unpinned except k = 1 == greedy.
+# beam search -- NOT in the reference: parity is pinned at k = 1 == greedy and, step by step, by a float64 replay of this
+# definition from the engine's own state (tests/beam_ref.py).
 # Definition used by the build: length-unnormalised sum of log_softmax(logits); k beams per image, only beam 0 live at
 # step 0; a beam that has emitted eos is finished and continues with eos at no cost; candidates are ranked by score with
 # ties broken by the lower flat index (beam * V + token); stop when every beam of every image is finished.

@@ -17,7 +17,7 @@ TXO_F32, TXO_BF16 = 0, 1
 TXO_E_INVALID, TXO_E_STATE, TXO_E_HIP = -1, -2, -3
 # txo_engine_query codes (include/texocr.h: TXO_Q_*; tests/test_abi_cpu.py holds the two lists together)
 (Q_LAST_PERSISTENT, Q_PERSIST_FALLBACKS, Q_LAST_ROW_RANGES, Q_LAST_LATENT, Q_RELOAD_KNOBS, Q_LAST_COMPACTIONS,
- Q_SAMPLE_VOCAB_MAX, Q_LAST_RAGGED) = 0, 1, 2, 3, 4, 5, 6, 7
+ Q_SAMPLE_VOCAB_MAX, Q_LAST_RAGGED, Q_LAST_LATENT_SELF) = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 
 class TxoConfig(C.Structure):

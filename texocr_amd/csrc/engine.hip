@@ -1972,6 +1972,7 @@ struct Engine : EngineBase {
         else if (what == TXO_Q_RELOAD_KNOBS) { knobs.run.read(); *out = 0; }
         else if (what == TXO_Q_LAST_COMPACTIONS) *out = last_compactions;
         else if (what == TXO_Q_LAST_RAGGED) *out = last_ragged ? 1 : 0;
+        else if (what == TXO_Q_LAST_LATENT_SELF) *out = (!last_persist && ses.latent && ses.lat_self) ? 1 : 0;
         else if (what == TXO_Q_SAMPLE_VOCAB_MAX) *out = std::max<int64_t>(64 * SR_PER, (int64_t)(sample_lds_max / sizeof(float)));
         else return fail(TXO_E_INVALID, "unknown query");
         return 0;
