@@ -141,6 +141,23 @@ int txo_generate_from_enc(txo_engine* e, const float* enc_dev, int32_t B, int32_
                           int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, float* logits_out_dev,
                           void* stream);
 
+/* txo_generate / txo_generate_from_enc that also return how sure the model was of every token it produced, from the token selection
+ * itself: no second pass and no [B, max_len, vocab] buffer.  logp_out_dev float [B, max_len] (row stride max_len like tokens_out_dev,
+ * caller-owned, must not be NULL): logp[b][t] = logits[b][t][tokens[b][t]] - logsumexp_v logits[b][t][v], natural log, on the f32
+ * logits the selection read, for the *n_steps_out returned positions.  ALWAYS at temperature 1 over the FULL vocabulary, greedy and
+ * sampled (txo_set_sampling) alike: it is the quantity txo_score's logp_out reports for the same tokens, NOT the probability under the
+ * sampler's top-k / temperature distribution the draw was made from.  TXO_STOP_GLOBAL: every returned position holds the true value,
+ * rows beyond their own eos included.  TXO_STOP_ROW: positions behind a row's first eos hold 0.0, so a row's sum is its sequence
+ * log-probability.  Every decode path carries it -- the persistent launch, row ranges, captured steps, live-row compaction, the
+ * sliding window -- and tokens, logits and draws are bit-identical to the calls without it.  A row whose logits are non-finite (a
+ * non-finite pixel) has unspecified logp; other rows are untouched.  logits_out_dev may be NULL as in txo_generate. */
+int txo_generate_logp(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t H, int32_t W,
+                      int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out,
+                      float* logits_out_dev, float* logp_out_dev, void* stream);
+int txo_generate_from_enc_logp(txo_engine* e, const float* enc_dev, int32_t B, int32_t N, int32_t max_len,
+                               int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, float* logits_out_dev,
+                               float* logp_out_dev, void* stream);
+
 /* Beam search over txo_generate's loop -- a BUILD EXTENSION: the reference has no beam search (BASELINE config 5 asks for
  * k = 5), so parity is anchored only at beams = 1 (== greedy).  Score = sum of log_softmax(logits) of the chosen tokens
  * (not length-normalised); a beam that has emitted eos is finished and continues with eos at no cost; the loop stops when
@@ -179,6 +196,10 @@ int txo_decode_begin_ragged(txo_engine* e, const float* enc_dev, int32_t B, int3
  * int64, *n_steps_out (HOST) the valid columns; 1 <= max_len <= cfg.max_len.  Synchronises the stream before returning. */
 int txo_generate_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
                         int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, void* stream);
+
+/* txo_generate_ragged with the per-token log-probabilities of txo_generate_logp: logp_out_dev float [B, max_len], must not be NULL. */
+int txo_generate_ragged_logp(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
+                             int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, float* logp_out_dev, void* stream);
 
 /* Token selection for the following decode steps / generate calls.  mode 0 (default): greedy argmax.  mode 1:
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits

@@ -71,7 +71,7 @@ struct EngineBase {
     virtual int encode_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, float* enc_out, int32_t* n_slot, hipStream_t s) = 0;
     virtual int decode_begin_ragged(const float* enc, int B, int Ns, const int32_t* n_tokens, int eos, hipStream_t s) = 0;
     virtual int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
-                                int* n_steps, hipStream_t s) = 0;
+                                int* n_steps, float* logp_out, hipStream_t s) = 0;
     virtual int decode_step(const int64_t* tok_in, int t, float* logits_out, int64_t* tok_out, hipStream_t s) = 0;
     virtual int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) = 0;
     virtual int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
@@ -79,7 +79,7 @@ struct EngineBase {
                       int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
     virtual int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) = 0;
     virtual int generate(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
-                         int64_t* tokens_out, int* n_steps, float* logits_out, hipStream_t s) = 0;
+                         int64_t* tokens_out, int* n_steps, float* logits_out, float* logp_out, hipStream_t s) = 0;
     virtual int generate_beam(const float* img, const float* enc, int B, int C, int H, int W, int N, int beams, int max_len,
                               int eos, int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps,
                               hipStream_t s) = 0;
@@ -193,6 +193,7 @@ struct Engine : EngineBase {
     bool last_ragged = false;         // TXO_Q_LAST_RAGGED
     Stamps stamps;                    // TXO_STAMPS / TXO_PSTAMPS diagnostics (stamps.h)
     int64_t* tok_buf = nullptr;            // [Bmax][Tmax] generated ids (engine-owned so graphs do not bake user pointers)
+    float* logp_buf = nullptr;             // [Bmax][Tmax] their log-probabilities, for a captured step that carries them (generate_impl)
     Session ses;                           // the open decode session (session.h)
     // persistent decode launch (persist.h): control block (device + pinned host copy), per-stage stamps of one position
     PersistCtl* pctl = nullptr; PersistCtl* pctl_host = nullptr; unsigned long long* pstamps = nullptr;
@@ -649,6 +650,7 @@ struct Engine : EngineBase {
         if (int r = dalloc(&done_flag, (size_t)Tmax * MAXL)) return r;
         if (int r = dalloc(&st, MAXL)) return r;
         if (int r = dalloc(&tok_buf, (size_t)Bmax * Tmax)) return r;
+        if (int r = dalloc(&logp_buf, (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&bscore, (size_t)Bmax)) return r;
         if (int r = dalloc(&bfin, (size_t)Bmax)) return r;
         if (int r = dalloc(&bpath[0], (size_t)Bmax * Tmax)) return r;
@@ -942,14 +944,14 @@ struct Engine : EngineBase {
         return begin_session(enc, B, Ns, eos, s, true, KeyCounts{nullptr, n_tokens});
     }
     int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
-                        int* n_steps, hipStream_t s) override {
+                        int* n_steps, float* logp_out, hipStream_t s) override {
         if (int r = ragged_refusals()) return r;
         if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
         if (max_len > Tmax)
             return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length (the sliding window runs through the prefill, which has no ragged form)");
         ImageBatch ib;
         if (int r = ragged_batch(B, C, Hc, Wc, sizes, s, &ib)) return r;
-        return generate_common(&ib, img, B, ib.N, max_len, eos, tokens_out, n_steps, nullptr, s);
+        return generate_common(&ib, img, B, ib.N, max_len, eos, tokens_out, n_steps, nullptr, logp_out, s);
     }
 
     // Opens the decode session on enc [B][N][D] (session.h), complete: no caller patches a field in behind this call.  kc: a ragged session's
@@ -1298,7 +1300,8 @@ struct Engine : EngineBase {
     // one decode position of lane `li` on stream s; tokens_out/logits_out are GLOBAL-batch base pointers
     // host_t: the decode position when the caller knows it (every eager loop does); -1 makes the kernels read the
     // device-side counter instead, which is what lets ONE captured graph serve every step
-    int enqueue_step(hipStream_t s, int li, int64_t* tokens_out, int out_stride, float* logits_out, int eos,
+    // logp_out: [rows][out_stride] like tokens_out, or null (step.h: StepArgs::logp_out)
+    int enqueue_step(hipStream_t s, int li, int64_t* tokens_out, int out_stride, float* logits_out, float* logp_out, int eos,
                      const BeamCtx* bm = nullptr, int host_t = -1) {
         const auto& ln = lanes[li];
         const int B = ses.rows, N = ses.keys, nb = ln.nb;
@@ -1392,7 +1395,8 @@ struct Engine : EngineBase {
         StepArgs sa{llog, V, nb, cur_tok + r0, tokens_out ? tokens_out + r0 * out_stride : nullptr, out_stride,
                     logits_out ? logits_out + r0 * (size_t)out_stride * V : nullptr, st + li, eos_seen + r0,
                     done_flag + (size_t)li * Tmax, eos, sample_topk, 1.0f / sample_temp, sample_seed, (int)r0,
-                    ses.row_stop ? 1 : 0, ses.row_stop ? row_map + r0 : nullptr};
+                    ses.row_stop ? 1 : 0, ses.row_stop ? row_map + r0 : nullptr,
+                    logp_out ? logp_out + r0 * out_stride : nullptr};
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
@@ -1405,14 +1409,15 @@ struct Engine : EngineBase {
     }
 
     // capture lane li's step (tokens into the engine-owned tok_buf) as a graph, or reuse the cached one
-    int lane_graph(int li, int eos) {
+    // logp: the step also writes its log-probabilities, into the engine-owned logp_buf (part of the key: it is another StepArgs)
+    int lane_graph(int li, int eos, bool logp) {
         const auto& ln = lanes[li];
-        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode);
+        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode, logp);
         if (lanes.cached(li, key)) return 0;
         hipStream_t cs = lanes.cap_stream;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         HIP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        const int r = enqueue_step(cs, li, tok_buf, Tmax, nullptr, eos);
+        const int r = enqueue_step(cs, li, tok_buf, Tmax, nullptr, logp ? logp_buf : nullptr, eos);
         hipError_t e = hipStreamEndCapture(cs, &graph);
         if (r) return r;
         if (e != hipSuccess) return fail(TXO_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1430,7 +1435,7 @@ struct Engine : EngineBase {
         lanes[0].stream = s;
         if (tok_in) hipLaunchKernelGGL(copy_tokens_kernel, dim3((ses.rows + 255) / 256), dim3(256), 0, s, cur_tok, tok_in, ses.rows, V);
         hipLaunchKernelGGL(set_position_kernel, dim3(1), dim3(1), 0, s, st, t);
-        if (int r = enqueue_step(s, 0, nullptr, 0, nullptr, -1, nullptr, t)) return r;
+        if (int r = enqueue_step(s, 0, nullptr, 0, nullptr, nullptr, -1, nullptr, t)) return r;
         if (logits_out) HIP_TRY(hipMemcpyAsync(logits_out, dlogits, sizeof(float) * ses.rows * V, hipMemcpyDeviceToDevice, s));
         if (tok_out) HIP_TRY(hipMemcpyAsync(tok_out, cur_tok, sizeof(int64_t) * ses.rows, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipGetLastError());
@@ -1599,7 +1604,8 @@ struct Engine : EngineBase {
     template <int D_, int H_>
     int launch_persist(const PersistArgs<T>& pa, hipStream_t s) {
         const size_t lds = persist_lds_bytes<T, D_, H_>();
-        auto kern = sample_mode ? decode_persist_kernel<T, D_, H_, true> : decode_persist_kernel<T, D_, H_, false>;
+        auto kern = pa.logp_out ? (sample_mode ? decode_persist_kernel<T, D_, H_, true, true> : decode_persist_kernel<T, D_, H_, false, true>)
+                                : (sample_mode ? decode_persist_kernel<T, D_, H_, true, false> : decode_persist_kernel<T, D_, H_, false, false>);
         // per DEVICE, not per process (one process may drive several GPUs through several engines): set on every launch, it is cheap
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             (void)hipGetLastError();
@@ -1617,7 +1623,8 @@ struct Engine : EngineBase {
     // returns 0 (done), TXO_E_STATE (the launch gave up: redo with launches), or an error
     // n_pos positions are decoded; rows of tokens_out / logits_out are out_stride positions apart
     // *broke: the reference's GLOBAL eos break fired inside these n_pos positions (possibly at the very last one)
-    int generate_persist(int B, int N, int n_pos, int out_stride, int eos, int64_t* tokens_out, float* logits_out, int* n_steps, bool* broke, hipStream_t s) {
+    int generate_persist(int B, int N, int n_pos, int out_stride, int eos, int64_t* tokens_out, float* logits_out, float* logp_out, int* n_steps, bool* broke,
+                         hipStream_t s) {
         const int max_len = n_pos;
         PersistArgs<T> pa{};
         pa.B = B; pa.N = N; pa.V = V; pa.Ld = cfg.dec_layers; pa.Tmax = Tmax; pa.max_len = max_len; pa.eos = eos; pa.bos = cfg.bos;
@@ -1647,7 +1654,7 @@ struct Engine : EngineBase {
         pa.dx = dx; pa.dy = dy; pa.dq = dq; pa.dlogits = dlogits; pa.dao = dao; pa.dhid = dhid;
         pa.cur_tok = cur_tok; pa.eos_seen = eos_seen; pa.skv = skv; pa.ckv = ckv;
         pa.self_stride = (size_t)ses.rows * Id * Tmax; pa.cross_stride = (size_t)ses.images * N * Id;
-        pa.tokens_out = tokens_out; pa.out_stride = out_stride; pa.logits_out = logits_out;
+        pa.tokens_out = tokens_out; pa.out_stride = out_stride; pa.logits_out = logits_out; pa.logp_out = logp_out;
         pa.sample = sample_mode; pa.sample_topk = sample_topk; pa.inv_temp = 1.0f / sample_temp; pa.seed = sample_seed;
         pa.ctl = pctl; pa.stamps = pstamps;
         const char* stamp_file = knobs.run.pstamps ? knobs.run.pstamps_file.c_str() : nullptr;
@@ -1691,7 +1698,7 @@ struct Engine : EngineBase {
     // are what the global-break run gives -- and every token BEHIND a row's first eos becomes cfg.pad (pad_after_eos_kernel); on the launch
     // path the finished rows also stop costing work (compact_lane).
     int generate(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
-                 int64_t* tokens_out, int* n_steps, float* logits_out, hipStream_t s) override {
+                 int64_t* tokens_out, int* n_steps, float* logits_out, float* logp_out, hipStream_t s) override {
         last_compactions = 0; last_ragged = false;                // (results of THIS call, also when it is refused)
         if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
         // the window's multi-position forward (generate_window) has two preconditions: refuse BEFORE decoding anything
@@ -1700,21 +1707,22 @@ struct Engine : EngineBase {
                                        "size that is a multiple of 8 and max_length <= max_batch * max_tokens (use decoder.generate's stepwise loop)");
         ImageBatch ib;
         if (img) if (int r = fixed_batch(B, C, H, W, &ib)) return r;
-        return generate_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, max_len, eos, tokens_out, n_steps, logits_out, s);
+        return generate_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, max_len, eos, tokens_out, n_steps, logits_out, logp_out, s);
     }
     // the common body of generate() / generate_ragged(): `ib` and its images, or (ib null) the caller's encoder rows src [B][N][D]
+    // logp_out [B][max_len] or null: log_softmax(logits)[token] of every returned position (txo_generate_logp), 0 behind a row's eos under the per-row stop
     int generate_common(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* n_steps,
-                        float* logits_out, hipStream_t s) {
+                        float* logits_out, float* logp_out, hipStream_t s) {
         int steps = 0; last_compactions = 0;
         last_ragged = ib && ib->ragged;
-        const int rc = generate_impl(ib, src, B, N, max_len, eos, tokens_out, &steps, logits_out, s);
+        const int rc = generate_impl(ib, src, B, N, max_len, eos, tokens_out, &steps, logits_out, logp_out, s);
         ses.row_stop = false;                                     // the decode is over (a txo_decode_step behind it steps every row)
         if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
         if (n_steps) *n_steps = steps;
         if (last_compactions > 0) ses.open = false;               // the session's rows are no longer the batch's: a new decode must begin
         if (stop_mode == 1 && eos >= 0 && steps > 0) {
-            hipLaunchKernelGGL(pad_after_eos_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tokens_out, max_len, steps, B, eos, cfg.bos, cfg.pad);
+            hipLaunchKernelGGL(pad_after_eos_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tokens_out, logp_out, max_len, steps, B, eos, cfg.bos, cfg.pad);
             HIP_TRY(hipStreamSynchronize(s));
             HIP_TRY(hipGetLastError());
         }
@@ -1746,7 +1754,7 @@ struct Engine : EngineBase {
         return 0;
     }
     int generate_impl(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* steps,
-                      float* logits_out, hipStream_t s) {
+                      float* logits_out, float* logp_out, hipStream_t s) {
         // max_len > decoder.max_len: the reference slides its window (decoder.py:99-100).  The first Tmax positions decode with the
         // KV cache as always (n_pos of them; rows of the outputs are max_len apart); every further token re-runs its window of the
         // last Tmax tokens, positions re-indexed from 0, through ONE multi-position forward (prefill) -- generate_window below.
@@ -1759,11 +1767,11 @@ struct Engine : EngineBase {
         if (persist_usable(B)) {
             ensure_ckv(s);                                        // (the persistent launch reads projected K/V panels: the session stays in the K/V form)
             bool broke = false;
-            const int pr = generate_persist(B, N, n_pos, max_len, eos, tokens_out, logits_out, steps, &broke, s);
+            const int pr = generate_persist(B, N, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, &broke, s);
             if (pr == 0) {
                 last_persist = true; persist_strikes = 0;
                 // (an eos break exactly at position n_pos - 1 also leaves steps == n_pos: the window must not start then)
-                if (!broke && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, steps, s);
+                if (!broke && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, s);
                 return 0;
             }
             if (pr != TXO_E_STATE) return pr;
@@ -1805,9 +1813,11 @@ struct Engine : EngineBase {
         last_ranges = lanes.n;
         reset_lanes(s, eos);
         bool use_graph = !eager && !prof && !prof_cross;   // event-carrying launches cannot be captured
-        if (use_graph) for (int i = 0; i < lanes.n; ++i) if (int r = lane_graph(i, eos)) return r;
+        const bool glogp = logp_out != nullptr;                    // a captured step carries the log-probabilities like the tokens: into the engine's buffer
+        if (use_graph) for (int i = 0; i < lanes.n; ++i) if (int r = lane_graph(i, eos, glogp)) return r;
         if (int r = lanes.fork(s)) return r;
         int64_t* tdst = use_graph ? tok_buf : tokens_out;
+        float* ldst = use_graph && logp_out ? logp_buf : logp_out;
         const int tstride = use_graph ? Tmax : max_len;               // rows of tokens_out are max_len apart (only n_pos positions are decoded here)
         DonePoll poll{lanes, done_flag, Tmax, n_pos};              // GLOBAL eos break: poll.done = it fired inside the positional table
         int live_pend = -1;                                        // per-row stop: position behind which the ranges' finished-row counts were requested
@@ -1820,7 +1830,7 @@ struct Engine : EngineBase {
             else if (stamps.slot >= 0) stamps.dump(stamp_file, knobs.has_stamps_raw ? &knobs.stamps_raw : nullptr, s);
             for (int i = 0; i < lanes.n; ++i) {
                 if (use_graph) HIP_TRY(hipGraphLaunch(lanes[i].exec, lanes[i].stream));
-                else if (int r2 = enqueue_step(lanes[i].stream, i, tdst, tstride, logits_out, eos, nullptr, t)) return r2;
+                else if (int r2 = enqueue_step(lanes[i].stream, i, tdst, tstride, logits_out, ldst, eos, nullptr, t)) return r2;
             }
             if (eos < 0) continue;
             if (ses.row_stop) {
@@ -1835,7 +1845,7 @@ struct Engine : EngineBase {
                         if (use_graph) bound = std::min(lanes[i].nb, (bound + 15) & ~15);      // a captured step per multiple of 16 rows
                         if (bound >= 1 && lanes[i].nb - bound >= knobs.stop_gain) {
                             if (int r2 = compact_lane(i, bound, t + 1, eos)) return r2;
-                            if (use_graph) { if (int r2 = lane_graph(i, eos)) return r2; }
+                            if (use_graph) { if (int r2 = lane_graph(i, eos, glogp)) return r2; }
                         }
                     }
                     live_pend = -1;
@@ -1855,14 +1865,17 @@ struct Engine : EngineBase {
         };
         if (int r = decode_loop()) return abandon_lanes(s, r);
         if (int r = lanes.join(s)) return r;
-        if (use_graph)
+        if (use_graph) {
             HIP_TRY(hipMemcpy2DAsync(tokens_out, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax,
                                      sizeof(int64_t) * n_pos, B, hipMemcpyDeviceToDevice, s));
+            if (logp_out)
+                HIP_TRY(hipMemcpy2DAsync(logp_out, sizeof(float) * max_len, logp_buf, sizeof(float) * Tmax, sizeof(float) * n_pos, B, hipMemcpyDeviceToDevice, s));
+        }
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         lanes.split(ses.rows, 1, s);
         *steps = poll.steps;
-        if (!poll.done && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, steps, s);
+        if (!poll.done && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, s);
         return 0;
     }
 
@@ -1871,7 +1884,7 @@ struct Engine : EngineBase {
     // decoder, the last position's logits.  Nothing cached survives the shift, so every such token costs one multi-position
     // forward of Tmax rows per image (prefill) + the single-position final LayerNorm / logits / token selection of the step path.
     // The GLOBAL eos test still looks at the whole output (:115), i.e. the per-row "seen" state carries over.
-    int generate_window(int B, int n_pos, int max_len, int eos, int64_t* tokens_out, float* logits_out, int* steps, hipStream_t s) {
+    int generate_window(int B, int n_pos, int max_len, int eos, int64_t* tokens_out, float* logits_out, float* logp_out, int* steps, hipStream_t s) {
         lanes.split(ses.rows, 1, s);
         lanes[0].stream = s;
         // the launch path's eos bookkeeping, rebuilt from the tokens decoded so far (a persistent launch keeps its own)
@@ -1882,7 +1895,8 @@ struct Engine : EngineBase {
         for (int i = n_pos; i < max_len; ++i) {
             if (int r = prefill(tokens_out + (i - Tmax), max_len, Tmax, nullptr, dlogits, s)) return r;
             hipLaunchKernelGGL(set_position_kernel, dim3(1), dim3(1), 0, s, st, i);
-            StepArgs sa{dlogits, V, B, cur_tok, tokens_out, max_len, logits_out, st, eos_seen, flag - i, eos, sample_topk, 1.0f / sample_temp, sample_seed, 0};
+            StepArgs sa{dlogits, V, B, cur_tok, tokens_out, max_len, logits_out, st, eos_seen, flag - i, eos, sample_topk, 1.0f / sample_temp, sample_seed, 0,
+                        0, nullptr, logp_out};
             if (sample_mode) launch_sample_step(s, B, sa);
             else hipLaunchKernelGGL(argmax_step_kernel, dim3(B), dim3(64), 0, s, sa);
             *steps = i + 1;
@@ -1937,7 +1951,7 @@ struct Engine : EngineBase {
         for (int t = 0; t < max_len; ++t) {
             BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1]};
             for (int i = 0; i < lanes.n; ++i)
-                if (int r2 = enqueue_step(lanes[i].stream, i, nullptr, 0, nullptr, eos, &bm, t)) return r2;
+                if (int r2 = enqueue_step(lanes[i].stream, i, nullptr, 0, nullptr, nullptr, eos, &bm, t)) return r2;
             cur ^= 1;
             if (eos < 0) continue;
             if (int r2 = poll.after(t)) return r2;
@@ -2087,7 +2101,13 @@ int txo_decode_begin_ragged(txo_engine* e, const float* enc, int32_t B, int32_t 
 int txo_generate_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, int32_t max_len,
                         int32_t eos, int64_t* tokens_out, int32_t* n_steps, void* stream) {
     if (!e || !img || !sizes || !tokens_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate_ragged(img, B, C, Hc, Wc, sizes, max_len, eos, tokens_out, n_steps, (hipStream_t)stream);
+    return e->impl->generate_ragged(img, B, C, Hc, Wc, sizes, max_len, eos, tokens_out, n_steps, nullptr, (hipStream_t)stream);
+}
+
+int txo_generate_ragged_logp(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, int32_t max_len,
+                             int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logp_out, void* stream) {
+    if (!e || !img || !sizes || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->generate_ragged(img, B, C, Hc, Wc, sizes, max_len, eos, tokens_out, n_steps, logp_out, (hipStream_t)stream);
 }
 
 int txo_decode_step(txo_engine* e, const int64_t* tok_in, int32_t t, float* logits_out, int64_t* tok_out, void* stream) {
@@ -2121,13 +2141,25 @@ int txo_decode_set_key_mask(txo_engine* e, const uint8_t* mask, int32_t cols, vo
 int txo_generate(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t max_len,
                  int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logits_out, void* stream) {
     if (!e || !img || !tokens_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate(img, nullptr, B, C, H, W, 0, max_len, eos, tokens_out, n_steps, logits_out, (hipStream_t)stream);
+    return e->impl->generate(img, nullptr, B, C, H, W, 0, max_len, eos, tokens_out, n_steps, logits_out, nullptr, (hipStream_t)stream);
+}
+
+int txo_generate_logp(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t max_len,
+                      int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logits_out, float* logp_out, void* stream) {
+    if (!e || !img || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->generate(img, nullptr, B, C, H, W, 0, max_len, eos, tokens_out, n_steps, logits_out, logp_out, (hipStream_t)stream);
 }
 
 int txo_generate_from_enc(txo_engine* e, const float* enc, int32_t B, int32_t N, int32_t max_len, int32_t eos,
                           int64_t* tokens_out, int32_t* n_steps, float* logits_out, void* stream) {
     if (!e || !enc || !tokens_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate(nullptr, enc, B, 0, 0, 0, N, max_len, eos, tokens_out, n_steps, logits_out, (hipStream_t)stream);
+    return e->impl->generate(nullptr, enc, B, 0, 0, 0, N, max_len, eos, tokens_out, n_steps, logits_out, nullptr, (hipStream_t)stream);
+}
+
+int txo_generate_from_enc_logp(txo_engine* e, const float* enc, int32_t B, int32_t N, int32_t max_len, int32_t eos,
+                               int64_t* tokens_out, int32_t* n_steps, float* logits_out, float* logp_out, void* stream) {
+    if (!e || !enc || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->generate(nullptr, enc, B, 0, 0, 0, N, max_len, eos, tokens_out, n_steps, logits_out, logp_out, (hipStream_t)stream);
 }
 
 int txo_generate_beam(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t beams, int32_t max_len,

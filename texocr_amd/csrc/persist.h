@@ -82,6 +82,7 @@ template <typename T> struct PersistArgs {
     int64_t* cur_tok; int* eos_seen;
     T *skv, *ckv; size_t self_stride, cross_stride;           // per (layer, k|v) plane
     int64_t* tokens_out; int out_stride; float* logits_out;
+    float* logp_out;                                          // [B][out_stride] or null: log_softmax(logits)[token] of every position (step.h: StepArgs::logp_out)
     PersistCtl* ctl;
     int w_tiled;                                              // the projections' weights (wqkv, wo_s, wo_c, w1, w2, wlog) are the TILED copies (dec_gemm.h); wq_c stays row-major (dec_attn.h reads it)
     int sample; int sample_topk; float inv_temp; unsigned long long seed;   // sample != 0: the reference's sampler ends a position (step.h: sample_row) instead of the arg-max
@@ -184,7 +185,10 @@ constexpr size_t persist_lds_bytes() {
 
 // SAMPLE: the position's last stage is the reference's sampler (step.h) instead of the arg-max.  Two instantiations: the greedy
 // kernel carries no sampler code (the sampler inlined into ONE kernel behind a run-time flag cost the greedy decode 40 VGPRs).
-template <typename T, int D_, int HEADS_, bool SAMPLE>
+// LOGP: the last stage also writes the chosen token's log-probability (a.logp_out).  A template parameter, not a run-time flag: behind a
+// flag the log-sum-exp cost the kernels that do NOT write it 2-3 VGPRs and 1-40 spilled SGPRs; with LOGP = false the
+// code is the one without the feature.
+template <typename T, int D_, int HEADS_, bool SAMPLE, bool LOGP>
 __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<T> a) {
     constexpr int D = D_, HEADS = HEADS_, ID = HEADS * DH, F = 4 * D;
     constexpr size_t GLDS = persist_group_lds<T, D_, HEADS_>();
@@ -421,13 +425,15 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                 const float* lg = a.dlogits + (size_t)row * a.V;
                 float* lo = a.logits_out ? a.logits_out + ((size_t)row * a.out_stride + t) * a.V : nullptr;
                 float best = -3.4e38f; int bi = 0x7fffffff;
+                constexpr bool lp = LOGP;                                      // the launch path's log-sum-exp (step.h), operation for operation
+                [[maybe_unused]] float logp = 0.f, lm = -3.4e38f, ls = 0.f;
                 if constexpr (SAMPLE) {
                     // the reference's default decode (decoder.py:104-108): top-k, softmax(/temp), one draw keyed by (seed; row, t) --
                     // the same function and key as the launch path's sample_step_kernel, hence the same draw.  The row lives in
                     // registers (step.h: vocabularies up to 1024 entries; Engine::persist_usable sends larger ones to the launch path).
                     auto ld = [&](int j) { return ldc_f32<true>(lg + j); };
                     auto ld4 = [&](int j) { return ldc16_at<true>(a.dlogits, (size_t)row * a.V + j); };
-                    bi = sample_row_regs(ld, ld4, lo, a.V, lane, a.sample_topk, a.inv_temp, a.seed, (unsigned)row, (unsigned)t);
+                    bi = sample_row_regs(ld, ld4, lo, a.V, lane, a.sample_topk, a.inv_temp, a.seed, (unsigned)row, (unsigned)t, lp, logp);
                 } else {
                 if ((a.V & 3) == 0) {                          // four 16-byte pieces per lane in flight
                     const int n4 = a.V >> 2;
@@ -443,6 +449,7 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                             const int j4 = base + u * 64 + lane;
                             if (j4 >= n4) continue;
                             if (lo) reinterpret_cast<float4*>(lo)[j4] = v[u];
+                            if constexpr (lp) lse_push4(lm, ls, v[u]);
                             const int j = j4 * 4;               // ascending index: first maximum wins inside a lane
                             if (v[u].x > best) { best = v[u].x; bi = j; }
                             if (v[u].y > best) { best = v[u].y; bi = j + 1; }
@@ -454,15 +461,18 @@ __global__ __launch_bounds__(PS_THREADS) void decode_persist_kernel(PersistArgs<
                     for (int j = lane; j < a.V; j += 64) {
                         const float v = ldc_f32<true>(lg + j);
                         if (lo) lo[j] = v;
+                        if constexpr (lp) lse_push(lm, ls, v);
                         if (v > best) { best = v; bi = j; }
                     }
                 }
                 wave_argmax(best, bi);                                        // ties -> lowest index (torch.argmax)
+                if constexpr (lp) logp = -lse_finish(lm, ls, best);
                 }
                 if (lane == 0) {
                     bi = in_vocab(bi, a.V);                                       // (non-finite logits: step.h)
                     a.cur_tok[row] = bi;
                     a.tokens_out[(size_t)row * a.out_stride + t] = bi;
+                    if constexpr (lp) a.logp_out[(size_t)row * a.out_stride + t] = logp;
                     if (a.eos >= 0 && bi == a.eos &&
                         __hip_atomic_load(reinterpret_cast<unsigned*>(a.eos_seen + row), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
                         __hip_atomic_store(reinterpret_cast<unsigned*>(a.eos_seen + row), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

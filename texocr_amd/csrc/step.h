@@ -35,6 +35,9 @@ struct StepArgs {
     // nothing more is written for it -- and the live rows of a range may have been compacted to its front (Engine::compact_lane):
     // row_map[row] = row of the BATCH that sits in slot `row` of the range (null: the identity).  Outputs and sampler keys follow it.
     int stop_rows; const int* row_map;
+    // log-probability of the chosen token under softmax(logits), temperature 1 over the FULL vocabulary -- greedy and sampled alike: the quantity
+    // txo_score's logp reports, NOT the sampler's top-k / temperature distribution the draw was made from
+    float* logp_out;            // [rows][out_stride] or null
 };
 // row of the range (relative to row0) whose outputs slot `row` produces
 __device__ inline int out_row(const StepArgs& a, int row) { return a.row_map ? a.row_map[row] - a.row0 : row; }
@@ -43,11 +46,12 @@ __device__ inline int out_row(const StepArgs& a, int row) { return a.row_map ? a
 // a token id a selection can produce only from non-finite logits (arg-max over NaNs finds nothing: index 0x7fffffff) must never reach
 // the next position's embedding lookup: ids are forced into the vocabulary (txo_encode: non-finite input gives unspecified, in-range tokens)
 __device__ inline int in_vocab(int tok, int V) { return (unsigned)tok < (unsigned)V ? tok : 0; }
-__device__ inline void commit_token(const StepArgs& a, int row, int t, int tok) {
+__device__ inline void commit_token(const StepArgs& a, int row, int t, int tok, float logp = 0.f) {
     tok = in_vocab(tok, a.V);
     a.cur_tok[row] = tok;
     const bool frozen = a.stop_rows && a.eos >= 0 && a.eos_seen[row];          // per-row stop: the host pads behind the row's first eos
     if (a.tokens_out && !frozen) a.tokens_out[(size_t)out_row(a, row) * a.out_stride + t] = tok;
+    if (a.logp_out && !frozen) a.logp_out[(size_t)out_row(a, row) * a.out_stride + t] = logp;
     unsigned add = 1u;
     if (a.eos >= 0 && tok == a.eos && !a.eos_seen[row]) { a.eos_seen[row] = 1; add += 1u << 16; }
     const unsigned old = atomicAdd(&a.st->arrive, add);
@@ -60,11 +64,33 @@ __device__ inline void commit_token(const StepArgs& a, int row, int t, int tok) 
     }
 }
 
+// log-sum-exp of a logits row beside the token selection, for logp_out: every lane keeps a running (max m, sum of exp(v - m)) over the
+// logits it streams anyway (rescaled when its max moves), the lanes' sums are brought to the row's max and added by ONE wave reduction.
+// Shared by the step kernels here and the persistent decode kernel's last stage (persist.h): the same operations in the same order ->
+// the same bits on every decode path.  (fmaf spelled out: a contraction the compiler chooses per surrounding code would not be.)
+__device__ inline void lse_push(float& m, float& s, float v) {
+    const float nm = fmaxf(m, v);
+    s = fmaf(s, expf(m - nm), expf(v - nm));
+    m = nm;
+}
+__device__ inline void lse_push4(float& m, float& s, const float4& v) {
+    const float nm = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+    s = fmaf(s, expf(m - nm), (expf(v.x - nm) + expf(v.y - nm)) + (expf(v.z - nm) + expf(v.w - nm)));
+    m = nm;
+}
+// log of the row's sum of exp(v - mx), mx = the row's maximum (every lane calls it; a lane that saw nothing holds m = -3.4e38, s = 0)
+__device__ inline float lse_finish(float m, float s, float mx) {
+    const float part = s * expf(m - mx);
+    return logf(wave_sum(part));
+}
+
 __global__ __launch_bounds__(64) void argmax_step_kernel(StepArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
     const int t = a.st->t;
     const float* lg = a.logits + (size_t)row * a.V;
     float best = -3.4e38f; int bi = 0x7fffffff;
+    float lm = -3.4e38f, ls = 0.f;             // logp_out: this lane's running (max, sum of exp) -- the row is read once
+    const bool lp = a.logp_out != nullptr;
     float* lo = a.logits_out ? a.logits_out + ((size_t)out_row(a, row) * a.out_stride + t) * a.V : nullptr;
     if ((a.V & 3) == 0) {                      // rows are 16-byte aligned: four float4 per lane in flight
         const int n4 = a.V >> 2;
@@ -80,6 +106,7 @@ __global__ __launch_bounds__(64) void argmax_step_kernel(StepArgs a) {
                 const int j4 = base + u * 64 + lane;
                 if (j4 >= n4) continue;
                 if (lo) reinterpret_cast<float4*>(lo)[j4] = v[u];
+                if (lp) lse_push4(lm, ls, v[u]);
                 const int j = j4 * 4;                          // ascending index: first maximum wins inside a lane
                 if (v[u].x > best) { best = v[u].x; bi = j; }
                 if (v[u].y > best) { best = v[u].y; bi = j + 1; }
@@ -91,11 +118,14 @@ __global__ __launch_bounds__(64) void argmax_step_kernel(StepArgs a) {
         for (int j = lane; j < a.V; j += 64) {
             const float v = lg[j];
             if (lo) lo[j] = v;
+            if (lp) lse_push(lm, ls, v);
             if (v > best) { best = v; bi = j; }
         }
     }
     wave_argmax(best, bi);                                                 // ties -> lowest index (torch.argmax)
-    if (lane == 0) commit_token(a, row, t, bi);
+    float logp = 0.f;
+    if (lp) logp = -lse_finish(lm, ls, best);                              // the chosen logit IS the maximum: best - (best + log sum exp(v - best))
+    if (lane == 0) commit_token(a, row, t, bi, logp);
 }
 
 // Philox4x32-10 (counter-based, no state to carry between steps): counter = (row, t, 0, 0), key = seed.
@@ -120,13 +150,20 @@ __device__ inline unsigned fkey(float f) {          // order-preserving float ->
 // Statistically equivalent to torch.multinomial (a different RNG stream), reproducible for a given seed.
 // Shared by sample_step_kernel (launch path) and the persistent decode kernel (persist.h; LOAD reads the logits another
 // workgroup of the same launch wrote): same operations in the same order -> the same draw for the same (seed, row, t).
+// want_lp (wave-uniform): also *lp = log_softmax(logits)[pick] of the UNSCALED logits over the whole row (StepArgs::logp_out); the draw is untouched.
 template <class Load>
 __device__ inline int sample_row_lds(Load&& load, float* row_lds, float* lo, int V, int lane, int topk, float inv_temp,
-                                 unsigned long long seed, unsigned row, unsigned t) {
+                                 unsigned long long seed, unsigned row, unsigned t, bool want_lp, float& lp) {
     float mx = -3.4e38f;
     for (int j = lane; j < V; j += 64) { const float v = load(j); row_lds[j] = v; if (lo) lo[j] = v; mx = fmaxf(mx, v); }
     mx = wave_max(mx);
     __builtin_amdgcn_s_waitcnt(0xC07F);              // own LDS writes done (single wave)
+    float lsum = 0.f;
+    if (want_lp) {                                   // before the probabilities replace the logits in LDS
+        float sl = 0.f;
+        for (int j = lane; j < V; j += 64) sl += expf(row_lds[j] - mx);
+        lsum = wave_sum(sl);
+    }
     // k-th largest key
     const int k = min(max(topk, 1), V);
     unsigned prefix = 0u;
@@ -180,6 +217,7 @@ __device__ inline int sample_row_lds(Load&& load, float* row_lds, float* lo, int
         wave_argmax(best, bi);
         pick = bi;
     }
+    if (want_lp) lp = (load(in_vocab(pick, V)) - mx) - logf(lsum);     // (one logit read again: LDS holds probabilities by now)
     return pick;
 }
 
@@ -200,7 +238,7 @@ constexpr int SR_PER = 16;
 // order and RNG key are unchanged: the same draws (token hashes equal).
 template <class Load, class Load4>
 __device__ __forceinline__ int sample_row_regs(Load&& load, Load4&& load4, float* lo, int V, int lane, int topk, float inv_temp,
-                                               unsigned long long seed, unsigned row, unsigned t) {
+                                               unsigned long long seed, unsigned row, unsigned t, bool want_lp, float& lp) {
     // (inlined on purpose: as a called function it put the persistent decode kernel under the calling convention -- values live
     // across the call site pinned to callee-saved registers -- and cost the GREEDY decode 1.5 %; ONE 16-register array keeps it
     // inside that kernel's budget)
@@ -240,6 +278,17 @@ __device__ __forceinline__ int sample_row_regs(Load&& load, Load4&& load4, float
         for (int u = 0; u < SR_PER; ++u) { if (u < nin) dst[u] = unfkey(key[u]); }
     }
     mx = wave_max(mx);
+    float lsum = 0.f;
+    if (want_lp) {                                            // (wave-uniform) sum of exp of the UNSCALED logits, before the keys become probabilities
+        float sl = 0.f;
+#pragma unroll
+        for (int u = 0; u < SR_PER; ++u) {
+            const bool in = u < nin;
+            const float e = expf((in ? unfkey(key[u]) : mx) - mx);
+            sl += in ? e : 0.f;
+        }
+        lsum = wave_sum(sl);
+    }
     const int k = min(max(topk, 1), V);
     unsigned prefix = 0u;
     for (int bit = 31; bit >= 0; --bit) {
@@ -307,6 +356,7 @@ __device__ __forceinline__ int sample_row_regs(Load&& load, Load4&& load4, float
         wave_argmax(best, bi);
         pick = bi;
     }
+    if (want_lp) lp = (load(in_vocab(pick, V)) - mx) - logf(lsum);     // (one logit read again: the registers hold probabilities by now)
     return pick;
 }
 
@@ -321,11 +371,13 @@ __global__ __launch_bounds__(64) void sample_step_kernel(StepArgs a) {
     const float* lg = a.logits + (size_t)row * V;
     const int orow = out_row(a, row);
     float* lo = a.logits_out ? a.logits_out + ((size_t)orow * a.out_stride + t) * V : nullptr;
-    int pick;
+    int pick; float logp = 0.f;
+    const bool lp = a.logp_out != nullptr;
     if constexpr (REGS) pick = sample_row_regs([&](int j) { return lg[j]; }, [&](int j) { return ld16(lg + j); }, lo, V, lane, a.topk, a.inv_temp, a.seed,
-                                               (unsigned)(a.row0 + orow), (unsigned)t);
-    else pick = sample_row_lds([&](int j) { return lg[j]; }, row_lds, lo, V, lane, a.topk, a.inv_temp, a.seed, (unsigned)(a.row0 + orow), (unsigned)t);
-    if (lane == 0) commit_token(a, row, t, pick);
+                                               (unsigned)(a.row0 + orow), (unsigned)t, lp, logp);
+    else pick = sample_row_lds([&](int j) { return lg[j]; }, row_lds, lo, V, lane, a.topk, a.inv_temp, a.seed, (unsigned)(a.row0 + orow), (unsigned)t,
+                               lp, logp);
+    if (lane == 0) commit_token(a, row, t, pick, logp);
 }
 inline void launch_sample_step(hipStream_t s, int rows, const StepArgs& sa) {
     if (sample_in_regs(sa.V)) hipLaunchKernelGGL(sample_step_kernel<true>, dim3(rows), dim3(64), 0, s, sa);
@@ -338,13 +390,15 @@ inline void launch_sample_step(hipStream_t s, int rows, const StepArgs& sa) {
 // over (every decode path); (2) on the launch path the live rows of a row range are compacted to the front of the range every few positions
 // and the range's launches shrink -- compact_scan_kernel builds the new small state and the list of row moves, move_rows_kernel moves the
 // rows of the K/V history and of the cross-attention operand (same bits per row: nothing a row computes depends on its slot).
-__global__ void pad_after_eos_kernel(int64_t* tokens, int stride, int steps, int rows, int eos, int bos, int pad) {
+// logp (the generate's log-probabilities, same stride, or null): 0 behind the eos -- a finished row adds nothing to its sequence log-probability
+__global__ void pad_after_eos_kernel(int64_t* tokens, float* logp, int stride, int steps, int rows, int eos, int bos, int pad) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     int64_t* row = tokens + (size_t)r * stride;
+    float* lp = logp ? logp + (size_t)r * stride : nullptr;
     bool done = bos == eos;                                   // the BOS column counts (decoder.py:115 looks at the whole output)
     for (int t = 0; t < steps; ++t) {
-        if (done) row[t] = pad;
+        if (done) { row[t] = pad; if (lp) lp[t] = 0.f; }
         else if (row[t] == eos) done = true;
     }
 }

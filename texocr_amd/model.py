@@ -180,11 +180,19 @@ class HipEngine:
         return (logits if want_logits else None), nxt
 
     def generate(self, img: Optional[torch.Tensor], max_len: int, eos: Optional[int], enc: Optional[torch.Tensor] = None,
-                 return_logits: bool = False):
+                 return_logits: bool = False, return_logp: bool = False):
+        """-> tokens (B, n); with return_logits (tokens, logits); with return_logp (tokens, logp) -- logp (B, n) float32, the
+        log-probability of every token under softmax(logits) at temperature 1 over the whole vocabulary, from the token selection
+        itself (txo_generate_logp); with both (tokens, logits, logp)."""
         if (img is None) == (enc is None):
             raise ValueError("pass exactly one of img / enc")
         self._ensure()
         e = -1 if eos is None else int(eos)
+        if return_logp:
+            op = torch.ops.texocr.generate_logp if img is not None else torch.ops.texocr.generate_from_enc_logp
+            toks, n, logp, logits = op(img if img is not None else enc, self.id, int(max_len), e, bool(return_logits))
+            n = int(n.item())
+            return (toks[:, :n], logits[:, :n], logp[:, :n]) if return_logits else (toks[:, :n], logp[:, :n])
         if img is not None:
             toks, n, logits = torch.ops.texocr.generate(img, self.id, int(max_len), e, bool(return_logits))
         else:
@@ -204,9 +212,12 @@ class HipEngine:
         self._ensure()
         torch.ops.texocr.decode_begin_ragged(enc, n_tokens, self.id)
 
-    def generate_ragged(self, images, max_len: int, eos: Optional[int]) -> torch.Tensor:
+    def generate_ragged(self, images, max_len: int, eos: Optional[int], return_logp: bool = False):
         self._ensure()
         box, sizes = ops.pack_ragged(images)
+        if return_logp:
+            toks, n, logp = torch.ops.texocr.generate_ragged_logp(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
+            return toks[:, :int(n.item())], logp[:, :int(n.item())]
         toks, n = torch.ops.texocr.generate_ragged(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
         return toks[:, :int(n.item())]
 
@@ -489,6 +500,9 @@ class AutoRegressiveDecoder(nn.Module):
         enc = kwargs.pop("enc", None)
         mask = kwargs.pop("mask", None)
         return_logits = bool(kwargs.pop("return_logits", False))   # build extension: also the logits every token was picked from
+        # build extension: also logp (B, n) float32 = log_softmax(logits)[token] of every position, temperature 1 over the whole vocabulary in
+        # greedy and sampled decode alike, 0 behind a row's first eos with stop='row'; with return_logits: (tokens, logits, logp)
+        return_logp = bool(kwargs.pop("return_logp", False))
         stop = kwargs.pop("stop", "global")                        # build extension: 'row' = per-row stop, pad behind a row's first eos
         pad = kwargs.pop("pad", None)
         if kwargs:
@@ -511,13 +525,16 @@ class AutoRegressiveDecoder(nn.Module):
             # that is a multiple of 8 and a table that fits its workspace -- else the general stepwise loop below
             window_ok = max_len <= self.max_len or (eng.dims.vocab % 8 == 0 and self.max_len <= eng.max_batch * eng.max_tokens)
             if padded:
-                if return_logits:
-                    raise ValueError("return_logits is not available with a padding mask")
+                if return_logits or return_logp:
+                    raise ValueError("return_logits / return_logp are not available with a padding mask")
                 out = self._generate_stepwise(st, eos_tok, max_len, enc, sample, mask=mask)
             elif T0 == 1 and bool((st == eng.dims.bos).all()) and (window_ok or return_logits):
-                out = eng.generate(None, max_len, eos_tok, enc=enc, return_logits=return_logits)
+                out = eng.generate(None, max_len, eos_tok, enc=enc, return_logits=return_logits, return_logp=return_logp)
             elif return_logits:
                 raise ValueError("return_logits needs a BOS start inside the positional table (max_len <= decoder.max_len)")
+            elif return_logp:
+                raise ValueError("return_logp needs a BOS start and the engine's own loop (beyond decoder.max_len: a vocabulary that is a "
+                                 "multiple of 8 and max_length <= max_batch * max_tokens)")
             else:
                 out = self._generate_stepwise(st, eos_tok, max_len, enc, sample)
         if stop == "row" and eos_tok is not None:
@@ -525,12 +542,12 @@ class AutoRegressiveDecoder(nn.Module):
             # return_logits form are padded here: the same rule, tokens behind a row's first eos, start tokens included in the test as
             # decoder.py:115 does.  Logits behind a row's eos are what the finished row kept producing: unspecified.)
             p_id = eng.dims.pad if pad is None else int(pad)
-            if return_logits:
-                out = (_pad_after_eos(out[0], st.to(out[0].device), eos_tok, p_id), out[1])
+            if return_logits or return_logp:                       # (logp behind a row's eos: the engine has written 0 there)
+                out = (_pad_after_eos(out[0], st.to(out[0].device), eos_tok, p_id), *out[1:])
             else:
                 out = _pad_after_eos(out, st.to(out.device), eos_tok, p_id)
-        if return_logits:
-            return (out[0].squeeze(0), out[1].squeeze(0)) if squeeze else out
+        if return_logits or return_logp:
+            return tuple(o.squeeze(0) for o in out) if squeeze else out
         return out.squeeze(0) if squeeze else out
 
     def _generate_stepwise(self, st, eos_tok, max_len, enc, sample, mask=None):
@@ -642,8 +659,14 @@ class OCRModel(nn.Module):
     @torch.no_grad()
     def generate(self, src: torch.Tensor, max_len: int, temp: float = 0.3, *, decode: str = "greedy",
                  generator: Optional[torch.Generator] = None, seed: Optional[int] = None, return_logits: bool = False,
-                 beam: int = 0, return_beams: bool = False, stop: str = "global"):
+                 beam: int = 0, return_beams: bool = False, stop: str = "global", return_logp: bool = False):
+        """return_logp=True (build extension): (tokens, logp), both (B, n_steps) -- logp[b, t] = log_softmax(logits[b, t])[tokens[b, t]],
+        what score(src, cat([bos], tokens)).logp reports, taken from the token selection itself: temperature 1 and the whole vocabulary
+        also with decode='sample' (not the sampler's top-k / temperature distribution); stop='row': 0 behind a row's first eos, so
+        logp.sum(1) is the sequence log-probability.  With return_logits: (tokens, logits, logp)."""
         _check_modes(stop)
+        if beam and return_logp:
+            raise ValueError("return_logp is not available with beam search (beam=k): it returns beam scores (return_beams=True)")
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
             if max_len > self.decoder.max_len:
                 raise ValueError(f"beam search needs max_len <= decoder.max_len ({self.decoder.max_len})")
@@ -652,21 +675,21 @@ class OCRModel(nn.Module):
             # (max_len > decoder.max_len: txo_generate slides the window like the reference, decoder.py:99-100)
             # (stop='row' with return_logits: the engine does not compact -- a finished row's logits would be missing -- and only pads)
             with self._engine.modes(stop=stop):
-                return self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits)
+                return self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits, return_logp=return_logp)
         enc = self.encoder(src)
         start = torch.full((src.shape[0], 1), self.bos_token, dtype=torch.int64, device=src.device)   # ocr_model.py:57
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
-                                     stop=stop, pad=self.trg_pad_idx)
+                                     stop=stop, pad=self.trg_pad_idx, return_logp=return_logp)
 
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
-                        stop: str = "global") -> torch.Tensor:
+                        stop: str = "global", return_logp: bool = False):
         """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
-        is keyed by the row of the batch).  max_len <= decoder.max_len."""
+        is keyed by the row of the batch).  max_len <= decoder.max_len.  return_logp=True: (tokens, logp) as generate() returns them."""
         with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode):
-            return self._engine.generate_ragged(images, max_len, self.eos_token)
+            return self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
 
     @torch.no_grad()
     def score(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:

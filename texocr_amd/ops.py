@@ -13,6 +13,9 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::generate          OCRModel.generate                         model/ocr_model.py:46-66
   texocr::generate_from_enc AutoRegressiveDecoder.generate            model/decoder.py:77-122
   texocr::generate_beam     (build extension, BASELINE config 5)
+  texocr::generate_logp / generate_from_enc_logp / generate_ragged_logp
+                            (build extension) generate / generate_from_enc / generate_ragged that also return the log-probability
+                            of every produced token, taken from the token selection itself (no second pass, no (B, T, V) tensor)
   texocr::encode_ragged / decode_begin_ragged / generate_ragged
                             (build extension) the same callables over a RAGGED batch: B images of different sizes in one
                             container, every image computed as if it had been passed on its own (``pack_ragged`` builds the container)
@@ -290,6 +293,50 @@ def _(src, engine, max_len, eos, want_logits):
             src.new_empty((B if want_logits else 0, max_len, d.vocab), dtype=torch.float32))
 
 
+def _logp_output(toks: torch.Tensor) -> torch.Tensor:
+    logp = torch.empty(toks.shape, device=toks.device, dtype=torch.float32)
+    if os.environ.get("TXO_DEBUG_POISON"):      # tests: a returned position the engine never wrote shows as nan
+        logp.fill_(float("nan"))
+    return logp
+
+
+@custom_op("texocr::generate_logp", mutates_args=())
+def generate_logp(img: torch.Tensor, engine: int, max_len: int, eos: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """texocr::generate plus logp (B, max_len) float32: log_softmax(logits)[token] of every valid position, at temperature 1 over the
+    whole vocabulary whatever the token selection (txo_generate_logp) -> (tokens, n, logp, logits (B, max_len, V) or (0, max_len, V))."""
+    e = _eng(engine, ready=True)
+    img = _img_arg(img, e)
+    B, Cc, H, W = img.shape
+    toks, logits = _gen_outputs(img, e, max_len, want_logits)
+    logp = _logp_output(toks)
+    n = C.c_int32(0)
+    _call(e, "txo_generate_logp", img.data_ptr(), B, Cc, H, W, int(max_len), int(eos), toks.data_ptr(), C.byref(n),
+          logits.data_ptr() if want_logits else None, logp.data_ptr(), leaves=(B, img))
+    return toks, torch.tensor([n.value], dtype=torch.int64), logp, logits
+
+
+@custom_op("texocr::generate_from_enc_logp", mutates_args=())
+def generate_from_enc_logp(enc: torch.Tensor, engine: int, max_len: int, eos: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    e = _eng(engine, ready=True)
+    enc = _enc_arg(enc, e)
+    toks, logits = _gen_outputs(enc, e, max_len, want_logits)
+    logp = _logp_output(toks)
+    n = C.c_int32(0)
+    _call(e, "txo_generate_from_enc_logp", enc.data_ptr(), enc.shape[0], enc.shape[1], int(max_len), int(eos), toks.data_ptr(), C.byref(n),
+          logits.data_ptr() if want_logits else None, logp.data_ptr(), leaves=(enc.shape[0], enc))
+    return toks, torch.tensor([n.value], dtype=torch.int64), logp, logits
+
+
+@generate_logp.register_fake
+@generate_from_enc_logp.register_fake
+def _(src, engine, max_len, eos, want_logits):
+    d = _eng(engine).dims
+    B = src.shape[0]
+    return (src.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
+            src.new_empty((B, max_len), dtype=torch.float32),
+            src.new_empty((B if want_logits else 0, max_len, d.vocab), dtype=torch.float32))
+
+
 @custom_op("texocr::generate_beam", mutates_args=())
 def generate_beam(img: torch.Tensor, engine: int, beams: int, max_len: int, eos: int, want_all: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """Beam search (build extension): (best tokens (B, max_len), scores (B, beams), all beams (B*beams, max_len) or (0, max_len),
@@ -417,3 +464,23 @@ def generate_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len
 @generate_ragged.register_fake
 def _(img, sizes, engine, max_len, eos):
     return img.new_empty((img.shape[0], max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu")
+
+
+@custom_op("texocr::generate_ragged_logp", mutates_args=())
+def generate_ragged_logp(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len: int, eos: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """txo_generate_ragged_logp: texocr::generate_ragged plus logp (B, max_len) float32 -> (tokens, n, logp)."""
+    e = _eng(engine, ready=True)
+    img, sizes = _ragged_args(img, sizes, e)
+    B, Cc, Hc, Wc = img.shape
+    toks, _ = _gen_outputs(img, e, max_len, False)
+    logp = _logp_output(toks)
+    n = C.c_int32(0)
+    _call(e, "txo_generate_ragged_logp", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), int(max_len), int(eos), toks.data_ptr(), C.byref(n),
+          logp.data_ptr(), leaves=())
+    return toks, torch.tensor([n.value], dtype=torch.int64), logp
+
+
+@generate_ragged_logp.register_fake
+def _(img, sizes, engine, max_len, eos):
+    return (img.new_empty((img.shape[0], max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
+            img.new_empty((img.shape[0], max_len), dtype=torch.float32))

@@ -60,31 +60,38 @@ class TeXOCRWrapper:
         return x.contiguous()
 
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
-              seed: Optional[int] = None) -> List[Tuple[list, str]]:
+              seed: Optional[int] = None, return_logp: bool = False) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
         window).  A sampled draw is keyed by (seed + chunk index, row of its chunk, position): with an explicit seed the result is
-        reproducible and no two images of the list share a stream of draws."""
+        reproducible and no two images of the list share a stream of draws.
+        return_logp=True: [(tokens, latex, logp)], logp the log-probability of every kept token (OCRModel.generate), cut as the tokens are."""
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
-        out: List[Tuple[list, str]] = []
+        out: List[tuple] = []
         xs = [self._tensor(im).cuda() for im in imgs]
         for c0 in range(0, len(xs), eng.max_batch):
             chunk_seed = None if seed is None else int(seed) + c0 // eng.max_batch
-            toks = self.model.generate_ragged(xs[c0:c0 + eng.max_batch], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row")
-            for row in toks.tolist():
+            toks = self.model.generate_ragged(xs[c0:c0 + eng.max_batch], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
+                                              return_logp=return_logp)
+            toks, logp = toks if return_logp else (toks, None)
+            for b, row in enumerate(toks.tolist()):
                 if self.model.eos_token in row:
                     row = row[:row.index(self.model.eos_token) + 1]
                 row = row[:-1]                                                        # ocr_model.py:104 (drops the last token)
-                out.append((row, process_output(self.tokenizer.decode(row))))
+                latex = process_output(self.tokenizer.decode(row))
+                out.append((row, latex, logp[b, :len(row)].tolist()) if return_logp else (row, latex))
         return out
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
-                 seed: Optional[int] = None) -> Tuple[list, str]:
+                 seed: Optional[int] = None, return_logp: bool = False) -> tuple:
+        """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate)"""
         x = self._tensor(img)[None].cuda()
         # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
         # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
-        toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed)
+        toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp)
+        toks, logp = toks if return_logp else (toks, None)
         out_tokens = toks.squeeze(0).tolist()[:-1]                                   # ocr_model.py:104 (drops the EOS)
-        return out_tokens, process_output(self.tokenizer.decode(out_tokens))         # :105-108
+        latex = process_output(self.tokenizer.decode(out_tokens))                    # :105-108
+        return (out_tokens, latex, logp.squeeze(0)[:len(out_tokens)].tolist()) if return_logp else (out_tokens, latex)
