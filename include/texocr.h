@@ -110,6 +110,26 @@ int txo_decode_prefill(txo_engine* e, const int64_t* tokens_dev, int32_t t, floa
 int txo_decode_score(txo_engine* e, const int64_t* tokens_dev, int32_t L, float* logp_out_dev, int64_t* top1_out_dev,
                      float* top1_logp_out_dev, void* stream);
 
+/* Transformer.forward(x, mask=, enc=, return_attn=True) (model/decoder.py:41-67): txo_decode_prefill that also returns WHERE every
+ * position looked -- the `post_softmax_attn` of every attention block (model/attention.py:166-178).  Same session, same preconditions
+ * and refusals, same tokens_dev / t / logits_out_dev (may be NULL; a multiple-of-8 vocabulary otherwise) and the same side effect (self
+ * K/V rows 0..t-1 are filled) as txo_decode_prefill; the key mask of txo_decode_set_key_mask is honoured.  Outputs, float32, caller-owned,
+ * each may be NULL but not all three (TXO_E_INVALID); Ld = cfg.dec_layers, B = the session's batch, heads = cfg.dec_heads, N = the
+ * session's encoder token count (the CLS row 0 included):
+ *   self_attn_out_dev  [Ld][B][heads][t][t]  causal self attention: entry [i][j] is exactly 0 for j > i, and for a padded key j at a
+ *                                            query i that is not padding; the row of a padded query is unspecified but finite;
+ *   cross_attn_out_dev [Ld][B][heads][t][N]  cross attention over the encoder rows;
+ *   cross_mean_out_dev [Ld][B][t][N]         the mean of the cross maps over the heads, summed in head order inside one kernel: it does
+ *                                            not need cross_attn_out_dev to exist (cfg.dec_heads <= 32, TXO_E_INVALID beyond).
+ * Every row sums to 1.  The probabilities are recomputed from the q / k operands of the pass (texocr_amd/csrc/attn_probs.h: two
+ * sweeps over the keys, nothing of size t x N is held); logits and K/V cache are bit for bit txo_decode_prefill's, and what one output
+ * holds does not depend on which others were asked for.  Asynchronous on `stream`; bit-reproducible run to run; no allocation. */
+int txo_decode_attn(txo_engine* e, const int64_t* tokens_dev, int32_t t, float* logits_out_dev,
+                    float* self_attn_out_dev,   /* [Ld][B][heads][t][t]  or NULL */
+                    float* cross_attn_out_dev,  /* [Ld][B][heads][t][N]  or NULL */
+                    float* cross_mean_out_dev,  /* [Ld][B][t][N]         or NULL: mean over heads */
+                    void* stream);
+
 /* OCRModel.forward's path (ocr_model.py:38-44) in one call: txo_encode + txo_decode_begin + txo_decode_set_key_mask(mask_dev, L) +
  * txo_decode_score.  mask_dev uint8 [B][L] (0 = padding; its first L-1 columns are the fed positions) or NULL.  The key mask is
  * cleared again before the call returns; the session stays open (txo_decode_step(e, tok, L-1, ...) continues behind it). */
@@ -119,7 +139,7 @@ int txo_score(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t
 /* The `mask` argument of decoder.generate / decoder.net (model/decoder.py:95-101,112: a (B, T0) bool over the start tokens, padded
  * with True for every generated token; model/attention.py:130-155: energy filled with -FLT_MAX where query or key is masked).
  * mask_dev: uint8 [B][cols] on the device, 0 = padding; positions >= cols are not padding; NULL clears the mask.  Applies to the
- * txo_decode_step, txo_decode_prefill and txo_decode_score calls of the session opened by txo_decode_begin: a padded position is never attended by a
+ * txo_decode_step, txo_decode_prefill, txo_decode_attn and txo_decode_score calls of the session opened by txo_decode_begin: a padded position is never attended by a
  * query that is not padding.  Rows of padded positions themselves are computed but unspecified (the reference softmaxes them
  * uniformly over all keys; nothing downstream reads them). */
 int txo_decode_set_key_mask(txo_engine* e, const uint8_t* mask_dev, int32_t cols, void* stream);
@@ -177,7 +197,7 @@ int txo_generate_beam(txo_engine* e, const float* img_dev, int32_t B, int32_t C,
  * tokens.  Nothing in a padding row or a padding pixel reaches a valid row.  Sizes are HOST arrays (launch geometry depends on them);
  * the engine copies them into its own device buffer (allocated at creation: no call allocates).
  * Out of scope, each refused with TXO_E_INVALID and a message naming ragged batches: the hybrid front end; the latent cross-attention
- * form forced by TXO_LATENT=1; the prefill, score and key-mask calls on a session opened by the ragged begin call; max_len >
+ * form forced by TXO_LATENT=1; the prefill, attention-map, score and key-mask calls on a session opened by the ragged begin call; max_len >
  * cfg.max_len.  Beam search and logits_out have no ragged entry point (the beam call takes one (H, W) and opens its own session).  The
  * container's width Wc must be a multiple of 4 (rows are read in 16-byte pieces).  The persistent launch is not taken: a ragged
  * generate runs one launch per stage (TXO_Q_LAST_PERSISTENT reads 0), and its session is closed when it returns.

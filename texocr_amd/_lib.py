@@ -38,6 +38,7 @@ SYMBOLS = {
     "txo_decode_step": (C.c_int, [_P, _I64P, _I, _FP, _I64P, _P]),
     "txo_decode_prefill": (C.c_int, [_P, _I64P, _I, _FP, _P]),
     "txo_decode_score": (C.c_int, [_P, _I64P, _I, _FP, _I64P, _FP, _P]),
+    "txo_decode_attn": (C.c_int, [_P, _I64P, _I, _FP, _FP, _FP, _FP, _P]),
     "txo_score": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.c_void_p, _I, _FP, _I64P, _FP, _P]),
     "txo_decode_set_key_mask": (C.c_int, [_P, C.c_void_p, _I, _P]),
     "txo_generate": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),

@@ -40,6 +40,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "lat_attn.h"
 #include "persist.h"
 #include "prefill.h"
+#include "attn_probs.h"
 #include "score.h"
 #include "rows.h"
 #include "step.h"
@@ -75,6 +76,8 @@ struct EngineBase {
     virtual int decode_step(const int64_t* tok_in, int t, float* logits_out, int64_t* tok_out, hipStream_t s) = 0;
     virtual int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) = 0;
     virtual int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
+    virtual int decode_attn(const int64_t* tokens, int t, float* logits_out, float* self_attn_out, float* cross_attn_out, float* cross_mean_out,
+                            hipStream_t s) = 0;
     virtual int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
                       int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
     virtual int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) = 0;
@@ -1459,12 +1462,27 @@ struct Engine : EngineBase {
         return 0;
     }
 
-    int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) override {
-        if (lanes.n != 1) return fail(TXO_E_STATE, "decode_prefill needs a session started by txo_decode_begin");
-        if (ses.images != ses.rows) return fail(TXO_E_STATE, "decode_prefill is not available inside a beam-search session");
-        if (ses.open && ses.ragged) return fail(TXO_E_INVALID, "txo_decode_prefill: not available on a ragged batch session (the multi-position forward has no ragged form)");
+    struct AttnOut { float* self_p; float* cross_p; float* cross_mean; };   // attention maps of every layer (decode_attn), each may be null
+    // the multi-position forward on the open session, with (decode_attn) or without (decode_prefill) the attention maps
+    int prefill_entry(const std::string& name, const int64_t* tokens, int t, float* logits_out, const AttnOut* attn, hipStream_t s) {
+        if (lanes.n != 1) return fail(TXO_E_STATE, name + " needs a session started by txo_decode_begin");
+        if (ses.images != ses.rows) return fail(TXO_E_STATE, name + " is not available inside a beam-search session");
+        if (ses.open && ses.ragged) return fail(TXO_E_INVALID, "txo_" + name + ": not available on a ragged batch session (the multi-position forward has no ragged form)");
         lanes[0].stream = s;
-        return prefill(tokens, t, t, logits_out, nullptr, s);
+        return prefill(tokens, t, t, logits_out, nullptr, s, nullptr, attn);
+    }
+    int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) override {
+        return prefill_entry("decode_prefill", tokens, t, logits_out, nullptr, s);
+    }
+    // decode_prefill that also writes the attention probabilities of every decoder layer (attn_probs.h): self [Ld][B][heads][t][t],
+    // cross [Ld][B][heads][t][N], the head mean of the cross maps [Ld][B][t][N]; each may be null
+    int decode_attn(const int64_t* tokens, int t, float* logits_out, float* self_attn_out, float* cross_attn_out, float* cross_mean_out,
+                    hipStream_t s) override {
+        // (the head walk keeps its statistics in LDS beside the kernel's 32 KB of tiles, inside the 64 KB every launch may ask for)
+        if (cross_mean_out && attn_probs_lds_bytes(cfg.dec_heads) > 32768)
+            return fail(TXO_E_INVALID, "txo_decode_attn: the head-mean map is built for at most 32 decoder heads");
+        const AttnOut ao{self_attn_out, cross_attn_out, cross_mean_out};
+        return prefill_entry("decode_attn", tokens, t, logits_out, &ao, s);
     }
 
     // AutoRegressiveDecoder.forward without autograd (decoder.py:124-145): tokens [B][L]; columns 0..L-2 are fed through the
@@ -1509,7 +1527,23 @@ struct Engine : EngineBase {
         else if (causal) hipLaunchKernelGGL((attn_mq_kernel<T, TO, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
         else hipLaunchKernelGGL((attn_mq_kernel<T, TO, false>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
     }
-    int prefill(const int64_t* tokens, int tok_stride, int t, float* logits_out, float* last_logits, hipStream_t s, const ScoreOut* score = nullptr) {
+    // the probabilities behind a launch_attn_mq call, from the same q / k (attn_probs.h); MEAN: one map per image, the mean over the heads
+    template <bool MEAN>
+    void launch_attn_probs(hipStream_t s, bool causal, const T* q, const T* k, float* out, int nb, int nq, int nk, int kv_rows,
+                           const unsigned char* km = nullptr) {
+        const int heads = cfg.dec_heads;
+        const dim3 grid((nq + EA_QBLK - 1) / EA_QBLK, MEAN ? nb : nb * heads);
+        const size_t lds = attn_probs_lds_bytes(MEAN ? heads : 1);
+        if constexpr (MEAN) {                                 // only the cross maps have a head mean: no causal form of it exists
+            hipLaunchKernelGGL((attn_probs_kernel<T, false, false, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
+        } else {
+            if (causal && km) hipLaunchKernelGGL((attn_probs_kernel<T, true, true, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, km, Tmax);
+            else if (causal) hipLaunchKernelGGL((attn_probs_kernel<T, true, false, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
+            else hipLaunchKernelGGL((attn_probs_kernel<T, false, false, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
+        }
+    }
+    int prefill(const int64_t* tokens, int tok_stride, int t, float* logits_out, float* last_logits, hipStream_t s, const ScoreOut* score = nullptr,
+                const AttnOut* attn = nullptr) {
         if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (t < 1 || t > Tmax) return fail(TXO_E_INVALID, "prefill length outside the decoder's positional table");
         // (only the logits GEMM's 8-wide store epilogue needs it: the scoring tail takes any vocabulary)
@@ -1537,6 +1571,9 @@ struct Engine : EngineBase {
                 T* vc = skv + (size_t)(2 * l + 1) * self_stride + (size_t)b0 * heads * Tmax * DH;
                 gemm_plain(s, ez, dec_self[l].wqkv, M, 3 * Id, D, EpiHeadsKV<T>{qbuf, kc, vc, Id, heads, t, Tmax});
                 launch_attn_mq<T>(s, true, qbuf, kc, vc, eao, nb, t, t, Tmax, ses.kmask_on ? kmask + (size_t)b0 * Tmax : nullptr);   // (padding mask of the session, if any)
+                if (attn && attn->self_p)                     // [Ld][B][heads][t][t], before the cross attention's q overwrites qbuf
+                    launch_attn_probs<false>(s, true, qbuf, kc, attn->self_p + ((size_t)l * B + b0) * heads * t * t, nb, t, t, Tmax,
+                                             ses.kmask_on ? kmask + (size_t)b0 * Tmax : nullptr);
                 gemm_plain(s, eao, dec_self[l].wo16, M, 2 * D, Id, EpiGluRes<sizeof(T) == 2>{ey, l == 0 ? res_first : res_x, dec_self[l].bo16});
                 // cross attention over the cached encoder projections (attention.py:114-126); one row per image: no prefill in a beam session
                 launch_ln<3, T>(s, ey, estats, ez, dec_g, dec_b, M);
@@ -1544,6 +1581,10 @@ struct Engine : EngineBase {
                 const T* ck = ckv + (size_t)(2 * l) * cross_stride + (size_t)b0 * heads * N * DH;
                 const T* cv = ckv + (size_t)(2 * l + 1) * cross_stride + (size_t)b0 * heads * N * DH;
                 launch_attn_mq<T>(s, false, qbuf, ck, cv, eao, nb, t, N, N);
+                if (attn && attn->cross_p)                    // [Ld][B][heads][t][N]
+                    launch_attn_probs<false>(s, false, qbuf, ck, attn->cross_p + ((size_t)l * B + b0) * heads * t * N, nb, t, N, N);
+                if (attn && attn->cross_mean)                 // [Ld][B][t][N]
+                    launch_attn_probs<true>(s, false, qbuf, ck, attn->cross_mean + ((size_t)l * B + b0) * t * N, nb, t, N, N);
                 gemm_plain(s, eao, dec_cross[l].wo16, M, 2 * D, Id, EpiGluRes<sizeof(T) == 2>{ey, res_x, dec_cross[l].bo16});
                 // GeGLU feed-forward
                 launch_ln<3, T>(s, ey, estats, ez, dec_g, dec_b, M);
@@ -2118,6 +2159,13 @@ int txo_decode_step(txo_engine* e, const int64_t* tok_in, int32_t t, float* logi
 int txo_decode_prefill(txo_engine* e, const int64_t* tokens, int32_t t, float* logits_out, void* stream) {
     if (!e || !tokens) return fail(TXO_E_INVALID, "null argument");
     return e->impl->decode_prefill(tokens, t, logits_out, (hipStream_t)stream);
+}
+
+int txo_decode_attn(txo_engine* e, const int64_t* tokens, int32_t t, float* logits_out, float* self_attn_out, float* cross_attn_out,
+                    float* cross_mean_out, void* stream) {
+    if (!e || !tokens) return fail(TXO_E_INVALID, "null argument");
+    if (!self_attn_out && !cross_attn_out && !cross_mean_out) return fail(TXO_E_INVALID, "txo_decode_attn: no attention map was asked for (all three outputs are NULL)");
+    return e->impl->decode_attn(tokens, t, logits_out, self_attn_out, cross_attn_out, cross_mean_out, (hipStream_t)stream);
 }
 
 int txo_decode_score(txo_engine* e, const int64_t* tokens, int32_t L, float* logp_out, int64_t* top1_out, float* top1_logp_out, void* stream) {

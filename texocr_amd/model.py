@@ -8,6 +8,7 @@ Mirrors (reference file:line):
   model.encoder(src) -> (B, N, D)                                         model/encoder.py:128-152
   model.decoder.generate(start_tokens, eos_tok, max_len, temp, enc=)      model/decoder.py:77-122
   model.decoder.net(x, mask=, enc=) -> (B, t, V)                          model/decoder.py:41-67
+  model.decoder.net(x, mask=, enc=, return_attn=True) -> (logits, maps)   model/decoder.py:62-65, model/attention.py:166-178
   create_model(config)                                                    model/ocr_model.py:113-130
   model.state_dict() / model.load_state_dict(reference_state_dict)        key layout: SURVEY.md 8a
 
@@ -173,6 +174,14 @@ class HipEngine:
     def decode_score(self, tokens: torch.Tensor):
         """Teacher-forced scores of the current session (txo_decode_score): tokens (B, L) -> (logp, top1, top1_logp), each (B, L-1)."""
         return torch.ops.texocr.decode_score(tokens, self.id)
+
+    def decode_attn(self, tokens: torch.Tensor, want_logits: bool = True, want_self: bool = True, want_cross: bool = True,
+                    want_mean: bool = False):
+        """decode_prefill plus the attention probabilities of every decoder layer (txo_decode_attn) -> (logits (B, t, V), self
+        (Ld, B, heads, t, t), cross (Ld, B, heads, t, N), mean (Ld, B, t, N) = cross averaged over the heads); None for a part that
+        was not asked for (it is never allocated)."""
+        out = torch.ops.texocr.decode_attn(tokens, self.id, bool(want_logits), bool(want_self), bool(want_cross), bool(want_mean))
+        return tuple(o if w else None for o, w in zip(out, (want_logits, want_self, want_cross, want_mean)))
 
     def decode_step(self, t: int, tok_in: Optional[torch.Tensor] = None, want_logits: bool = True):
         batch = ops.session(self, "decode_step").rows
@@ -417,6 +426,29 @@ def score_summary(logp: torch.Tensor, top1: torch.Tensor, top1_logp: torch.Tenso
     return Score(logp, top1, top1_logp, valid, nll64.float(), (nll64.sum() / n).float(), (hit.sum().double() / n).float())
 
 
+class Alignment(NamedTuple):
+    """What OCRModel.align / AutoRegressiveDecoder.align return -- where in the image every fed position looked (position p of row b is
+    the one that predicts trg[b, p + 1]): maps, the head-mean cross attention on the encoder's patch rows, (B, L-1, H/16, W/16) from
+    OCRModel.align and (B, L-1, N-1) from the decoder's; cls (B, L-1) the mass on the CLS row; peak (B, L-1, 2) the arg-max patch as
+    (row, col) -- (B, L-1) flat patch indices from the decoder's.  maps[b, p].sum() + cls[b, p] is 1.  Rows of padded positions are
+    unspecified."""
+    maps: torch.Tensor
+    cls: torch.Tensor
+    peak: torch.Tensor
+
+
+def alignment(cross_mean: torch.Tensor, layer: Optional[int] = -1, grid: Optional[Tuple[int, int]] = None) -> Alignment:
+    """The arithmetic on top of the engine's head-mean maps (plain torch, any device): cross_mean (Ld, B, t, N) with the CLS row at key 0;
+    layer: which decoder layer, None = the mean over the layers; grid = (rows, cols) of the patch grid, None leaves the patches flat."""
+    m = cross_mean.mean(dim=0) if layer is None else cross_mean[layer]
+    cls, maps = m[..., 0], m[..., 1:]
+    peak = maps.argmax(dim=-1)
+    if grid is not None:
+        maps = maps.reshape(*maps.shape[:2], *grid)
+        peak = torch.stack((peak // grid[1], peak % grid[1]), dim=-1)
+    return Alignment(maps, cls, peak)
+
+
 class Transformer(nn.Module):
     """model.decoder.net: (B,t) int64 tokens -> (B,t,V) logits over the whole prefix (decoder.py:41-67): ONE causal
     multi-position pass (txo_decode_prefill), which also leaves the K/V cache filled for the positions given."""
@@ -428,6 +460,9 @@ class Transformer(nn.Module):
         _build_params(self, engine.dims, "decoder.net.", _shared if _shared is not None else {}, torch.device("cuda", engine.device))
 
     def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None, **kw):
+        """return_attn=True: (logits, attn_maps) as the reference returns them (decoder.py:62-65): the post-softmax attention of every
+        block in stack order -- self 0, cross 0, self 1, cross 1, ... -- each (B, heads, t, keys), views into two buffers."""
+        return_attn = bool(kw.pop("return_attn", False))
         if kw:
             raise ValueError(f"unsupported arguments for the inference path: {sorted(kw)}")
         _need_enc(enc)
@@ -446,7 +481,13 @@ class Transformer(nn.Module):
         # attention.py:130-155: a padded position is never attended by a query that is not padding.  Logits AT padded positions are
         # unspecified here (the reference softmaxes such a row uniformly over all keys, future ones included; nothing reads it)
         with eng.key_mask(mask.to(x.device) if padded else None):
-            return eng.decode_prefill(x) if one_pass else self._net_stepwise(x)
+            if not return_attn:
+                return eng.decode_prefill(x) if one_pass else self._net_stepwise(x)
+            # (the maps need no logits: a vocabulary the one-pass logits cannot take gets them from the stepwise route behind)
+            logits, self_p, cross_p, _ = eng.decode_attn(x, want_logits=one_pass)
+            if not one_pass:
+                logits = self._net_stepwise(x)
+        return logits, [m[l] for l in range(self_p.shape[0]) for m in (self_p, cross_p)]
 
     def _net_stepwise(self, x: torch.Tensor) -> torch.Tensor:
         """fallback (odd vocabulary sizes; tests): one cached step per position"""
@@ -492,6 +533,29 @@ class AutoRegressiveDecoder(nn.Module):
         with eng.key_mask(m[:, :-1]):                              # (the last column is a target only, never a key)
             logp, top1, top1_logp = eng.decode_score(x)
         return score_summary(logp, top1, top1_logp, x, m)
+
+    @torch.no_grad()
+    def align(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None, layer: Optional[int] = -1,
+              grid: Optional[Tuple[int, int]] = None) -> Alignment:
+        """Build extension: where every position of a teacher-forced pass looked.  x (B, L) and mask as score() takes them; x[:, :-1] is
+        fed in one causal pass that returns only the head mean of the cross-attention maps (the per-head tensors are never made).
+        layer: the decoder layer (-1 = the last), None = the mean over the layers.  -> Alignment over the N - 1 patch rows of enc."""
+        _need_enc(enc)
+        _check_x(x, "(B, L)")
+        if x.shape[1] < 2:
+            raise ValueError("x needs at least two columns (one fed token and its target)")
+        if x.shape[1] - 1 > self.max_len:
+            raise ValueError("sequence longer than decoder.max_len + 1")
+        if mask is not None and tuple(mask.shape) != tuple(x.shape):
+            raise ValueError("mask must have the shape of x")
+        eng = self._engine
+        if layer is not None and not -eng.dims.dec_layers <= layer < eng.dims.dec_layers:
+            raise ValueError(f"layer must be None or in [{-eng.dims.dec_layers}, {eng.dims.dec_layers})")
+        _check_token_ids(x, eng.dims.vocab)
+        eng.decode_begin(enc)
+        with eng.key_mask(None if mask is None else mask.to(device=x.device, dtype=torch.bool)[:, :-1]):
+            mean = eng.decode_attn(x[:, :-1].contiguous(), want_logits=False, want_self=False, want_cross=False, want_mean=True)[3]
+        return alignment(mean, layer, grid)
 
     @torch.no_grad()
     def generate(self, start_tokens: torch.Tensor, eos_tok: Optional[int], max_len: int, temp: float = 1.0,
@@ -699,6 +763,16 @@ class OCRModel(nn.Module):
         if mask is None:
             mask = trg != self.trg_pad_idx
         return self.decoder.score(trg, mask=mask, enc=self.encoder(src))
+
+    @torch.no_grad()
+    def align(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None, layer: Optional[int] = -1) -> Alignment:
+        """Build extension: where in the image every token of trg (B, L) came from -- the companion of score(): the head-mean cross
+        attention of decoder layer `layer` (None: the mean over the layers) on the image's patch grid, from one teacher-forced pass
+        over trg[:, :-1].  mask defaults to trg != trg_pad_idx.  See Alignment."""
+        if mask is None:
+            mask = trg != self.trg_pad_idx
+        grid = (int(src.shape[2]) // self.encoder.patch_size, int(src.shape[3]) // self.encoder.patch_size)
+        return self.decoder.align(trg, mask=mask, enc=self.encoder(src), layer=layer, grid=grid)
 
     def forward(self, *a, **k):
         raise NotImplementedError("OCRModel.forward is the training loss (ocr_model.py:38-44); this engine "

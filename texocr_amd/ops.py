@@ -10,6 +10,7 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::decode_begin      the ``enc=`` hand-over of decoder.generate model/decoder.py:56,103 (+ attention.py:125-126 once)
   texocr::decode_step       Transformer.forward, one position         model/decoder.py:41-67
   texocr::decode_score      AutoRegressiveDecoder.forward, no autograd  model/decoder.py:124-145
+  texocr::decode_attn       Transformer.forward(return_attn=True)     model/decoder.py:41-67 (+ attention.py:166-178: post_softmax_attn)
   texocr::generate          OCRModel.generate                         model/ocr_model.py:46-66
   texocr::generate_from_enc AutoRegressiveDecoder.generate            model/decoder.py:77-122
   texocr::generate_beam     (build extension, BASELINE config 5)
@@ -248,6 +249,45 @@ def _(tokens, engine):
     B, L = tokens.shape
     return (tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1), dtype=torch.int64),
             tokens.new_empty((B, L - 1), dtype=torch.float32))
+
+
+def _session_keys(e, ses: Session) -> int:
+    """N of the open session: the encoder rows it was opened on, or those of the images a generate call encoded itself"""
+    src = ses.src
+    return int(src.shape[1]) if src.ndim == 3 else e.dims.n_tokens(int(src.shape[2]), int(src.shape[3]))
+
+
+def _attn_shapes(d, B: int, t: int, N: int, want_logits: bool, want_self: bool, want_cross: bool, want_mean: bool):
+    """(logits, self, cross, mean) of decode_attn; a part not asked for keeps its trailing dimensions and has no rows"""
+    Ld, H = d.dec_layers, d.dec_heads
+    return ((B if want_logits else 0, t, d.vocab), (Ld if want_self else 0, B, H, t, t), (Ld if want_cross else 0, B, H, t, N),
+            (Ld if want_mean else 0, B, t, N))
+
+
+@custom_op("texocr::decode_attn", mutates_args=())
+def decode_attn(tokens: torch.Tensor, engine: int, want_logits: bool, want_self: bool, want_cross: bool,
+                want_mean: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_prefill that also returns the attention probabilities of every decoder layer (txo_decode_attn): tokens (B, t) int64 ->
+    (logits (B, t, V), self (Ld, B, heads, t, t), cross (Ld, B, heads, t, N), mean (Ld, B, t, N) = the cross maps averaged over the
+    heads); a part that was not asked for comes back with no rows.  N counts the CLS row 0.  The session record is left as it is."""
+    e = _eng(engine)
+    ses = session(e, "decode_attn")
+    B = ses.rows
+    tokens = _i64_dev(tokens, "tokens", e, B, 2, "(B, t) matching the session started by texocr::decode_begin")
+    if not (want_self or want_cross or want_mean):
+        raise ValueError("texocr::decode_attn: ask for at least one of the self, cross and head-mean maps")
+    shapes = _attn_shapes(e.dims, B, int(tokens.shape[1]), _session_keys(e, ses), want_logits, want_self, want_cross, want_mean)
+    outs = [torch.empty(sh, device=tokens.device, dtype=torch.float32) for sh in shapes]
+    _call(e, "txo_decode_attn", tokens.data_ptr(), int(tokens.shape[1]), *[o.data_ptr() if o.shape[0] else None for o in outs])
+    return outs[0], outs[1], outs[2], outs[3]
+
+
+@decode_attn.register_fake
+def _(tokens, engine, want_logits, want_self, want_cross, want_mean):
+    e = _eng(engine)
+    shapes = _attn_shapes(e.dims, tokens.shape[0], tokens.shape[1], _session_keys(e, session(e, "decode_attn")), want_logits, want_self,
+                          want_cross, want_mean)
+    return tuple(tokens.new_empty(sh, dtype=torch.float32) for sh in shapes)
 
 
 def _gen_outputs(src, e, max_len, want_logits):

@@ -85,8 +85,11 @@ class TeXOCRWrapper:
         return out
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
-                 seed: Optional[int] = None, return_logp: bool = False) -> tuple:
-        """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate)"""
+                 seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False) -> tuple:
+        """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
+        return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
+        came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
+        [bos] + tokens behind the generate.  Not available once the output outgrew the positional table (the window has slid)."""
         x = self._tensor(img)[None].cuda()
         # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
         # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
@@ -94,4 +97,12 @@ class TeXOCRWrapper:
         toks, logp = toks if return_logp else (toks, None)
         out_tokens = toks.squeeze(0).tolist()[:-1]                                   # ocr_model.py:104 (drops the EOS)
         latex = process_output(self.tokenizer.decode(out_tokens))                    # :105-108
-        return (out_tokens, latex, logp.squeeze(0)[:len(out_tokens)].tolist()) if return_logp else (out_tokens, latex)
+        out = (out_tokens, latex, logp.squeeze(0)[:len(out_tokens)].tolist()) if return_logp else (out_tokens, latex)
+        if return_align:
+            if toks.shape[1] > self.dims.max_len:
+                raise ValueError(f"return_align: {toks.shape[1]} tokens were generated, more than the positional table holds "
+                                 f"({self.dims.max_len}): the window has slid and no single pass sees the whole sequence")
+            bos = torch.full((1, 1), self.model.bos_token, dtype=torch.int64, device=toks.device)
+            maps = self.model.align(x, torch.cat((bos, toks), dim=1), mask=torch.ones((1, toks.shape[1] + 1), dtype=torch.bool)).maps
+            out = (*out, maps[0, :len(out_tokens)].cpu())
+        return out
