@@ -139,7 +139,8 @@ int txo_score(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t
 /* The `mask` argument of decoder.generate / decoder.net (model/decoder.py:95-101,112: a (B, T0) bool over the start tokens, padded
  * with True for every generated token; model/attention.py:130-155: energy filled with -FLT_MAX where query or key is masked).
  * mask_dev: uint8 [B][cols] on the device, 0 = padding; positions >= cols are not padding; NULL clears the mask.  Applies to the
- * txo_decode_step, txo_decode_prefill, txo_decode_attn and txo_decode_score calls of the session opened by txo_decode_begin: a padded position is never attended by a
+ * txo_decode_step, txo_decode_prefill, txo_decode_attn and txo_decode_score calls of the session opened by txo_decode_begin or
+ * txo_decode_begin_ragged: a padded position is never attended by a
  * query that is not padding.  Rows of padded positions themselves are computed but unspecified (the reference softmaxes them
  * uniformly over all keys; nothing downstream reads them). */
 int txo_decode_set_key_mask(txo_engine* e, const uint8_t* mask_dev, int32_t cols, void* stream);
@@ -196,11 +197,17 @@ int txo_generate_beam(txo_engine* e, const float* img_dev, int32_t B, int32_t C,
  * passed on its own: its n_b encoder rows (position ids grid[:h_b, :w_b] of the canvas grid, encoder.py:136-143), its logits, its
  * tokens.  Nothing in a padding row or a padding pixel reaches a valid row.  Sizes are HOST arrays (launch geometry depends on them);
  * the engine copies them into its own device buffer (allocated at creation: no call allocates).
- * Out of scope, each refused with TXO_E_INVALID and a message naming ragged batches: the hybrid front end; the latent cross-attention
- * form forced by TXO_LATENT=1; the prefill, attention-map, score and key-mask calls on a session opened by the ragged begin call; max_len >
- * cfg.max_len.  Beam search and logits_out have no ragged entry point (the beam call takes one (H, W) and opens its own session).  The
- * container's width Wc must be a multiple of 4 (rows are read in 16-byte pieces).  The persistent launch is not taken: a ragged
- * generate runs one launch per stage (TXO_Q_LAST_PERSISTENT reads 0), and its session is closed when it returns.
+ * The multi-position forward has a ragged form, switched on by txo_set_ragged_forward(e, 1): txo_decode_prefill, txo_decode_attn,
+ * txo_decode_score and txo_decode_set_key_mask then work on a session opened by txo_decode_begin_ragged (the cross attention of image b
+ * sees its own n_b keys in panels Ns rows apart; N = Ns in every layout those calls document), and the ragged generate calls slide the
+ * window beyond cfg.max_len like the fixed-shape ones.  txo_score_ragged (txo_score over a container) needs no switch.  Rows n_b..Ns-1 of
+ * a slot are never read by any of them: they may hold anything.  With the switch off -- the default, and the behaviour of every engine
+ * before the switch existed -- those session calls, txo_score while a ragged session is open, and max_len > cfg.max_len are refused with
+ * TXO_E_INVALID and a message naming ragged batches, so a caller that relied on the refusal still gets it.
+ * Out of scope in either setting, each refused with TXO_E_INVALID and a message naming ragged batches: the hybrid front end; the latent
+ * cross-attention form forced by TXO_LATENT=1.  Beam search and logits_out have no ragged entry point (the beam call takes one (H, W) and opens its own
+ * session).  The container's width Wc must be a multiple of 4 (rows are read in 16-byte pieces).  The persistent launch is not taken: a
+ * ragged generate runs one launch per stage (TXO_Q_LAST_PERSISTENT reads 0), and its session is closed when it returns.
  *
  * Encode: sizes_host int32 [B][2] = (H_b, W_b).  enc_out_dev float [B][Ns][D]: rows n_b..Ns-1 of slot b are written as zeros.
  * *n_slot_out (HOST, may be NULL) receives Ns.  Asynchronous on `stream`. */
@@ -208,18 +215,42 @@ int txo_encode_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C,
                       float* enc_out_dev, int32_t* n_slot_out, void* stream);
 
 /* Open a decode session over a ragged encoder output enc_dev [B][Ns][D]: n_tokens_host int32 [B], 1 <= n_b <= Ns, the rows of slot b
- * the cross attention may see.  txo_decode_step (its logits included) then works as on a fixed-shape session. */
+ * the cross attention may see.  txo_decode_step (its logits included) then works as on a fixed-shape session.  Under
+ * txo_set_ragged_forward(e, 1) so does every other session call, each row as if its image had been begun alone: txo_decode_prefill,
+ * txo_decode_score, txo_decode_set_key_mask (it masks decoder positions, which the image sizes do not touch; txo_decode_step honours it
+ * on a ragged session too) and txo_decode_attn -- with N = Ns: cross_attn_out [Ld][B][heads][t][Ns],
+ * cross_mean_out [Ld][B][t][Ns], columns n_b..Ns-1 of every row written as exactly 0 (the buffers may be uninitialised); self-attention
+ * maps as on a fixed-shape session.  txo_decode_step(e, tok, t, ...) continues behind the multi-position calls. */
 int txo_decode_begin_ragged(txo_engine* e, const float* enc_dev, int32_t B, int32_t Ns, const int32_t* n_tokens_host, void* stream);
 
 /* The loop of the fixed-shape generate call over a ragged batch: same eos rules (global break by default, TXO_STOP_ROW as set by
  * txo_set_stop_mode), same token selection (txo_set_sampling; a draw is keyed by the row of the batch).  tokens_out_dev [B, max_len]
- * int64, *n_steps_out (HOST) the valid columns; 1 <= max_len <= cfg.max_len.  Synchronises the stream before returning. */
+ * int64, *n_steps_out (HOST) the valid columns; max_len >= 1.  Under txo_set_ragged_forward(e, 1) max_len may exceed cfg.max_len (refused
+ * otherwise): the window slides as in txo_generate (one ragged multi-position forward per further token), under the same two preconditions -- a vocabulary that is a multiple of 8 and
+ * cfg.max_len <= max_batch * max_tokens -- checked before anything is decoded (TXO_E_INVALID, tokens_out_dev untouched).  Synchronises
+ * the stream before returning. */
 int txo_generate_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
                         int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, void* stream);
 
 /* txo_generate_ragged with the per-token log-probabilities of txo_generate_logp: logp_out_dev float [B, max_len], must not be NULL. */
 int txo_generate_ragged_logp(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
                              int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, float* logp_out_dev, void* stream);
+
+/* txo_score over a ragged container: txo_encode_ragged + txo_decode_begin_ragged + txo_decode_set_key_mask(mask_dev, L) + txo_decode_score.
+ * img_dev / sizes_host as in txo_encode_ragged; tokens_dev int64 [B][L], mask_dev uint8 [B][L] or NULL, the three outputs [B][L-1], each
+ * may be NULL, all as in txo_score.  Row b is what txo_score returns for image b passed on its own with tokens_dev[b] / mask_dev[b].  The key
+ * mask is cleared again before the call returns; the (ragged) session stays open: txo_decode_step(e, tok, L-1, ...) continues behind it.
+ * Works with txo_set_ragged_forward on or off (the call is new with the ragged forward: nothing relied on its refusal). */
+int txo_score_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
+                     const int64_t* tokens_dev, const uint8_t* mask_dev, int32_t L, float* logp_out_dev, int64_t* top1_out_dev,
+                     float* top1_logp_out_dev, void* stream);
+
+/* The ragged form of the multi-position forward, for the following calls on this engine.  on = 0 (default): txo_decode_prefill,
+ * txo_decode_attn, txo_decode_score and txo_decode_set_key_mask on a session opened by txo_decode_begin_ragged, txo_score while such a
+ * session is open, and txo_generate_ragged[_logp] with max_len > cfg.max_len answer TXO_E_INVALID with a message naming ragged batches,
+ * as they did before that form existed.  on = 1: they are accepted (see "Ragged batches" above).  Nothing else depends on it; fixed-shape
+ * sessions are not affected. */
+int txo_set_ragged_forward(txo_engine* e, int32_t on);
 
 /* Token selection for the following decode steps / generate calls.  mode 0 (default): greedy argmax.  mode 1:
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits

@@ -40,6 +40,7 @@ SYMBOLS = {
     "txo_decode_score": (C.c_int, [_P, _I64P, _I, _FP, _I64P, _FP, _P]),
     "txo_decode_attn": (C.c_int, [_P, _I64P, _I, _FP, _FP, _FP, _FP, _P]),
     "txo_score": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.c_void_p, _I, _FP, _I64P, _FP, _P]),
+    "txo_score_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I64P, C.c_void_p, _I, _FP, _I64P, _FP, _P]),
     "txo_decode_set_key_mask": (C.c_int, [_P, C.c_void_p, _I, _P]),
     "txo_generate": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
     "txo_generate_from_enc": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
@@ -52,6 +53,7 @@ SYMBOLS = {
     "txo_generate_ragged_logp": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
     "txo_set_sampling": (C.c_int, [_P, _I, _I, C.c_float, C.c_uint64]),
     "txo_set_stop_mode": (C.c_int, [_P, _I]),
+    "txo_set_ragged_forward": (C.c_int, [_P, _I]),
     "txo_profile_enable": (C.c_int, [_P, _I]),
     "txo_profile_read": (C.c_int, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "txo_engine_query": (C.c_int, [_P, _I, C.POINTER(C.c_int64)]),

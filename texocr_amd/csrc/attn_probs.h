@@ -21,16 +21,23 @@ namespace txo {
 
 constexpr size_t attn_probs_lds_bytes(int heads_walked) { return (size_t)heads_walked * EA_QBLK * 2 * sizeof(float); }
 
-template <typename TI, bool CAUSAL, bool KMASK, bool MEAN>
-__global__ __launch_bounds__(256) void attn_probs_kernel(const TI* __restrict__ Q, const TI* __restrict__ Kg, float* __restrict__ P, int nq, int nk,
+// RAGGED (cross maps of a ragged batch session, never causal): image b has nk = lens[b] keys in K panels kv_rows apart, as in
+//   attn_mq_kernel<.., RAGGED>; the output rows stay nk_arg (= the slot stride Ns) floats apart and columns lens[b] .. nk_arg-1 of every row
+//   are written as exactly 0.f (the caller's buffer may be uninitialised): inside the image's last stage by the masked-score rule, behind it
+//   by plain stores -- those stages are not walked.  RAGGED = false is the kernel without the parameter.
+template <typename TI, bool CAUSAL, bool KMASK, bool MEAN, bool RAGGED = false>
+__global__ __launch_bounds__(256) void attn_probs_kernel(const TI* __restrict__ Q, const TI* __restrict__ Kg, float* __restrict__ P, int nq, int nk_arg,
                                                          int kv_rows, int heads, const unsigned char* __restrict__ kmask = nullptr,
-                                                         int kmask_stride = 0) {
+                                                         int kmask_stride = 0, const int* __restrict__ lens = nullptr) {
+    static_assert(!(RAGGED && (CAUSAL || KMASK)), "per-image key counts exist for the cross attention only");
     __shared__ __attribute__((aligned(16))) unsigned char Ks[EA_KSTAGE * 256];   // one 64-key stage, f32 rows
     __shared__ __attribute__((aligned(16))) float tiles[4][16 * 64];             // per wave: 16 queries x 64 keys on their way out
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
     float2* stats = reinterpret_cast<float2*>(dyn_lds);                          // [head walked][query of the block] = (max, 1 / sum)
     const int b = MEAN ? blockIdx.y : blockIdx.y / heads;
     const int h0 = MEAN ? 0 : blockIdx.y - b * heads, nh = MEAN ? heads : 1;
+    const int nk = RAGGED ? lens[b] : nk_arg;                 // keys that take part
+    const int prow = RAGGED ? nk_arg : nk;                    // floats between two output rows
     const int q0 = blockIdx.x * EA_QBLK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lc = lane & 15, lg = lane >> 4;
@@ -154,7 +161,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const TI* __restrict__ 
     // ---- sweep 2: S again, p = exp(S - max) / sum; per key stage the heads in index order, then one write of the stage's tile.
     // (the statistics are read behind the barriers of stage_in; every stage of the row is written: the ones sweep 1 skipped hold zeros)
     float* tile = tiles[wave];
-    float* Pb = P + (MEAN ? (size_t)b : (size_t)b * heads + h0) * nq * nk;
+    float* Pb = P + (MEAN ? (size_t)b : (size_t)b * heads + h0) * nq * prow;
     [[maybe_unused]] const float fheads = (float)heads;
     for (int s = 0; s < nstage; ++s) {
         f32x4 acc[2][4];
@@ -190,11 +197,21 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const TI* __restrict__ 
             for (int qq = 0; qq < 16; ++qq) {
                 const int qrow = q0 + wave * 32 + qt * 16 + qq;
                 const float v = tile[qq * 64 + (lane ^ ((qq & 7) << 2))];
-                if (qrow < nq && key < nk) Pb[(size_t)qrow * nk + key] = v;   // queries >= nq store nothing
+                // (RAGGED: the stage's columns behind nk are written too; their scores were masked, so v is exactly 0.f there)
+                if (qrow < nq && key < prow) Pb[(size_t)qrow * prow + key] = v;   // queries >= nq store nothing
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the tile has been read before the next 16 queries overwrite it
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+    if constexpr (RAGGED) {                                   // the stages behind the image's last: zeros, without walking them
+        for (int s = nstage; s * EA_KSTAGE < prow; ++s) {
+            const int key = s * EA_KSTAGE + lane;
+            for (int qq = 0; qq < 32; ++qq) {
+                const int qrow = q0 + wave * 32 + qq;
+                if (qrow < nq && key < prow) Pb[(size_t)qrow * prow + key] = 0.f;
+            }
         }
     }
 }

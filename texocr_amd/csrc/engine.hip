@@ -71,6 +71,8 @@ struct EngineBase {
     virtual int decode_begin(const float* enc, int B, int N, int eos, hipStream_t s) = 0;
     virtual int encode_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, float* enc_out, int32_t* n_slot, hipStream_t s) = 0;
     virtual int decode_begin_ragged(const float* enc, int B, int Ns, const int32_t* n_tokens, int eos, hipStream_t s) = 0;
+    virtual int score_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, const int64_t* tokens, const unsigned char* mask,
+                             int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
     virtual int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
                                 int* n_steps, float* logp_out, hipStream_t s) = 0;
     virtual int decode_step(const int64_t* tok_in, int t, float* logits_out, int64_t* tok_out, hipStream_t s) = 0;
@@ -89,6 +91,7 @@ struct EngineBase {
     int sample_mode = 0, sample_topk = 0; float sample_temp = 1.f; unsigned long long sample_seed = 0;
     size_t sample_lds_max = 65536;              // dynamic LDS the LDS-form sampler may ask for (init: the device's per-workgroup limit)
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
+    bool rag_fwd = false;                       // txo_set_ragged_forward: the multi-position forward on ragged sessions and the ragged sliding window are accepted
     virtual int query(int what, int64_t* out) = 0;
     virtual int profile_enable(int on) = 0;
     virtual int profile_read(int kind, double* avg_ms, int64_t* count) = 0;
@@ -194,6 +197,10 @@ struct Engine : EngineBase {
     int32_t* rag_host = nullptr; hipEvent_t rag_ev = nullptr; bool rag_ev_pending = false;
     std::vector<int32_t> rag_stage;   // host scratch [3 Bmax] (sized at creation)
     bool last_ragged = false;         // TXO_Q_LAST_RAGGED
+    // rag_fwd off (the default): these calls answer as they did before the forward had a ragged form
+    int refuse_ragged_forward(const std::string& call) const {
+        return fail(TXO_E_INVALID, call + ": not available on a ragged batch session unless txo_set_ragged_forward(e, 1) is in effect");
+    }
     Stamps stamps;                    // TXO_STAMPS / TXO_PSTAMPS diagnostics (stamps.h)
     int64_t* tok_buf = nullptr;            // [Bmax][Tmax] generated ids (engine-owned so graphs do not bake user pointers)
     float* logp_buf = nullptr;             // [Bmax][Tmax] their log-probabilities, for a captured step that carries them (generate_impl)
@@ -950,8 +957,12 @@ struct Engine : EngineBase {
                         int* n_steps, float* logp_out, hipStream_t s) override {
         if (int r = ragged_refusals()) return r;
         if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
-        if (max_len > Tmax)
-            return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length (the sliding window runs through the prefill, which has no ragged form)");
+        if (max_len > Tmax && !rag_fwd)
+            return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length (the sliding window of a ragged batch needs txo_set_ragged_forward(e, 1))");
+        // beyond the positional table the window slides through generate_window, under the fixed-shape call's two preconditions (generate())
+        if (max_len > Tmax && (V % 8 != 0 || (size_t)Tmax > (size_t)Bmax * Nmax))
+            return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a "
+                                       "vocabulary size that is a multiple of 8 and max_length <= max_batch * max_tokens");
         ImageBatch ib;
         if (int r = ragged_batch(B, C, Hc, Wc, sizes, s, &ib)) return r;
         return generate_common(&ib, img, B, ib.N, max_len, eos, tokens_out, n_steps, nullptr, logp_out, s);
@@ -1452,7 +1463,7 @@ struct Engine : EngineBase {
     int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) override {
         if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (ses.images != ses.rows) return fail(TXO_E_STATE, "key masks are not available inside a beam-search session");
-        if (ses.ragged) return fail(TXO_E_INVALID, "txo_decode_set_key_mask: not available on a ragged batch session");
+        if (ses.ragged && !rag_fwd) return refuse_ragged_forward("txo_decode_set_key_mask");
         if (!mask) { ses.kmask_on = false; return 0; }
         if (cols < 1 || cols > Tmax) return fail(TXO_E_INVALID, "mask columns must be in [1, max_length]");
         const int n = ses.rows * Tmax;
@@ -1467,7 +1478,7 @@ struct Engine : EngineBase {
     int prefill_entry(const std::string& name, const int64_t* tokens, int t, float* logits_out, const AttnOut* attn, hipStream_t s) {
         if (lanes.n != 1) return fail(TXO_E_STATE, name + " needs a session started by txo_decode_begin");
         if (ses.images != ses.rows) return fail(TXO_E_STATE, name + " is not available inside a beam-search session");
-        if (ses.open && ses.ragged) return fail(TXO_E_INVALID, "txo_" + name + ": not available on a ragged batch session (the multi-position forward has no ragged form)");
+        if (ses.open && ses.ragged && !rag_fwd) return refuse_ragged_forward("txo_" + name);
         lanes[0].stream = s;
         return prefill(tokens, t, t, logits_out, nullptr, s, nullptr, attn);
     }
@@ -1491,7 +1502,11 @@ struct Engine : EngineBase {
         if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (lanes.n != 1) return fail(TXO_E_STATE, "decode_score needs a session started by txo_decode_begin");
         if (ses.images != ses.rows) return fail(TXO_E_STATE, "decode_score is not available inside a beam-search session");
-        if (ses.ragged) return fail(TXO_E_INVALID, "txo_decode_score: not available on a ragged batch session (the multi-position forward has no ragged form)");
+        if (ses.ragged && !rag_fwd) return refuse_ragged_forward("txo_decode_score");
+        return score_pass(tokens, L, logp_out, top1_out, top1_logp_out, s);
+    }
+    // (the session is open, has one row per image and one row range: decode_score checked it, or txo_score / txo_score_ragged just opened it)
+    int score_pass(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) {
         lanes[0].stream = s;
         const ScoreOut so{logp_out, top1_out, top1_logp_out};
         return prefill(tokens, L, L - 1, nullptr, nullptr, s, &so);
@@ -1500,18 +1515,31 @@ struct Engine : EngineBase {
     // OCRModel.forward's path (ocr_model.py:38-44) in one call: encode into the engine's own buffer, open the session, mask, score
     int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
               int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
-        if (ses.open && ses.ragged)
-            return fail(TXO_E_INVALID, "txo_score: a ragged batch session is open and ragged batches have no scoring path (open a fixed-shape session first)");
+        if (ses.open && ses.ragged && !rag_fwd) return refuse_ragged_forward("txo_score (a ragged batch session is open)");
         if (int r = encode(img, B, C, H, W, eenc, s)) return r;
         if (int r = begin_session(eenc, B, 1 + (H / 16) * (W / 16), cfg.eos, s, true)) return r;
+        return score_open_session(tokens, mask, L, logp_out, top1_out, top1_logp_out, s);
+    }
+    // the tail txo_score and txo_score_ragged share: the [B][L] mask's first L - 1 columns as the key mask, the scores, the mask cleared
+    int score_open_session(const int64_t* tokens, const unsigned char* mask, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out,
+                           hipStream_t s) {
         if (mask) {
             const int n = ses.rows * Tmax;
             hipLaunchKernelGGL(set_key_mask_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, kmask, ses.rows, L, L - 1, Tmax);
             ses.kmask_on = true;
         }
-        const int rc = decode_score(tokens, L, logp_out, top1_out, top1_logp_out, s);
+        const int rc = score_pass(tokens, L, logp_out, top1_out, top1_logp_out, s);
         ses.kmask_on = false;
         return rc;
+    }
+    // txo_score over a ragged container: every row is what txo_score returns for that image passed on its own
+    int score_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, const int64_t* tokens, const unsigned char* mask, int L,
+                     float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
+        ImageBatch ib;
+        if (int r = ragged_batch(B, C, Hc, Wc, sizes, s, &ib)) return r;
+        if (int r = encode_batch(ib, img, eenc, s)) return r;
+        if (int r = begin_session(eenc, B, ib.N, cfg.eos, s, true, KeyCounts{rag_ntok})) return r;
+        return score_open_session(tokens, mask, L, logp_out, top1_out, top1_logp_out, s);
     }
 
     // ---- multi-position decoder forward (prefill.h): Transformer.forward over t positions at once, filling the self K/V cache ----
@@ -1521,23 +1549,27 @@ struct Engine : EngineBase {
     struct ScoreOut { float* logp; int64_t* top1; float* top1_logp; };
     template <typename TO>
     void launch_attn_mq(hipStream_t s, bool causal, const T* q, const T* k, const T* v, TO* out, int nb, int nq, int nk, int kv_rows,
-                        const unsigned char* km = nullptr) {
+                        const unsigned char* km = nullptr, const int* lens = nullptr) {
         const dim3 grid((nq + EA_QBLK - 1) / EA_QBLK, nb * cfg.dec_heads);
-        if (causal && km) hipLaunchKernelGGL((attn_mq_kernel<T, TO, true, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads, km, Tmax);
+        if (lens)                                             // cross attention of a ragged session: nk = lens[image], panels kv_rows apart
+            hipLaunchKernelGGL((attn_mq_kernel<T, TO, false, false, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads, nullptr, 0, lens);
+        else if (causal && km) hipLaunchKernelGGL((attn_mq_kernel<T, TO, true, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads, km, Tmax);
         else if (causal) hipLaunchKernelGGL((attn_mq_kernel<T, TO, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
         else hipLaunchKernelGGL((attn_mq_kernel<T, TO, false>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
     }
     // the probabilities behind a launch_attn_mq call, from the same q / k (attn_probs.h); MEAN: one map per image, the mean over the heads
     template <bool MEAN>
     void launch_attn_probs(hipStream_t s, bool causal, const T* q, const T* k, float* out, int nb, int nq, int nk, int kv_rows,
-                           const unsigned char* km = nullptr) {
+                           const unsigned char* km = nullptr, const int* lens = nullptr) {
         const int heads = cfg.dec_heads;
         const dim3 grid((nq + EA_QBLK - 1) / EA_QBLK, MEAN ? nb : nb * heads);
         const size_t lds = attn_probs_lds_bytes(MEAN ? heads : 1);
         if constexpr (MEAN) {                                 // only the cross maps have a head mean: no causal form of it exists
-            hipLaunchKernelGGL((attn_probs_kernel<T, false, false, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
+            if (lens) hipLaunchKernelGGL((attn_probs_kernel<T, false, false, true, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, nullptr, 0, lens);
+            else hipLaunchKernelGGL((attn_probs_kernel<T, false, false, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
         } else {
-            if (causal && km) hipLaunchKernelGGL((attn_probs_kernel<T, true, true, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, km, Tmax);
+            if (lens) hipLaunchKernelGGL((attn_probs_kernel<T, false, false, false, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, nullptr, 0, lens);
+            else if (causal && km) hipLaunchKernelGGL((attn_probs_kernel<T, true, true, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, km, Tmax);
             else if (causal) hipLaunchKernelGGL((attn_probs_kernel<T, true, false, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
             else hipLaunchKernelGGL((attn_probs_kernel<T, false, false, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
         }
@@ -1580,11 +1612,13 @@ struct Engine : EngineBase {
                 gemm_plain(s, ez, dec_cross[l].wq, M, Id, D, EpiHeads<T>{qbuf, 0, Id, heads, t});
                 const T* ck = ckv + (size_t)(2 * l) * cross_stride + (size_t)b0 * heads * N * DH;
                 const T* cv = ckv + (size_t)(2 * l + 1) * cross_stride + (size_t)b0 * heads * N * DH;
-                launch_attn_mq<T>(s, false, qbuf, ck, cv, eao, nb, t, N, N);
+                // a ragged session: N is the slot stride Ns and image b attends its own slens[b] keys; the counts move with the chunk
+                const int* lens = ses.ragged ? slens + b0 : nullptr;
+                launch_attn_mq<T>(s, false, qbuf, ck, cv, eao, nb, t, N, N, nullptr, lens);
                 if (attn && attn->cross_p)                    // [Ld][B][heads][t][N]
-                    launch_attn_probs<false>(s, false, qbuf, ck, attn->cross_p + ((size_t)l * B + b0) * heads * t * N, nb, t, N, N);
+                    launch_attn_probs<false>(s, false, qbuf, ck, attn->cross_p + ((size_t)l * B + b0) * heads * t * N, nb, t, N, N, nullptr, lens);
                 if (attn && attn->cross_mean)                 // [Ld][B][t][N]
-                    launch_attn_probs<true>(s, false, qbuf, ck, attn->cross_mean + ((size_t)l * B + b0) * t * N, nb, t, N, N);
+                    launch_attn_probs<true>(s, false, qbuf, ck, attn->cross_mean + ((size_t)l * B + b0) * t * N, nb, t, N, N, nullptr, lens);
                 gemm_plain(s, eao, dec_cross[l].wo16, M, 2 * D, Id, EpiGluRes<sizeof(T) == 2>{ey, res_x, dec_cross[l].bo16});
                 // GeGLU feed-forward
                 launch_ln<3, T>(s, ey, estats, ez, dec_g, dec_b, M);
@@ -2181,6 +2215,13 @@ int txo_score(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, 
     return e->impl->score(img, B, C, H, W, tokens, mask, L, logp_out, top1_out, top1_logp_out, (hipStream_t)stream);
 }
 
+int txo_score_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, const int64_t* tokens,
+                     const uint8_t* mask, int32_t L, float* logp_out, int64_t* top1_out, float* top1_logp_out, void* stream) {
+    if (!e || !img || !sizes || !tokens) return fail(TXO_E_INVALID, "null argument");
+    if (L < 2 || L > e->impl->cfg.max_len + 1) return fail(TXO_E_INVALID, "score: L must be in [2, max_len + 1]");
+    return e->impl->score_ragged(img, B, C, Hc, Wc, sizes, tokens, mask, L, logp_out, top1_out, top1_logp_out, (hipStream_t)stream);
+}
+
 int txo_decode_set_key_mask(txo_engine* e, const uint8_t* mask, int32_t cols, void* stream) {
     if (!e) return fail(TXO_E_INVALID, "null engine");
     return e->impl->decode_set_key_mask(mask, cols, (hipStream_t)stream);
@@ -2226,6 +2267,13 @@ int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint
         return fail(TXO_E_INVALID, "sampling: the vocabulary does not fit the sampler's LDS (vocab * 4 bytes per workgroup: txo_engine_query "
                                    "TXO_Q_SAMPLE_VOCAB_MAX)");
     e->impl->sample_mode = mode; e->impl->sample_topk = topk; e->impl->sample_temp = mode ? temp : 1.f; e->impl->sample_seed = seed;
+    return 0;
+}
+
+int txo_set_ragged_forward(txo_engine* e, int32_t on) {
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (on != 0 && on != 1) return fail(TXO_E_INVALID, "txo_set_ragged_forward: on must be 0 or 1");
+    e->impl->rag_fwd = on != 0;
     return 0;
 }
 

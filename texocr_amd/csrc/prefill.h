@@ -72,12 +72,20 @@ template <> __device__ inline u32x4 ld4_f32<bf16>(const bf16* p) {
 //   False).  kmask [images][kmask_stride] bytes, 0 = padding.  A key that is padding is never attended by a query that is not; the row of a
 //   query that IS padding is unspecified here as on the single-position path (the reference softmaxes it uniformly over all keys, future ones
 //   included; nothing reads it): it ignores the mask, so that it stays finite -- its k / v rows land in the cache and are masked at every use.
-template <typename TI, typename TO, bool CAUSAL, bool KMASK = false>
+// RAGGED (cross attention of a ragged batch session, never causal): image b attends its own lens[b] keys -- nk = lens[b], the argument
+//   nk_arg is not read -- in K / V panels that stay kv_rows (the slot stride Ns) rows apart.  Everything below then runs on the image's own
+//   nk: the stage count (whole 64-key stages behind a short image are not walked), the load clamp behind nk - 1 (no row of another
+//   image's length is ever read: rows lens[b] .. kv_rows-1 may hold anything), the last stage's mask.  A valid row's arithmetic is the
+//   fixed-shape call's on that image alone, operation for operation.  RAGGED = false is the kernel without the parameter.
+template <typename TI, typename TO, bool CAUSAL, bool KMASK = false, bool RAGGED = false>
 __global__ __launch_bounds__(256) void attn_mq_kernel(const TI* __restrict__ Q, const TI* __restrict__ Kg, const TI* __restrict__ Vg,
-                                                      TO* __restrict__ out, int nq, int nk, int kv_rows, int heads,
-                                                      const unsigned char* __restrict__ kmask = nullptr, int kmask_stride = 0) {
+                                                      TO* __restrict__ out, int nq, int nk_arg, int kv_rows, int heads,
+                                                      const unsigned char* __restrict__ kmask = nullptr, int kmask_stride = 0,
+                                                      const int* __restrict__ lens = nullptr) {
+    static_assert(!(RAGGED && (CAUSAL || KMASK)), "per-image key counts exist for the cross attention only");
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][EA_KSTAGE * 256];   // [buf][K|V], f32 rows
     const int bh = blockIdx.y, b = bh / heads, head = bh - b * heads;
+    const int nk = RAGGED ? lens[b] : nk_arg;
     const int q0 = blockIdx.x * EA_QBLK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lc = lane & 15, lg = lane >> 4;

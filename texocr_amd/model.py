@@ -34,7 +34,7 @@ import ctypes as C
 import math
 import os
 import re
-from typing import Dict, NamedTuple, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -221,14 +221,22 @@ class HipEngine:
         self._ensure()
         torch.ops.texocr.decode_begin_ragged(enc, n_tokens, self.id)
 
+    def score_ragged(self, images, tokens: torch.Tensor, mask: Optional[torch.Tensor] = None):
+        """txo_score_ragged: images of different sizes, tokens (B, L), mask (B, L) or None -> (logp, top1, top1_logp), each (B, L-1)"""
+        self._ensure()
+        box, sizes = ops.pack_ragged(images)
+        return torch.ops.texocr.score_ragged(box, sizes, tokens, mask, self.id)
+
     def generate_ragged(self, images, max_len: int, eos: Optional[int], return_logp: bool = False):
         self._ensure()
         box, sizes = ops.pack_ragged(images)
-        if return_logp:
-            toks, n, logp = torch.ops.texocr.generate_ragged_logp(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
-            return toks[:, :int(n.item())], logp[:, :int(n.item())]
-        toks, n = torch.ops.texocr.generate_ragged(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
-        return toks[:, :int(n.item())]
+        # beyond the positional table the window slides through the ragged multi-position forward
+        with self.ragged_forward() if int(max_len) > self.dims.max_len else contextlib.nullcontext():
+            if return_logp:
+                toks, n, logp = torch.ops.texocr.generate_ragged_logp(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
+                return toks[:, :int(n.item())], logp[:, :int(n.item())]
+            toks, n = torch.ops.texocr.generate_ragged(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
+            return toks[:, :int(n.item())]
 
     def generate_beam(self, img: torch.Tensor, beams: int, max_len: int, eos: Optional[int], return_beams: bool = False):
         """Beam search (build extension; the reference has none).  Returns the best beam's tokens (B, n), or with
@@ -277,6 +285,22 @@ class HipEngine:
                 self.set_sampling(False)
             if stop == "row":
                 self.set_stop_mode("global")
+
+    @contextlib.contextmanager
+    def ragged_forward(self):
+        """txo_set_ragged_forward(1) around calls that run the multi-position forward on a ragged session (decode_prefill / decode_score /
+        decode_attn / set_key_mask behind decode_begin_ragged) or slide the window of a ragged generate; put back behind every exit.  Outside
+        it those calls are refused with a message naming ragged batches, as before the forward had a ragged form."""
+        self._ensure()                                             # (a reload of the weights makes a new handle: before the switch, not after)
+        before = getattr(self, "_ragged_forward", False)
+        _lib.check(self.lib.txo_set_ragged_forward(self.handle, 1))
+        self._ragged_forward = True
+        try:
+            yield
+        finally:
+            self._ragged_forward = before
+            if self.handle:
+                _lib.check(self.lib.txo_set_ragged_forward(self.handle, 1 if before else 0))
 
     @contextlib.contextmanager
     def key_mask(self, mask: Optional[torch.Tensor]):
@@ -400,6 +424,29 @@ def _check_token_ids(tokens: torch.Tensor, vocab: int) -> None:
         raise IndexError(f"token id outside the vocabulary [0, {vocab})")
 
 
+def _check_n_tokens(n_tokens, enc: torch.Tensor) -> torch.Tensor:
+    """n_tokens of a ragged encoder output enc (B, Ns, D), as VisionEncoder.forward_ragged returns it -> (B,) int32 on the host"""
+    n = torch.as_tensor(n_tokens).to(device="cpu", dtype=torch.int32)
+    if n.ndim != 1 or n.shape[0] != enc.shape[0]:
+        raise ValueError(f"n_tokens must have one entry per row of enc ({enc.shape[0]}), got shape {tuple(n.shape)}")
+    if int(n.min()) < 1 or int(n.max()) > enc.shape[1]:
+        raise ValueError(f"n_tokens must be in [1, {enc.shape[1]}] (the rows of a slot of enc)")
+    return n.contiguous()
+
+
+@contextlib.contextmanager
+def _session(eng, enc: torch.Tensor, n_tokens: Optional[torch.Tensor]):
+    """the session on enc around a facade's multi-position calls: fixed shape, or (n_tokens, checked by _check_n_tokens) ragged, with the
+    engine's ragged forward switched on for the length of the block"""
+    if n_tokens is None:
+        eng.decode_begin(enc)
+        yield
+    else:
+        with eng.ragged_forward():
+            eng.decode_begin_ragged(enc, n_tokens)
+            yield
+
+
 class Score(NamedTuple):
     """What AutoRegressiveDecoder.score / OCRModel.score return (position p of row b scores the target trg[b, p + 1]):
     logp (B, L-1) log-probability of the target; top1 (B, L-1) arg-max of the logits; top1_logp (B, L-1) its log-probability;
@@ -449,6 +496,21 @@ def alignment(cross_mean: torch.Tensor, layer: Optional[int] = -1, grid: Optiona
     return Alignment(maps, cls, peak)
 
 
+def alignment_ragged(cross_mean: torch.Tensor, n_tokens: Sequence[int], layer: Optional[int] = -1,
+                     grids: Optional[Sequence[Tuple[int, int]]] = None) -> List[Alignment]:
+    """alignment() per image of a ragged session: cross_mean (Ld, B, t, Ns), image b owns the keys 0 .. n_tokens[b]-1 of row b (the engine
+    writes zeros behind them; they are cut off, not looked at) -> B Alignments with a leading dimension of 1, element b over image b's own
+    n_b - 1 patches, on the grid grids[b] = (h_b, w_b) if given."""
+    n = [int(v) for v in n_tokens]
+    if len(n) != cross_mean.shape[1] or (grids is not None and len(grids) != len(n)):
+        raise ValueError("n_tokens / grids must have one entry per image")
+    for b, nb in enumerate(n):
+        if grids is not None and 1 + int(grids[b][0]) * int(grids[b][1]) != nb:
+            raise ValueError(f"grids[{b}] = {tuple(grids[b])} does not hold the {nb - 1} patches of image {b}")
+    return [alignment(cross_mean[:, b:b + 1, :, :nb], layer, None if grids is None else (int(grids[b][0]), int(grids[b][1])))
+            for b, nb in enumerate(n)]
+
+
 class Transformer(nn.Module):
     """model.decoder.net: (B,t) int64 tokens -> (B,t,V) logits over the whole prefix (decoder.py:41-67): ONE causal
     multi-position pass (txo_decode_prefill), which also leaves the K/V cache filled for the positions given."""
@@ -461,11 +523,17 @@ class Transformer(nn.Module):
 
     def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None, **kw):
         """return_attn=True: (logits, attn_maps) as the reference returns them (decoder.py:62-65): the post-softmax attention of every
-        block in stack order -- self 0, cross 0, self 1, cross 1, ... -- each (B, heads, t, keys), views into two buffers."""
+        block in stack order -- self 0, cross 0, self 1, cross 1, ... -- each (B, heads, t, keys), views into two buffers.
+        n_tokens= (build extension): enc is a ragged encoder output (B, Ns, D) and n_tokens its valid rows per image, both as
+        VisionEncoder.forward_ragged returns them; row b is what the call gives on enc[b:b+1, :n_tokens[b]], and the cross maps are
+        (B, heads, t, Ns) with exact zeros behind an image's own keys."""
         return_attn = bool(kw.pop("return_attn", False))
+        n_tokens = kw.pop("n_tokens", None)
         if kw:
             raise ValueError(f"unsupported arguments for the inference path: {sorted(kw)}")
         _need_enc(enc)
+        if n_tokens is not None:
+            n_tokens = _check_n_tokens(n_tokens, enc)
         padded = mask is not None and not bool(mask.all())
         if padded and tuple(mask.shape) != tuple(x.shape):
             raise ValueError("mask must have the shape of x")
@@ -474,13 +542,12 @@ class Transformer(nn.Module):
             raise ValueError("prefix longer than decoder.max_len")
         eng = self._engine
         _check_token_ids(x, eng.dims.vocab)
-        eng.decode_begin(enc)
         # the one-pass prefill (csrc/prefill.h, with or without a key mask) needs a vocabulary that is a multiple of 8 and a prefix that
         # fits the engine's workspace (max_batch * max_tokens rows); anything else takes the single-position steps
         one_pass = eng.dims.vocab % 8 == 0 and x.shape[1] <= eng.max_batch * eng.max_tokens and os.environ.get("TXO_NET_STEPWISE") is None
         # attention.py:130-155: a padded position is never attended by a query that is not padding.  Logits AT padded positions are
         # unspecified here (the reference softmaxes such a row uniformly over all keys, future ones included; nothing reads it)
-        with eng.key_mask(mask.to(x.device) if padded else None):
+        with _session(eng, enc, n_tokens), eng.key_mask(mask.to(x.device) if padded else None):
             if not return_attn:
                 return eng.decode_prefill(x) if one_pass else self._net_stepwise(x)
             # (the maps need no logits: a vocabulary the one-pass logits cannot take gets them from the stepwise route behind)
@@ -513,12 +580,16 @@ class AutoRegressiveDecoder(nn.Module):
                                   "implements the generate() inference path only")
 
     @torch.no_grad()
-    def score(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None) -> Score:
+    def score(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None,
+              n_tokens: Optional[torch.Tensor] = None) -> Score:
         """The quantity forward() trains on, for inference (decoder.py:124-145 without autograd): x (B, L) int64 target sequences
         (bos first), x[:, :-1] is fed in one causal pass and x[:, 1:] are the targets.  mask (B, L) bool, False = padding (None: no
         padding).  The logits are never materialised (csrc/score.h).  Unlike the reference's loss, `loss` averages over the valid
-        positions only (F.cross_entropy there has no ignore_index); without padding the two are the same number."""
+        positions only (F.cross_entropy there has no ignore_index); without padding the two are the same number.
+        n_tokens= (build extension): enc / n_tokens as VisionEncoder.forward_ragged returns them; row b scores against image b's own rows."""
         _need_enc(enc)
+        if n_tokens is not None:
+            n_tokens = _check_n_tokens(n_tokens, enc)
         _check_x(x, "(B, L)")
         if x.shape[1] < 2:
             raise ValueError("x needs at least two columns (one fed token and its target)")
@@ -529,18 +600,26 @@ class AutoRegressiveDecoder(nn.Module):
         eng = self._engine
         _check_token_ids(x, eng.dims.vocab)
         m = torch.ones_like(x, dtype=torch.bool) if mask is None else mask.to(device=x.device, dtype=torch.bool)
-        eng.decode_begin(enc)
-        with eng.key_mask(m[:, :-1]):                              # (the last column is a target only, never a key)
+        with _session(eng, enc, n_tokens), eng.key_mask(m[:, :-1]):   # (the last column is a target only, never a key)
             logp, top1, top1_logp = eng.decode_score(x)
         return score_summary(logp, top1, top1_logp, x, m)
 
     @torch.no_grad()
     def align(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None, layer: Optional[int] = -1,
-              grid: Optional[Tuple[int, int]] = None) -> Alignment:
+              grid: Optional[Tuple[int, int]] = None, n_tokens: Optional[torch.Tensor] = None,
+              grids: Optional[Sequence[Tuple[int, int]]] = None):
         """Build extension: where every position of a teacher-forced pass looked.  x (B, L) and mask as score() takes them; x[:, :-1] is
         fed in one causal pass that returns only the head mean of the cross-attention maps (the per-head tensors are never made).
-        layer: the decoder layer (-1 = the last), None = the mean over the layers.  -> Alignment over the N - 1 patch rows of enc."""
+        layer: the decoder layer (-1 = the last), None = the mean over the layers.  -> Alignment over the N - 1 patch rows of enc.
+        n_tokens= (build extension): enc / n_tokens as VisionEncoder.forward_ragged returns them -> a list of B Alignments (leading
+        dimension 1), element b over image b's own n_b - 1 patches, on grids[b] = (h_b, w_b) if grids is given (alignment_ragged)."""
         _need_enc(enc)
+        if n_tokens is not None:
+            n_tokens = _check_n_tokens(n_tokens, enc)
+            if grids is not None and len(grids) != n_tokens.shape[0]:
+                raise ValueError("grids must have one (rows, cols) per image")
+        elif grids is not None:
+            raise ValueError("grids belongs to a ragged encoder output (pass n_tokens); a fixed-shape call takes grid")
         _check_x(x, "(B, L)")
         if x.shape[1] < 2:
             raise ValueError("x needs at least two columns (one fed token and its target)")
@@ -552,9 +631,10 @@ class AutoRegressiveDecoder(nn.Module):
         if layer is not None and not -eng.dims.dec_layers <= layer < eng.dims.dec_layers:
             raise ValueError(f"layer must be None or in [{-eng.dims.dec_layers}, {eng.dims.dec_layers})")
         _check_token_ids(x, eng.dims.vocab)
-        eng.decode_begin(enc)
-        with eng.key_mask(None if mask is None else mask.to(device=x.device, dtype=torch.bool)[:, :-1]):
+        with _session(eng, enc, n_tokens), eng.key_mask(None if mask is None else mask.to(device=x.device, dtype=torch.bool)[:, :-1]):
             mean = eng.decode_attn(x[:, :-1].contiguous(), want_logits=False, want_self=False, want_cross=False, want_mean=True)[3]
+        if n_tokens is not None:
+            return alignment_ragged(mean, n_tokens.tolist(), layer, grids)
         return alignment(mean, layer, grid)
 
     @torch.no_grad()
@@ -751,7 +831,9 @@ class OCRModel(nn.Module):
                         stop: str = "global", return_logp: bool = False):
         """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
-        is keyed by the row of the batch).  max_len <= decoder.max_len.  return_logp=True: (tokens, logp) as generate() returns them."""
+        is keyed by the row of the batch).  max_len may exceed decoder.max_len: the window slides as in generate(), under the engine's
+        two preconditions (a vocabulary that is a multiple of 8, max_length <= max_batch * max_tokens; ValueError before anything is
+        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them."""
         with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode):
             return self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
 
@@ -763,6 +845,42 @@ class OCRModel(nn.Module):
         if mask is None:
             mask = trg != self.trg_pad_idx
         return self.decoder.score(trg, mask=mask, enc=self.encoder(src))
+
+    def _ragged_trg(self, images, trg: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
+        """the checks score_ragged / align_ragged share, before the engine is touched -> the mask (default trg != trg_pad_idx)"""
+        if trg.ndim != 2 or trg.shape[0] != len(images):
+            raise ValueError(f"trg must be (B, L) with one row per image ({len(images)}), got {tuple(trg.shape)}")
+        if trg.shape[1] < 2:
+            raise ValueError("trg needs at least two columns (one fed token and its target)")
+        if trg.shape[1] - 1 > self.decoder.max_len:
+            raise ValueError("sequence longer than decoder.max_len + 1")
+        if mask is None:
+            mask = trg != self.trg_pad_idx
+        if tuple(mask.shape) != tuple(trg.shape):
+            raise ValueError("mask must have the shape of trg")
+        return mask
+
+    @torch.no_grad()
+    def score_ragged(self, images, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:
+        """Build extension: score() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call (txo_score_ragged): row b
+        is what score(images[b][None], trg[b:b+1], mask[b:b+1]) returns; loss and token_acc run over the whole batch's valid positions."""
+        mask = self._ragged_trg(images, trg, mask)
+        _check_x(trg, "(B, L)")
+        _check_token_ids(trg, self._engine.dims.vocab)
+        m = mask.to(device=trg.device, dtype=torch.bool)
+        logp, top1, top1_logp = self._engine.score_ragged(images, trg, m)
+        return score_summary(logp, top1, top1_logp, trg, m)
+
+    @torch.no_grad()
+    def align_ragged(self, images, trg: torch.Tensor, mask: Optional[torch.Tensor] = None, layer: Optional[int] = -1) -> List[Alignment]:
+        """Build extension: align() over a sequence of (C, H_b, W_b) images of different sizes in one encode and one teacher-forced pass:
+        a list of B Alignments, element b what align(images[b][None], trg[b:b+1], mask[b:b+1], layer) returns, on image b's own
+        (H_b / 16, W_b / 16) patch grid."""
+        mask = self._ragged_trg(images, trg, mask)
+        ps = self.encoder.patch_size
+        grids = [(int(im.shape[1]) // ps, int(im.shape[2]) // ps) for im in images]
+        enc, ntok = self.encoder.forward_ragged(images)
+        return self.decoder.align(trg, mask=mask, enc=enc, layer=layer, n_tokens=ntok, grids=grids)
 
     @torch.no_grad()
     def align(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None, layer: Optional[int] = -1) -> Alignment:

@@ -17,9 +17,10 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::generate_logp / generate_from_enc_logp / generate_ragged_logp
                             (build extension) generate / generate_from_enc / generate_ragged that also return the log-probability
                             of every produced token, taken from the token selection itself (no second pass, no (B, T, V) tensor)
-  texocr::encode_ragged / decode_begin_ragged / generate_ragged
+  texocr::encode_ragged / decode_begin_ragged / generate_ragged / score_ragged
                             (build extension) the same callables over a RAGGED batch: B images of different sizes in one
-                            container, every image computed as if it had been passed on its own (``pack_ragged`` builds the container)
+                            container, every image computed as if it had been passed on its own (``pack_ragged`` builds the container);
+                            decode_prefill / decode_score / decode_attn / decode_set_key_mask run on a ragged session as on any other
 
 An engine is named by an integer id (operators take tensors and scalars only); ``register_engine`` hands one out.
 There is no CPU implementation: calling an operator on CPU tensors raises.
@@ -108,14 +109,15 @@ class Session:
     rows: int                               # rows of a decode_step / decode_prefill / decode_score / key mask
     src: torch.Tensor                       # what the session was opened on: kept alive while the engine may read it
     mask: Optional[torch.Tensor] = None     # the uint8 key mask handed to the engine, kept alive likewise
+    keys: Optional[int] = None              # N of the session where `src` does not say it: the slot stride Ns behind score_ragged (src = the container)
 
 
-def _open(e, rows: int, src: torch.Tensor) -> None:
+def _open(e, rows: int, src: torch.Tensor, keys: Optional[int] = None) -> None:
     """The one writer of ``e.session``, behind every entry point that leaves the engine with an open session (_call).  Invariant: whenever the
     engine's session is open, the record's ``rows`` equals the engine's ``ses.rows`` -- the operators size their outputs by it and the
     engine writes ``ses.rows`` rows into them.  Not the converse: the engine also closes a session on its own (a stop='row' generate
     that compacted) while the record stays; it then refuses the next step (TXO_E_STATE) before it writes anything."""
-    e.session = Session(int(rows), src)
+    e.session = Session(int(rows), src, keys=keys)
 
 
 def _close(e) -> None:
@@ -133,7 +135,7 @@ def session(e, op: str) -> Session:
 
 def _call(e, fn: str, *args, leaves: Optional[tuple] = None) -> None:
     """ONE entry point ``fn(handle, *args, stream)`` on the engine's device and torch's current stream; raises what _lib.check raises.
-    leaves: the engine's session behind an entry point that opens, replaces or closes it -- (rows, src): this one, open; (): none.
+    leaves: the engine's session behind an entry point that opens, replaces or closes it -- (rows, src[, keys]): this one, open; (): none.
     If such a call fails the engine's state is not known here and the record stays closed: the engine will say what it holds."""
     if leaves is not None:
         _close(e)
@@ -252,7 +254,10 @@ def _(tokens, engine):
 
 
 def _session_keys(e, ses: Session) -> int:
-    """N of the open session: the encoder rows it was opened on, or those of the images a generate call encoded itself"""
+    """N of the open session: the encoder rows it was opened on (a ragged session: the slot stride Ns), or those of the images a generate
+    call encoded itself"""
+    if ses.keys is not None:
+        return ses.keys
     src = ses.src
     return int(src.shape[1]) if src.ndim == 3 else e.dims.n_tokens(int(src.shape[2]), int(src.shape[3]))
 
@@ -479,6 +484,37 @@ def decode_begin_ragged(enc: torch.Tensor, n_tokens: torch.Tensor, engine: int) 
         raise ValueError("n_tokens must be an int32 CPU tensor of shape (B,)")
     n_tokens = n_tokens.contiguous()
     _call(e, "txo_decode_begin_ragged", enc.data_ptr(), enc.shape[0], enc.shape[1], _i32p(n_tokens), leaves=(enc.shape[0], enc))
+
+
+@custom_op("texocr::score_ragged", mutates_args=())
+def score_ragged(img: torch.Tensor, sizes: torch.Tensor, tokens: torch.Tensor, mask: Optional[torch.Tensor], engine: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """txo_score_ragged: container (B, C, Hc, Wc) + sizes (B, 2) int32 CPU, tokens (B, L) int64, mask (B, L) bool / uint8 (False = padding) or
+    None -> (logp, top1, top1_logp), each (B, L-1), row b what the fixed-shape pipeline gives image b on its own.  The ragged session stays open."""
+    e = _eng(engine, ready=True)
+    img, sizes = _ragged_args(img, sizes, e)
+    B, Cc, Hc, Wc = img.shape
+    tokens = _i64_dev(tokens, "tokens", e, B, 2, "(B, L) with one row per image")
+    L = int(tokens.shape[1])
+    if L < 2 or L - 1 > e.dims.max_len:
+        raise ValueError(f"tokens must have 2 <= L <= max_len + 1 = {e.dims.max_len + 1} columns, got {L}")
+    m8 = None
+    if mask is not None:
+        if tuple(mask.shape) != (B, L) or not mask.is_cuda:
+            raise ValueError("mask must be a GPU tensor of the shape of tokens")
+        m8 = mask.to(torch.uint8).contiguous()
+    logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    top1 = torch.empty((B, L - 1), device=tokens.device, dtype=torch.int64)
+    top1_logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    _call(e, "txo_score_ragged", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), tokens.data_ptr(), None if m8 is None else m8.data_ptr(), L,
+          logp.data_ptr(), top1.data_ptr(), top1_logp.data_ptr(), leaves=(B, img, int(ragged_tokens(sizes).max())))
+    return logp, top1, top1_logp
+
+
+@score_ragged.register_fake
+def _(img, sizes, tokens, mask, engine):
+    B, L = tokens.shape
+    return (tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1), dtype=torch.int64),
+            tokens.new_empty((B, L - 1), dtype=torch.float32))
 
 
 @decode_begin.register_fake

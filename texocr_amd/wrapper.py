@@ -34,6 +34,25 @@ def preprocess_image(img, patch: int = 16) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(g))[None]
 
 
+def cut_at_eos(row: List[int], eos: Optional[int]) -> List[int]:
+    """a generated row up to and including its first eos (the whole row if it has none)"""
+    return row[:row.index(eos) + 1] if eos is not None and eos in row else row
+
+
+def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What batch(return_align=True) hands to OCRModel.align_ragged: rows = every image's tokens, cut at its eos (the eos included) ->
+    (trg (B, L) int64 = [bos] + row padded with `pad` to the longest, mask (B, L) bool, False behind a row's own length).  Position p of
+    row b is the one that produced rows[b][p]."""
+    L = 1 + max(len(r) for r in rows)
+    trg = torch.full((len(rows), L), pad, dtype=torch.int64)
+    mask = torch.zeros((len(rows), L), dtype=torch.bool)
+    for b, r in enumerate(rows):
+        trg[b, 0] = bos
+        trg[b, 1:1 + len(r)] = torch.tensor(r, dtype=torch.int64)
+        mask[b, :1 + len(r)] = True
+    return trg, mask
+
+
 class TeXOCRWrapper:
     def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1):
         self.tokenizer = RegExTokenizer()
@@ -60,13 +79,15 @@ class TeXOCRWrapper:
         return x.contiguous()
 
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
-              seed: Optional[int] = None, return_logp: bool = False) -> List[tuple]:
+              seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
         window).  A sampled draw is keyed by (seed + chunk index, row of its chunk, position): with an explicit seed the result is
         reproducible and no two images of the list share a stream of draws.
-        return_logp=True: [(tokens, latex, logp)], logp the log-probability of every kept token (OCRModel.generate), cut as the tokens are."""
+        return_logp=True: [(tokens, latex, logp)], logp the log-probability of every kept token (OCRModel.generate), cut as the tokens are.
+        return_align=True appends to every tuple the maps (len(tokens), H_b/16, W_b/16) __call__(return_align=True) returns for that image,
+        from ONE OCRModel.align_ragged pass per chunk over [bos] + tokens (positions behind a row's eos are masked)."""
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
         out: List[tuple] = []
@@ -76,12 +97,16 @@ class TeXOCRWrapper:
             toks = self.model.generate_ragged(xs[c0:c0 + eng.max_batch], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
                                               return_logp=return_logp)
             toks, logp = toks if return_logp else (toks, None)
-            for b, row in enumerate(toks.tolist()):
-                if self.model.eos_token in row:
-                    row = row[:row.index(self.model.eos_token) + 1]
+            full = [cut_at_eos(row, self.model.eos_token) for row in toks.tolist()]
+            maps = None
+            if return_align:
+                trg, mask = align_inputs(full, self.model.bos_token, self.model.trg_pad_idx)
+                maps = [a.maps[0].cpu() for a in self.model.align_ragged(xs[c0:c0 + eng.max_batch], trg.cuda(), mask=mask.cuda())]
+            for b, row in enumerate(full):
                 row = row[:-1]                                                        # ocr_model.py:104 (drops the last token)
                 latex = process_output(self.tokenizer.decode(row))
-                out.append((row, latex, logp[b, :len(row)].tolist()) if return_logp else (row, latex))
+                item = (row, latex, logp[b, :len(row)].tolist()) if return_logp else (row, latex)
+                out.append((*item, maps[b][:len(row)]) if return_align else item)
         return out
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
