@@ -26,6 +26,18 @@ constexpr int EA_QBLK = 128, EA_KSTAGE = 64;
 
 __device__ inline int swz256(int row, int piece) { return row * 256 + ((piece ^ (row & 15)) << 4); }
 
+// 4 outputs of a row as TO (f32, or bf16 packed): enc_attn_kernel, attn_mq_kernel (through it, enc_attn_bf16_v2_kernel<., true> compiles to other instructions)
+template <typename TO> __device__ __forceinline__ void ea_store4(TO* dst, float4 v4) {
+    if constexpr (sizeof(TO) == 4) {
+        *reinterpret_cast<float4*>(dst) = v4;
+    } else {
+        union { bf16 h[4]; uint2 u; } t;
+        t.h[0] = __float2bfloat16(v4.x); t.h[1] = __float2bfloat16(v4.y);
+        t.h[2] = __float2bfloat16(v4.z); t.h[3] = __float2bfloat16(v4.w);
+        *reinterpret_cast<uint2*>(dst) = t.u;
+    }
+}
+
 // Block -> (batch*head, query block).  One-dimensional grid of 8 * ceil(nbh / 8) * nq workgroups: workgroups b and b + 8 run on one XCD
 // (round-robin dispatch), so the nq query blocks of ONE (image, head) go to ONE XCD and its L2 fetches that head's K / V panel once for
 // all of them.  (With the (query block, batch*head) grid the five query blocks of a head landed on five XCDs: every K / V panel crossed
@@ -218,14 +230,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__
             float4 v4 = *reinterpret_cast<const float4*>(&tile[qq * 64 + c0]);
             if constexpr (RAGGED) { if (qrow >= n) v4 = make_float4(0.f, 0.f, 0.f, 0.f); }
             TO* dst = out + ((size_t)(b * N + qrow)) * inner + head * DH + piece * 4;
-            if constexpr (sizeof(TO) == 4) {
-                *reinterpret_cast<float4*>(dst) = v4;
-            } else {
-                union { bf16 h[4]; uint2 u; } t;
-                t.h[0] = __float2bfloat16(v4.x); t.h[1] = __float2bfloat16(v4.y);
-                t.h[2] = __float2bfloat16(v4.z); t.h[3] = __float2bfloat16(v4.w);
-                *reinterpret_cast<uint2*>(dst) = t.u;
-            }
+            ea_store4<TO>(dst, v4);
         }
     }
 }

@@ -1551,11 +1551,13 @@ struct Engine : EngineBase {
     void launch_attn_mq(hipStream_t s, bool causal, const T* q, const T* k, const T* v, TO* out, int nb, int nq, int nk, int kv_rows,
                         const unsigned char* km = nullptr, const int* lens = nullptr) {
         const dim3 grid((nq + EA_QBLK - 1) / EA_QBLK, nb * cfg.dec_heads);
-        if (lens)                                             // cross attention of a ragged session: nk = lens[image], panels kv_rows apart
-            hipLaunchKernelGGL((attn_mq_kernel<T, TO, false, false, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads, nullptr, 0, lens);
-        else if (causal && km) hipLaunchKernelGGL((attn_mq_kernel<T, TO, true, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads, km, Tmax);
-        else if (causal) hipLaunchKernelGGL((attn_mq_kernel<T, TO, true>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
-        else hipLaunchKernelGGL((attn_mq_kernel<T, TO, false>), grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads);
+        if (!causal || lens) km = nullptr;                    // (only the causal self attention of a fixed-shape session reads the padding mask)
+        auto kern = attn_mq_kernel<T, TO, false, false, true>;   // lens: cross attention of a ragged session, nk = lens[image], panels kv_rows apart
+        if (!lens) {                                          // (assigned in the order the kernels have in the code object: see wide_min_rows)
+            if (causal) kern = km ? attn_mq_kernel<T, TO, true, true> : attn_mq_kernel<T, TO, true>;
+            else kern = attn_mq_kernel<T, TO, false>;
+        }
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, q, k, v, out, nq, nk, kv_rows, cfg.dec_heads, km, km ? Tmax : 0, lens);
     }
     // the probabilities behind a launch_attn_mq call, from the same q / k (attn_probs.h); MEAN: one map per image, the mean over the heads
     template <bool MEAN>
@@ -1564,15 +1566,14 @@ struct Engine : EngineBase {
         const int heads = cfg.dec_heads;
         const dim3 grid((nq + EA_QBLK - 1) / EA_QBLK, MEAN ? nb : nb * heads);
         const size_t lds = attn_probs_lds_bytes(MEAN ? heads : 1);
-        if constexpr (MEAN) {                                 // only the cross maps have a head mean: no causal form of it exists
-            if (lens) hipLaunchKernelGGL((attn_probs_kernel<T, false, false, true, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, nullptr, 0, lens);
-            else hipLaunchKernelGGL((attn_probs_kernel<T, false, false, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
-        } else {
-            if (lens) hipLaunchKernelGGL((attn_probs_kernel<T, false, false, false, true>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, nullptr, 0, lens);
-            else if (causal && km) hipLaunchKernelGGL((attn_probs_kernel<T, true, true, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, km, Tmax);
-            else if (causal) hipLaunchKernelGGL((attn_probs_kernel<T, true, false, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
-            else hipLaunchKernelGGL((attn_probs_kernel<T, false, false, false>), grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads);
+        if (MEAN) causal = false;                             // only the cross maps have a head mean: no causal form of it exists
+        if (!causal || lens) km = nullptr;
+        auto kern = attn_probs_kernel<T, false, false, MEAN, true>;   // lens: the cross maps of a ragged session
+        if (!lens) {
+            if constexpr (!MEAN) { if (causal) kern = km ? attn_probs_kernel<T, true, true, false> : attn_probs_kernel<T, true, false, false>; }
+            if (!causal) kern = attn_probs_kernel<T, false, false, MEAN>;
         }
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, q, k, out, nq, nk, kv_rows, heads, km, km ? Tmax : 0, lens);
     }
     int prefill(const int64_t* tokens, int tok_stride, int t, float* logits_out, float* last_logits, hipStream_t s, const ScoreOut* score = nullptr,
                 const AttnOut* attn = nullptr) {

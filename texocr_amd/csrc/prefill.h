@@ -251,14 +251,7 @@ __global__ __launch_bounds__(256) void attn_mq_kernel(const TI* __restrict__ Q, 
             const int c0 = (piece * 4) ^ ((qq & 7) << 2);
             const float4 v4 = *reinterpret_cast<const float4*>(&tile[qq * 64 + c0]);
             TO* dst = out + ((size_t)(b * nq + qrow)) * inner + head * DH + piece * 4;
-            if constexpr (sizeof(TO) == 4) {
-                *reinterpret_cast<float4*>(dst) = v4;
-            } else {
-                union { bf16 h[4]; uint2 u; } t;
-                t.h[0] = __float2bfloat16(v4.x); t.h[1] = __float2bfloat16(v4.y);
-                t.h[2] = __float2bfloat16(v4.z); t.h[3] = __float2bfloat16(v4.w);
-                *reinterpret_cast<uint2*>(dst) = t.u;
-            }
+            ea_store4<TO>(dst, v4);
         }
     }
 }
