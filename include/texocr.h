@@ -204,8 +204,10 @@ int txo_generate_beam(txo_engine* e, const float* img_dev, int32_t B, int32_t C,
  * a slot are never read by any of them: they may hold anything.  With the switch off -- the default, and the behaviour of every engine
  * before the switch existed -- those session calls, txo_score while a ragged session is open, and max_len > cfg.max_len are refused with
  * TXO_E_INVALID and a message naming ragged batches, so a caller that relied on the refusal still gets it.
- * Out of scope in either setting, each refused with TXO_E_INVALID and a message naming ragged batches: the hybrid front end; the latent
- * cross-attention form forced by TXO_LATENT=1.  Beam search and logits_out have no ragged entry point (the beam call takes one (H, W) and opens its own
+ * The hybrid ResNetV2 front end takes ragged batches only under txo_set_ragged_hybrid(e, 1) (below); off, the default, every ragged call on
+ * such an engine is refused with TXO_E_INVALID and a message naming ragged batches and the hybrid front end, as before that switch existed.
+ * Out of scope in every setting, refused with TXO_E_INVALID and a message naming ragged batches: the latent cross-attention form forced by
+ * TXO_LATENT=1.  Beam search and logits_out have no ragged entry point (the beam call takes one (H, W) and opens its own
  * session).  The container's width Wc must be a multiple of 4 (rows are read in 16-byte pieces).  The persistent launch is not taken: a
  * ragged generate runs one launch per stage (TXO_Q_LAST_PERSISTENT reads 0), and its session is closed when it returns.
  *
@@ -251,6 +253,15 @@ int txo_score_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, 
  * as they did before that form existed.  on = 1: they are accepted (see "Ragged batches" above).  Nothing else depends on it; fixed-shape
  * sessions are not affected. */
 int txo_set_ragged_forward(txo_engine* e, int32_t on);
+
+/* Ragged batches on the hybrid ResNetV2 front end (cfg.embed = TXO_EMBED_HYBRID), for the following calls on this engine.  on = 0
+ * (default): every ragged call answers TXO_E_INVALID ("ragged batches: the hybrid front end is not supported ..."), as it did before the
+ * backbone had a ragged form.  on = 1: txo_encode_ragged, txo_decode_begin_ragged, txo_generate_ragged[_logp] and txo_score_ragged are
+ * accepted and keep every promise of "Ragged batches" above: the backbone runs over the smallest box that holds every image of the batch
+ * with each convolution, pool and GroupNorm bounded by the image's OWN extent, so padding to a common size never enters a statistic.  That
+ * box's patch count must not exceed max_tokens - 1 (only a cfg.max_tokens below the canvas's can make it).  Any other value of `on`:
+ * TXO_E_INVALID.  Engines with the patch front end accept the call and are not affected. */
+int txo_set_ragged_hybrid(txo_engine* e, int32_t on);
 
 /* Token selection for the following decode steps / generate calls.  mode 0 (default): greedy argmax.  mode 1:
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits

@@ -92,6 +92,7 @@ struct EngineBase {
     size_t sample_lds_max = 65536;              // dynamic LDS the LDS-form sampler may ask for (init: the device's per-workgroup limit)
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
     bool rag_fwd = false;                       // txo_set_ragged_forward: the multi-position forward on ragged sessions and the ragged sliding window are accepted
+    bool rag_hybrid = false;                    // txo_set_ragged_hybrid: ragged batches are accepted on the hybrid front end (conv.h: the RAGGED forms)
     virtual int query(int what, int64_t* out) = 0;
     virtual int profile_enable(int on) = 0;
     virtual int profile_read(int kind, double* avg_ms, int64_t* count) = 0;
@@ -197,6 +198,7 @@ struct Engine : EngineBase {
     int32_t* rag_host = nullptr; hipEvent_t rag_ev = nullptr; bool rag_ev_pending = false;
     std::vector<int32_t> rag_stage;   // host scratch [3 Bmax] (sized at creation)
     bool last_ragged = false;         // TXO_Q_LAST_RAGGED
+    int rag_box[2] = {0, 0};          // the smallest H x W (multiples of 16) that holds every image of the last ragged batch
     // rag_fwd off (the default): these calls answer as they did before the forward had a ragged form
     int refuse_ragged_forward(const std::string& call) const {
         return fail(TXO_E_INVALID, call + ": not available on a ragged batch session unless txo_set_ragged_forward(e, 1) is in effect");
@@ -698,25 +700,37 @@ struct Engine : EngineBase {
         const int pad = std::max((*out - 1) * stride + (k - 1) + 1 - in, 0);
         *pad_lo = pad / 2;
     }
+    // A ragged batch on the backbone (conv.h: the RAGGED forms): hw = the images' patch grids (rag_hw of the chunk), mul = 16 / s at the
+    // resolution of the tensor in hand; H x W below is then the CONTAINER's grid at that resolution.  hw null: a fixed-shape batch.
+    struct RagExt { const int* hw = nullptr; int mul = 0; };
     template <typename TB>
-    void conv(hipStream_t s, const TB* in, const TB* w, TB* out, int B, int H, int W, int C, int OC, int k, int stride) {
+    void conv(hipStream_t s, const TB* in, const TB* w, TB* out, int B, int H, int W, int C, int OC, int k, int stride, RagExt rg = {}) {
         int OH, OW, pt, pl;
         same_pad(H, k, stride, &OH, &pt); same_pad(W, k, stride, &OW, &pl);
+        // (ragged: the container's sides are multiples of 16 like every image's, so pt / pl are each image's own; gn_hw = 0 -- see bk_gemm)
+        const int gn_in = rg.hw ? 0 : H * W, gn_out = rg.hw ? 0 : OH * OW;
         // a 1x1 stride-1 convolution on NHWC activations IS a plain row-major GEMM: [B*H*W][C] x [OC][C]^T -> (bf16 backbone) the 256x256
         // LDS-DMA kernel where the shape fits it (the bottlenecks' expanding convolutions, 256 / 512 / 1024 output channels)
         if (k == 1 && stride == 1) {
             if constexpr (std::is_same<TB, T>::value) gemm_plain(s, in, w, B * H * W, OC, C, EpiStore<T>{out, OC, nullptr});
-            else bk_gemm(s, LoadPlain<TB>{in, C}, w, B * H * W, OC, C, EpiStore<TB>{out, OC, nullptr}, H * W);
+            else bk_gemm(s, LoadPlain<TB>{in, C}, w, B * H * W, OC, C, EpiStore<TB>{out, OC, nullptr}, gn_in);
+            return;
+        }
+        if (rg.hw) {
+            LoadConv<TB, true> ld{in, rg.hw, rg.mul, H, W, C, stride, pt, pl, FastDiv(OH * OW), FastDiv(OW), FastDiv(C), FastDiv(k)};
+            bk_gemm(s, ld, w, B * OH * OW, OC, k * k * C, EpiStore<TB>{out, OC, nullptr}, gn_out);
             return;
         }
         LoadConv<TB> ld{in, H, W, C, stride, pt, pl, FastDiv(OH * OW), FastDiv(OW), FastDiv(C), FastDiv(k)};
-        bk_gemm(s, ld, w, B * OH * OW, OC, k * k * C, EpiStore<TB>{out, OC, nullptr}, OH * OW);
+        bk_gemm(s, ld, w, B * OH * OW, OC, k * k * C, EpiStore<TB>{out, OC, nullptr}, gn_out);
     }
     // a backbone GEMM in storage type TB.  fp32 backbone INSIDE the bf16 engine: fp32 operands split onto the bf16 matrix pipe
     // (gemm_split.h: ~2^-16 per product, 5x less matrix time than exact-f32 MFMA); everything else -- the fp32 parity engine first of all --
     // the exact kernel.  TXO_BACKBONE_EXACT=1 keeps the exact-f32 kernel in the bf16 engine too (A/B, tests).
     // gn_hw > 0: the output is the input of a GroupNorm over images of gn_hw pixels -- the split kernel then leaves the norm's partial sums
-    // behind (gemm_split.h: GnPart) and group_norm() skips its own pass over the tensor (gn_fused)
+    // behind (gemm_split.h: GnPart) and group_norm() skips its own pass over the tensor (gn_fused).  A RAGGED encode never asks for them
+    // (gn_hw = 0 from every caller): GnPart / gn_finish_tiles_kernel assume one HW for the whole batch and at most two images per row tile,
+    // and a container row tile mixes pixels inside and outside an extent.  Its statistics are the unfused, per-image ones of conv.h.
     bool gn_fused = false;
     float* gn_tiles = nullptr;        // [row tiles][2 halves][2 images][32 groups][2]
     template <typename TB, class ALoad, class Epi>
@@ -733,49 +747,64 @@ struct Engine : EngineBase {
         launch_gemm_big<TB>(s, ld, w, M, N, K, epi);
     }
     template <bool RELU, bool RES, typename TB>
-    void group_norm(hipStream_t s, const TB* x, const TB* res, TB* y, const GnW& g, int B, int HW, int C) {
+    void group_norm(hipStream_t s, const TB* x, const TB* res, TB* y, const GnW& g, int B, int HW, int C, RagExt rg = {}, int Wc = 0) {
+        if (rg.hw) {                                         // HW = the container's pixels per slot, Wc its width; sizes per image on the device
+            const int chunk_px = std::max(256, (HW + 63) / 64), nchunk = (HW + chunk_px - 1) / chunk_px;   // (the grid: no image has more chunks)
+            hipLaunchKernelGGL((gn_partial_kernel<TB, true>), dim3(nchunk, B), dim3(256), 0, s, x, gn_partial, HW, C, 0, rg.hw, rg.mul, Wc);
+            hipLaunchKernelGGL(gn_finish_kernel<true>, dim3(B), dim3(32), 0, s, gn_partial, gn_stats, nchunk, (double)(C / 32), rg.hw, rg.mul);
+            const size_t nvec = (size_t)B * HW * C / Elem<TB>::PER16;
+            hipLaunchKernelGGL((gn_apply_kernel<TB, RELU, RES, true>), dim3((nvec + 255) / 256), dim3(256), 0, s, x, res, y, gn_stats, g.g,
+                               g.b, HW, C, nvec, rg.hw, rg.mul, Wc);
+            return;
+        }
         if (gn_fused) {                                      // the convolution that wrote x left the partial sums per output tile (bk_gemm)
             gn_fused = false;
             hipLaunchKernelGGL(gn_finish_tiles_kernel, dim3(B), dim3(32), 0, s, gn_tiles, gn_stats, HW, (double)HW * (C / 32));
         } else {
             const int chunk_px = std::max(256, (HW + 63) / 64), nchunk = (HW + chunk_px - 1) / chunk_px;
-            hipLaunchKernelGGL((gn_partial_kernel<TB>), dim3(nchunk, B), dim3(256), 0, s, x, gn_partial, HW, C, chunk_px);
-            hipLaunchKernelGGL(gn_finish_kernel, dim3(B), dim3(32), 0, s, gn_partial, gn_stats, nchunk, (double)HW * (C / 32));
+            hipLaunchKernelGGL((gn_partial_kernel<TB>), dim3(nchunk, B), dim3(256), 0, s, x, gn_partial, HW, C, chunk_px, nullptr, 0, 0);
+            hipLaunchKernelGGL(gn_finish_kernel<false>, dim3(B), dim3(32), 0, s, gn_partial, gn_stats, nchunk, (double)HW * (C / 32), nullptr, 0);
         }
         const size_t nvec = (size_t)B * HW * C / Elem<TB>::PER16;
         hipLaunchKernelGGL((gn_apply_kernel<TB, RELU, RES>), dim3((nvec + 255) / 256), dim3(256), 0, s, x, res, y, gn_stats, g.g,
-                           g.b, HW, C, nvec);
+                           g.b, HW, C, nvec, nullptr, 0, 0);
     }
+    // H x W: the images' size; a ragged batch (hw = the chunk's patch grids): the size of the ACTIVATION container -- the smallest multiples of
+    // 16 that hold every image of the batch (ragged_batch: rag_box), never more than the canvas the workspaces are sized for -- while the
+    // image array itself is [B][1][Hi][Wi], the caller's container
     template <typename TB>
-    int backbone(Backbone<TB>& k, const float* img, int B, int H, int W, const TB** feat, hipStream_t s) {
+    int backbone(Backbone<TB>& k, const float* img, int B, int H, int W, const TB** feat, hipStream_t s, const int* hw = nullptr, int Hi = 0, int Wi = 0) {
         TB* const* act = k.act;
         int h1, w1, pt, pl;
         same_pad(H, 7, 2, &h1, &pt); same_pad(W, 7, 2, &w1, &pl);
-        bk_gemm(s, LoadStem<TB>{img, H, W, pt, pl, FastDiv(h1 * w1), FastDiv(w1)}, k.stem_w, B * h1 * w1, 64, 64, EpiStore<TB>{act[1], 64, nullptr}, h1 * w1);
-        group_norm<true, false>(s, (const TB*)act[1], (const TB*)nullptr, act[1], k.stem_gn, B, h1 * w1, 64);
+        if (hw) bk_gemm(s, LoadStem<TB, true>{img, hw, Hi, Wi, pt, pl, FastDiv(h1 * w1), FastDiv(w1)}, k.stem_w, B * h1 * w1, 64, 64, EpiStore<TB>{act[1], 64, nullptr});
+        else bk_gemm(s, LoadStem<TB>{img, H, W, pt, pl, FastDiv(h1 * w1), FastDiv(w1)}, k.stem_w, B * h1 * w1, 64, 64, EpiStore<TB>{act[1], 64, nullptr}, h1 * w1);
+        group_norm<true, false>(s, (const TB*)act[1], (const TB*)nullptr, act[1], k.stem_gn, B, h1 * w1, 64, RagExt{hw, 8}, w1);
         int hc, wc, ppt, ppl;
         same_pad(h1, 3, 2, &hc, &ppt); same_pad(w1, 3, 2, &wc, &ppl);
         {
             const size_t nvec = (size_t)B * hc * wc * 64 / Elem<TB>::PER16;
-            hipLaunchKernelGGL((maxpool3x3s2_kernel<TB>), dim3((nvec + 255) / 256), dim3(256), 0, s, act[1], act[0], h1, w1, 64,
-                               hc, wc, ppt, ppl, nvec);
+            auto pool = hw ? maxpool3x3s2_kernel<TB, true> : maxpool3x3s2_kernel<TB, false>;
+            hipLaunchKernelGGL(pool, dim3((nvec + 255) / 256), dim3(256), 0, s, act[1], act[0], h1, w1, 64, hc, wc, ppt, ppl, nvec, hw, 8);
         }
         TB* cur = act[0];
+        int mul = 4;                                          // 16 / stride of `cur` against the image (ragged extents)
         for (const BlockW<TB>& b : k.blocks) {                // Bottleneck.forward (resnet.py:143-149)
             const int ho = (hc + b.stride - 1) / b.stride, wo = (wc + b.stride - 1) / b.stride;
+            const RagExt ri{hw, mul}, ro{hw, mul / b.stride};
             const TB* res = cur;
             if (b.has_ds) {                                   // DownSample: 1x1 stride-s StdConv + GroupNorm (no act)
-                conv<TB>(s, cur, b.ds, act[1], B, hc, wc, b.cin, b.cout, 1, b.stride);
-                group_norm<false, false>(s, (const TB*)act[1], (const TB*)nullptr, act[1], b.nds, B, ho * wo, b.cout);
+                conv<TB>(s, cur, b.ds, act[1], B, hc, wc, b.cin, b.cout, 1, b.stride, ri);
+                group_norm<false, false>(s, (const TB*)act[1], (const TB*)nullptr, act[1], b.nds, B, ho * wo, b.cout, ro, wo);
                 res = act[1];
             }
-            conv<TB>(s, cur, b.c1, act[2], B, hc, wc, b.cin, b.mid, 1, 1);
-            group_norm<true, false>(s, (const TB*)act[2], (const TB*)nullptr, act[2], b.n1, B, hc * wc, b.mid);
-            conv<TB>(s, act[2], b.c2, act[3], B, hc, wc, b.mid, b.mid, 3, b.stride);
-            group_norm<true, false>(s, (const TB*)act[3], (const TB*)nullptr, act[3], b.n2, B, ho * wo, b.mid);
-            conv<TB>(s, act[3], b.c3, act[2], B, ho, wo, b.mid, b.cout, 1, 1);
-            group_norm<true, true>(s, (const TB*)act[2], res, act[0], b.n3, B, ho * wo, b.cout);   // relu(norm(x) + res)
-            cur = act[0]; hc = ho; wc = wo;
+            conv<TB>(s, cur, b.c1, act[2], B, hc, wc, b.cin, b.mid, 1, 1, ri);
+            group_norm<true, false>(s, (const TB*)act[2], (const TB*)nullptr, act[2], b.n1, B, hc * wc, b.mid, ri, wc);
+            conv<TB>(s, act[2], b.c2, act[3], B, hc, wc, b.mid, b.mid, 3, b.stride, ri);
+            group_norm<true, false>(s, (const TB*)act[3], (const TB*)nullptr, act[3], b.n2, B, ho * wo, b.mid, ro, wo);
+            conv<TB>(s, act[3], b.c3, act[2], B, ho, wo, b.mid, b.cout, 1, 1, ro);
+            group_norm<true, true>(s, (const TB*)act[2], res, act[0], b.n3, B, ho * wo, b.cout, ro, wo);   // relu(norm(x) + res)
+            cur = act[0]; hc = ho; wc = wo; mul /= b.stride;
         }
         if (hc != H / 16 || wc != W / 16) return fail(TXO_E_INVALID, "backbone output grid does not match H/16 x W/16");
         *feat = cur;
@@ -845,8 +874,25 @@ struct Engine : EngineBase {
         const int M = B * N, G = cfg.canvas_w / 16;
 
         hipLaunchKernelGGL(cls_rows_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, ex, cls, pos, B, N, D);
-        if (!hybrid) launch_patch_embed(s, ib, img);              // (a ragged batch is refused on the hybrid front end)
-        else {
+        if (!hybrid) launch_patch_embed(s, ib, img);
+        else if (ib.ragged) {
+            // (txo_set_ragged_hybrid.)  The backbone runs in container layout over the batch's bounding box (rag_box) and the projection packs
+            // image b's own grid into rows 1 .. n_b-1 of slot b; the container grid does not map onto a slot's padding rows, so those are zeroed here
+            const int* rhw = rag_hw + 2 * ib.first;
+            const int Hb = rag_box[0], Wb = rag_box[1], hwC = (Hb / 16) * (Wb / 16);
+            const size_t n4 = (size_t)M * (D / 4);
+            hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ex, ragged_tokens(ib), B, N, D / 4);
+            const EpiTokensRagged epi{ex, patch_b, pos, rhw, D, hwC, Wb / 16, N, G};
+            if (bk_fp32) {
+                const float* feat = nullptr;
+                if (int r = backbone<float>(bk32, img, B, Hb, Wb, &feat, s, rhw, H, W)) return r;
+                bk_gemm(s, LoadPlain<float>{feat, 1024}, (const float*)bk32.proj_w, B * hwC, D, 1024, epi);
+            } else {
+                const T* feat = nullptr;
+                if (int r = backbone<T>(bk, img, B, Hb, Wb, &feat, s, rhw, H, W)) return r;
+                gemm_plain(s, feat, patch_w, B * hwC, D, 1024, epi);
+            }
+        } else {
             if (bk_fp32) {
                 const float* feat = nullptr;
                 if (int r = backbone<float>(bk32, img, B, H, W, &feat, s)) return r;
@@ -909,7 +955,9 @@ struct Engine : EngineBase {
     }
     int ragged_refusals() {
         if (!ready) return fail(TXO_E_STATE, "weights not finalized");
-        if (hybrid) return fail(TXO_E_INVALID, "ragged batches: the hybrid front end is not supported (GroupNorm statistics and SAME padding are per image extent)");
+        if (hybrid && !rag_hybrid)
+            return fail(TXO_E_INVALID, "ragged batches: the hybrid front end is not supported (GroupNorm statistics and SAME padding are per image extent) "
+                                       "unless txo_set_ragged_hybrid(e, 1) is in effect");
         if (latent_ok && knobs.lat_mode == 1)
             return fail(TXO_E_INVALID, "ragged batches: the latent cross-attention form (TXO_LATENT=1) is not supported; a ragged decode runs in the K/V form");
         return 0;
@@ -924,13 +972,19 @@ struct Engine : EngineBase {
         if (Wc % 4) return fail(TXO_E_INVALID, "ragged batches: the container's width must be a multiple of 4 (rows are read in 16-byte pieces)");
         int Ns = 0;
         std::vector<int32_t>& st = rag_stage;
+        rag_box[0] = rag_box[1] = 0;
         for (int b = 0; b < B; ++b) {
             const int H = sizes[2 * b], W = sizes[2 * b + 1];
             if (int r = check_image_size("ragged batches: image " + std::to_string(b), " is ", H, W, Hc, Wc)) return r;
+            rag_box[0] = std::max(rag_box[0], H); rag_box[1] = std::max(rag_box[1], W);
             st[2 * b] = H / 16; st[2 * b + 1] = W / 16; st[2 * Bmax + b] = 1 + (H / 16) * (W / 16);
             Ns = std::max(Ns, st[2 * Bmax + b]);
         }
         if (Ns > Nmax) return fail(TXO_E_INVALID, "ragged batches: token count of the largest image exceeds engine max_tokens");
+        // (the backbone's workspaces hold max_tokens - 1 patches per image, and its container is the batch's bounding box)
+        if (hybrid && (rag_box[0] / 16) * (rag_box[1] / 16) > Nmax - 1)
+            return fail(TXO_E_INVALID, "ragged batches: the hybrid front end works on the smallest box that holds every image of the batch, and its "
+                                       "patch count exceeds engine max_tokens - 1");
         // one staged copy: [2 B] patch grids followed by [B] token counts
         for (int b = 0; b < B; ++b) st[2 * B + b] = st[2 * Bmax + b];
         if (int r = upload_i32(st.data(), rag_hw, 2 * B, rag_ntok, B, s)) return r;
@@ -2268,6 +2322,13 @@ int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint
         return fail(TXO_E_INVALID, "sampling: the vocabulary does not fit the sampler's LDS (vocab * 4 bytes per workgroup: txo_engine_query "
                                    "TXO_Q_SAMPLE_VOCAB_MAX)");
     e->impl->sample_mode = mode; e->impl->sample_topk = topk; e->impl->sample_temp = mode ? temp : 1.f; e->impl->sample_seed = seed;
+    return 0;
+}
+
+int txo_set_ragged_hybrid(txo_engine* e, int32_t on) {
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (on != 0 && on != 1) return fail(TXO_E_INVALID, "txo_set_ragged_hybrid: on must be 0 or 1");
+    e->impl->rag_hybrid = on != 0;
     return 0;
 }
 

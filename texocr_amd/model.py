@@ -98,6 +98,8 @@ class HipEngine:
             _lib.check(self.lib.txo_engine_create(C.byref(cfg), C.byref(h)))
         self.handle = h
         self.loaded = False
+        if getattr(self, "_ragged_hybrid", False):   # (a reload of the weights makes a new handle: the switch follows the engine object)
+            _lib.check(self.lib.txo_set_ragged_hybrid(h, 1))
         self._env_seen = self._txo_env()             # what the engine saw when it read its knobs
 
     @staticmethod
@@ -285,6 +287,20 @@ class HipEngine:
                 self.set_sampling(False)
             if stop == "row":
                 self.set_stop_mode("global")
+
+    @property
+    def ragged_hybrid(self) -> bool:
+        """txo_set_ragged_hybrid: ragged batches on the hybrid ResNetV2 front end.  False (the default): every ragged call of a hybrid
+        engine raises ValueError naming ragged batches and the hybrid front end, as before the backbone had a ragged form.  True: they run,
+        each image's convolutions and GroupNorm statistics bounded by its own extent.  No effect on the patch front end."""
+        return getattr(self, "_ragged_hybrid", False)
+
+    @ragged_hybrid.setter
+    def ragged_hybrid(self, on) -> None:
+        if on not in (False, True, 0, 1):
+            raise ValueError("ragged_hybrid must be False or True")
+        _lib.check(self.lib.txo_set_ragged_hybrid(self.handle, 1 if on else 0))
+        self._ragged_hybrid = bool(on)
 
     @contextlib.contextmanager
     def ragged_forward(self):
@@ -765,6 +781,16 @@ class OCRModel(nn.Module):
         self._engine._stale = True
         self.eval()
 
+    @property
+    def ragged_hybrid(self) -> bool:
+        """Build extension: accept ragged batches (forward_ragged, generate_ragged, score_ragged, align_ragged) on the hybrid front end
+        (HipEngine.ragged_hybrid); off by default."""
+        return self._engine.ragged_hybrid
+
+    @ragged_hybrid.setter
+    def ragged_hybrid(self, on) -> None:
+        self._engine.ragged_hybrid = on
+
     # ---- weights: the reference's state_dict layout, aliases included ----
     def _export_weights(self) -> Dict[str, torch.Tensor]:
         return dict(self.state_dict())
@@ -897,20 +923,23 @@ class OCRModel(nn.Module):
                                   "implements the generate() inference path only")
 
 
-def _assemble(dims: Dims, dtype: str, max_batch: int, max_tokens: int, device: torch.device) -> OCRModel:
+def _assemble(dims: Dims, dtype: str, max_batch: int, max_tokens: int, device: torch.device, ragged_hybrid: bool = False) -> OCRModel:
     eng = HipEngine(dims, dtype=dtype, max_batch=max_batch, max_tokens=max_tokens)
+    if ragged_hybrid:
+        eng.ragged_hybrid = True
     shared: Dict[str, nn.Parameter] = {}
     return OCRModel(VisionEncoder(eng, shared), AutoRegressiveDecoder(eng, shared), dims.bos, dims.eos, dims.pad, device)
 
 
-def create_model(config: dict, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0) -> OCRModel:
+def create_model(config: dict, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0, ragged_hybrid: bool = False) -> OCRModel:
     """create_model(config) (ocr_model.py:113-130).  As in the reference the model comes back with default-initialised
-    parameters; load_state_dict replaces them."""
+    parameters; load_state_dict replaces them.  ragged_hybrid=True (build extension): the model's ragged calls work on the hybrid
+    front end (OCRModel.ragged_hybrid)."""
     dims = Dims.from_config(config)
     device = torch.device(config.get("device", "cuda"))
     if device.type != "cuda":
         device = torch.device("cuda")
-    return _assemble(dims, dtype, max_batch, max_tokens, device)
+    return _assemble(dims, dtype, max_batch, max_tokens, device, ragged_hybrid)
 
 
 def model_from_dims(dims: Dims, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0) -> OCRModel:

@@ -54,7 +54,8 @@ def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.T
 
 
 class TeXOCRWrapper:
-    def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1):
+    def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False):
+        """ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)"""
         self.tokenizer = RegExTokenizer()
         self.tokenizer.load(config["tokenizer_path"])                                # ocr_model.py:74-75
         config = dict(config)
@@ -67,7 +68,7 @@ class TeXOCRWrapper:
             key = "decoder.net.pos_embedding.embedding.weight"
             if key in sd:                                                            # ocr_model.py:84-88: the checkpoint decides
                 config["max_length"] = int(sd[key].shape[0])
-        self.model: OCRModel = create_model(config, dtype=dtype, max_batch=max_batch)
+        self.model: OCRModel = create_model(config, dtype=dtype, max_batch=max_batch, ragged_hybrid=ragged_hybrid)
         if sd is not None:
             self.model.load_state_dict(sd)
         self.dims: Dims = self.model._engine.dims
