@@ -189,6 +189,39 @@ int txo_generate_beam(txo_engine* e, const float* img_dev, int32_t B, int32_t C,
                       int32_t max_len, int32_t eos, int64_t* tokens_out_dev, float* scores_out_dev,
                       int64_t* all_tokens_out_dev, int32_t* n_steps_out, void* stream);
 
+/* What txo_beam_search / txo_beam_search_ragged return (a BUILD EXTENSION like txo_generate_beam): every beam of every image with its
+ * score, its length and the log-probability of each of its tokens.  Device pointers; rows are (image, rank): row b * beams + i is the
+ * i-th best beam of image b.
+ *   tokens  int64 [B * beams][max_len], never NULL.  Columns 0 .. *n_steps_out - 1 are written, the rest is left as it was.
+ *   scores  float [B * beams] or NULL: the sum of the beam's log-probabilities, the value txo_generate_beam reports.
+ *   logp    float [B * beams][max_len] or NULL: logp[r][t] = log_softmax(logits)[tokens[r][t]] at the beam's own prefix -- the very float
+ *           the search added to the beam's score at position t, so the floats of a row summed left to right give scores[r] bit for bit.
+ *   lengths int32 [B * beams] or NULL: index of the beam's first eos + 1, or *n_steps_out if it has none (or eos < 0).
+ *           Behind a beam's length tokens hold eos and logp holds exactly 0.0f.
+ *   length_alpha  0: beams are ordered by score (txo_generate_beam's order).  > 0: the k beams of an image are ordered by
+ *           score / length^alpha, descending, ties in the search's order.  Only this final order: the search itself ranks by the
+ *           unnormalised score, so the SET of beams does not depend on length_alpha.  Negative or non-finite: TXO_E_INVALID. */
+typedef struct {
+    int64_t* tokens;
+    float*   scores;
+    float*   logp;
+    int32_t* lengths;
+    float    length_alpha;
+} txo_beam_out;
+
+/* txo_generate_beam's search (same loop, same bits for tokens and scores) with the outputs of txo_beam_out.  Refused with TXO_E_INVALID
+ * before anything is decoded: beams outside [1, 8], B * beams beyond cfg.max_batch or 32767, max_len outside [1, cfg.max_len], a
+ * positional table beyond 1024, out or out->tokens NULL, a bad length_alpha.  Leaves a session of one row per image, as txo_generate_beam. */
+int txo_beam_search(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t H, int32_t W, int32_t beams, int32_t max_len,
+                    int32_t eos, const txo_beam_out* out, int32_t* n_steps_out, void* stream);
+
+/* txo_beam_search over a ragged batch (below: txo_encode_ragged's container and sizes): one encode and one decode for B images of
+ * different sizes; the beams of image b are what txo_beam_search gives that image on its own, over the batch's *n_steps_out (behind
+ * the image's own step count its rows hold eos and 0.0f).  Every refusal of txo_beam_search and of a ragged batch (TXO_LATENT=1, the
+ * hybrid front end without txo_set_ragged_hybrid); runs in the K/V form; no session is open behind it. */
+int txo_beam_search_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
+                           int32_t beams, int32_t max_len, int32_t eos, const txo_beam_out* out, int32_t* n_steps_out, void* stream);
+
 /* ---- Ragged batches (a BUILD EXTENSION: the reference's callables take one (H, W) per batch) ------------------------------------
  * B images of DIFFERENT sizes in one call.  The container img_dev is float32 [B][C][Hc][Wc]; image b sits in the top-left
  * H_b x W_b corner of its slot, every side a positive multiple of 16, H_b <= min(Hc, canvas_h), W_b <= min(Wc, canvas_w).  Pixels

@@ -26,6 +26,11 @@ class TxoConfig(C.Structure):
         "enc_exp", "dec_exp", "vocab", "max_len", "bos", "eos", "pad", "dtype", "max_batch", "max_tokens")]
 
 
+class TxoBeamOut(C.Structure):
+    """txo_beam_out: device pointers (tokens never NULL) and the final ranking's length_alpha"""
+    _fields_ = [("tokens", C.c_void_p), ("scores", C.c_void_p), ("logp", C.c_void_p), ("lengths", C.c_void_p), ("length_alpha", C.c_float)]
+
+
 # every symbol include/texocr.h declares: (restype, argtypes)
 _P, _I, _I64P, _FP = C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p
 SYMBOLS = {
@@ -47,6 +52,9 @@ SYMBOLS = {
     "txo_generate_logp": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _FP, _P]),
     "txo_generate_from_enc_logp": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _FP, _P]),
     "txo_generate_beam": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I, _I64P, _FP, _I64P, C.POINTER(C.c_int32), _P]),
+    "txo_beam_search": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I, C.POINTER(TxoBeamOut), C.POINTER(C.c_int32), _P]),
+    "txo_beam_search_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(TxoBeamOut),
+                                         C.POINTER(C.c_int32), _P]),
     "txo_encode_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _FP, C.POINTER(C.c_int32), _P]),
     "txo_decode_begin_ragged": (C.c_int, [_P, _FP, _I, _I, C.POINTER(C.c_int32), _P]),
     "txo_generate_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _P]),

@@ -88,6 +88,9 @@ struct EngineBase {
     virtual int generate_beam(const float* img, const float* enc, int B, int C, int H, int W, int N, int beams, int max_len,
                               int eos, int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps,
                               hipStream_t s) = 0;
+    // txo_beam_search (sizes null: B images of H x W) / txo_beam_search_ragged (sizes: the container is H x W)
+    virtual int beam_search(const float* img, int B, int C, int H, int W, const int32_t* sizes, int beams, int max_len, int eos,
+                            const txo_beam_out* out, int* n_steps, hipStream_t s) = 0;
     int sample_mode = 0, sample_topk = 0; float sample_temp = 1.f; unsigned long long sample_seed = 0;
     size_t sample_lds_max = 65536;              // dynamic LDS the LDS-form sampler may ask for (init: the device's per-workgroup limit)
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
@@ -215,7 +218,8 @@ struct Engine : EngineBase {
     int last_ranges = 1;                                  // row ranges (streams) the last launch-path decode ran on
     // beam search state (rows = images * beams)
     float* bscore = nullptr; int* bfin = nullptr; short* bpath[2] = {nullptr, nullptr}; short* bparent = nullptr; int* btok = nullptr;
-    struct BeamCtx { int k; const short* path_cur; short* path_nxt; };
+    float* blogp = nullptr;                // [Tmax][Bmax] beside btok: the selected candidates' increments (txo_beam_search with logp)
+    struct BeamCtx { int k; const short* path_cur; short* path_nxt; bool logp = false; };   // logp: the step also records blogp
     // ----- profiling -----
     bool prof = false;                // full: per-launch cross-attention events + markers around every encode and step
     bool prof_cross = false;          // light: only the cross-attention dispatches carry events (no extra packets)
@@ -669,6 +673,7 @@ struct Engine : EngineBase {
         if (int r = dalloc(&bpath[1], (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&bparent, (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&btok, (size_t)Bmax * Tmax)) return r;
+        if (int r = dalloc(&blogp, (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&pctl, 1)) return r;
         if (int r = dalloc(&pstamps, (size_t)PS_TEAMS * PS_STAMP_RANKS * PS_MAX_STAGES * PS_STAMP_WORDS)) return r;
         return 0;
@@ -1467,8 +1472,9 @@ struct Engine : EngineBase {
                     logp_out ? logp_out + r0 * out_stride : nullptr};
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
-                        bparent + r0, btok + r0, Bmax, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
-            hipLaunchKernelGGL(beam_select_kernel, dim3(nb / bm->k), dim3(256), 0, s, ba);
+                        bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
+            if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
+            else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba);
         } else if (sample_mode) launch_sample_step(s, nb, sa);
         else hipLaunchKernelGGL(argmax_step_kernel, dim3(nb), dim3(64), 0, s, sa);
         dbg(s, "argmax");
@@ -2041,21 +2047,57 @@ struct Engine : EngineBase {
         return 0;
     }
 
-    int generate_beam(const float* img, const float* enc, int B, int C, int H, int W, int N, int beams, int max_len, int eos,
-                      int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps, hipStream_t s) override {
+    // ---- beam search: txo_generate_beam, txo_beam_search, txo_beam_search_ragged -- one loop (beam_common), two tails ----
+    // what all three refuse before anything is encoded or decoded
+    int beam_refusals(int B, int beams, int max_len) {
         if (beams < 1 || beams > 8) return fail(TXO_E_INVALID, "beams must be in [1, 8]");
         if (max_len < 1 || max_len > Tmax)
             return fail(TXO_E_INVALID, "max_len exceeds the decoder's max_length (a KV cache cannot slide the window)");
         if (Tmax > 1024) return fail(TXO_E_INVALID, "beam search supports max_length <= 1024");
-        const int rows = B * beams;
-        if (B < 1 || rows > Bmax || rows > 32767) return fail(TXO_E_INVALID, "images * beams exceeds engine max_batch");
-        if (img) {
-            if (int r = encode(img, B, C, H, W, eenc, s)) return r;
-            enc = eenc; N = 1 + (H / 16) * (W / 16);
+        if (B < 1 || B * beams > Bmax || B * beams > 32767) return fail(TXO_E_INVALID, "images * beams exceeds engine max_batch");
+        return 0;
+    }
+    // where a search's results go: txo_generate_beam's three buffers (best beam [B][max_len], scores, every beam), or a txo_beam_out
+    struct BeamSink { int64_t* best; float* scores; int64_t* all; const txo_beam_out* out; };
+    int generate_beam(const float* img, const float* enc, int B, int C, int H, int W, int N, int beams, int max_len, int eos,
+                      int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps, hipStream_t s) override {
+        if (int r = beam_refusals(B, beams, max_len)) return r;
+        ImageBatch ib;
+        if (img) if (int r = fixed_batch(B, C, H, W, &ib)) return r;
+        return beam_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, beams, max_len, eos,
+                           BeamSink{tokens_out, scores_out, all_tokens_out, nullptr}, n_steps, s);
+    }
+    int beam_search(const float* img, int B, int C, int H, int W, const int32_t* sizes, int beams, int max_len, int eos,
+                    const txo_beam_out* out, int* n_steps, hipStream_t s) override {
+        last_compactions = 0; last_ragged = false;                // (results of THIS call, also when it is refused, as generate(); txo_generate_beam
+                                                                  // leaves both as they were, as it always did)
+        if (int r = beam_refusals(B, beams, max_len)) return r;
+        if (!out || !out->tokens) return fail(TXO_E_INVALID, "beam search: null out / out->tokens");
+        {   // by its bits: the library is built with -fno-honor-nans, which lets a float comparison assume its operand is no NaN
+            uint32_t ab; memcpy(&ab, &out->length_alpha, sizeof ab);
+            const bool nonfinite = (ab & 0x7f800000u) == 0x7f800000u, negative = (ab >> 31) != 0 && (ab << 1) != 0;
+            if (nonfinite || negative) return fail(TXO_E_INVALID, "beam search: length_alpha must be finite and >= 0");
         }
+        ImageBatch ib;
+        if (int r = sizes ? ragged_batch(B, C, H, W, sizes, s, &ib) : fixed_batch(B, C, H, W, &ib)) return r;
+        last_ragged = ib.ragged;
+        return beam_common(&ib, img, B, ib.N, beams, max_len, eos, BeamSink{nullptr, nullptr, nullptr, out}, n_steps, s);
+    }
+    // `ib` and its images, or (ib null) the caller's encoder rows src [B][N][D]
+    int beam_common(const ImageBatch* ib, const float* src, int B, int N, int beams, int max_len, int eos, const BeamSink& sink,
+                    int* n_steps, hipStream_t s) {
+        const int rc = beam_impl(ib, src, B, N, beams, max_len, eos, sink, n_steps, s);
+        if (ib && ib->ragged) ses.open = false;                        // nothing ragged outlives the call (generate_common)
+        return rc;
+    }
+    int beam_impl(const ImageBatch* ib, const float* src, int B, int N, int beams, int max_len, int eos, const BeamSink& sink,
+                  int* n_steps, hipStream_t s) {
+        const int rows = B * beams;
+        if (ib) { if (int r = encode_batch(*ib, src, eenc, s)) return r; src = eenc; }
         // decode rows are (image, beam) slots for the length of this call: whatever way it ends, the session it leaves has one row per image
         struct Rows { Session& ses; ~Rows() { ses.rows = ses.images; } } restore{ses};
-        if (int r = begin_session(enc, B, N, eos, s, false, {}, beams)) return r;
+        // (a ragged session's key counts are per IMAGE: the k beams of an image share its cross K/V panel and its count, launch_dec_attn)
+        if (int r = begin_session(src, B, N, eos, s, false, KeyCounts{ib && ib->ragged ? rag_ntok : nullptr}, beams)) return r;
         choose_form(false, s);
         last_persist = false;
         // Two row ranges on two streams from 256 rows on, as generate() does beyond 128 images: one range's latency-bound projection
@@ -2076,10 +2118,11 @@ struct Engine : EngineBase {
         // same non-draining eos look as generate(): once every beam is finished further steps only repeat eos at no cost
         // (beam_select_kernel), so the few steps enqueued ahead of the look change neither scores nor slots.
         DonePoll poll{lanes, done_flag, Tmax, max_len};
+        const bool want_logp = sink.out && sink.out->logp;
         int cur = 0;
         auto beam_loop = [&]() -> int {
         for (int t = 0; t < max_len; ++t) {
-            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1]};
+            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1], want_logp};
             for (int i = 0; i < lanes.n; ++i)
                 if (int r2 = enqueue_step(lanes[i].stream, i, nullptr, 0, nullptr, nullptr, eos, &bm, t)) return r2;
             cur ^= 1;
@@ -2093,15 +2136,23 @@ struct Engine : EngineBase {
         if (int r = lanes.join(s)) return r;
         const int steps = poll.steps;
         lanes.split(rows, 1, s);
-        // backtrack every beam into tok_buf rows, then hand out the best beam (slot 0: selection order is by score)
-        hipLaunchKernelGGL(beam_backtrack_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, bparent, btok, Bmax, steps, rows,
-                           tok_buf, Tmax);
-        HIP_TRY(hipMemcpy2DAsync(tokens_out, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax * beams,
-                                 sizeof(int64_t) * steps, B, hipMemcpyDeviceToDevice, s));
-        if (all_tokens_out)
-            HIP_TRY(hipMemcpy2DAsync(all_tokens_out, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax,
-                                     sizeof(int64_t) * steps, rows, hipMemcpyDeviceToDevice, s));
-        if (scores_out) HIP_TRY(hipMemcpyAsync(scores_out, bscore, sizeof(float) * rows, hipMemcpyDeviceToDevice, s));
+        if (sink.out) {
+            // one workgroup per image: lengths, the final order, tokens and increments straight into the caller's rows (step.h)
+            const txo_beam_out& o = *sink.out;
+            BeamFinishArgs fa{bparent, btok, want_logp ? blogp : nullptr, Bmax, bscore, steps, beams, eos, o.length_alpha,
+                              o.tokens, o.logp, o.scores, o.lengths, max_len};
+            hipLaunchKernelGGL(beam_finish_kernel, dim3(B), dim3(64), 0, s, fa);
+        } else {
+            // backtrack every beam into tok_buf rows, then hand out the best beam (slot 0: selection order is by score)
+            hipLaunchKernelGGL(beam_backtrack_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, bparent, btok, Bmax, steps, rows,
+                               tok_buf, Tmax);
+            HIP_TRY(hipMemcpy2DAsync(sink.best, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax * beams,
+                                     sizeof(int64_t) * steps, B, hipMemcpyDeviceToDevice, s));
+            if (sink.all)
+                HIP_TRY(hipMemcpy2DAsync(sink.all, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax,
+                                         sizeof(int64_t) * steps, rows, hipMemcpyDeviceToDevice, s));
+            if (sink.scores) HIP_TRY(hipMemcpyAsync(sink.scores, bscore, sizeof(float) * rows, hipMemcpyDeviceToDevice, s));
+        }
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         if (n_steps) *n_steps = steps;
@@ -2311,6 +2362,18 @@ int txo_generate_beam(txo_engine* e, const float* img, int32_t B, int32_t C, int
     if (!e || !img || !tokens_out) return fail(TXO_E_INVALID, "null argument");
     return e->impl->generate_beam(img, nullptr, B, C, H, W, 0, beams, max_len, eos, tokens_out, scores_out, all_tokens_out, n_steps,
                                   (hipStream_t)stream);
+}
+
+int txo_beam_search(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t beams, int32_t max_len,
+                    int32_t eos, const txo_beam_out* out, int32_t* n_steps, void* stream) {
+    if (!e || !img) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->beam_search(img, B, C, H, W, nullptr, beams, max_len, eos, out, n_steps, (hipStream_t)stream);
+}
+
+int txo_beam_search_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes,
+                           int32_t beams, int32_t max_len, int32_t eos, const txo_beam_out* out, int32_t* n_steps, void* stream) {
+    if (!e || !img || !sizes) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->beam_search(img, B, C, Hc, Wc, sizes, beams, max_len, eos, out, n_steps, (hipStream_t)stream);
 }
 
 int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint64_t seed) {

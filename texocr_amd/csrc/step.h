@@ -489,11 +489,16 @@ struct BeamArgs {
     float* score; int* fin;               // [images*k] running log-prob, finished flag (updated in place)
     const short* path_cur; short* path_nxt; int path_stride;   // [rows][tmax] slot of every history position
     short* parent_hist; int* tok_hist; int hist_stride;        // [tmax][rows] back-pointers for the final backtrack
+    float* logp_hist;                     // [tmax][rows] beside tok_hist, or null (LOGP = false): the increment of the selected candidate (below)
     StepState* st; int* done_flag; int eos;
     int row0;                             // this row range's first row in the batch: every pointer above is the RANGE's (slots in `path` are range-local,
                                           // like the range's K/V base), only the back-pointers name rows of the whole batch (beam_backtrack_kernel)
 };
 
+// LOGP: also record logp_hist[t][slot] = the float that was added to the parent's score for the selected candidate, logits[j][v] - lse[j]
+// (exactly 0.0f where the parent was already finished), so that a beam's increments summed left to right in float give its score bit
+// for bit.  A template parameter: the <false> form is the kernel as it was (profiles/beam_select_logp_resource_usage.txt).
+template <bool LOGP>
 __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     constexpr int KMAX = 8;
     __shared__ float red[8], s_lse[KMAX], s_score[KMAX], selv[KMAX];
@@ -589,6 +594,14 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
                 a.score[row] = sv[r]; a.fin[row] = nf; a.cur_tok[row] = v;
                 a.tok_hist[(size_t)t * a.hist_stride + row] = v;
                 a.parent_hist[(size_t)t * a.hist_stride + row] = (short)(a.row0 + img * k + j);
+                if constexpr (LOGP) {
+                    // x[j][.] holds candidates by now and lives in another thread: the one logit is read again, and minus the same
+                    // lse[j] it is the very float the candidate was built from (never new score - old score: that is rounded twice)
+                    float lj = 0.f;
+#pragma unroll
+                    for (int q = 0; q < KMAX; ++q) if (q == j) lj = lse[q];
+                    a.logp_hist[(size_t)t * a.hist_stride + row] = fj ? 0.f : lg[(size_t)j * V + v] - lj;
+                }
             }
             const short* src = a.path_cur + (size_t)(img * k + j) * a.path_stride;
             short* dst = a.path_nxt + (size_t)(img * k + r) * a.path_stride;
@@ -659,6 +672,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
             a.score[row] = selv[r]; a.fin[row] = nf; a.cur_tok[row] = v;
             a.tok_hist[(size_t)t * a.hist_stride + row] = v;
             a.parent_hist[(size_t)t * a.hist_stride + row] = (short)(a.row0 + img * k + j);
+            if constexpr (LOGP) a.logp_hist[(size_t)t * a.hist_stride + row] = s_fin[j] ? 0.f : lg[sel] - s_lse[j];
         }
         // history slots of the new beam: the parent's, plus the parent's own slot for position t
         const short* src = a.path_cur + (size_t)(img * k + j) * a.path_stride;
@@ -694,6 +708,51 @@ __global__ void beam_backtrack_kernel(const short* parent_hist, const int* tok_h
     for (int t = n - 1; t >= 0; --t) {
         tokens_all[(size_t)row * out_stride + t] = tok_hist[(size_t)t * hist_stride + cur];
         cur = parent_hist[(size_t)t * hist_stride + cur];
+    }
+}
+
+// The tail of txo_beam_search / txo_beam_search_ragged (texocr.h: txo_beam_out): ONE workgroup per image, thread r < k owns the beam in
+// slot r.  Walk 1 follows the back-pointers for the beam's length (first eos + 1, or n), the k beams are ranked -- alpha > 0: descending
+// score / length^alpha, ties in slot order; alpha == 0: the search's own order --, walk 2 writes tokens (and the increments of logp_hist)
+// into the beam's output row.  Behind a beam's first eos the histories already hold eos and 0.0f (beam_select_kernel: a finished parent).
+// Columns n .. out_stride-1 are not written.
+struct BeamFinishArgs {
+    const short* parent_hist; const int* tok_hist; const float* logp_hist; int hist_stride;   // logp_hist: null when logp is
+    const float* score;                   // [images*k] final scores, in slot order
+    int n, k, eos; float alpha;
+    int64_t* tokens; float* logp; float* scores; int* lengths; int out_stride;   // rows of the caller; logp / scores / lengths may be null
+};
+__global__ __launch_bounds__(64) void beam_finish_kernel(BeamFinishArgs a) {
+    __shared__ float s_key[8];
+    const int img = blockIdx.x, r = threadIdx.x, k = a.k, row = img * k + r;
+    int len = a.n; float sc = 0.f;
+    if (r < k) {
+        int cur = row;
+        for (int t = a.n - 1; t >= 0; --t) {
+            const size_t h = (size_t)t * a.hist_stride + cur;
+            if (a.eos >= 0 && a.tok_hist[h] == a.eos) len = t + 1;
+            cur = a.parent_hist[h];
+        }
+        sc = a.score[row];
+        float key = a.alpha > 0.f ? sc / powf((float)len, a.alpha) : 0.f;
+        if ((__float_as_uint(key) & 0x7fffffffu) > 0x7f800000u) key = -INFINITY;      // (a NaN would compare false both ways: two beams, one row)
+        s_key[r] = key;
+    }
+    __syncthreads();
+    if (r >= k) return;
+    int dst = 0;
+    for (int q = 0; q < k; ++q) dst += (s_key[q] > s_key[r] || (s_key[q] == s_key[r] && q < r)) ? 1 : 0;
+    const int orow = img * k + dst;
+    if (a.scores) a.scores[orow] = sc;
+    if (a.lengths) a.lengths[orow] = len;
+    int64_t* tk = a.tokens + (size_t)orow * a.out_stride;
+    float* lp = a.logp ? a.logp + (size_t)orow * a.out_stride : nullptr;
+    int cur = row;
+    for (int t = a.n - 1; t >= 0; --t) {
+        const size_t h = (size_t)t * a.hist_stride + cur;
+        tk[t] = a.tok_hist[h];
+        if (lp) lp[t] = a.logp_hist[h];
+        cur = a.parent_hist[h];
     }
 }
 

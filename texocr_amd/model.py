@@ -251,6 +251,22 @@ class HipEngine:
             return allt[:, :n].reshape(img.shape[0], beams, n), scores
         return toks[:, :n]
 
+    def beam_search(self, src, beams: int, max_len: int, eos: Optional[int], return_logp: bool = False, length_alpha: float = 0.0):
+        """txo_beam_search (src a (B, C, H, W) tensor) / txo_beam_search_ragged (src a sequence of (C, H_b, W_b) tensors) ->
+        (tokens (B, beams, n), scores (B, beams), lengths (B, beams) int32, logp (B, beams, n) or None), best first per image."""
+        self._ensure()
+        args = (self.id, int(beams), int(max_len), -1 if eos is None else int(eos), bool(return_logp), float(length_alpha))
+        if isinstance(src, torch.Tensor):
+            B = src.shape[0]
+            toks, scores, lengths, logp, n = torch.ops.texocr.beam_search(src, *args)
+        else:
+            B = len(src)
+            box, sizes = ops.pack_ragged(src)
+            toks, scores, lengths, logp, n = torch.ops.texocr.beam_search_ragged(box, sizes, *args)
+        n = int(n.item())
+        return (toks[:, :n].reshape(B, beams, n), scores.reshape(B, beams), lengths.reshape(B, beams),
+                logp[:, :n].reshape(B, beams, n) if return_logp else None)
+
     def set_sampling(self, on: bool, temp: float = 1.0, seed: int = 0, threshold: float = 0.9) -> None:
         """on=True: the reference sampler (top-k with k = int((1 - threshold) * vocab), utils.py:85-91 -- 99 for
         vocab 1000 because of float rounding -- then softmax(/temp) and one multinomial draw, decoder.py:104-108)."""
@@ -487,6 +503,36 @@ def score_summary(logp: torch.Tensor, top1: torch.Tensor, top1_logp: torch.Tenso
     nll64 = -(torch.where(valid, logp, torch.zeros_like(logp)).double().sum(dim=1))
     hit = (top1 == trg[:, 1:].to(top1.device)) & valid
     return Score(logp, top1, top1_logp, valid, nll64.float(), (nll64.sum() / n).float(), (hit.sum().double() / n).float())
+
+
+class Beams(NamedTuple):
+    """What OCRModel.beam_search returns, the beams of every image best first: tokens (B, beams, n) int64; scores (B, beams) the sum of a
+    beam's log-probabilities; lengths (B, beams) int32, the index of the beam's first eos + 1, or n without one; logp (B, beams, n)
+    float32 or None, the log-probability of every token at the beam's own prefix -- the floats the search summed, left to right, into
+    scores.  Behind a beam's length tokens hold eos and logp holds 0."""
+    tokens: torch.Tensor
+    scores: torch.Tensor
+    lengths: torch.Tensor
+    logp: Optional[torch.Tensor]
+
+
+def check_beam_args(beams, max_len, length_alpha, n_images: int, table: int, max_batch: int) -> None:
+    """OCRModel.beam_search's refusals, before the engine is touched (ValueError): beams in [1, 8], max_len inside the positional table,
+    a finite length_alpha >= 0, images * beams within the engine's max_batch"""
+    if isinstance(beams, bool) or not isinstance(beams, int) or not 1 <= beams <= 8:
+        raise ValueError(f"beam search needs beams in [1, 8], got {beams!r}")
+    if isinstance(max_len, bool) or not isinstance(max_len, int) or max_len < 1:
+        raise ValueError(f"beam search needs max_len >= 1, got {max_len!r}")
+    if max_len > table:
+        raise ValueError(f"beam search needs max_len <= decoder.max_len ({table})")
+    if table > 1024:
+        raise ValueError(f"beam search needs decoder.max_len <= 1024, this decoder has {table}")
+    if isinstance(length_alpha, bool) or not isinstance(length_alpha, (int, float)) or not math.isfinite(length_alpha) or length_alpha < 0:
+        raise ValueError(f"beam search needs a finite length_alpha >= 0, got {length_alpha!r}")
+    if n_images < 1:
+        raise ValueError("beam search needs at least one image")
+    if n_images * beams > max_batch or n_images * beams > 32767:
+        raise ValueError(f"beam search needs images * beams <= the engine's max_batch ({min(max_batch, 32767)}), got {n_images} * {beams}")
 
 
 class Alignment(NamedTuple):
@@ -851,6 +897,25 @@ class OCRModel(nn.Module):
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
                                      stop=stop, pad=self.trg_pad_idx, return_logp=return_logp)
+
+    @torch.no_grad()
+    def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0) -> Beams:
+        """Build extension: the k = beams best sequences of every image, with score, length and (return_logp=True) the log-probability of
+        every token -> Beams.  src is a (B, C, H, W) tensor, or a sequence of (C, H_b, W_b) tensors of different sizes: those go
+        through ONE ragged encode and ONE decode, and the beams of image b are what beam_search(src[b][None]) returns, over the batch's n.
+        The search is generate(beam=k)'s (same tokens and scores); eos is the model's eos_token.  length_alpha > 0 orders an image's beams
+        by score / length ** length_alpha instead of by score -- the final order only, the set of beams does not depend on it.
+        Needs beams in [1, 8], max_len <= decoder.max_len and images * beams <= the engine's max_batch (ValueError otherwise)."""
+        if isinstance(src, torch.Tensor):
+            if src.ndim != 4:
+                raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
+            n_images = int(src.shape[0])
+        elif isinstance(src, (list, tuple)):
+            n_images = len(src)
+        else:
+            raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
+        check_beam_args(beams, max_len, length_alpha, n_images, self.decoder.max_len, self._engine.max_batch)
+        return Beams(*self._engine.beam_search(src, beams, max_len, self.eos_token, return_logp=return_logp, length_alpha=length_alpha))
 
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,

@@ -14,6 +14,9 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::generate          OCRModel.generate                         model/ocr_model.py:46-66
   texocr::generate_from_enc AutoRegressiveDecoder.generate            model/decoder.py:77-122
   texocr::generate_beam     (build extension, BASELINE config 5)
+  texocr::beam_search / beam_search_ragged
+                            (build extension) generate_beam's search returning every beam with its score, its length and the
+                            log-probability of each token, on a fixed batch or a ragged container (txo_beam_out)
   texocr::generate_logp / generate_from_enc_logp / generate_ragged_logp
                             (build extension) generate / generate_from_enc / generate_ragged that also return the log-probability
                             of every produced token, taken from the token selection itself (no second pass, no (B, T, V) tensor)
@@ -540,6 +543,65 @@ def generate_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len
 @generate_ragged.register_fake
 def _(img, sizes, engine, max_len, eos):
     return img.new_empty((img.shape[0], max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu")
+
+
+def _beam_outputs(img: torch.Tensor, beams: int, max_len: int, want_logp: bool, length_alpha: float):
+    """the four outputs of a beam search over img.shape[0] images and the txo_beam_out that names them"""
+    rows = img.shape[0] * int(beams)
+    toks = torch.empty((rows, max_len), device=img.device, dtype=torch.int64)
+    if os.environ.get("TXO_DEBUG_POISON"):      # tests: a column the engine returns as valid but never wrote shows as -7
+        toks.fill_(-7)
+    scores = torch.empty((rows,), device=img.device, dtype=torch.float32)
+    lengths = torch.empty((rows,), device=img.device, dtype=torch.int32)
+    logp = _logp_output(toks) if want_logp else torch.empty((0, max_len), device=img.device, dtype=torch.float32)
+    out = _lib.TxoBeamOut(toks.data_ptr(), scores.data_ptr(), logp.data_ptr() if want_logp else None, lengths.data_ptr(), float(length_alpha))
+    return toks, scores, lengths, logp, out
+
+
+@custom_op("texocr::beam_search", mutates_args=())
+def beam_search(img: torch.Tensor, engine: int, beams: int, max_len: int, eos: int, want_logp: bool,
+                length_alpha: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """txo_beam_search: (tokens (B*beams, max_len) of which the first n columns are valid, scores (B*beams,), lengths (B*beams,) int32,
+    logp (B*beams, max_len) or (0, max_len), n as an int64 CPU tensor of shape (1,)); row b * beams + i is the i-th best beam of image b."""
+    e = _eng(engine, ready=True)
+    img = _img_arg(img, e)
+    B, Cc, H, W = img.shape
+    toks, scores, lengths, logp, out = _beam_outputs(img, beams, max_len, want_logp, length_alpha)
+    n = C.c_int32(0)
+    _call(e, "txo_beam_search", img.data_ptr(), B, Cc, H, W, int(beams), int(max_len), int(eos), C.byref(out), C.byref(n),
+          leaves=(B, img))                      # one row per IMAGE, as behind txo_generate_beam
+    return toks, scores, lengths, logp, torch.tensor([n.value], dtype=torch.int64)
+
+
+@custom_op("texocr::beam_search_ragged", mutates_args=())
+def beam_search_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int, beams: int, max_len: int, eos: int, want_logp: bool,
+                       length_alpha: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """txo_beam_search_ragged: texocr::beam_search over a container (B, C, Hc, Wc) + sizes (B, 2) int32 CPU."""
+    e = _eng(engine, ready=True)
+    img, sizes = _ragged_args(img, sizes, e)
+    B, Cc, Hc, Wc = img.shape
+    toks, scores, lengths, logp, out = _beam_outputs(img, beams, max_len, want_logp, length_alpha)
+    n = C.c_int32(0)
+    _call(e, "txo_beam_search_ragged", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), int(beams), int(max_len), int(eos), C.byref(out),
+          C.byref(n), leaves=())                # nothing ragged outlives the call (engine.hip: beam_common)
+    return toks, scores, lengths, logp, torch.tensor([n.value], dtype=torch.int64)
+
+
+def _beam_fake(img, beams, max_len, want_logp):
+    rows = img.shape[0] * beams
+    return (img.new_empty((rows, max_len), dtype=torch.int64), img.new_empty((rows,), dtype=torch.float32),
+            img.new_empty((rows,), dtype=torch.int32), img.new_empty((rows if want_logp else 0, max_len), dtype=torch.float32),
+            torch.empty((1,), dtype=torch.int64, device="cpu"))
+
+
+@beam_search.register_fake
+def _(img, engine, beams, max_len, eos, want_logp, length_alpha):
+    return _beam_fake(img, beams, max_len, want_logp)
+
+
+@beam_search_ragged.register_fake
+def _(img, sizes, engine, beams, max_len, eos, want_logp, length_alpha):
+    return _beam_fake(img, beams, max_len, want_logp)
 
 
 @custom_op("texocr::generate_ragged_logp", mutates_args=())

@@ -6,7 +6,8 @@ Differences from the reference, all on the host side of the path:
     Grayscale(1) -> Invert) WITHOUT the train-time ``RandomAffine``; torchvision is not needed;
   * images whose sides are not multiples of 16 are padded (bottom/right, background = 0 after inversion); the
     reference relies on the dataset renderer having padded them already (render_data.py:81-92);
-  * ``decode`` selects the reference's sampler ('sample', its default, temp 0.3) or greedy;
+  * ``decode`` selects the reference's sampler ('sample', its default, temp 0.3), greedy, or 'beam' (build extension: the best of
+    ``beams`` beams, OCRModel.beam_search);
   * ``max_len`` is passed through unchanged (default 350, ocr_model.py:94): beyond the positional table the decoder
     slides its window as the reference does.
 """
@@ -37,6 +38,15 @@ def preprocess_image(img, patch: int = 16) -> torch.Tensor:
 def cut_at_eos(row: List[int], eos: Optional[int]) -> List[int]:
     """a generated row up to and including its first eos (the whole row if it has none)"""
     return row[:row.index(eos) + 1] if eos is not None and eos in row else row
+
+
+def beam_chunk(max_batch: int, beams: int) -> int:
+    """images per beam-search call of batch(decode='beam'): every image takes `beams` of the engine's max_batch decode rows"""
+    if isinstance(beams, bool) or not isinstance(beams, int) or not 1 <= beams <= 8:
+        raise ValueError(f"decode='beam' needs beams in [1, 8], got {beams!r}")
+    if max_batch < beams:
+        raise ValueError(f"decode='beam' with beams={beams} needs a wrapper created with max_batch >= {beams} (it has {max_batch})")
+    return max_batch // beams
 
 
 def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -79,8 +89,18 @@ class TeXOCRWrapper:
             x = x.expand(self.dims.in_channels, -1, -1)
         return x.contiguous()
 
+    def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool):
+        """decode='beam': one OCRModel.beam_search over the images xs (a (B, C, H, W) tensor or a list of (C, H_b, W_b)) -> per image
+        (the best beam's tokens up to and including its eos, their log-probabilities or None)"""
+        res = self.model.beam_search(xs, beams, max_len, return_logp=return_logp, length_alpha=length_alpha)
+        lengths = res.lengths[:, 0].tolist()
+        rows = [res.tokens[b, 0, :n].tolist() for b, n in enumerate(lengths)]
+        logp = [res.logp[b, 0, :n].tolist() for b, n in enumerate(lengths)] if return_logp else [None] * len(rows)
+        return rows, logp
+
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
-              seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False) -> List[tuple]:
+              seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
+              length_alpha: float = 0.0) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -88,39 +108,55 @@ class TeXOCRWrapper:
         reproducible and no two images of the list share a stream of draws.
         return_logp=True: [(tokens, latex, logp)], logp the log-probability of every kept token (OCRModel.generate), cut as the tokens are.
         return_align=True appends to every tuple the maps (len(tokens), H_b/16, W_b/16) __call__(return_align=True) returns for that image,
-        from ONE OCRModel.align_ragged pass per chunk over [bos] + tokens (positions behind a row's eos are masked)."""
+        from ONE OCRModel.align_ragged pass per chunk over [bos] + tokens (positions behind a row's eos are masked).
+        decode='beam': every image's best beam of `beams` (OCRModel.beam_search, ranked with length_alpha), from ONE ragged beam search
+        per chunk of max_batch // beams images; temp and seed play no part.  A max_batch below beams is a ValueError."""
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
+        step = beam_chunk(eng.max_batch, beams) if decode == "beam" else eng.max_batch
         out: List[tuple] = []
         xs = [self._tensor(im).cuda() for im in imgs]
-        for c0 in range(0, len(xs), eng.max_batch):
-            chunk_seed = None if seed is None else int(seed) + c0 // eng.max_batch
-            toks = self.model.generate_ragged(xs[c0:c0 + eng.max_batch], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
-                                              return_logp=return_logp)
-            toks, logp = toks if return_logp else (toks, None)
-            full = [cut_at_eos(row, self.model.eos_token) for row in toks.tolist()]
+        for c0 in range(0, len(xs), step):
+            if decode == "beam":
+                full, logp = self._best_beams(xs[c0:c0 + step], beams, max_len, length_alpha, return_logp)
+            else:
+                chunk_seed = None if seed is None else int(seed) + c0 // step
+                toks = self.model.generate_ragged(xs[c0:c0 + step], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
+                                                  return_logp=return_logp)
+                toks, logp = toks if return_logp else (toks, None)
+                full = [cut_at_eos(row, self.model.eos_token) for row in toks.tolist()]
+                logp = logp.tolist() if return_logp else None
             maps = None
             if return_align:
                 trg, mask = align_inputs(full, self.model.bos_token, self.model.trg_pad_idx)
-                maps = [a.maps[0].cpu() for a in self.model.align_ragged(xs[c0:c0 + eng.max_batch], trg.cuda(), mask=mask.cuda())]
+                maps = [a.maps[0].cpu() for a in self.model.align_ragged(xs[c0:c0 + step], trg.cuda(), mask=mask.cuda())]
             for b, row in enumerate(full):
                 row = row[:-1]                                                        # ocr_model.py:104 (drops the last token)
                 latex = process_output(self.tokenizer.decode(row))
-                item = (row, latex, logp[b, :len(row)].tolist()) if return_logp else (row, latex)
+                item = (row, latex, logp[b][:len(row)]) if return_logp else (row, latex)
                 out.append((*item, maps[b][:len(row)]) if return_align else item)
         return out
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
-                 seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False) -> tuple:
+                 seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
+                 length_alpha: float = 0.0) -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
-        [bos] + tokens behind the generate.  Not available once the output outgrew the positional table (the window has slid)."""
+        [bos] + tokens behind the generate.  Not available once the output outgrew the positional table (the window has slid).
+        decode='beam' (build extension): the best of `beams` beams (OCRModel.beam_search, ranked with length_alpha), cut at its eos;
+        max_len is capped at the positional table; temp and seed play no part."""
         x = self._tensor(img)[None].cuda()
-        # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
-        # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
-        toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp)
-        toks, logp = toks if return_logp else (toks, None)
+        if decode == "beam":
+            beam_chunk(self.model._engine.max_batch, beams)
+            rows, lps = self._best_beams(x, beams, min(int(max_len), self.dims.max_len), length_alpha, return_logp)
+            toks = torch.tensor(rows, dtype=torch.int64, device=x.device)
+            logp = torch.tensor(lps, dtype=torch.float32) if return_logp else None   # (every float32 is exact in the list's doubles)
+        else:
+            # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
+            # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
+            toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp)
+            toks, logp = toks if return_logp else (toks, None)
         out_tokens = toks.squeeze(0).tolist()[:-1]                                   # ocr_model.py:104 (drops the EOS)
         latex = process_output(self.tokenizer.decode(out_tokens))                    # :105-108
         out = (out_tokens, latex, logp.squeeze(0)[:len(out_tokens)].tolist()) if return_logp else (out_tokens, latex)
