@@ -16,5 +16,9 @@ int main(void) {
     txo_engine* e = NULL;
     int rc = txo_engine_create(&cfg, &e);
     printf("create with embed_dim=250 -> %d (%s)\n", rc, txo_last_error());
-    return rc == TXO_E_INVALID ? 0 : 1;
+    /* a prompted decode checks its pointers before it looks at the engine: the same protocol without one */
+    int32_t n = 0;
+    int rp = txo_generate_prefix(NULL, NULL, 1, 3, 224, 672, NULL, 4, NULL, 16, cfg.eos, NULL, &n, NULL, NULL, NULL);
+    printf("generate_prefix without an engine => %d (%s)\n", rp, txo_last_error());
+    return rc == TXO_E_INVALID && rp == TXO_E_INVALID ? 0 : 1;
 }

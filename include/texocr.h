@@ -179,6 +179,45 @@ int txo_generate_from_enc_logp(txo_engine* e, const float* enc_dev, int32_t B, i
                                int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out, float* logits_out_dev,
                                float* logp_out_dev, void* stream);
 
+/* Prompted decode -- AutoRegressiveDecoder.generate(start_tokens of any length T, ...) (decoder.py:77-122), with a BUILD EXTENSION: a
+ * length per row.  The loop of txo_generate continues a caller's token prefix instead of starting at BOS, with everything that loop has:
+ * captured steps, row ranges, TXO_STOP_ROW with live-row compaction, either cross-attention form, the sampler, ragged batches.
+ *   prefix_dev      int64 [B][P] on the device.  prefix[b][0] need not be BOS.  Ids outside the vocabulary are forced into it (as
+ *                   txo_decode_score does).
+ *   prefix_len_host int32 [B] on the HOST, or NULL = every row has length P.  1 <= len_b <= P; columns of row b at and behind len_b are
+ *                   never read.  m = min_b len_b, M = max_b len_b.
+ * Positions 0 .. m-2 are computed by ONE multi-position pass (txo_decode_prefill's, without logits; nothing when m == 1); the loop then
+ * decodes positions t = m-1 .. M+max_len-2.  At position t a row with t + 1 < len_b commits prefix[b][t+1] as its next token -- no arg-max
+ * or draw decides, no output column is written, a sampled decode consumes no draw (draws stay keyed by (seed; row, position)) -- and any
+ * other row's pick goes to output column j = t + 1 - len_b if j < max_len.  So column j of row b is the j-th token behind row b's OWN
+ * prefix; with equal lengths the result is the reference's output[:, T:].
+ *   tokens_out_dev  int64 [B][max_len]; *n_steps_out (HOST) = min(max_len, t_last + 2 - m) valid columns, t_last the last position decoded.
+ *                   A column a longer-prefix row did not reach holds cfg.pad (and 0.0 in logp).
+ *   logp_out_dev    float [B][max_len] or NULL: txo_generate_logp's log-probabilities of the output columns.
+ *   prefix_logp_out_dev float [B][P] or NULL: prefix_logp[b][i] = the log-probability of prefix[b][i] given what precedes it, for the
+ *                   tokens the loop forced (m <= i < len_b), computed as (logit[forced] - row max) - log sum exp: where the forced token
+ *                   is the arg-max it is bit for bit the float txo_generate_logp reports.  Exactly 0.0 for i < m (the multi-position pass
+ *                   does not score), for i >= len_b, and for positions an eos break left undecoded.  Under TXO_STOP_ROW also for every
+ *                   column of a row whose prefix holds eos: such a row is finished from the start, nothing is scored for it (under
+ *                   TXO_STOP_GLOBAL it is scored like any other).
+ * eos: a row counts as containing eos from the start if prefix[b][:len_b] holds it (decoder.py:115 tests the whole output); the global
+ * break fires after the first position at which every row contains eos.  TXO_STOP_ROW: columns behind a row's first eos -- every column
+ * if the prefix holds one -- are cfg.pad and 0.0.
+ * Refused with TXO_E_INVALID before anything is encoded (messages name the prefix): len_b outside [1, P]; M - 1 + max_len > cfg.max_len (a
+ * prompted decode does not slide the window); m - 1 beyond the multi-position pass's workspace (max_batch * max_tokens rows).  There is no
+ * logits_out.  Runs one launch per stage (TXO_Q_LAST_PERSISTENT reads 0), never with the latent self-attention history.
+ * Synchronises the stream before returning; leaves the session generate leaves (none behind the ragged call). */
+int txo_generate_prefix(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t H, int32_t W, const int64_t* prefix_dev, int32_t P,
+                        const int32_t* prefix_len_host, int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out,
+                        float* logp_out_dev, float* prefix_logp_out_dev, void* stream);
+int txo_generate_prefix_from_enc(txo_engine* e, const float* enc_dev, int32_t B, int32_t N, const int64_t* prefix_dev, int32_t P,
+                                 const int32_t* prefix_len_host, int32_t max_len, int32_t eos, int64_t* tokens_out_dev, int32_t* n_steps_out,
+                                 float* logp_out_dev, float* prefix_logp_out_dev, void* stream);
+/* ... over a ragged batch (below: txo_encode_ragged's container and sizes), with every refusal of a ragged batch. */
+int txo_generate_prefix_ragged(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes_host,
+                               const int64_t* prefix_dev, int32_t P, const int32_t* prefix_len_host, int32_t max_len, int32_t eos,
+                               int64_t* tokens_out_dev, int32_t* n_steps_out, float* logp_out_dev, float* prefix_logp_out_dev, void* stream);
+
 /* Beam search over txo_generate's loop -- a BUILD EXTENSION: the reference has no beam search (BASELINE config 5 asks for
  * k = 5), so parity is anchored only at beams = 1 (== greedy).  Score = sum of log_softmax(logits) of the chosen tokens
  * (not length-normalised); a beam that has emitted eos is finished and continues with eos at no cost; the loop stops when

@@ -51,6 +51,10 @@ SYMBOLS = {
     "txo_generate_from_enc": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
     "txo_generate_logp": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _FP, _P]),
     "txo_generate_from_enc_logp": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _FP, _P]),
+    "txo_generate_prefix": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _FP, _P]),
+    "txo_generate_prefix_from_enc": (C.c_int, [_P, _FP, _I, _I, _I64P, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _FP, _P]),
+    "txo_generate_prefix_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I64P, _I, C.POINTER(C.c_int32), _I, _I, _I64P,
+                                             C.POINTER(C.c_int32), _FP, _FP, _P]),
     "txo_generate_beam": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I, _I64P, _FP, _I64P, C.POINTER(C.c_int32), _P]),
     "txo_beam_search": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I, _I, _I, C.POINTER(TxoBeamOut), C.POINTER(C.c_int32), _P]),
     "txo_beam_search_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(TxoBeamOut),

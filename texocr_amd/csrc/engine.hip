@@ -44,6 +44,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "score.h"
 #include "rows.h"
 #include "step.h"
+#include "step_prefix.h"   // (behind every other kernel: the kernels above keep their places in the code object)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -85,6 +86,10 @@ struct EngineBase {
     virtual int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) = 0;
     virtual int generate(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
                          int64_t* tokens_out, int* n_steps, float* logits_out, float* logp_out, hipStream_t s) = 0;
+    // txo_generate_prefix (img, sizes null) / _from_enc (enc, N) / _ragged (img, sizes: the container is H x W)
+    virtual int generate_prefix(const float* img, const float* enc, const int32_t* sizes, int B, int C, int H, int W, int N, const int64_t* prefix,
+                                int P, const int32_t* prefix_len, int max_len, int eos, int64_t* tokens_out, int* n_steps, float* logp_out,
+                                float* prefix_logp_out, hipStream_t s) = 0;
     virtual int generate_beam(const float* img, const float* enc, int B, int C, int H, int W, int N, int beams, int max_len,
                               int eos, int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps,
                               hipStream_t s) = 0;
@@ -209,6 +214,10 @@ struct Engine : EngineBase {
     Stamps stamps;                    // TXO_STAMPS / TXO_PSTAMPS diagnostics (stamps.h)
     int64_t* tok_buf = nullptr;            // [Bmax][Tmax] generated ids (engine-owned so graphs do not bake user pointers)
     float* logp_buf = nullptr;             // [Bmax][Tmax] their log-probabilities, for a captured step that carries them (generate_impl)
+    // prompted decode (step_prefix.h): the caller's prefix [Bmax][Tmax] with ids forced into the vocabulary, its per-row lengths [Bmax], and the forced
+    // tokens' log-probabilities [Bmax][Tmax] -- engine-owned, so that a captured step can carry them
+    int64_t* ftab = nullptr; int* flen = nullptr; float* fplogp = nullptr;
+    int prefix_cols = 0;                   // StepArgs::out_cols of the running prompted decode
     Session ses;                           // the open decode session (session.h)
     // persistent decode launch (persist.h): control block (device + pinned host copy), per-stage stamps of one position
     PersistCtl* pctl = nullptr; PersistCtl* pctl_host = nullptr; unsigned long long* pstamps = nullptr;
@@ -594,6 +603,10 @@ struct Engine : EngineBase {
                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sample_lds_max) != hipSuccess) {
                 (void)hipGetLastError(); sample_lds_max = 65536;
             }
+            if (sample_lds_max > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_prefix_step_kernel<false>),   // (its prompted form)
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sample_lds_max) != hipSuccess) {
+                (void)hipGetLastError(); sample_lds_max = 65536;
+            }
         }
         {
             bool exists = (D == 64 && la_supported<T, 64>()) || (D == 256 && la_supported<T, 256>()) || (D == 768 && la_supported<T, 768>());
@@ -667,6 +680,9 @@ struct Engine : EngineBase {
         if (int r = dalloc(&st, MAXL)) return r;
         if (int r = dalloc(&tok_buf, (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&logp_buf, (size_t)Bmax * Tmax)) return r;
+        if (int r = dalloc(&ftab, (size_t)Bmax * Tmax)) return r;
+        if (int r = dalloc(&flen, (size_t)Bmax)) return r;
+        if (int r = dalloc(&fplogp, (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&bscore, (size_t)Bmax)) return r;
         if (int r = dalloc(&bfin, (size_t)Bmax)) return r;
         if (int r = dalloc(&bpath[0], (size_t)Bmax * Tmax)) return r;
@@ -1068,10 +1084,16 @@ struct Engine : EngineBase {
     }
 
     int abandon_lanes(hipStream_t s, int rc) { stamps.slot = -1; return lanes.abandon(s, ses.images, rc); }
-    void reset_lanes(hipStream_t s, int eos) {
+    // start_m > 0: a prompted decode -- every range starts at position start_m - 1, fed from the prefix table (step_prefix.h)
+    void reset_lanes(hipStream_t s, int eos, int start_m = 0) {
         for (int i = 0; i < lanes.n; ++i) {
             const LaneSet::Lane& ln = lanes[i];
             const int n = ln.nb > Tmax ? ln.nb : Tmax;
+            if (start_m > 0) {
+                (void)hipMemsetAsync(st + i, 0, sizeof(StepState), s);
+                hipLaunchKernelGGL(prefix_start_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st + i, cur_tok + ln.b0, eos_seen + ln.b0,
+                                   done_flag + (size_t)i * Tmax, ln.nb, Tmax, eos, ftab + (size_t)ln.b0 * Tmax, Tmax, flen + ln.b0, start_m);
+            } else
             hipLaunchKernelGGL(reset_state_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st + i, cur_tok + ln.b0,
                                eos_seen + ln.b0, done_flag + (size_t)i * Tmax, ln.nb, Tmax, cfg.bos, eos);
             if (ses.row_stop) hipLaunchKernelGGL(iota_kernel, dim3((ln.nb + 255) / 256), dim3(256), 0, s, row_map + ln.b0, ln.nb, ln.b0);
@@ -1470,12 +1492,16 @@ struct Engine : EngineBase {
                     done_flag + (size_t)li * Tmax, eos, sample_topk, 1.0f / sample_temp, sample_seed, (int)r0,
                     ses.row_stop ? 1 : 0, ses.row_stop ? row_map + r0 : nullptr,
                     logp_out ? logp_out + r0 * out_stride : nullptr};
+        if (ses.forced) {   // prompted decode: the range's slices of the prefix table, indexed through row_map like the outputs
+            sa.forced = ftab + r0 * Tmax; sa.forced_stride = Tmax; sa.forced_len = flen + r0; sa.out_cols = prefix_cols; sa.prefix_logp = fplogp + r0 * Tmax;
+        }
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
             if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
             else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba);
-        } else if (sample_mode) launch_sample_step(s, nb, sa);
+        } else if (ses.forced) launch_prefix_step(s, nb, sa, sample_mode != 0);
+        else if (sample_mode) launch_sample_step(s, nb, sa);
         else hipLaunchKernelGGL(argmax_step_kernel, dim3(nb), dim3(64), 0, s, sa);
         dbg(s, "argmax");
         if (prof) { (void)hipEventRecord(e1, s); ev_step.push_back({e0, e1}); }
@@ -1724,6 +1750,7 @@ struct Engine : EngineBase {
         if (sample_mode && V > 64 * SR_PER) return false;
         if (prof || prof_cross || g_dbg || knobs.run.stamps || knobs.run.graph >= 0 || knobs.run.lanes > 0) return false;
         if (ses.ragged) return false;                                 // a ragged batch decodes with launches (persist.h has no per-row key count)
+        if (ses.forced) return false;                                 // so does a prompted decode (persist.h starts at BOS and forces nothing)
         if (cfg.dec_exp != 4 || cfg.dec_layers > PS_MAXLD) return false;
         const bool exists = (D == 256 && cfg.dec_heads == 8) || (D == 768 && cfg.dec_heads == 12 && sizeof(T) == 2);
         if (!exists) return false;
@@ -1845,19 +1872,57 @@ struct Engine : EngineBase {
         if (img) if (int r = fixed_batch(B, C, H, W, &ib)) return r;
         return generate_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, max_len, eos, tokens_out, n_steps, logits_out, logp_out, s);
     }
+    // A prompted decode's prefix: tokens [B][P] on the device (its lengths are in flen already), m / M the shortest / longest length,
+    // logp_out [B][P] or null for the forced tokens' log-probabilities
+    struct PrefixIn { const int64_t* tokens; int P, m, M; float* logp_out; };
+    // txo_generate_prefix / _from_enc / _ragged: generate()'s loop continued behind a caller's prefix (texocr.h).  Everything is refused before
+    // anything is encoded.
+    int generate_prefix(const float* img, const float* enc, const int32_t* sizes, int B, int C, int H, int W, int N, const int64_t* prefix, int P,
+                        const int32_t* prefix_len, int max_len, int eos, int64_t* tokens_out, int* n_steps, float* logp_out, float* prefix_logp_out,
+                        hipStream_t s) override {
+        last_compactions = 0; last_ragged = false;
+        if (sizes) { if (int r = ragged_refusals()) return r; }
+        if (max_len < 1) return fail(TXO_E_INVALID, "prefix decode: max_len must be >= 1");
+        if (B < 1 || B > Bmax) return fail(TXO_E_INVALID, "prefix decode: batch exceeds engine max_batch");
+        if (P < 1) return fail(TXO_E_INVALID, "prefix decode: the prefix needs at least one column");
+        int m = P, M = P;
+        if (prefix_len) {
+            M = 1;
+            for (int b = 0; b < B; ++b) {
+                if (prefix_len[b] < 1 || prefix_len[b] > P)
+                    return fail(TXO_E_INVALID, "prefix decode: prefix_len[" + std::to_string(b) + "] must be in [1, P]");
+                m = std::min(m, (int)prefix_len[b]); M = std::max(M, (int)prefix_len[b]);
+            }
+        }
+        if ((long long)M - 1 + max_len > Tmax)
+            return fail(TXO_E_INVALID, "prefix decode: the longest prefix - 1 + max_len exceeds the decoder's max_length (a prompted decode does not slide the window)");
+        if ((size_t)(m - 1) > (size_t)Bmax * Nmax)
+            return fail(TXO_E_INVALID, "prefix decode: the shortest prefix does not fit the multi-position pass's workspace (max_batch * max_tokens rows)");
+        ImageBatch ib;
+        if (img) { if (int r = sizes ? ragged_batch(B, C, H, W, sizes, s, &ib) : fixed_batch(B, C, H, W, &ib)) return r; }
+        {   // the lengths to the device, through the pinned staging of the ragged sizes (behind ragged_batch's own copy)
+            std::vector<int32_t> len((size_t)B, P);
+            if (prefix_len) len.assign(prefix_len, prefix_len + B);
+            if (int r = upload_i32(len.data(), flen, B, nullptr, 0, s)) return r;
+        }
+        const PrefixIn px{prefix, P, m, M, prefix_logp_out};
+        return generate_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, max_len, eos, tokens_out, n_steps, nullptr, logp_out, s, &px);
+    }
     // the common body of generate() / generate_ragged(): `ib` and its images, or (ib null) the caller's encoder rows src [B][N][D]
     // logp_out [B][max_len] or null: log_softmax(logits)[token] of every returned position (txo_generate_logp), 0 behind a row's eos under the per-row stop
+    // px: a prompted decode (generate_prefix) -- the loop starts behind the shortest prefix and forces the rest (step_prefix.h)
     int generate_common(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* n_steps,
-                        float* logits_out, float* logp_out, hipStream_t s) {
+                        float* logits_out, float* logp_out, hipStream_t s, const PrefixIn* px = nullptr) {
         int steps = 0; last_compactions = 0;
         last_ragged = ib && ib->ragged;
-        const int rc = generate_impl(ib, src, B, N, max_len, eos, tokens_out, &steps, logits_out, logp_out, s);
+        const int rc = generate_impl(ib, src, B, N, max_len, eos, tokens_out, &steps, logits_out, logp_out, s, px);
         ses.row_stop = false;                                     // the decode is over (a txo_decode_step behind it steps every row)
+        ses.forced = false;                                       // ... and picks every row's token itself: the prefix table belongs to the finished call
         if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
         if (n_steps) *n_steps = steps;
         if (last_compactions > 0) ses.open = false;               // the session's rows are no longer the batch's: a new decode must begin
-        if (stop_mode == 1 && eos >= 0 && steps > 0) {
+        if (stop_mode == 1 && eos >= 0 && steps > 0 && !px) {      // (a prompted decode has padded already: prefix_finish_kernel)
             hipLaunchKernelGGL(pad_after_eos_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tokens_out, logp_out, max_len, steps, B, eos, cfg.bos, cfg.pad);
             HIP_TRY(hipStreamSynchronize(s));
             HIP_TRY(hipGetLastError());
@@ -1890,14 +1955,21 @@ struct Engine : EngineBase {
         return 0;
     }
     int generate_impl(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* steps,
-                      float* logits_out, float* logp_out, hipStream_t s) {
+                      float* logits_out, float* logp_out, hipStream_t s, const PrefixIn* px = nullptr) {
         // max_len > decoder.max_len: the reference slides its window (decoder.py:99-100).  The first Tmax positions decode with the
         // KV cache as always (n_pos of them; rows of the outputs are max_len apart); every further token re-runs its window of the
         // last Tmax tokens, positions re-indexed from 0, through ONE multi-position forward (prefill) -- generate_window below.
-        const int n_pos = std::min(max_len, Tmax);
+        // A prompted decode (px; generate_prefix checked that it stays inside the table): the loop decodes positions t0 = m-1 .. M+max_len-2.
+        const int t0 = px ? px->m - 1 : 0;
+        const int n_pos = px ? px->M + max_len - 1 : std::min(max_len, Tmax);
         if (ib) { if (int r = encode_batch(*ib, src, eenc, s)) return r; src = eenc; }
         // (eos also decides whether the BOS column counts; a ragged session's key count per slot = the images' token counts)
         if (int r = begin_session(src, B, N, eos, s, false, KeyCounts{ib && ib->ragged ? rag_ntok : nullptr})) return r;
+        ses.forced = px != nullptr;
+        if (px) {   // the prefix into the engine's table (lengths are in flen: generate_prefix), no forced token scored yet
+            hipLaunchKernelGGL(prefix_table_kernel, dim3((B * Tmax + 255) / 256), dim3(256), 0, s, ftab, Tmax, px->tokens, px->P, flen, B, V);
+            HIP_TRY(hipMemsetAsync(fplogp, 0, sizeof(float) * (size_t)B * Tmax, s));
+        }
         last_persist = false;
         if (persist_cooldown > 0) --persist_cooldown;
         if (persist_usable(B)) {
@@ -1927,6 +1999,7 @@ struct Engine : EngineBase {
         // 34.2 vs 37.2 ms per generate at B = 1 -- from B = 8 on it is equal); TXO_GRAPH=1 / 0 forces it on / off
         // per-row stop with live-row compaction: inside the positional table, tokens only (a finished row's logits would be unspecified)
         choose_form(stop_mode == 1 && eos >= 0 && logits_out == nullptr && max_len <= Tmax && knobs.stop_every > 0 && !prof && !prof_cross, s);
+        if (px) ses.lat_self = false;                              // (the multi-position pass fills the K/V history, not the z history)
         const bool want_graph = knobs.run.graph >= 0 ? knobs.run.graph != 0 : B <= 4;
         // per-row stop replays captured steps: as the ranges shrink a position's launches take less time than the host needs to enqueue them
         // (68 launches for two ranges: ~230 us per position on the host against 130 us on the device at 40 % of the rows), and a step
@@ -1947,8 +2020,11 @@ struct Engine : EngineBase {
         if (want == 2 && knobs.tune_lanes && !lanes.tuned) { if (int r = lanes.tune(n_cus, knobs.tune_verbose)) return r; }
         lanes.split(ses.rows, want, s);
         last_ranges = lanes.n;
-        reset_lanes(s, eos);
+        reset_lanes(s, eos, px ? px->m : 0);
+        // a prompted decode: positions 0 .. m-2 of every row in ONE multi-position pass, no logits (it fills the K/V history the loop reads)
+        if (px && px->m > 1) { if (int r = prefill(ftab, Tmax, px->m - 1, nullptr, nullptr, s)) return r; }
         bool use_graph = !eager && !prof && !prof_cross;   // event-carrying launches cannot be captured
+        prefix_cols = use_graph ? Tmax : max_len;                  // (a captured step writes the engine's buffers: every column of theirs exists)
         const bool glogp = logp_out != nullptr;                    // a captured step carries the log-probabilities like the tokens: into the engine's buffer
         if (use_graph) for (int i = 0; i < lanes.n; ++i) if (int r = lane_graph(i, eos, glogp)) return r;
         if (int r = lanes.fork(s)) return r;
@@ -1961,7 +2037,7 @@ struct Engine : EngineBase {
         if (stamp_file && !stamps.buf) { if (int r = dalloc(&stamps.buf, (size_t)Stamps::KERNELS * Stamps::BLOCKS * 3)) return r; }
         const int stamp_step = stamp_file ? std::min(n_pos - 1, 200) : -1;
         auto decode_loop = [&]() -> int {
-        for (int t = 0; t < n_pos; ++t) {
+        for (int t = t0; t < n_pos; ++t) {
             if (t == stamp_step) { if (int r2 = stamps.begin(s)) return r2; }
             else if (stamps.slot >= 0) stamps.dump(stamp_file, knobs.has_stamps_raw ? &knobs.stamps_raw : nullptr, s);
             for (int i = 0; i < lanes.n; ++i) {
@@ -2001,17 +2077,22 @@ struct Engine : EngineBase {
         };
         if (int r = decode_loop()) return abandon_lanes(s, r);
         if (int r = lanes.join(s)) return r;
+        // a prompted decode returns min(max_len, t_last + 2 - m) columns: the shortest prefix's row wrote column t_last + 1 - m last
+        const int n_cols = px ? std::min(max_len, poll.steps + 1 - px->m) : n_pos;
         if (use_graph) {
             HIP_TRY(hipMemcpy2DAsync(tokens_out, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax,
-                                     sizeof(int64_t) * n_pos, B, hipMemcpyDeviceToDevice, s));
+                                     sizeof(int64_t) * n_cols, B, hipMemcpyDeviceToDevice, s));
             if (logp_out)
-                HIP_TRY(hipMemcpy2DAsync(logp_out, sizeof(float) * max_len, logp_buf, sizeof(float) * Tmax, sizeof(float) * n_pos, B, hipMemcpyDeviceToDevice, s));
+                HIP_TRY(hipMemcpy2DAsync(logp_out, sizeof(float) * max_len, logp_buf, sizeof(float) * Tmax, sizeof(float) * n_cols, B, hipMemcpyDeviceToDevice, s));
         }
+        if (px)   // pad / 0.0 where a row did not get to (or is finished, per-row stop); the forced tokens' log-probabilities to the caller
+            hipLaunchKernelGGL(prefix_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tokens_out, logp_out, max_len, n_cols, B, poll.steps, eos,
+                               cfg.pad, stop_mode == 1 ? 1 : 0, ftab, Tmax, flen, px->m, fplogp, px->logp_out, px->P);
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         lanes.split(ses.rows, 1, s);
-        *steps = poll.steps;
-        if (!poll.done && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, s);
+        *steps = px ? n_cols : poll.steps;
+        if (!px && !poll.done && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, s);
         return 0;
     }
 
@@ -2355,6 +2436,30 @@ int txo_generate_from_enc_logp(txo_engine* e, const float* enc, int32_t B, int32
                                int64_t* tokens_out, int32_t* n_steps, float* logits_out, float* logp_out, void* stream) {
     if (!e || !enc || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
     return e->impl->generate(nullptr, enc, B, 0, 0, 0, N, max_len, eos, tokens_out, n_steps, logits_out, logp_out, (hipStream_t)stream);
+}
+
+int txo_generate_prefix(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, const int64_t* prefix, int32_t P,
+                        const int32_t* prefix_len, int32_t max_len, int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logp_out,
+                        float* prefix_logp_out, void* stream) {
+    if (!e || !img || !prefix || !tokens_out) return fail(TXO_E_INVALID, "prefix decode: null argument");
+    return e->impl->generate_prefix(img, nullptr, nullptr, B, C, H, W, 0, prefix, P, prefix_len, max_len, eos, tokens_out, n_steps, logp_out,
+                                    prefix_logp_out, (hipStream_t)stream);
+}
+
+int txo_generate_prefix_from_enc(txo_engine* e, const float* enc, int32_t B, int32_t N, const int64_t* prefix, int32_t P, const int32_t* prefix_len,
+                                 int32_t max_len, int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logp_out, float* prefix_logp_out,
+                                 void* stream) {
+    if (!e || !enc || !prefix || !tokens_out) return fail(TXO_E_INVALID, "prefix decode: null argument");
+    return e->impl->generate_prefix(nullptr, enc, nullptr, B, 0, 0, 0, N, prefix, P, prefix_len, max_len, eos, tokens_out, n_steps, logp_out,
+                                    prefix_logp_out, (hipStream_t)stream);
+}
+
+int txo_generate_prefix_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes,
+                               const int64_t* prefix, int32_t P, const int32_t* prefix_len, int32_t max_len, int32_t eos, int64_t* tokens_out,
+                               int32_t* n_steps, float* logp_out, float* prefix_logp_out, void* stream) {
+    if (!e || !img || !sizes || !prefix || !tokens_out) return fail(TXO_E_INVALID, "prefix decode: null argument");
+    return e->impl->generate_prefix(img, nullptr, sizes, B, C, Hc, Wc, 0, prefix, P, prefix_len, max_len, eos, tokens_out, n_steps, logp_out,
+                                    prefix_logp_out, (hipStream_t)stream);
 }
 
 int txo_generate_beam(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t beams, int32_t max_len,

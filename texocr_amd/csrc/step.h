@@ -38,6 +38,12 @@ struct StepArgs {
     // log-probability of the chosen token under softmax(logits), temperature 1 over the FULL vocabulary -- greedy and sampled alike: the quantity
     // txo_score's logp reports, NOT the sampler's top-k / temperature distribution the draw was made from
     float* logp_out;            // [rows][out_stride] or null
+    // prompted decode (txo_generate_prefix; the *_prefix_step kernels below, null for every other step): the caller's prefix in an engine-owned
+    // table, indexed by row of the BATCH like outputs and sampler keys (the range's slices, through out_row): at position t the row commits
+    // forced[r][t + 1] while t + 1 < forced_len[r], and its own pick into output column t + 1 - forced_len[r] (the per-row output shift) otherwise
+    const int64_t* forced; int forced_stride; const int* forced_len;
+    int out_cols;               // output columns of a row (max_len): a pick whose column lies beyond is committed but not written
+    float* prefix_logp;         // [rows][forced_stride] or null: log-probability of the forced token forced[r][t + 1], at column t + 1
 };
 // row of the range (relative to row0) whose outputs slot `row` produces
 __device__ inline int out_row(const StepArgs& a, int row) { return a.row_map ? a.row_map[row] - a.row0 : row; }
@@ -46,12 +52,8 @@ __device__ inline int out_row(const StepArgs& a, int row) { return a.row_map ? a
 // a token id a selection can produce only from non-finite logits (arg-max over NaNs finds nothing: index 0x7fffffff) must never reach
 // the next position's embedding lookup: ids are forced into the vocabulary (txo_encode: non-finite input gives unspecified, in-range tokens)
 __device__ inline int in_vocab(int tok, int V) { return (unsigned)tok < (unsigned)V ? tok : 0; }
-__device__ inline void commit_token(const StepArgs& a, int row, int t, int tok, float logp = 0.f) {
-    tok = in_vocab(tok, a.V);
-    a.cur_tok[row] = tok;
-    const bool frozen = a.stop_rows && a.eos >= 0 && a.eos_seen[row];          // per-row stop: the host pads behind the row's first eos
-    if (a.tokens_out && !frozen) a.tokens_out[(size_t)out_row(a, row) * a.out_stride + t] = tok;
-    if (a.logp_out && !frozen) a.logp_out[(size_t)out_row(a, row) * a.out_stride + t] = logp;
+// the bookkeeping behind every committed token, picked or forced (step_prefix.h): the row's eos state, the range's arrival word, done flag, position
+__device__ inline void arrive_token(const StepArgs& a, int row, int t, int tok) {
     unsigned add = 1u;
     if (a.eos >= 0 && tok == a.eos && !a.eos_seen[row]) { a.eos_seen[row] = 1; add += 1u << 16; }
     const unsigned old = atomicAdd(&a.st->arrive, add);
@@ -62,6 +64,14 @@ __device__ inline void commit_token(const StepArgs& a, int row, int t, int tok, 
         a.st->arrive = 0u;
         a.st->t = t + 1;
     }
+}
+__device__ inline void commit_token(const StepArgs& a, int row, int t, int tok, float logp = 0.f) {
+    tok = in_vocab(tok, a.V);
+    a.cur_tok[row] = tok;
+    const bool frozen = a.stop_rows && a.eos >= 0 && a.eos_seen[row];          // per-row stop: the host pads behind the row's first eos
+    if (a.tokens_out && !frozen) a.tokens_out[(size_t)out_row(a, row) * a.out_stride + t] = tok;
+    if (a.logp_out && !frozen) a.logp_out[(size_t)out_row(a, row) * a.out_stride + t] = logp;
+    arrive_token(a, row, t, tok);
 }
 
 // log-sum-exp of a logits row beside the token selection, for logp_out: every lane keeps a running (max m, sum of exp(v - m)) over the
@@ -84,6 +94,8 @@ __device__ inline float lse_finish(float m, float s, float mx) {
     return logf(wave_sum(part));
 }
 
+// (step_prefix.h: stream_row repeats both loops below, operation for operation -- a prompted decode's log-probabilities are promised to be
+// these bits where the forced token is the arg-max.  Change the two together; tests/test_gpu_prefix.py compares them bit for bit.)
 __global__ __launch_bounds__(64) void argmax_step_kernel(StepArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
     const int t = a.st->t;

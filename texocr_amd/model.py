@@ -212,6 +212,30 @@ class HipEngine:
         toks = toks[:, :n]
         return (toks, logits[:, :n]) if return_logits else toks
 
+    def generate_prefix(self, src, prefix: torch.Tensor, max_len: int, eos: Optional[int], prefix_len=None,
+                        enc: Optional[torch.Tensor] = None, return_logp: bool = False):
+        """Prompted decode (txo_generate_prefix / _ragged / _from_enc): the engine's loop continued behind prefix (B, P) int64 -- src a
+        (B, C, H, W) tensor or a sequence of (C, H_b, W_b) images, or enc -- with prefix_len (B,) (None: every row has length P).
+        -> tokens (B, n), column j of row b the j-th token behind row b's own prefix; with return_logp (tokens, logp (B, n),
+        prefix_logp (B, P): the log-probabilities of the forced tokens, 0.0 where the loop forced none)."""
+        if (src is None) == (enc is None):
+            raise ValueError("pass exactly one of src / enc")
+        if prefix_len is not None:
+            prefix_len = torch.as_tensor(prefix_len).to(device="cpu", dtype=torch.int32).reshape(-1).contiguous()
+        ops.check_prefix(tuple(prefix.shape), prefix_len, max_len, self.dims.max_len, self.max_batch * self.max_tokens)   # before anything changes
+        self._ensure()
+        e = -1 if eos is None else int(eos)
+        if enc is not None:
+            out = torch.ops.texocr.generate_prefix_from_enc(enc, prefix, prefix_len, self.id, int(max_len), e, bool(return_logp))
+        elif isinstance(src, torch.Tensor):
+            out = torch.ops.texocr.generate_prefix(src, prefix, prefix_len, self.id, int(max_len), e, bool(return_logp))
+        else:
+            box, sizes = ops.pack_ragged(src)
+            out = torch.ops.texocr.generate_prefix_ragged(box, sizes, prefix, prefix_len, self.id, int(max_len), e, bool(return_logp))
+        toks, n, logp, plogp = out
+        n = int(n.item())
+        return (toks[:, :n], logp[:, :n], plogp) if return_logp else toks[:, :n]
+
     # ---- ragged batches (build extension): images of different sizes in one call; `images` is a sequence of (C, H_b, W_b) tensors ----
     def encode_ragged(self, images):
         """-> (enc (B, Ns, D) with zero rows behind each image's own token count, n_tokens (B,) int32 CPU)"""
@@ -711,6 +735,9 @@ class AutoRegressiveDecoder(nn.Module):
         return_logp = bool(kwargs.pop("return_logp", False))
         stop = kwargs.pop("stop", "global")                        # build extension: 'row' = per-row stop, pad behind a row's first eos
         pad = kwargs.pop("pad", None)
+        # build extension: (B,) lengths of the rows of start_tokens (columns at and behind a row's length are never read); the result's
+        # column j of row b is then the j-th token behind row b's own start.  Needs the engine's prompted loop (see below).
+        prefix_len = kwargs.pop("prefix_len", None)
         if kwargs:
             raise ValueError(f"unsupported arguments: {sorted(kwargs)}")
         _need_enc(enc)
@@ -723,10 +750,37 @@ class AutoRegressiveDecoder(nn.Module):
         st = start_tokens[None, :] if squeeze else start_tokens                  # decoder.py:88
         B, T0 = st.shape
         eng = self._engine
-        _check_token_ids(st, eng.dims.vocab)
+        if prefix_len is not None:                                 # (columns at and behind a row's length are never read: nor checked)
+            if padded:
+                raise ValueError("prefix_len is not available with a padding mask")
+            prefix_len = torch.as_tensor(prefix_len).to(device="cpu", dtype=torch.int32).reshape(-1)
+            ops.check_prefix(tuple(st.shape), prefix_len, max_len, self.max_len, eng.max_batch * eng.max_tokens)
+        _check_token_ids(_inside_lengths(st, prefix_len, 0), eng.dims.vocab)
         if seed is None and generator is not None:
             seed = generator.initial_seed()
+        # A start that is not the single BOS column continues in the ENGINE's loop (txo_generate_prefix_from_enc: one multi-position pass
+        # over the start, then the loop with everything generate() has -- and return_logp) where the loop can take it: no padding mask,
+        # (T0 - 1) + max_len inside the positional table, T0 - 1 rows inside the multi-position pass's workspace.  Otherwise the stepwise
+        # loop below, as before.  return_logp=True on this route: (tokens, logp, prefix_logp).
+        bos_start = T0 == 1 and prefix_len is None and bool((st == eng.dims.bos).all())
+        prompted = (not padded and not bos_start and not return_logits and T0 - 1 + max_len <= self.max_len
+                    and T0 - 1 <= eng.max_batch * eng.max_tokens)
+        if prefix_len is not None:
+            prompted = True
+            if return_logits:
+                raise ValueError("return_logits is not available with prefix_len (a prompted decode keeps no logits)")
         with eng.modes(sample=(temp, seed), stop=stop, decode=decode) as sample:
+            if prompted:
+                out = eng.generate_prefix(None, st.to(enc.device), max_len, eos_tok, prefix_len=prefix_len, enc=enc, return_logp=return_logp)
+                # stop='row': the engine has padded with its own pad id, by each row's own prefix; a caller's pad= is put in its place -- every
+                # column the engine padded lies behind the row's first eos (the loop breaks only once every row holds one)
+                if stop == "row" and eos_tok is not None and pad is not None and int(pad) != eng.dims.pad:
+                    toks = out[0] if return_logp else out
+                    toks = _pad_after_eos(toks, _inside_lengths(st, prefix_len, -1).to(toks.device), eos_tok, int(pad))
+                    out = (toks, *out[1:]) if return_logp else toks
+                if return_logp:
+                    return tuple(o.squeeze(0) for o in out) if squeeze else out
+                return out.squeeze(0) if squeeze else out
             # beyond the positional table the engine slides the window with its multi-position forward, which needs a vocabulary
             # that is a multiple of 8 and a table that fits its workspace -- else the general stepwise loop below
             window_ok = max_len <= self.max_len or (eng.dims.vocab % 8 == 0 and self.max_len <= eng.max_batch * eng.max_tokens)
@@ -799,6 +853,15 @@ class AutoRegressiveDecoder(nn.Module):
                 if eos_tok is not None and bool((output == eos_tok).any(dim=1).all()):
                     break
         return output[:, T0:]
+
+
+def _inside_lengths(tokens: torch.Tensor, lens, fill: int) -> torch.Tensor:
+    """tokens (B, P) with every column at and behind its row's length lens[b] replaced by `fill` (lens None: as they are)"""
+    if lens is None:
+        return tokens
+    cols = torch.arange(tokens.shape[1], device=tokens.device)[None, :]
+    keep = cols < torch.as_tensor(lens).to(device=tokens.device, dtype=torch.int64).reshape(-1, 1)
+    return torch.where(keep, tokens, torch.full_like(tokens, fill))
 
 
 def _pad_after_eos(tokens: torch.Tensor, start: torch.Tensor, eos: int, pad: int) -> torch.Tensor:
@@ -875,12 +938,21 @@ class OCRModel(nn.Module):
     @torch.no_grad()
     def generate(self, src: torch.Tensor, max_len: int, temp: float = 0.3, *, decode: str = "greedy",
                  generator: Optional[torch.Generator] = None, seed: Optional[int] = None, return_logits: bool = False,
-                 beam: int = 0, return_beams: bool = False, stop: str = "global", return_logp: bool = False):
+                 beam: int = 0, return_beams: bool = False, stop: str = "global", return_logp: bool = False,
+                 prefix: Optional[torch.Tensor] = None, prefix_len=None):
         """return_logp=True (build extension): (tokens, logp), both (B, n_steps) -- logp[b, t] = log_softmax(logits[b, t])[tokens[b, t]],
         what score(src, cat([bos], tokens)).logp reports, taken from the token selection itself: temperature 1 and the whole vocabulary
         also with decode='sample' (not the sampler's top-k / temperature distribution); stop='row': 0 behind a row's first eos, so
-        logp.sum(1) is the sequence log-probability.  With return_logits: (tokens, logits, logp)."""
+        logp.sum(1) is the sequence log-probability.  With return_logits: (tokens, logits, logp).
+        prefix= (build extension): (B, P) int64 tokens the decode continues instead of starting at BOS (put BOS in column 0 yourself),
+        prefix_len= (B,) their lengths per row (None: P) -> tokens (B, n), column j of row b the j-th token behind row b's own prefix;
+        with return_logp (tokens, logp, prefix_logp (B, P)): prefix_logp[b, i] scores prefix[b, i] for min(prefix_len) <= i < prefix_len[b],
+        0.0 elsewhere.  Needs (longest prefix - 1) + max_len <= decoder.max_len; not with beam= or return_logits."""
         _check_modes(stop)
+        if prefix is not None:
+            return self._generate_prefix(src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len)
+        if prefix_len is not None:
+            raise ValueError("prefix_len needs prefix")
         if beam and return_logp:
             raise ValueError("return_logp is not available with beam search (beam=k): it returns beam scores (return_beams=True)")
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
@@ -897,6 +969,28 @@ class OCRModel(nn.Module):
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
                                      stop=stop, pad=self.trg_pad_idx, return_logp=return_logp)
+
+    def _generate_prefix(self, src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len):
+        """generate(prefix=) / generate_ragged(prefix=): src a (B, C, H, W) tensor or a sequence of images.  Every refusal comes before
+        the engine is touched."""
+        if beam:
+            raise ValueError("prefix= is not available with beam search (beam=k)")
+        if return_logits:
+            raise ValueError("prefix= is not available with return_logits (a prompted decode keeps no logits)")
+        _check_modes(stop, decode)
+        B = src.shape[0] if isinstance(src, torch.Tensor) else len(src)
+        if not isinstance(prefix, torch.Tensor) or prefix.ndim != 2 or prefix.dtype != torch.int64 or prefix.shape[0] != B:
+            raise ValueError(f"prefix must be an int64 tensor of shape (B, P) with one row per image ({B})")
+        eng = self._engine
+        if prefix_len is not None:
+            prefix_len = torch.as_tensor(prefix_len).to(device="cpu", dtype=torch.int32).reshape(-1)
+        ops.check_prefix(tuple(prefix.shape), prefix_len, max_len, self.decoder.max_len, eng.max_batch * eng.max_tokens)
+        _check_token_ids(_inside_lengths(prefix, prefix_len, 0), eng.dims.vocab)   # (columns at and behind a row's length are never read)
+        if seed is None and generator is not None:
+            seed = generator.initial_seed()
+        dev = src.device if isinstance(src, torch.Tensor) else src[0].device
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode):
+            return eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
 
     @torch.no_grad()
     def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0) -> Beams:
@@ -919,12 +1013,16 @@ class OCRModel(nn.Module):
 
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
-                        stop: str = "global", return_logp: bool = False):
+                        stop: str = "global", return_logp: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len=None):
         """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
         is keyed by the row of the batch).  max_len may exceed decoder.max_len: the window slides as in generate(), under the engine's
         two preconditions (a vocabulary that is a multiple of 8, max_length <= max_batch * max_tokens; ValueError before anything is
-        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them."""
+        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them.  prefix= / prefix_len=: as generate() takes them."""
+        if prefix is not None:
+            return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len)
+        if prefix_len is not None:
+            raise ValueError("prefix_len needs prefix")
         with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode):
             return self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
 

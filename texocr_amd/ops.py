@@ -604,6 +604,121 @@ def _(img, sizes, engine, beams, max_len, eos, want_logp, length_alpha):
     return _beam_fake(img, beams, max_len, want_logp)
 
 
+# ---- prompted decode (txo_generate_prefix*): generate()'s loop continued behind a caller's token prefix -------------------------------
+def check_prefix(prefix_shape, prefix_len, max_len: int, table: int, workspace: Optional[int] = None) -> Tuple[int, int]:
+    """The refusals of a prompted decode that need no device (ValueError, every message names the prefix), shared by the operators and
+    the facades so that they fire before the engine's session changes: prefix (B, P) with P >= 1; prefix_len None or B lengths in
+    [1, P]; (longest - 1) + max_len inside the positional table (a prompted decode does not slide the window); (shortest - 1) rows
+    inside the multi-position pass's workspace.  -> (shortest, longest)"""
+    if len(prefix_shape) != 2 or prefix_shape[1] < 1:
+        raise ValueError("prefix must be (B, P) with at least one column")
+    B, P = int(prefix_shape[0]), int(prefix_shape[1])
+    if int(max_len) < 1:
+        raise ValueError("prefix decode: max_len must be >= 1")
+    m = M = P
+    if prefix_len is not None:
+        lens = [int(v) for v in (prefix_len.tolist() if hasattr(prefix_len, "tolist") else prefix_len)]
+        if len(lens) != B:
+            raise ValueError(f"prefix_len must have one entry per row of prefix ({B}), got {len(lens)}")
+        if lens and (min(lens) < 1 or max(lens) > P):
+            raise ValueError(f"prefix_len must be in [1, {P}] (the columns of prefix)")
+        if lens:
+            m, M = min(lens), max(lens)
+    if M - 1 + int(max_len) > table:
+        raise ValueError(f"prefix decode: the longest prefix ({M}) - 1 + max_len ({int(max_len)}) exceeds decoder.max_len ({table}); a prompted "
+                         "decode does not slide the window")
+    if workspace is not None and m - 1 > workspace:
+        raise ValueError(f"prefix decode: the shortest prefix ({m}) does not fit the multi-position pass's workspace (max_batch * max_tokens = {workspace} rows)")
+    return m, M
+
+
+def _prefix_args(prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], e, B: int, max_len: int):
+    prefix = _i64_dev(prefix, "prefix", e, B, 2, "(B, P) with one row per image")
+    if prefix_len is not None:
+        if prefix_len.is_cuda or prefix_len.dtype != torch.int32 or tuple(prefix_len.shape) != (B,):
+            raise ValueError("prefix_len must be an int32 CPU tensor of shape (B,): the loop's start and length depend on it")
+        prefix_len = prefix_len.contiguous()
+    ws = e.max_batch * e.max_tokens if hasattr(e, "max_batch") else None
+    check_prefix(tuple(prefix.shape), prefix_len, max_len, e.dims.max_len, ws)
+    return prefix, prefix_len
+
+
+def _prefix_outputs(prefix: torch.Tensor, e, max_len: int, want_logp: bool):
+    toks, _ = _gen_outputs(prefix, e, max_len, False)
+    logp = _logp_output(toks) if want_logp else torch.empty((0, max_len), device=prefix.device, dtype=torch.float32)
+    plogp = torch.empty((prefix.shape[0] if want_logp else 0, prefix.shape[1]), device=prefix.device, dtype=torch.float32)
+    return toks, logp, plogp
+
+
+def _prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp):
+    """the arguments every txo_generate_prefix* takes behind its images"""
+    return (prefix.data_ptr(), int(prefix.shape[1]), None if prefix_len is None else _i32p(prefix_len), int(max_len), int(eos), toks.data_ptr(),
+            C.byref(n), logp.data_ptr() if want_logp else None, plogp.data_ptr() if want_logp else None)
+
+
+@custom_op("texocr::generate_prefix", mutates_args=())
+def generate_prefix(img: torch.Tensor, prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], engine: int, max_len: int, eos: int,
+                    want_logp: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """txo_generate_prefix: prefix (B, P) int64 on the GPU, prefix_len (B,) int32 CPU or None (every row has length P) -> (tokens (B, max_len)
+    of which the first n are valid -- column j of row b is the j-th token behind row b's own prefix --, n as an int64 CPU tensor of shape
+    (1,), logp (B, max_len) or (0, max_len), prefix_logp (B, P) or (0, P): the log-probabilities of the forced tokens)."""
+    e = _eng(engine, ready=True)
+    img = _img_arg(img, e)
+    B, Cc, H, W = img.shape
+    prefix, prefix_len = _prefix_args(prefix, prefix_len, e, B, max_len)
+    toks, logp, plogp = _prefix_outputs(prefix, e, max_len, want_logp)
+    n = C.c_int32(0)
+    _call(e, "txo_generate_prefix", img.data_ptr(), B, Cc, H, W, *_prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp),
+          leaves=(B, img))
+    return toks, torch.tensor([n.value], dtype=torch.int64), logp, plogp
+
+
+@custom_op("texocr::generate_prefix_from_enc", mutates_args=())
+def generate_prefix_from_enc(enc: torch.Tensor, prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], engine: int, max_len: int, eos: int,
+                             want_logp: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    e = _eng(engine, ready=True)
+    enc = _enc_arg(enc, e)
+    B = enc.shape[0]
+    prefix, prefix_len = _prefix_args(prefix, prefix_len, e, B, max_len)
+    toks, logp, plogp = _prefix_outputs(prefix, e, max_len, want_logp)
+    n = C.c_int32(0)
+    _call(e, "txo_generate_prefix_from_enc", enc.data_ptr(), B, enc.shape[1], *_prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp),
+          leaves=(B, enc))
+    return toks, torch.tensor([n.value], dtype=torch.int64), logp, plogp
+
+
+@custom_op("texocr::generate_prefix_ragged", mutates_args=())
+def generate_prefix_ragged(img: torch.Tensor, sizes: torch.Tensor, prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], engine: int,
+                           max_len: int, eos: int, want_logp: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """txo_generate_prefix_ragged: texocr::generate_prefix over a container (B, C, Hc, Wc) + sizes (B, 2) int32 CPU."""
+    e = _eng(engine, ready=True)
+    img, sizes = _ragged_args(img, sizes, e)
+    B, Cc, Hc, Wc = img.shape
+    prefix, prefix_len = _prefix_args(prefix, prefix_len, e, B, max_len)
+    toks, logp, plogp = _prefix_outputs(prefix, e, max_len, want_logp)
+    n = C.c_int32(0)
+    _call(e, "txo_generate_prefix_ragged", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes),
+          *_prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp), leaves=())   # nothing ragged outlives the call
+    return toks, torch.tensor([n.value], dtype=torch.int64), logp, plogp
+
+
+def _prefix_fake(prefix, max_len, want_logp):
+    B, P = prefix.shape
+    return (prefix.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
+            prefix.new_empty((B if want_logp else 0, max_len), dtype=torch.float32), prefix.new_empty((B if want_logp else 0, P), dtype=torch.float32))
+
+
+@generate_prefix.register_fake
+@generate_prefix_from_enc.register_fake
+def _(src, prefix, prefix_len, engine, max_len, eos, want_logp):
+    return _prefix_fake(prefix, max_len, want_logp)
+
+
+@generate_prefix_ragged.register_fake
+def _(img, sizes, prefix, prefix_len, engine, max_len, eos, want_logp):
+    return _prefix_fake(prefix, max_len, want_logp)
+
+
 @custom_op("texocr::generate_ragged_logp", mutates_args=())
 def generate_ragged_logp(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len: int, eos: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """txo_generate_ragged_logp: texocr::generate_ragged plus logp (B, max_len) float32 -> (tokens, n, logp)."""

@@ -98,9 +98,26 @@ class TeXOCRWrapper:
         logp = [res.logp[b, 0, :n].tolist() for b, n in enumerate(lengths)] if return_logp else [None] * len(rows)
         return rows, logp
 
+    def _prefix_rows(self, prefixes: Sequence, decode: str, return_align: bool, max_len: int):
+        """prefix= of __call__ / batch: one LaTeX string or token list per image -> (prefix (B, P) int64 with BOS in front, padded with the
+        pad id; lengths (B,); the token lists; max_len capped so that the longest prefix and the continuation stay inside the positional
+        table -- a prompted decode does not slide the window)"""
+        if decode == "beam" or return_align:
+            raise ValueError("prefix= is not available with decode='beam' or return_align")
+        rows = [self.tokenizer.encode(p) if isinstance(p, str) else [int(t) for t in p] for p in prefixes]
+        lens = [1 + len(r) for r in rows]
+        room = self.dims.max_len - (max(lens) - 1)
+        if room < 1:
+            raise ValueError(f"prefix of {max(lens) - 1} tokens leaves no room in the positional table ({self.dims.max_len})")
+        pre = torch.full((len(rows), max(lens)), self.model.trg_pad_idx, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            pre[b, 0] = self.model.bos_token
+            pre[b, 1:1 + len(r)] = torch.tensor(r, dtype=torch.int64)
+        return pre, torch.tensor(lens, dtype=torch.int32), rows, min(int(max_len), room)
+
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-              length_alpha: float = 0.0) -> List[tuple]:
+              length_alpha: float = 0.0, prefix: Optional[Sequence] = None) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -110,9 +127,16 @@ class TeXOCRWrapper:
         return_align=True appends to every tuple the maps (len(tokens), H_b/16, W_b/16) __call__(return_align=True) returns for that image,
         from ONE OCRModel.align_ragged pass per chunk over [bos] + tokens (positions behind a row's eos are masked).
         decode='beam': every image's best beam of `beams` (OCRModel.beam_search, ranked with length_alpha), from ONE ragged beam search
-        per chunk of max_batch // beams images; temp and seed play no part.  A max_batch below beams is a ValueError."""
+        per chunk of max_batch // beams images; temp and seed play no part.  A max_batch below beams is a ValueError.
+        prefix=[...]: one LaTeX string or token list per image that the decode continues (BOS is put in front; OCRModel.generate_ragged
+        with prefix= / prefix_len=): `tokens` (and logp) is the continuation, `latex` is decoded from prefix + continuation."""
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
+        pre = plen = prows = None
+        if prefix is not None:
+            if len(prefix) != len(imgs):
+                raise ValueError(f"prefix needs one entry per image ({len(imgs)}), got {len(prefix)}")
+            pre, plen, prows, max_len = self._prefix_rows(prefix, decode, return_align, max_len)
         step = beam_chunk(eng.max_batch, beams) if decode == "beam" else eng.max_batch
         out: List[tuple] = []
         xs = [self._tensor(im).cuda() for im in imgs]
@@ -121,9 +145,10 @@ class TeXOCRWrapper:
                 full, logp = self._best_beams(xs[c0:c0 + step], beams, max_len, length_alpha, return_logp)
             else:
                 chunk_seed = None if seed is None else int(seed) + c0 // step
+                kw = {} if pre is None else dict(prefix=pre[c0:c0 + step].cuda(), prefix_len=plen[c0:c0 + step])
                 toks = self.model.generate_ragged(xs[c0:c0 + step], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
-                                                  return_logp=return_logp)
-                toks, logp = toks if return_logp else (toks, None)
+                                                  return_logp=return_logp, **kw)
+                toks, logp = toks[:2] if return_logp else (toks, None)
                 full = [cut_at_eos(row, self.model.eos_token) for row in toks.tolist()]
                 logp = logp.tolist() if return_logp else None
             maps = None
@@ -132,21 +157,28 @@ class TeXOCRWrapper:
                 maps = [a.maps[0].cpu() for a in self.model.align_ragged(xs[c0:c0 + step], trg.cuda(), mask=mask.cuda())]
             for b, row in enumerate(full):
                 row = row[:-1]                                                        # ocr_model.py:104 (drops the last token)
-                latex = process_output(self.tokenizer.decode(row))
+                latex = process_output(self.tokenizer.decode(row if prows is None else prows[c0 + b] + row))
                 item = (row, latex, logp[b][:len(row)]) if return_logp else (row, latex)
                 out.append((*item, maps[b][:len(row)]) if return_align else item)
         return out
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-                 length_alpha: float = 0.0) -> tuple:
+                 length_alpha: float = 0.0, prefix=None) -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
         [bos] + tokens behind the generate.  Not available once the output outgrew the positional table (the window has slid).
         decode='beam' (build extension): the best of `beams` beams (OCRModel.beam_search, ranked with length_alpha), cut at its eos;
-        max_len is capped at the positional table; temp and seed play no part."""
+        max_len is capped at the positional table; temp and seed play no part.
+        prefix= (a LaTeX string or a token list): the decode continues it (BOS is put in front; OCRModel.generate(prefix=)); `tokens` (and
+        logp) is the continuation, `latex` is decoded from prefix + continuation; max_len is capped so that both fit the positional table."""
         x = self._tensor(img)[None].cuda()
+        prow: List[int] = []
+        gen_kw = {}
+        if prefix is not None:
+            pre, _, (prow,), max_len = self._prefix_rows([prefix], decode, return_align, max_len)
+            gen_kw = dict(prefix=pre.cuda())
         if decode == "beam":
             beam_chunk(self.model._engine.max_batch, beams)
             rows, lps = self._best_beams(x, beams, min(int(max_len), self.dims.max_len), length_alpha, return_logp)
@@ -155,10 +187,10 @@ class TeXOCRWrapper:
         else:
             # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
             # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
-            toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp)
-            toks, logp = toks if return_logp else (toks, None)
+            toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp, **gen_kw)
+            toks, logp = toks[:2] if return_logp else (toks, None)
         out_tokens = toks.squeeze(0).tolist()[:-1]                                   # ocr_model.py:104 (drops the EOS)
-        latex = process_output(self.tokenizer.decode(out_tokens))                    # :105-108
+        latex = process_output(self.tokenizer.decode(prow + out_tokens))             # :105-108
         out = (out_tokens, latex, logp.squeeze(0)[:len(out_tokens)].tolist()) if return_logp else (out_tokens, latex)
         if return_align:
             if toks.shape[1] > self.dims.max_len:
