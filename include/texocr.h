@@ -335,6 +335,30 @@ int txo_set_ragged_forward(txo_engine* e, int32_t on);
  * TXO_E_INVALID.  Engines with the patch front end accept the call and are not affected. */
 int txo_set_ragged_hybrid(txo_engine* e, int32_t on);
 
+/* ---- Device-side image ingest (a BUILD EXTENSION: the reference prepares every image on the host, data_wrangling/dataset.py:365-371) ----
+ * The raw uint8 pixels of B images of DIFFERENT sizes and channel counts -> the float32 container [B][C][Hc][Wc] and the sizes [B][2]
+ * every ragged call above takes, in ONE launch (texocr_amd/csrc/ingest.h).  What comes out is bit for bit what the host path makes of the
+ * same pixels: ToTensor -> Grayscale -> Invert, i.e. a_c = c / 255.0f (an IEEE division), s = (0.2989f a_r + 0.587f a_g) + 0.114f a_b,
+ * out = 1.0f - s, every step rounded to float32 on its own.
+ *   pix_dev       one DEVICE byte buffer that holds every image: interleaved channels, rows tightly packed (no row padding).
+ *   offsets_host  int64 [B] on the HOST: the byte offset of image b's first pixel in pix_dev, >= 0, any alignment.  Image b occupies
+ *                 h_b * w_b * ch_b bytes from there; the caller guarantees that they lie inside the buffer.  No byte outside them is read.
+ *   shapes_host   int32 [B][3] on the HOST = (h_b, w_b, ch_b), h_b, w_b >= 1, ch_b 1 (L: r = g = b), 3 (RGB) or 4 (RGBA: alpha is ignored).
+ *   box_out_dev   float [B][C][Hc][Wc], 16-byte aligned.  EVERY element is written: image b in the top-left corner of slot b, the same
+ *                 plane C times; the image's own pad up to the next multiple of 16 and the rest of the slot are exactly 0.0f (not the value
+ *                 white maps to, 9.9957e-05).  Wc must be a multiple of 4.  C is the consumer's in_channels; it is not checked here.
+ *   sizes_out_host int32 [B][2] on the HOST = (h_b, w_b) rounded up to multiples of 16: the sizes_host of the ragged calls.
+ * The container must hold every rounded-up image; the smallest that does is (Hc, Wc) = the maxima of the rounded-up heights and widths, which
+ * txo_ingest_box returns (no engine needed).  Refused with TXO_E_INVALID and a message naming the image, before anything is enqueued and --
+ * the list and the container are checked first -- before the engine or the device is looked at: null arguments, B < 1, ch outside
+ * {1, 3, 4}, h or w < 1, a negative offset, a rounded-up size beyond (Hc, Wc), Wc % 4, an unaligned container; B beyond cfg.max_batch
+ * (the engine's descriptor staging holds that many).  No limit comes from the canvas or max_tokens: the ragged call that takes the container
+ * keeps all of its own refusals.  Works before the weights are finalized.  Asynchronous on `stream`; the host arrays are copied before the
+ * call returns; no allocation.  Under txo_profile_enable(e, 1) the launch carries events (txo_profile_read kind 4). */
+int txo_ingest_box(const int32_t* shapes_host, int32_t B, int32_t* Hc_out, int32_t* Wc_out);
+int txo_ingest_u8(txo_engine* e, const uint8_t* pix_dev, const int64_t* offsets_host, const int32_t* shapes_host, int32_t B, int32_t C,
+                  int32_t Hc, int32_t Wc, float* box_out_dev, int32_t* sizes_out_host, void* stream);
+
 /* Token selection for the following decode steps / generate calls.  mode 0 (default): greedy argmax.  mode 1:
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits
  * (the reference uses int((1 - 0.9) * vocab) = 99 for vocab 1000), softmax(logits / temp), one multinomial draw,
@@ -361,7 +385,7 @@ int txo_set_stop_mode(txo_engine* e, int32_t mode);
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
  * enabled (txo_profile_enable(e, 1) also clears the previous samples); *count = number of launches averaged.  kind: 0 = cross-attention decode kernel,
- * 1 = encoder (whole txo_encode), 2 = whole decode step.
+ * 1 = encoder (whole txo_encode), 2 = whole decode step, 4 = the ingest kernel of txo_ingest_u8 (events bound to the dispatch).
  * on = 1: everything above (adds marker commands around every encode and step -- use in a separate pass); on = 2: only every
  * fourth cross-attention dispatch carries events (bound to the dispatch, no extra commands; safe inside a timed region; samples are
  * kept for the first 16 generate() calls after enabling); on = 3: the persistent decode launch carries events (kind 3 =

@@ -63,6 +63,8 @@ SYMBOLS = {
     "txo_decode_begin_ragged": (C.c_int, [_P, _FP, _I, _I, C.POINTER(C.c_int32), _P]),
     "txo_generate_ragged": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _P]),
     "txo_generate_ragged_logp": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
+    "txo_ingest_box": (C.c_int, [C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "txo_ingest_u8": (C.c_int, [_P, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _I, _I, _I, _FP, C.POINTER(C.c_int32), _P]),
     "txo_set_sampling": (C.c_int, [_P, _I, _I, C.c_float, C.c_uint64]),
     "txo_set_stop_mode": (C.c_int, [_P, _I]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),

@@ -45,6 +45,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "rows.h"
 #include "step.h"
 #include "step_prefix.h"   // (behind every other kernel: the kernels above keep their places in the code object)
+#include "ingest.h"        // (likewise: the newest kernel goes last)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -101,6 +102,9 @@ struct EngineBase {
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
     bool rag_fwd = false;                       // txo_set_ragged_forward: the multi-position forward on ragged sessions and the ragged sliding window are accepted
     bool rag_hybrid = false;                    // txo_set_ragged_hybrid: ragged batches are accepted on the hybrid front end (conv.h: the RAGGED forms)
+    // txo_ingest_u8 behind its checks (ingest_check): descriptors up in one staged copy, one launch
+    virtual int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc, float* box,
+                          hipStream_t s) = 0;
     virtual int query(int what, int64_t* out) = 0;
     virtual int profile_enable(int on) = 0;
     virtual int profile_read(int kind, double* avg_ms, int64_t* count) = 0;
@@ -206,6 +210,8 @@ struct Engine : EngineBase {
     int32_t* rag_host = nullptr; hipEvent_t rag_ev = nullptr; bool rag_ev_pending = false;
     std::vector<int32_t> rag_stage;   // host scratch [3 Bmax] (sized at creation)
     bool last_ragged = false;         // TXO_Q_LAST_RAGGED
+    // device-side image ingest (ingest.h): the descriptors [Bmax] of the list on the device, their pinned staging, its last copy
+    IngestDesc *ing_desc = nullptr, *ing_host = nullptr; hipEvent_t ing_ev = nullptr; bool ing_ev_pending = false;
     int rag_box[2] = {0, 0};          // the smallest H x W (multiples of 16) that holds every image of the last ragged batch
     // rag_fwd off (the default): these calls answer as they did before the forward had a ragged form
     int refuse_ragged_forward(const std::string& call) const {
@@ -236,7 +242,7 @@ struct Engine : EngineBase {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_persist;
     unsigned cross_seq = 0;
     EventPool pool;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_cross, ev_enc, ev_step;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_cross, ev_enc, ev_step, ev_ingest;
 
     int D, Ie, Id, Fe, Fd, V, Tmax, Nmax, Bmax;
 
@@ -244,6 +250,8 @@ struct Engine : EngineBase {
         if (pctl_host) (void)hipHostFree(pctl_host);
         if (rag_host) (void)hipHostFree(rag_host);
         if (rag_ev) (void)hipEventDestroy(rag_ev);
+        if (ing_host) (void)hipHostFree(ing_host);
+        if (ing_ev) (void)hipEventDestroy(ing_ev);
         for (void* p : allocs) (void)hipFree(p);
     }
 
@@ -584,6 +592,8 @@ struct Engine : EngineBase {
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&rag_host), sizeof(int32_t) * 3 * (size_t)Bmax, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&rag_ev, hipEventDisableTiming));
         rag_stage.assign((size_t)3 * Bmax, 0);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ing_host), sizeof(IngestDesc) * (size_t)Bmax, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&ing_ev, hipEventDisableTiming));
         return lanes.init(Tmax);
     }
     int init_buffers() {
@@ -692,6 +702,7 @@ struct Engine : EngineBase {
         if (int r = dalloc(&blogp, (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&pctl, 1)) return r;
         if (int r = dalloc(&pstamps, (size_t)PS_TEAMS * PS_STAMP_RANKS * PS_MAX_STAGES * PS_STAMP_WORDS)) return r;
+        if (int r = dalloc(&ing_desc, (size_t)Bmax)) return r;   // (last: no earlier buffer moves)
         return 0;
     }
 
@@ -972,6 +983,28 @@ struct Engine : EngineBase {
         if (n1 > 0) HIP_TRY(hipMemcpyAsync(dst1, rag_host + n0, sizeof(int32_t) * n1, hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(rag_ev, s));
         rag_ev_pending = true;
+        return 0;
+    }
+    // Device-side image ingest (ingest.h).  The list has passed ingest_check; works before the weights are finalized (it reads none).
+    // The three host arrays go up as ONE staged copy of B descriptors, the way ragged_batch uploads its grids; no allocation.
+    int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc, float* box,
+                  hipStream_t s) override {
+        if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
+        if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
+        for (int b = 0; b < B; ++b) ing_host[b] = IngestDesc{(long long)offsets[b], shapes[3 * b], shapes[3 * b + 1], shapes[3 * b + 2], 0};
+        HIP_TRY(hipMemcpyAsync(ing_desc, ing_host, sizeof(IngestDesc) * B, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ing_ev, s));
+        ing_ev_pending = true;
+        const dim3 grid((unsigned)((Wc + IG_BLOCK_W - 1) / IG_BLOCK_W), (unsigned)((Hc + IG_ROWS - 1) / IG_ROWS), (unsigned)B), blk(IG_LANES_X * IG_ROWS);
+        if (prof) {                                           // txo_profile_read kind 4: events bound to the dispatch itself
+            hipEvent_t e0 = pool.next(), e1 = pool.next();
+            if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
+            hipExtLaunchKernelGGL(ingest_u8_kernel, grid, blk, 0, s, e0, e1, 0, pix, ing_desc, box, C, Hc, Wc);
+            ev_ingest.push_back({e0, e1});
+        } else {
+            hipLaunchKernelGGL(ingest_u8_kernel, grid, blk, 0, s, pix, ing_desc, box, C, Hc, Wc);
+        }
+        HIP_TRY(hipGetLastError());
         return 0;
     }
     int ragged_refusals() {
@@ -2255,7 +2288,7 @@ struct Engine : EngineBase {
     }
     int profile_enable(int on) override {
         prof = on == 1; prof_cross = on == 2; prof_persist = on == 3;
-        ev_cross.clear(); ev_enc.clear(); ev_step.clear(); ev_persist.clear(); pool.used = 0;
+        ev_cross.clear(); ev_enc.clear(); ev_step.clear(); ev_persist.clear(); ev_ingest.clear(); pool.used = 0;
         if (prof_persist) while (pool.ev.size() < 64) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); pool.ev.push_back(e); }
         if (prof_cross) {           // events for 16 generate() calls, created now
             const size_t want = (size_t)16 * 2 * cfg.dec_layers * Tmax / 4;
@@ -2264,7 +2297,7 @@ struct Engine : EngineBase {
         return 0;
     }
     int profile_read(int kind, double* avg_ms, int64_t* count) override {
-        auto& v = kind == 0 ? ev_cross : (kind == 1 ? ev_enc : (kind == 2 ? ev_step : ev_persist));
+        auto& v = kind == 0 ? ev_cross : (kind == 1 ? ev_enc : (kind == 2 ? ev_step : (kind == 4 ? ev_ingest : ev_persist)));
         double tot = 0; int64_t n = 0;
         for (auto& p : v) {
             float ms = 0;
@@ -2296,6 +2329,47 @@ static int validate(const txo_config& c) {
     if (c.max_tokens < 0 || c.max_tokens > 1 + (c.canvas_h / 16) * (c.canvas_w / 16))
         return fail(TXO_E_INVALID, "max_tokens exceeds 1 + canvas_h*canvas_w/256");
     if (c.dtype != TXO_F32 && c.dtype != TXO_BF16) return fail(TXO_E_INVALID, "dtype must be TXO_F32 or TXO_BF16");
+    return 0;
+}
+
+// ---- device-side image ingest: the refusals that need no engine (texocr.h: txo_ingest_u8 / txo_ingest_box) -------------------------------
+static long long ingest_round16(long long v) { return (v + 15) / 16 * 16; }
+
+// shapes int32 [B][3] = (h, w, ch); every message names the image.  box (may be null): the largest rounded-up height / width
+static int ingest_check_shapes(const int32_t* shapes, int B, long long* box) {
+    if (B < 1) return fail(TXO_E_INVALID, "ingest: no images (B must be >= 1)");
+    if (!shapes) return fail(TXO_E_INVALID, "ingest: null shapes");
+    if (B > 65535) return fail(TXO_E_INVALID, "ingest: more than 65535 images in one call");
+    long long H = 0, W = 0;
+    for (int b = 0; b < B; ++b) {
+        const int h = shapes[3 * b], w = shapes[3 * b + 1], ch = shapes[3 * b + 2];
+        const std::string who = "ingest: image " + std::to_string(b);
+        if (ch != 1 && ch != 3 && ch != 4)
+            return fail(TXO_E_INVALID, who + " has ch = " + std::to_string(ch) + "; the channel count must be 1 (L), 3 (RGB) or 4 (RGBA)");
+        if (h < 1 || w < 1) return fail(TXO_E_INVALID, who + " is " + std::to_string(h) + "x" + std::to_string(w) + "; both sides must be >= 1");
+        H = std::max(H, ingest_round16(h)); W = std::max(W, ingest_round16(w));
+    }
+    if (box) { box[0] = H; box[1] = W; }
+    return 0;
+}
+
+// everything txo_ingest_u8 refuses about the list and the container, before the engine or the device is looked at
+static int ingest_check(const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc) {
+    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+    if (!offsets) return fail(TXO_E_INVALID, "ingest: null offsets");
+    if (C < 1) return fail(TXO_E_INVALID, "ingest: the container's channel count must be >= 1");
+    if (Hc < 1 || Wc < 1) return fail(TXO_E_INVALID, "ingest: the container's height/width must be positive");
+    if (Wc % 4) return fail(TXO_E_INVALID, "ingest: the container's width must be a multiple of 4 (rows are written in 16-byte pieces)");
+    if ((Hc + IG_ROWS - 1) / IG_ROWS > 65535) return fail(TXO_E_INVALID, "ingest: the container's height exceeds the launch grid");
+    for (int b = 0; b < B; ++b) {
+        const long long h16 = ingest_round16(shapes[3 * b]), w16 = ingest_round16(shapes[3 * b + 1]);
+        const std::string who = "ingest: image " + std::to_string(b);
+        if (offsets[b] < 0) return fail(TXO_E_INVALID, who + " has a negative byte offset");
+        if (h16 > Hc || w16 > Wc)
+            return fail(TXO_E_INVALID, who + " is " + std::to_string(shapes[3 * b]) + "x" + std::to_string(shapes[3 * b + 1]) + ", " + std::to_string(h16) + "x" +
+                                           std::to_string(w16) + " rounded up to multiples of 16: it does not fit the container's " + std::to_string(Hc) + "x" +
+                                           std::to_string(Wc));
+    }
     return 0;
 }
 
@@ -2370,6 +2444,25 @@ int txo_generate_ragged_logp(txo_engine* e, const float* img, int32_t B, int32_t
                              int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logp_out, void* stream) {
     if (!e || !img || !sizes || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
     return e->impl->generate_ragged(img, B, C, Hc, Wc, sizes, max_len, eos, tokens_out, n_steps, logp_out, (hipStream_t)stream);
+}
+
+int txo_ingest_box(const int32_t* shapes, int32_t B, int32_t* Hc_out, int32_t* Wc_out) {
+    if (!Hc_out || !Wc_out) return fail(TXO_E_INVALID, "ingest: null argument");
+    long long box[2];
+    if (int r = ingest_check_shapes(shapes, B, box)) return r;
+    *Hc_out = (int32_t)box[0]; *Wc_out = (int32_t)box[1];
+    return 0;
+}
+
+// (the list and the container are checked first: those refusals need neither an engine nor a device)
+int txo_ingest_u8(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Hc, int32_t Wc,
+                  float* box_out, int32_t* sizes_out, void* stream) {
+    if (int r = ingest_check(offsets, shapes, B, C, Hc, Wc)) return r;
+    if (!e || !pix || !box_out || !sizes_out) return fail(TXO_E_INVALID, "ingest: null argument");
+    if (reinterpret_cast<uintptr_t>(box_out) % 16) return fail(TXO_E_INVALID, "ingest: the container must be 16-byte aligned (rows are written in 16-byte pieces)");
+    if (int r = e->impl->ingest_u8(pix, offsets, shapes, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
+    for (int b = 0; b < B; ++b) { sizes_out[2 * b] = (int32_t)ingest_round16(shapes[3 * b]); sizes_out[2 * b + 1] = (int32_t)ingest_round16(shapes[3 * b + 1]); }
+    return 0;
 }
 
 int txo_decode_step(txo_engine* e, const int64_t* tok_in, int32_t t, float* logits_out, int64_t* tok_out, void* stream) {

@@ -236,7 +236,13 @@ class HipEngine:
         n = int(n.item())
         return (toks[:, :n], logp[:, :n], plogp) if return_logp else toks[:, :n]
 
-    # ---- ragged batches (build extension): images of different sizes in one call; `images` is a sequence of (C, H_b, W_b) tensors ----
+    # ---- ragged batches (build extension): images of different sizes in one call; `images` is a sequence of (C, H_b, W_b) tensors, or a
+    # container that already exists (ops.PackedImages: what ingest returns) ----
+    def ingest(self, images) -> "ops.PackedImages":
+        """Device-side image ingest (txo_ingest_u8): raw uint8 images (PIL, numpy, uint8 tensors on the CPU or this device; L, RGB, RGBA) ->
+        the container of a ragged batch, in one copy of the pixel bytes and one launch.  Needs no weights."""
+        return ops.pack_u8(images, self.dims.in_channels, torch.device("cuda", self.device), engine=self.id)
+
     def encode_ragged(self, images):
         """-> (enc (B, Ns, D) with zero rows behind each image's own token count, n_tokens (B,) int32 CPU)"""
         self._ensure()
@@ -988,9 +994,20 @@ class OCRModel(nn.Module):
         _check_token_ids(_inside_lengths(prefix, prefix_len, 0), eng.dims.vocab)   # (columns at and behind a row's length are never read)
         if seed is None and generator is not None:
             seed = generator.initial_seed()
-        dev = src.device if isinstance(src, torch.Tensor) else src[0].device
+        dev = src[0].device if isinstance(src, (list, tuple)) else src.device           # (a tensor or a PackedImages says it itself)
         with eng.modes(sample=(temp, seed), stop=stop, decode=decode):
             return eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
+
+    @torch.no_grad()
+    def ingest(self, images) -> "ops.PackedImages":
+        """Build extension: device-side image ingest.  A list of raw uint8 images of any sizes -- PIL images, numpy arrays or uint8 tensors
+        (on the CPU or the model's device) of shape (H, W), (H, W, 3) or (H, W, 4): L, RGB, RGBA with the alpha ignored -> PackedImages(box
+        (B, in_channels, Hc, Wc) float32, sizes (B, 2) int32 CPU), from ONE copy of the pixel bytes and ONE launch (txo_ingest_u8).  box is
+        bit for bit ops.pack_ragged of the images preprocessed on the host (wrapper.preprocess_image: ToTensor -> Grayscale -> Invert, zero
+        pad to multiples of 16, expanded to in_channels).  Every *_ragged method, beam_search and generate_ragged(prefix=) take the result
+        in place of a list of (C, H_b, W_b) tensors; if all images have one size, box is a valid (B, C, H, W) for generate / score / align /
+        beam_search.  PIL modes other than L / RGB / RGBA are converted with convert('RGB') on the host first."""
+        return self._engine.ingest(images)
 
     @torch.no_grad()
     def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0) -> Beams:
@@ -1004,7 +1021,7 @@ class OCRModel(nn.Module):
             if src.ndim != 4:
                 raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
             n_images = int(src.shape[0])
-        elif isinstance(src, (list, tuple)):
+        elif isinstance(src, (list, tuple, ops.PackedImages)):
             n_images = len(src)
         else:
             raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
@@ -1067,7 +1084,10 @@ class OCRModel(nn.Module):
         (H_b / 16, W_b / 16) patch grid."""
         mask = self._ragged_trg(images, trg, mask)
         ps = self.encoder.patch_size
-        grids = [(int(im.shape[1]) // ps, int(im.shape[2]) // ps) for im in images]
+        if isinstance(images, ops.PackedImages):
+            grids = images.grids(ps)
+        else:
+            grids = [(int(im.shape[1]) // ps, int(im.shape[2]) // ps) for im in images]
         enc, ntok = self.encoder.forward_ragged(images)
         return self.decoder.align(trg, mask=mask, enc=enc, layer=layer, n_tokens=ntok, grids=grids)
 

@@ -24,6 +24,8 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
                             (build extension) the same callables over a RAGGED batch: B images of different sizes in one
                             container, every image computed as if it had been passed on its own (``pack_ragged`` builds the container);
                             decode_prefill / decode_score / decode_attn / decode_set_key_mask run on a ragged session as on any other
+  texocr::ingest_u8         (build extension) the raw uint8 pixels of B images of different sizes and channel counts -> that container, on
+                            the device in one launch, bit for bit what the host preprocessing makes of them (``pack_u8`` is its front end)
 
 An engine is named by an integer id (operators take tensors and scalars only); ``register_engine`` hands one out.
 There is no CPU implementation: calling an operator on CPU tensors raises.
@@ -409,10 +411,33 @@ def _(img, engine, beams, max_len, eos, want_all):
 
 
 # ---- ragged batches (build extension): images of different sizes in one call ---------------------------------------------------
+@dataclass(frozen=True)
+class PackedImages:
+    """A ragged batch that is already in its container -- what pack_u8 / OCRModel.ingest return, and what every *_ragged method takes in
+    place of a sequence of (C, H_b, W_b) tensors: box (B, C, Hc, Wc) float32 on the device, image b in the top-left corner of slot b and
+    zeros around it; sizes (B, 2) int32 CPU = (H_b, W_b), multiples of 16.  len() is the number of images."""
+    box: torch.Tensor
+    sizes: torch.Tensor
+
+    def __len__(self) -> int:
+        return int(self.box.shape[0])
+
+    @property
+    def device(self) -> torch.device:
+        return self.box.device
+
+    def grids(self, patch: int = 16):
+        """the patch grid (H_b / patch, W_b / patch) of every image"""
+        return [(int(h) // patch, int(w) // patch) for h, w in self.sizes.tolist()]
+
+
 def pack_ragged(images: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """B images (C, H_b, W_b) -> (container (B, C, Hc, Wc) float32, sizes (B, 2) int32 CPU = (H_b, W_b)).  Image b sits in the
     top-left corner of its slot; Hc / Wc are the largest height / width; the rest of the container is zero (the engine never reads
-    it).  Every side must be a positive multiple of 16; all images share C, the device and float32."""
+    it).  Every side must be a positive multiple of 16; all images share C, the device and float32.  A PackedImages is passed through
+    untouched: (its box, its sizes)."""
+    if isinstance(images, PackedImages):         # already a container (pack_u8): handed on as it is
+        return images.box, images.sizes
     if len(images) == 0:
         raise ValueError("pack_ragged: no images")
     first = images[0]
@@ -737,3 +762,118 @@ def generate_ragged_logp(img: torch.Tensor, sizes: torch.Tensor, engine: int, ma
 def _(img, sizes, engine, max_len, eos):
     return (img.new_empty((img.shape[0], max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
             img.new_empty((img.shape[0], max_len), dtype=torch.float32))
+
+
+# ---- device-side image ingest (txo_ingest_u8): raw uint8 pixels -> the container of a ragged batch, one copy and one launch ----------
+U8_ALIGN = 16        # byte alignment of every host image inside the staged buffer
+
+
+def _u8_array(im, i: int):
+    """one image of pack_u8's list -> a contiguous uint8 numpy array (host images) or a contiguous uint8 device tensor, of shape (H, W) or
+    (H, W, ch).  PIL modes other than L / RGB / RGBA go through convert('RGB') first, as preprocess_image does with every mode."""
+    import numpy as np
+    if isinstance(im, torch.Tensor):
+        if im.dtype != torch.uint8:
+            raise ValueError(f"pack_u8: image {i} must be uint8, got {im.dtype}")
+        a = im.contiguous() if im.is_cuda else np.ascontiguousarray(im.numpy())
+    elif isinstance(im, np.ndarray):
+        if im.dtype != np.uint8:
+            raise ValueError(f"pack_u8: image {i} must be uint8, got {im.dtype}")
+        a = np.ascontiguousarray(im)
+    elif hasattr(im, "convert") and hasattr(im, "mode"):                       # a PIL image
+        a = np.ascontiguousarray(np.asarray(im if im.mode in ("L", "RGB", "RGBA") else im.convert("RGB"), dtype=np.uint8))
+    else:
+        raise ValueError(f"pack_u8: image {i} must be a PIL image, a numpy array or a tensor, got {type(im).__name__}")
+    if a.ndim not in (2, 3):
+        raise ValueError(f"pack_u8: image {i} must be (H, W), (H, W, 3) or (H, W, 4), got {tuple(a.shape)}")
+    return a
+
+
+def plan_u8(images: Sequence):
+    """The host side of pack_u8, no device needed: -> (staged, device_tensors, src, shapes).
+    staged: uint8 CPU tensor (n,), every HOST image of the list (PIL, numpy, CPU tensor) copied in at an offset aligned to 16, in list order;
+    device_tensors: the uint8 device tensors of the list, contiguous, used where they lie;
+    src: int64 CPU (B, 2) = (k, byte offset): image b starts `offset` bytes into the staged buffer (k = 0) or into device_tensors[k - 1];
+    shapes: int32 CPU (B, 3) = (h, w, ch), ch = 1 for an (H, W) image.  The channel count is the engine's to judge (txo_ingest_u8)."""
+    import numpy as np
+    arrs = [_u8_array(im, i) for i, im in enumerate(images)]
+    src, shapes, dev, total = [], [], [], 0
+    for a in arrs:
+        shapes.append([a.shape[0], a.shape[1], a.shape[2] if a.ndim == 3 else 1])
+        if isinstance(a, torch.Tensor):
+            dev.append(a)
+            src.append([len(dev), 0])
+        else:
+            src.append([0, total])
+            total = (total + a.size + U8_ALIGN - 1) // U8_ALIGN * U8_ALIGN
+    staged = np.zeros((total,), dtype=np.uint8)
+    for (k, o), a in zip(src, arrs):
+        if k == 0:
+            staged[o:o + a.size] = a.reshape(-1)
+    return (torch.from_numpy(staged), dev, torch.tensor(src, dtype=torch.int64).reshape(-1, 2),
+            torch.tensor(shapes, dtype=torch.int32).reshape(-1, 3))
+
+
+def box_u8(shapes: torch.Tensor) -> Tuple[int, int]:
+    """(Hc, Wc) of the smallest container that holds the list: the maxima of the heights / widths rounded up to 16 (txo_ingest_box's rule)"""
+    if shapes.shape[0] == 0:
+        return 0, 0
+    r = (shapes[:, :2].to(torch.int64) + 15) // 16 * 16
+    return int(r[:, 0].max()), int(r[:, 1].max())
+
+
+@custom_op("texocr::ingest_u8", mutates_args=())
+def ingest_u8(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Tensor, engine: int, channels: int, Hc: int,
+              Wc: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """txo_ingest_u8: bufs = uint8 device tensors that hold the pixels (contiguous), src (B, 2) int64 CPU = (index into bufs, byte offset),
+    shapes (B, 3) int32 CPU = (h, w, ch) -> (box (B, channels, Hc, Wc) float32 with every element written, sizes (B, 2) int32 CPU = (h, w)
+    rounded up to 16).  One launch; the refusals are the engine's (ValueError with its message)."""
+    e = _eng(engine)
+    B = int(shapes.shape[0])
+    if src.is_cuda or src.dtype != torch.int64 or tuple(src.shape) != (B, 2):
+        raise ValueError("src must be an int64 CPU tensor of shape (B, 2) = (index into bufs, byte offset)")
+    if shapes.is_cuda or shapes.dtype != torch.int32 or shapes.ndim != 2 or shapes.shape[1] != 3:
+        raise ValueError("shapes must be an int32 CPU tensor of shape (B, 3) = (h, w, ch)")
+    for k, t in enumerate(bufs):
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"bufs[{k}] must be a contiguous uint8 GPU tensor")
+        if t.device.index != e.device:
+            raise ValueError(f"bufs[{k}] lives on cuda:{t.device.index} but the engine was created on cuda:{e.device}")
+    dev = torch.device("cuda", e.device)
+    shapes = shapes.contiguous()
+    first = []                                   # the address of every image's first byte
+    for b, ((k, off), (h, w, ch)) in enumerate(zip(src.tolist(), shapes.tolist())):
+        if not 0 <= k < len(bufs) or off < 0:
+            raise ValueError(f"src[{b}] = ({k}, {off}) does not name a byte of bufs")
+        if h >= 1 and w >= 1 and ch >= 1 and off + h * w * ch > bufs[k].numel():      # (anything else is the engine's to refuse)
+            raise ValueError(f"image {b}: {h}x{w}x{ch} bytes from offset {off} reach beyond bufs[{k}] ({bufs[k].numel()} bytes)")
+        first.append(bufs[k].data_ptr() + off)
+    base = min(first) if first else 0
+    offsets = torch.tensor([p - base for p in first], dtype=torch.int64)
+    box = torch.empty((B, int(channels), int(Hc), int(Wc)), device=dev, dtype=torch.float32)
+    if os.environ.get("TXO_DEBUG_POISON"):      # tests: an element the kernel left unwritten shows as nan
+        box.fill_(float("nan"))
+    sizes = torch.zeros((B, 2), dtype=torch.int32)
+    _call(e, "txo_ingest_u8", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), B, int(channels), int(Hc), int(Wc),
+          box.data_ptr(), _i32p(sizes))
+    return box, sizes
+
+
+@ingest_u8.register_fake
+def _(bufs, src, shapes, engine, channels, Hc, Wc):
+    B = shapes.shape[0]
+    return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
+
+
+def pack_u8(images: Sequence, in_channels: int, device, *, engine: int) -> PackedImages:
+    """Raw uint8 pixels -> the container of a ragged batch, prepared on the DEVICE: the counterpart of
+    pack_ragged([wrapper._tensor(im) for im in images]), bit for bit, with one host-to-device copy of the pixel BYTES and one launch
+    (texocr::ingest_u8 on the engine `engine`) instead of a float32 conversion, a copy and a slice assignment per image.
+    images: PIL images, numpy arrays or uint8 tensors (CPU or `device`) of shape (H, W), (H, W, 3) or (H, W, 4) -- L, RGB, RGBA (alpha is
+    ignored); sizes need not be multiples of 16 (the pad is zero).  Host images are concatenated into one buffer (every offset aligned to
+    16) and sent in one copy; device tensors are used where they lie if they are contiguous."""
+    staged, dev, src, shapes = plan_u8(images)
+    device = torch.device(device)
+    Hc, Wc = box_u8(shapes)
+    box, sizes = torch.ops.texocr.ingest_u8([staged.to(device)] + dev, src, shapes, int(engine), int(in_channels), Hc, Wc)
+    return PackedImages(box, sizes)

@@ -89,6 +89,16 @@ class TeXOCRWrapper:
             x = x.expand(self.dims.in_channels, -1, -1)
         return x.contiguous()
 
+    def _images(self, imgs: Sequence, ingest: str):
+        """imgs as one ragged call takes them -- ingest='host': a list of (C, H_b, W_b) tensors on the device, every image preprocessed
+        on the host and copied on its own (the path that has always been there); 'device': ONE OCRModel.ingest over the raw pixels (a
+        PackedImages, bit for bit the container the host path ends in)"""
+        if ingest == "device":
+            return self.model.ingest(imgs)
+        if ingest != "host":
+            raise ValueError(f"ingest must be 'host' or 'device', got {ingest!r}")
+        return [self._tensor(im).cuda() for im in imgs]
+
     def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool):
         """decode='beam': one OCRModel.beam_search over the images xs (a (B, C, H, W) tensor or a list of (C, H_b, W_b)) -> per image
         (the best beam's tokens up to and including its eos, their log-probabilities or None)"""
@@ -117,7 +127,7 @@ class TeXOCRWrapper:
 
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-              length_alpha: float = 0.0, prefix: Optional[Sequence] = None) -> List[tuple]:
+              length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host") -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -129,7 +139,11 @@ class TeXOCRWrapper:
         decode='beam': every image's best beam of `beams` (OCRModel.beam_search, ranked with length_alpha), from ONE ragged beam search
         per chunk of max_batch // beams images; temp and seed play no part.  A max_batch below beams is a ValueError.
         prefix=[...]: one LaTeX string or token list per image that the decode continues (BOS is put in front; OCRModel.generate_ragged
-        with prefix= / prefix_len=): `tokens` (and logp) is the continuation, `latex` is decoded from prefix + continuation."""
+        with prefix= / prefix_len=): `tokens` (and logp) is the continuation, `latex` is decoded from prefix + continuation.
+        ingest='device' (build extension; default 'host'): every chunk's images go to the device as raw uint8 pixels in ONE copy and are
+        preprocessed there by ONE launch (OCRModel.ingest) instead of one float32 conversion, copy and slice assignment per image.  imgs may
+        then also hold uint8 numpy arrays or tensors (H, W), (H, W, 3) or (H, W, 4).  The container is bit for bit the host path's, so
+        every result is identical."""
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
         pre = plen = prows = None
@@ -139,14 +153,15 @@ class TeXOCRWrapper:
             pre, plen, prows, max_len = self._prefix_rows(prefix, decode, return_align, max_len)
         step = beam_chunk(eng.max_batch, beams) if decode == "beam" else eng.max_batch
         out: List[tuple] = []
-        xs = [self._tensor(im).cuda() for im in imgs]
-        for c0 in range(0, len(xs), step):
+        xs = self._images(imgs, ingest) if ingest != "device" else None
+        for c0 in range(0, len(imgs), step):
+            chunk = xs[c0:c0 + step] if xs is not None else self._images(imgs[c0:c0 + step], ingest)
             if decode == "beam":
-                full, logp = self._best_beams(xs[c0:c0 + step], beams, max_len, length_alpha, return_logp)
+                full, logp = self._best_beams(chunk, beams, max_len, length_alpha, return_logp)
             else:
                 chunk_seed = None if seed is None else int(seed) + c0 // step
                 kw = {} if pre is None else dict(prefix=pre[c0:c0 + step].cuda(), prefix_len=plen[c0:c0 + step])
-                toks = self.model.generate_ragged(xs[c0:c0 + step], max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
+                toks = self.model.generate_ragged(chunk, max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
                                                   return_logp=return_logp, **kw)
                 toks, logp = toks[:2] if return_logp else (toks, None)
                 full = [cut_at_eos(row, self.model.eos_token) for row in toks.tolist()]
@@ -154,7 +169,7 @@ class TeXOCRWrapper:
             maps = None
             if return_align:
                 trg, mask = align_inputs(full, self.model.bos_token, self.model.trg_pad_idx)
-                maps = [a.maps[0].cpu() for a in self.model.align_ragged(xs[c0:c0 + step], trg.cuda(), mask=mask.cuda())]
+                maps = [a.maps[0].cpu() for a in self.model.align_ragged(chunk, trg.cuda(), mask=mask.cuda())]
             for b, row in enumerate(full):
                 row = row[:-1]                                                        # ocr_model.py:104 (drops the last token)
                 latex = process_output(self.tokenizer.decode(row if prows is None else prows[c0 + b] + row))
@@ -164,7 +179,7 @@ class TeXOCRWrapper:
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-                 length_alpha: float = 0.0, prefix=None) -> tuple:
+                 length_alpha: float = 0.0, prefix=None, ingest: str = "host") -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
@@ -172,8 +187,10 @@ class TeXOCRWrapper:
         decode='beam' (build extension): the best of `beams` beams (OCRModel.beam_search, ranked with length_alpha), cut at its eos;
         max_len is capped at the positional table; temp and seed play no part.
         prefix= (a LaTeX string or a token list): the decode continues it (BOS is put in front; OCRModel.generate(prefix=)); `tokens` (and
-        logp) is the continuation, `latex` is decoded from prefix + continuation; max_len is capped so that both fit the positional table."""
-        x = self._tensor(img)[None].cuda()
+        logp) is the continuation, `latex` is decoded from prefix + continuation; max_len is capped so that both fit the positional table.
+        ingest='device': the image is preprocessed on the device (see batch); the result is identical."""
+        x = self._images([img], ingest)
+        x = x.box if ingest == "device" else x[0][None]
         prow: List[int] = []
         gen_kw = {}
         if prefix is not None:
