@@ -359,6 +359,39 @@ int txo_ingest_box(const int32_t* shapes_host, int32_t B, int32_t* Hc_out, int32
 int txo_ingest_u8(txo_engine* e, const uint8_t* pix_dev, const int64_t* offsets_host, const int32_t* shapes_host, int32_t B, int32_t C,
                   int32_t Hc, int32_t Wc, float* box_out_dev, int32_t* sizes_out_host, void* stream);
 
+/* ---- Fit-to-canvas ingest (a BUILD EXTENSION; opt-in: txo_ingest_u8 is unchanged and keeps refusing what does not fit) ----
+ * An image with a side beyond the target (Fh, Fw) -- both positive multiples of 16, usually the canvas -- is DOWNSCALED to fit it, aspect
+ * ratio kept, on the device in front of the ingest arithmetic (texocr_amd/csrc/ingest_fit.h).  The rule, for an image (h, w), in 64-bit
+ * integers:  h <= Fh and w <= Fw: unchanged (never upscaled; it takes txo_ingest_u8's path and bytes);  else if w * Fh <= h * Fw:
+ * h' = Fh, w' = max(1, (w * Fh) / h);  else w' = Fw, h' = max(1, (h * Fw) / w).
+ * The fitted pixels are bit for bit PIL's Image.resize((w', h'), BILINEAR) applied to the uint8 channels the ingest reads: L as it is, R, G, B
+ * of RGB and RGBA (alpha is not read: img.convert('RGB').resize(...), NOT PIL's own RGBA resize, which premultiplies).  That resample is
+ * integer arithmetic: two passes (horizontal into a uint8 intermediate, then vertical; a pass whose axis keeps its size is skipped), each
+ * out = clamp((2^21 + sum_x K[x] src[xmin + x]) >> 22, 0, 255) over a window and coefficients K[x] = (int)(0.5 + k[x] * 2^22) that
+ * txo_ingest_fit_coeffs returns; they come from IEEE double operations rounded one by one (tests/fit_ref.py restates them).  The fitted
+ * bytes then go through txo_ingest_u8's arithmetic unchanged.  An axis that would shrink by more than 32 times (in > 32 * out) is refused
+ * before anything is enqueued, with a message naming the image: 32 bounds the taps per output pixel (TXO_FIT_TAPS), not the quality.
+ *   txo_ingest_fit          fitted_out_host int32 [B][2] = (h', w') by the rule above.  No engine needed.  txo_ingest_box composes with it:
+ *                           call it on shapes whose (h, w) are the fitted ones.
+ *   txo_ingest_fit_scratch  *bytes_out = the device scratch txo_ingest_u8_fit needs for this list: one uint8 intermediate h x w' x (1 or 3),
+ *                           rounded up to 16 bytes, per image whose width changes; 0 when nothing is oversized.  No engine needed.
+ *   txo_ingest_fit_coeffs   one axis with `in` source and `out` target pixels, in <= 32 * out: xmin_out [out], n_out [out] and
+ *                           K_out [out][TXO_FIT_TAPS] (zeros behind n).  No engine, no device: the very function the kernels run.
+ *   txo_ingest_u8_fit       txo_ingest_u8 with the fit in front: the container holds the FITTED images and sizes_out_host is the fitted sizes
+ *                           rounded up to 16, so (Hc, Wc) need only hold those.  scratch_dev / scratch_bytes: at least what
+ *                           txo_ingest_fit_scratch returns (may be NULL / 0 when that is 0); it is written by this call and free again when
+ *                           the call's work on `stream` is done.  Every refusal of txo_ingest_u8 (on the fitted sizes), as early as there,
+ *                           and: Fh or Fw not a positive multiple of 16, a scale above 32, scratch too small or null when needed.  With no
+ *                           oversized image the launch, the container and the sizes are txo_ingest_u8's.  Asynchronous; no allocation;
+ *                           under txo_profile_enable(e, 1) every launch carries events (txo_profile_read kind 4). */
+#define TXO_FIT_TAPS 65
+int txo_ingest_fit(const int32_t* shapes_host, int32_t B, int32_t Fh, int32_t Fw, int32_t* fitted_out_host);
+int txo_ingest_fit_scratch(const int32_t* shapes_host, int32_t B, int32_t Fh, int32_t Fw, int64_t* bytes_out);
+int txo_ingest_fit_coeffs(int32_t in, int32_t out, int32_t* xmin_out, int32_t* n_out, int32_t* K_out);
+int txo_ingest_u8_fit(txo_engine* e, const uint8_t* pix_dev, const int64_t* offsets_host, const int32_t* shapes_host, int32_t B, int32_t C,
+                      int32_t Fh, int32_t Fw, int32_t Hc, int32_t Wc, float* box_out_dev, int32_t* sizes_out_host, void* scratch_dev,
+                      int64_t scratch_bytes, void* stream);
+
 /* Token selection for the following decode steps / generate calls.  mode 0 (default): greedy argmax.  mode 1:
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits
  * (the reference uses int((1 - 0.9) * vocab) = 99 for vocab 1000), softmax(logits / temp), one multinomial draw,
@@ -385,7 +418,7 @@ int txo_set_stop_mode(txo_engine* e, int32_t mode);
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
  * enabled (txo_profile_enable(e, 1) also clears the previous samples); *count = number of launches averaged.  kind: 0 = cross-attention decode kernel,
- * 1 = encoder (whole txo_encode), 2 = whole decode step, 4 = the ingest kernel of txo_ingest_u8 (events bound to the dispatch).
+ * 1 = encoder (whole txo_encode), 2 = whole decode step, 4 = the ingest kernel of txo_ingest_u8 and the launches of txo_ingest_u8_fit (events bound to the dispatch).
  * on = 1: everything above (adds marker commands around every encode and step -- use in a separate pass); on = 2: only every
  * fourth cross-attention dispatch carries events (bound to the dispatch, no extra commands; safe inside a timed region; samples are
  * kept for the first 16 generate() calls after enabling); on = 3: the persistent decode launch carries events (kind 3 =

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("TXO_LIB_PATH") or os.path.join(_HERE, "libtexocr_hip.
 
 TXO_F32, TXO_BF16 = 0, 1
 TXO_E_INVALID, TXO_E_STATE, TXO_E_HIP = -1, -2, -3
+TXO_FIT_TAPS = 65        # include/texocr.h: the K_out row length of txo_ingest_fit_coeffs
 # txo_engine_query codes (include/texocr.h: TXO_Q_*; tests/test_abi_cpu.py holds the two lists together)
 (Q_LAST_PERSISTENT, Q_PERSIST_FALLBACKS, Q_LAST_ROW_RANGES, Q_LAST_LATENT, Q_RELOAD_KNOBS, Q_LAST_COMPACTIONS,
  Q_SAMPLE_VOCAB_MAX, Q_LAST_RAGGED, Q_LAST_LATENT_SELF) = 0, 1, 2, 3, 4, 5, 6, 7, 8
@@ -65,6 +66,11 @@ SYMBOLS = {
     "txo_generate_ragged_logp": (C.c_int, [_P, _FP, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I64P, C.POINTER(C.c_int32), _FP, _P]),
     "txo_ingest_box": (C.c_int, [C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "txo_ingest_u8": (C.c_int, [_P, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _I, _I, _I, _FP, C.POINTER(C.c_int32), _P]),
+    "txo_ingest_fit": (C.c_int, [C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(C.c_int32)]),
+    "txo_ingest_fit_scratch": (C.c_int, [C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(C.c_int64)]),
+    "txo_ingest_fit_coeffs": (C.c_int, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "txo_ingest_u8_fit": (C.c_int, [_P, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _I, _I, _I, _I, _I, _FP, C.POINTER(C.c_int32),
+                                    C.c_void_p, C.c_int64, _P]),
     "txo_set_sampling": (C.c_int, [_P, _I, _I, C.c_float, C.c_uint64]),
     "txo_set_stop_mode": (C.c_int, [_P, _I]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),

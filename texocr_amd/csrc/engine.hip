@@ -46,6 +46,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "step.h"
 #include "step_prefix.h"   // (behind every other kernel: the kernels above keep their places in the code object)
 #include "ingest.h"        // (likewise: the newest kernel goes last)
+#include "ingest_fit.h"    // (the fit-to-canvas passes in front of it; uses ingest.h's per-pixel pieces)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -105,6 +106,9 @@ struct EngineBase {
     // txo_ingest_u8 behind its checks (ingest_check): descriptors up in one staged copy, one launch
     virtual int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc, float* box,
                           hipStream_t s) = 0;
+    // txo_ingest_u8_fit behind its checks, with at least one oversized image: fitted [B][2] from ingest_fit_sizes, scratch holds the intermediates
+    virtual int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* fitted, int B, int C, int Hc,
+                              int Wc, float* box, unsigned char* scratch, hipStream_t s) = 0;
     virtual int query(int what, int64_t* out) = 0;
     virtual int profile_enable(int on) = 0;
     virtual int profile_read(int kind, double* avg_ms, int64_t* count) = 0;
@@ -212,6 +216,9 @@ struct Engine : EngineBase {
     bool last_ragged = false;         // TXO_Q_LAST_RAGGED
     // device-side image ingest (ingest.h): the descriptors [Bmax] of the list on the device, their pinned staging, its last copy
     IngestDesc *ing_desc = nullptr, *ing_host = nullptr; hipEvent_t ing_ev = nullptr; bool ing_ev_pending = false;
+    // fit-to-canvas ingest (ingest_fit.h): FitDesc [Bmax] followed by the list int [Bmax] of the images that need a horizontal pass; staged like ing_host
+    char *fit_dev = nullptr, *fit_host = nullptr;
+    size_t fit_bytes(int B) const { return (sizeof(FitDesc) + sizeof(int)) * (size_t)B; }
     int rag_box[2] = {0, 0};          // the smallest H x W (multiples of 16) that holds every image of the last ragged batch
     // rag_fwd off (the default): these calls answer as they did before the forward had a ragged form
     int refuse_ragged_forward(const std::string& call) const {
@@ -251,6 +258,7 @@ struct Engine : EngineBase {
         if (rag_host) (void)hipHostFree(rag_host);
         if (rag_ev) (void)hipEventDestroy(rag_ev);
         if (ing_host) (void)hipHostFree(ing_host);
+        if (fit_host) (void)hipHostFree(fit_host);
         if (ing_ev) (void)hipEventDestroy(ing_ev);
         for (void* p : allocs) (void)hipFree(p);
     }
@@ -594,6 +602,7 @@ struct Engine : EngineBase {
         rag_stage.assign((size_t)3 * Bmax, 0);
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ing_host), sizeof(IngestDesc) * (size_t)Bmax, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&ing_ev, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&fit_host), fit_bytes(Bmax), hipHostMallocDefault));
         return lanes.init(Tmax);
     }
     int init_buffers() {
@@ -703,6 +712,7 @@ struct Engine : EngineBase {
         if (int r = dalloc(&pctl, 1)) return r;
         if (int r = dalloc(&pstamps, (size_t)PS_TEAMS * PS_STAMP_RANKS * PS_MAX_STAGES * PS_STAMP_WORDS)) return r;
         if (int r = dalloc(&ing_desc, (size_t)Bmax)) return r;   // (last: no earlier buffer moves)
+        if (int r = dalloc(&fit_dev, fit_bytes(Bmax))) return r;
         return 0;
     }
 
@@ -1003,6 +1013,51 @@ struct Engine : EngineBase {
             ev_ingest.push_back({e0, e1});
         } else {
             hipLaunchKernelGGL(ingest_u8_kernel, grid, blk, 0, s, pix, ing_desc, box, C, Hc, Wc);
+        }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    // Fit-to-canvas ingest (ingest_fit.h).  The list has passed ingest_fit_check and holds an oversized image.  One staged copy of the
+    // descriptors and of the list of images with a horizontal pass, then that pass (if any image has one) and the fused vertical pass + ingest.
+    int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* fitted, int B, int C, int Hc, int Wc,
+                      float* box, unsigned char* scratch, hipStream_t s) override {
+        if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
+        if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
+        FitDesc* fd = reinterpret_cast<FitDesc*>(fit_host);
+        int* hl = reinterpret_cast<int*>(fit_host + sizeof(FitDesc) * (size_t)B);
+        long long mid = 0;
+        int nh = 0, hmax = 0, wmax = 0;
+        for (int b = 0; b < B; ++b) {
+            const int h = shapes[3 * b], w = shapes[3 * b + 1], ch = shapes[3 * b + 2], fh = fitted[2 * b], fw = fitted[2 * b + 1];
+            fd[b] = FitDesc{(long long)offsets[b], -1, h, w, ch, fh, fw, 0};
+            if (fw != w) {
+                fd[b].mid = mid;
+                mid += ingest_fit_mid_bytes(h, fw, ch);
+                hl[nh++] = b;
+                hmax = std::max(hmax, h); wmax = std::max(wmax, fw);
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(fit_dev, fit_host, fit_bytes(B), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ing_ev, s));
+        ing_ev_pending = true;
+        const FitDesc* dd = reinterpret_cast<const FitDesc*>(fit_dev);
+        const int* dl = reinterpret_cast<const int*>(fit_dev + sizeof(FitDesc) * (size_t)B);
+        const dim3 hgrid((unsigned)((wmax + FR_COLS - 1) / FR_COLS), (unsigned)((hmax + FR_ROWS - 1) / FR_ROWS), (unsigned)nh), hblk(FR_COLS * FR_LANES_Y);
+        const dim3 grid((unsigned)((Wc + IG_BLOCK_W - 1) / IG_BLOCK_W), (unsigned)((Hc + IG_ROWS - 1) / IG_ROWS), (unsigned)B), blk(IG_LANES_X * IG_ROWS);
+        if (prof) {                                           // txo_profile_read kind 4: events bound to each dispatch
+            if (nh) {
+                hipEvent_t h0 = pool.next(), h1 = pool.next();
+                if (!h0 || !h1) return fail(TXO_E_HIP, "hipEventCreate failed");
+                hipExtLaunchKernelGGL(fit_rows_kernel, hgrid, hblk, 0, s, h0, h1, 0, pix, dd, dl, scratch);
+                ev_ingest.push_back({h0, h1});
+            }
+            hipEvent_t e0 = pool.next(), e1 = pool.next();
+            if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
+            hipExtLaunchKernelGGL(ingest_fit_kernel, grid, blk, 0, s, e0, e1, 0, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
+            ev_ingest.push_back({e0, e1});
+        } else {
+            if (nh) hipLaunchKernelGGL(fit_rows_kernel, hgrid, hblk, 0, s, pix, dd, dl, scratch);
+            hipLaunchKernelGGL(ingest_fit_kernel, grid, blk, 0, s, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
         }
         HIP_TRY(hipGetLastError());
         return 0;
@@ -2353,9 +2408,8 @@ static int ingest_check_shapes(const int32_t* shapes, int B, long long* box) {
     return 0;
 }
 
-// everything txo_ingest_u8 refuses about the list and the container, before the engine or the device is looked at
-static int ingest_check(const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc) {
-    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+// what txo_ingest_u8 refuses about the offsets and the container, for a list that has passed ingest_check_shapes
+static int ingest_check_container(const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc) {
     if (!offsets) return fail(TXO_E_INVALID, "ingest: null offsets");
     if (C < 1) return fail(TXO_E_INVALID, "ingest: the container's channel count must be >= 1");
     if (Hc < 1 || Wc < 1) return fail(TXO_E_INVALID, "ingest: the container's height/width must be positive");
@@ -2370,6 +2424,38 @@ static int ingest_check(const int64_t* offsets, const int32_t* shapes, int B, in
                                            std::to_string(w16) + " rounded up to multiples of 16: it does not fit the container's " + std::to_string(Hc) + "x" +
                                            std::to_string(Wc));
     }
+    return 0;
+}
+
+// everything txo_ingest_u8 refuses about the list and the container, before the engine or the device is looked at
+static int ingest_check(const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc) {
+    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+    return ingest_check_container(offsets, shapes, B, C, Hc, Wc);
+}
+
+// ---- fit-to-canvas ingest: the rule, the scratch and the refusals, none of which needs an engine (texocr.h: txo_ingest_fit ...) -----------
+// *fitted (may be null; sized here, once the list has passed) [B][2] = (h', w') of every image under the target (Fh, Fw); *scratch (may be
+// null): the bytes of the horizontal passes' intermediates
+static_assert(TXO_FIT_TAPS == FIT_TAPS, "texocr.h and ingest_fit.h disagree on the taps per output pixel");
+static int ingest_fit_sizes(const int32_t* shapes, int B, int Fh, int Fw, std::vector<int32_t>* fitted, long long* scratch) {
+    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+    if (fitted) fitted->assign((size_t)2 * B, 0);
+    if (Fh < 16 || Fh % 16 || Fw < 16 || Fw % 16)
+        return fail(TXO_E_INVALID, "ingest: the fit target is " + std::to_string(Fh) + "x" + std::to_string(Fw) + "; both sides must be positive multiples of 16");
+    if ((32LL * Fh + FR_ROWS - 1) / FR_ROWS > 65535) return fail(TXO_E_INVALID, "ingest: the fit target's height exceeds the launch grid");
+    long long need = 0;
+    for (int b = 0; b < B; ++b) {
+        const int h = shapes[3 * b], w = shapes[3 * b + 1];
+        int fh, fw;
+        fit_size(h, w, Fh, Fw, &fh, &fw);
+        if ((long long)h > (long long)FIT_MAX_SCALE * fh || (long long)w > (long long)FIT_MAX_SCALE * fw)
+            return fail(TXO_E_INVALID, "ingest: image " + std::to_string(b) + " is " + std::to_string(h) + "x" + std::to_string(w) + ", " + std::to_string(fh) + "x" +
+                                           std::to_string(fw) + " fitted to " + std::to_string(Fh) + "x" + std::to_string(Fw) + ": an axis shrinks by more than " +
+                                           std::to_string(FIT_MAX_SCALE) + " times");
+        if (fitted) { (*fitted)[2 * b] = fh; (*fitted)[2 * b + 1] = fw; }
+        if (fw != w) need += ingest_fit_mid_bytes(h, fw, shapes[3 * b + 2]);
+    }
+    if (scratch) *scratch = need;
     return 0;
 }
 
@@ -2462,6 +2548,63 @@ int txo_ingest_u8(txo_engine* e, const uint8_t* pix, const int64_t* offsets, con
     if (reinterpret_cast<uintptr_t>(box_out) % 16) return fail(TXO_E_INVALID, "ingest: the container must be 16-byte aligned (rows are written in 16-byte pieces)");
     if (int r = e->impl->ingest_u8(pix, offsets, shapes, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
     for (int b = 0; b < B; ++b) { sizes_out[2 * b] = (int32_t)ingest_round16(shapes[3 * b]); sizes_out[2 * b + 1] = (int32_t)ingest_round16(shapes[3 * b + 1]); }
+    return 0;
+}
+
+int txo_ingest_fit(const int32_t* shapes, int32_t B, int32_t Fh, int32_t Fw, int32_t* fitted_out) {
+    if (!fitted_out) return fail(TXO_E_INVALID, "ingest: null argument");
+    std::vector<int32_t> fitted;                                      // (nothing is written on a refusal)
+    if (int r = ingest_fit_sizes(shapes, B, Fh, Fw, &fitted, nullptr)) return r;
+    memcpy(fitted_out, fitted.data(), sizeof(int32_t) * 2 * (size_t)B);
+    return 0;
+}
+
+int txo_ingest_fit_scratch(const int32_t* shapes, int32_t B, int32_t Fh, int32_t Fw, int64_t* bytes_out) {
+    if (!bytes_out) return fail(TXO_E_INVALID, "ingest: null argument");
+    long long need = 0;
+    if (int r = ingest_fit_sizes(shapes, B, Fh, Fw, nullptr, &need)) return r;
+    *bytes_out = need;
+    return 0;
+}
+
+int txo_ingest_fit_coeffs(int32_t in, int32_t out, int32_t* xmin_out, int32_t* n_out, int32_t* K_out) {
+    if (!xmin_out || !n_out || !K_out) return fail(TXO_E_INVALID, "ingest: null argument");
+    if (in < 1 || out < 1) return fail(TXO_E_INVALID, "ingest: fit coefficients need in >= 1 and out >= 1");
+    if ((long long)in > (long long)FIT_MAX_SCALE * out)
+        return fail(TXO_E_INVALID, "ingest: fit coefficients for " + std::to_string(in) + " -> " + std::to_string(out) + ": the axis shrinks by more than " +
+                                       std::to_string(FIT_MAX_SCALE) + " times");
+    for (int xx = 0; xx < out; ++xx) {
+        int* K = K_out + (size_t)xx * TXO_FIT_TAPS;
+        std::fill(K, K + TXO_FIT_TAPS, 0);
+        int xmin, n;
+        fit_axis_coeffs(in, out, xx, &xmin, &n, K, 1, 0, 1);
+        xmin_out[xx] = xmin; n_out[xx] = n;
+    }
+    return 0;
+}
+
+// (as txo_ingest_u8: the list, the target, the container and the scratch are checked before the engine or the device is looked at)
+int txo_ingest_u8_fit(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Fh, int32_t Fw,
+                      int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes, void* stream) {
+    std::vector<int32_t> fitted;
+    long long need = 0;
+    if (int r = ingest_fit_sizes(shapes, B, Fh, Fw, &fitted, &need)) return r;        // (the list is checked here, once)
+    std::vector<int32_t> fshapes((size_t)3 * B);
+    bool oversized = false;
+    for (int b = 0; b < B; ++b) {
+        fshapes[3 * b] = fitted[2 * b]; fshapes[3 * b + 1] = fitted[2 * b + 1]; fshapes[3 * b + 2] = shapes[3 * b + 2];
+        oversized = oversized || fitted[2 * b] != shapes[3 * b] || fitted[2 * b + 1] != shapes[3 * b + 1];
+    }
+    if (int r = ingest_check_container(offsets, fshapes.data(), B, C, Hc, Wc)) return r;   // (the container holds the FITTED sizes)
+    if (need > 0 && (!scratch || scratch_bytes < need))
+        return fail(TXO_E_INVALID, "ingest: the fit scratch is " + (scratch ? std::to_string((long long)scratch_bytes) + " bytes" : std::string("null")) +
+                                       "; the horizontal passes of this list need " + std::to_string(need) + " bytes (txo_ingest_fit_scratch)");
+    if (!e || !pix || !box_out || !sizes_out) return fail(TXO_E_INVALID, "ingest: null argument");
+    if (reinterpret_cast<uintptr_t>(box_out) % 16) return fail(TXO_E_INVALID, "ingest: the container must be 16-byte aligned (rows are written in 16-byte pieces)");
+    // nothing oversized: txo_ingest_u8's own launch, its container bit for bit
+    if (int r = oversized ? e->impl->ingest_u8_fit(pix, offsets, shapes, fitted.data(), B, C, Hc, Wc, box_out, (unsigned char*)scratch, (hipStream_t)stream)
+                          : e->impl->ingest_u8(pix, offsets, shapes, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
+    for (int b = 0; b < B; ++b) { sizes_out[2 * b] = (int32_t)ingest_round16(fitted[2 * b]); sizes_out[2 * b + 1] = (int32_t)ingest_round16(fitted[2 * b + 1]); }
     return 0;
 }
 

@@ -49,6 +49,8 @@ __global__ __launch_bounds__(IG_LANES_X * IG_ROWS) void ingest_u8_kernel(const u
     if ((int)blockIdx.y * IG_ROWS < d.h && (int)blockIdx.x * IG_BLOCK_W < d.w) {
         unit[threadIdx.x] = __fdiv_rn((float)threadIdx.x, 255.0f);
         __syncthreads();
+        // (ingest_fit.h: ingest_fit_kernel restates this block, statement for statement, for the images of a fitted batch that keep their
+        // height; a change here goes there too, or a mixed batch stops being bit for bit this kernel's -- tests/test_gpu_ingest_fit.py)
         if (y < d.h && x0 < d.w) {
             const unsigned char* p = pix + d.off + ((long long)y * d.w + x0) * d.ch;
             const int n = d.w - x0;                              // pixels of this row from x0 on: the piece reads min(n, 4) of them

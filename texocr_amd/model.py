@@ -238,10 +238,12 @@ class HipEngine:
 
     # ---- ragged batches (build extension): images of different sizes in one call; `images` is a sequence of (C, H_b, W_b) tensors, or a
     # container that already exists (ops.PackedImages: what ingest returns) ----
-    def ingest(self, images) -> "ops.PackedImages":
+    def ingest(self, images, fit: bool = False) -> "ops.PackedImages":
         """Device-side image ingest (txo_ingest_u8): raw uint8 images (PIL, numpy, uint8 tensors on the CPU or this device; L, RGB, RGBA) ->
-        the container of a ragged batch, in one copy of the pixel bytes and one launch.  Needs no weights."""
-        return ops.pack_u8(images, self.dims.in_channels, torch.device("cuda", self.device), engine=self.id)
+        the container of a ragged batch, in one copy of the pixel bytes and one launch.  Needs no weights.  fit=True (txo_ingest_u8_fit): an
+        image beyond the canvas is downscaled on the device to fit it."""
+        return ops.pack_u8(images, self.dims.in_channels, torch.device("cuda", self.device), engine=self.id,
+                           fit=self.dims.canvas_hw if fit else None)
 
     def encode_ragged(self, images):
         """-> (enc (B, Ns, D) with zero rows behind each image's own token count, n_tokens (B,) int32 CPU)"""
@@ -999,15 +1001,20 @@ class OCRModel(nn.Module):
             return eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
 
     @torch.no_grad()
-    def ingest(self, images) -> "ops.PackedImages":
+    def ingest(self, images, fit: bool = False) -> "ops.PackedImages":
         """Build extension: device-side image ingest.  A list of raw uint8 images of any sizes -- PIL images, numpy arrays or uint8 tensors
         (on the CPU or the model's device) of shape (H, W), (H, W, 3) or (H, W, 4): L, RGB, RGBA with the alpha ignored -> PackedImages(box
         (B, in_channels, Hc, Wc) float32, sizes (B, 2) int32 CPU), from ONE copy of the pixel bytes and ONE launch (txo_ingest_u8).  box is
         bit for bit ops.pack_ragged of the images preprocessed on the host (wrapper.preprocess_image: ToTensor -> Grayscale -> Invert, zero
         pad to multiples of 16, expanded to in_channels).  Every *_ragged method, beam_search and generate_ragged(prefix=) take the result
         in place of a list of (C, H_b, W_b) tensors; if all images have one size, box is a valid (B, C, H, W) for generate / score / align /
-        beam_search.  PIL modes other than L / RGB / RGBA are converted with convert('RGB') on the host first."""
-        return self._engine.ingest(images)
+        beam_search.  PIL modes other than L / RGB / RGBA are converted with convert('RGB') on the host first.
+        fit=True (default False: an image beyond the canvas is refused by the call that takes the container, as ever): every image with a
+        side beyond the canvas (dims.canvas_hw) is downscaled on the device to fit it, aspect ratio kept (ops.fit_size; never upscaled), bit
+        for bit PIL's Image.resize(..., BILINEAR) of its L / RGB channels -- an RGBA image is fitted on its RGB channels, the alpha is not
+        read -- and `sizes` holds the fitted sizes.  Still one copy of the raw bytes.  An axis that would shrink by more than 32 times is a
+        ValueError naming the image."""
+        return self._engine.ingest(images, fit=fit)
 
     @torch.no_grad()
     def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0) -> Beams:

@@ -26,6 +26,8 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
                             decode_prefill / decode_score / decode_attn / decode_set_key_mask run on a ragged session as on any other
   texocr::ingest_u8         (build extension) the raw uint8 pixels of B images of different sizes and channel counts -> that container, on
                             the device in one launch, bit for bit what the host preprocessing makes of them (``pack_u8`` is its front end)
+  texocr::ingest_u8_fit     (build extension) the same with every image beyond a target size downscaled to fit it first, bit for bit PIL's
+                            BILINEAR resize (``pack_u8(..., fit=(Fh, Fw))``)
 
 An engine is named by an integer id (operators take tensors and scalars only); ``register_engine`` hands one out.
 There is no CPU implementation: calling an operator on CPU tensors raises.
@@ -829,6 +831,16 @@ def ingest_u8(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Ten
     shapes (B, 3) int32 CPU = (h, w, ch) -> (box (B, channels, Hc, Wc) float32 with every element written, sizes (B, 2) int32 CPU = (h, w)
     rounded up to 16).  One launch; the refusals are the engine's (ValueError with its message)."""
     e = _eng(engine)
+    base, offsets, shapes = _u8_source(bufs, src, shapes, e)
+    B = int(shapes.shape[0])
+    box, sizes = _u8_outputs(e, B, channels, Hc, Wc)
+    _call(e, "txo_ingest_u8", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), B, int(channels), int(Hc), int(Wc),
+          box.data_ptr(), _i32p(sizes))
+    return box, sizes
+
+
+def _u8_source(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Tensor, e):
+    """the checks texocr::ingest_u8 and ingest_u8_fit share -> (base address, offsets (B,) int64 CPU from it, shapes contiguous)"""
     B = int(shapes.shape[0])
     if src.is_cuda or src.dtype != torch.int64 or tuple(src.shape) != (B, 2):
         raise ValueError("src must be an int64 CPU tensor of shape (B, 2) = (index into bufs, byte offset)")
@@ -839,7 +851,6 @@ def ingest_u8(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Ten
             raise ValueError(f"bufs[{k}] must be a contiguous uint8 GPU tensor")
         if t.device.index != e.device:
             raise ValueError(f"bufs[{k}] lives on cuda:{t.device.index} but the engine was created on cuda:{e.device}")
-    dev = torch.device("cuda", e.device)
     shapes = shapes.contiguous()
     first = []                                   # the address of every image's first byte
     for b, ((k, off), (h, w, ch)) in enumerate(zip(src.tolist(), shapes.tolist())):
@@ -849,14 +860,14 @@ def ingest_u8(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Ten
             raise ValueError(f"image {b}: {h}x{w}x{ch} bytes from offset {off} reach beyond bufs[{k}] ({bufs[k].numel()} bytes)")
         first.append(bufs[k].data_ptr() + off)
     base = min(first) if first else 0
-    offsets = torch.tensor([p - base for p in first], dtype=torch.int64)
-    box = torch.empty((B, int(channels), int(Hc), int(Wc)), device=dev, dtype=torch.float32)
+    return base, torch.tensor([p - base for p in first], dtype=torch.int64), shapes
+
+
+def _u8_outputs(e, B: int, channels: int, Hc: int, Wc: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    box = torch.empty((B, int(channels), int(Hc), int(Wc)), device=torch.device("cuda", e.device), dtype=torch.float32)
     if os.environ.get("TXO_DEBUG_POISON"):      # tests: an element the kernel left unwritten shows as nan
         box.fill_(float("nan"))
-    sizes = torch.zeros((B, 2), dtype=torch.int32)
-    _call(e, "txo_ingest_u8", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), B, int(channels), int(Hc), int(Wc),
-          box.data_ptr(), _i32p(sizes))
-    return box, sizes
+    return box, torch.zeros((B, 2), dtype=torch.int32)
 
 
 @ingest_u8.register_fake
@@ -865,15 +876,70 @@ def _(bufs, src, shapes, engine, channels, Hc, Wc):
     return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
 
 
-def pack_u8(images: Sequence, in_channels: int, device, *, engine: int) -> PackedImages:
+# ---- fit-to-canvas ingest (txo_ingest_u8_fit): an oversized image is downscaled on the device, bit for bit PIL's BILINEAR resize ----------
+FIT_MAX_SCALE = 32       # an axis that would shrink by more than this is refused (txo_ingest_fit)
+
+
+def fit_size(h: int, w: int, Fh: int, Fw: int) -> Tuple[int, int]:
+    """txo_ingest_fit's rule in Python integers: (h, w) -> the size it is given under the target (Fh, Fw).  An image that fits is unchanged
+    (never upscaled); otherwise the binding side becomes the target's and the other keeps the aspect ratio, rounded down, at least 1."""
+    h, w, Fh, Fw = int(h), int(w), int(Fh), int(Fw)
+    if h <= Fh and w <= Fw:
+        return h, w
+    if w * Fh <= h * Fw:
+        return Fh, max(1, (w * Fh) // h)
+    return max(1, (h * Fw) // w), Fw
+
+
+def fit_shapes(shapes: torch.Tensor, Fh: int, Fw: int) -> torch.Tensor:
+    """shapes (B, 3) = (h, w, ch) -> the same with every (h, w) fitted to (Fh, Fw): what box_u8 sizes the container of a fitted list from"""
+    out = shapes.clone()
+    for b, (h, w, _) in enumerate(shapes.tolist()):
+        if h >= 1 and w >= 1:                    # (anything else is the engine's to refuse)
+            out[b, 0], out[b, 1] = fit_size(h, w, Fh, Fw)
+    return out
+
+
+@custom_op("texocr::ingest_u8_fit", mutates_args=())
+def ingest_u8_fit(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Tensor, engine: int, channels: int, Fh: int, Fw: int,
+                  Hc: int, Wc: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """txo_ingest_u8_fit: texocr::ingest_u8 with every image that exceeds (Fh, Fw) downscaled to fit it first (fit_size; bit for bit PIL's
+    BILINEAR resize of its L / RGB channels) -> (box (B, channels, Hc, Wc), sizes (B, 2) int32 CPU = the FITTED sizes rounded up to 16).
+    The scratch of the horizontal passes (txo_ingest_fit_scratch) is a tensor of this call; nothing is allocated when no image is oversized."""
+    e = _eng(engine)
+    base, offsets, shapes = _u8_source(bufs, src, shapes, e)
+    B = int(shapes.shape[0])
+    need = C.c_int64(0)
+    _lib.check(_lib.load().txo_ingest_fit_scratch(_i32p(shapes), B, int(Fh), int(Fw), C.byref(need)))
+    scratch = torch.empty((need.value,), dtype=torch.uint8, device=torch.device("cuda", e.device)) if need.value else None
+    box, sizes = _u8_outputs(e, B, channels, Hc, Wc)
+    _call(e, "txo_ingest_u8_fit", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), B, int(channels), int(Fh), int(Fw),
+          int(Hc), int(Wc), box.data_ptr(), _i32p(sizes), scratch.data_ptr() if scratch is not None else None, need.value)
+    return box, sizes
+
+
+@ingest_u8_fit.register_fake
+def _(bufs, src, shapes, engine, channels, Fh, Fw, Hc, Wc):
+    B = shapes.shape[0]
+    return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
+
+
+def pack_u8(images: Sequence, in_channels: int, device, *, engine: int, fit: Optional[Tuple[int, int]] = None) -> PackedImages:
     """Raw uint8 pixels -> the container of a ragged batch, prepared on the DEVICE: the counterpart of
     pack_ragged([wrapper._tensor(im) for im in images]), bit for bit, with one host-to-device copy of the pixel BYTES and one launch
     (texocr::ingest_u8 on the engine `engine`) instead of a float32 conversion, a copy and a slice assignment per image.
     images: PIL images, numpy arrays or uint8 tensors (CPU or `device`) of shape (H, W), (H, W, 3) or (H, W, 4) -- L, RGB, RGBA (alpha is
     ignored); sizes need not be multiples of 16 (the pad is zero).  Host images are concatenated into one buffer (every offset aligned to
-    16) and sent in one copy; device tensors are used where they lie if they are contiguous."""
+    16) and sent in one copy; device tensors are used where they lie if they are contiguous.
+    fit=(Fh, Fw) (default None: today's path): an image with a side beyond it is downscaled on the device to fit_size(h, w, Fh, Fw) first
+    (texocr::ingest_u8_fit), bit for bit PIL's resize(..., BILINEAR) of its L / RGB channels; the container is sized by the fitted list."""
     staged, dev, src, shapes = plan_u8(images)
     device = torch.device(device)
-    Hc, Wc = box_u8(shapes)
-    box, sizes = torch.ops.texocr.ingest_u8([staged.to(device)] + dev, src, shapes, int(engine), int(in_channels), Hc, Wc)
+    if fit is None:
+        Hc, Wc = box_u8(shapes)
+        box, sizes = torch.ops.texocr.ingest_u8([staged.to(device)] + dev, src, shapes, int(engine), int(in_channels), Hc, Wc)
+    else:
+        Fh, Fw = int(fit[0]), int(fit[1])
+        Hc, Wc = box_u8(fit_shapes(shapes, Fh, Fw))
+        box, sizes = torch.ops.texocr.ingest_u8_fit([staged.to(device)] + dev, src, shapes, int(engine), int(in_channels), Fh, Fw, Hc, Wc)
     return PackedImages(box, sizes)

@@ -89,14 +89,34 @@ class TeXOCRWrapper:
             x = x.expand(self.dims.in_channels, -1, -1)
         return x.contiguous()
 
-    def _images(self, imgs: Sequence, ingest: str):
+    def _fitted(self, img, i: int = 0):
+        """fit='canvas' on the host path: a PIL image with a side beyond the canvas -> PIL's resize(ops.fit_size, BILINEAR) of it, an L image
+        as it is and any other mode through convert('RGB') first (the channels the ingest reads; PIL's own RGBA resize premultiplies by
+        alpha).  An image that fits is returned untouched: PIL is called for oversized images only.  i: the image's place in its list, which
+        the refusal names in the engine's words (txo_ingest_u8_fit)."""
+        from PIL import Image
+        from . import ops
+        (w, h), (Fh, Fw) = img.size, self.dims.canvas_hw
+        fh, fw = ops.fit_size(h, w, Fh, Fw)
+        if (fh, fw) == (h, w):
+            return img
+        if h > ops.FIT_MAX_SCALE * fh or w > ops.FIT_MAX_SCALE * fw:
+            raise ValueError(f"ingest: image {i} is {h}x{w}, {fh}x{fw} fitted to {Fh}x{Fw}: an axis shrinks by more than {ops.FIT_MAX_SCALE} times")
+        return (img if img.mode == "L" else img.convert("RGB")).resize((fw, fh), Image.BILINEAR)
+
+    def _images(self, imgs: Sequence, ingest: str, fit: str = "none"):
         """imgs as one ragged call takes them -- ingest='host': a list of (C, H_b, W_b) tensors on the device, every image preprocessed
         on the host and copied on its own (the path that has always been there); 'device': ONE OCRModel.ingest over the raw pixels (a
-        PackedImages, bit for bit the container the host path ends in)"""
+        PackedImages, bit for bit the container the host path ends in).  fit='canvas': oversized images are downscaled to the canvas first,
+        by PIL on the host path and by the engine on the device path, to the same bytes."""
+        if fit not in ("none", "canvas"):
+            raise ValueError(f"fit must be 'none' or 'canvas', got {fit!r}")
         if ingest == "device":
-            return self.model.ingest(imgs)
+            return self.model.ingest(imgs, fit=True) if fit == "canvas" else self.model.ingest(imgs)
         if ingest != "host":
             raise ValueError(f"ingest must be 'host' or 'device', got {ingest!r}")
+        if fit == "canvas":
+            imgs = [self._fitted(im, i) for i, im in enumerate(imgs)]
         return [self._tensor(im).cuda() for im in imgs]
 
     def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool):
@@ -127,7 +147,7 @@ class TeXOCRWrapper:
 
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-              length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host") -> List[tuple]:
+              length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host", fit: str = "none") -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -143,7 +163,13 @@ class TeXOCRWrapper:
         ingest='device' (build extension; default 'host'): every chunk's images go to the device as raw uint8 pixels in ONE copy and are
         preprocessed there by ONE launch (OCRModel.ingest) instead of one float32 conversion, copy and slice assignment per image.  imgs may
         then also hold uint8 numpy arrays or tensors (H, W), (H, W, 3) or (H, W, 4).  The container is bit for bit the host path's, so
-        every result is identical."""
+        every result is identical.
+        fit='canvas' (build extension; default 'none': an image with a side beyond the canvas is a ValueError, as ever): such an image is
+        downscaled to fit the canvas, aspect ratio kept (ops.fit_size; small images are never upscaled), with PIL's
+        resize(..., BILINEAR) -- by PIL itself with ingest='host', by the engine (OCRModel.ingest(fit=True)) with ingest='device', to the
+        same bytes, so every result is identical by either ingest here too.  An RGBA image is fitted on its RGB channels (convert('RGB');
+        the alpha is not read).  An axis that would shrink by more than 32 times is a ValueError.  return_align maps of a fitted image
+        are on the FITTED grid: (len(tokens), h'/16, w'/16) with (h', w') the fitted size rounded up to 16."""
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
         pre = plen = prows = None
@@ -153,9 +179,9 @@ class TeXOCRWrapper:
             pre, plen, prows, max_len = self._prefix_rows(prefix, decode, return_align, max_len)
         step = beam_chunk(eng.max_batch, beams) if decode == "beam" else eng.max_batch
         out: List[tuple] = []
-        xs = self._images(imgs, ingest) if ingest != "device" else None
+        xs = self._images(imgs, ingest, fit) if ingest != "device" else None
         for c0 in range(0, len(imgs), step):
-            chunk = xs[c0:c0 + step] if xs is not None else self._images(imgs[c0:c0 + step], ingest)
+            chunk = xs[c0:c0 + step] if xs is not None else self._images(imgs[c0:c0 + step], ingest, fit)
             if decode == "beam":
                 full, logp = self._best_beams(chunk, beams, max_len, length_alpha, return_logp)
             else:
@@ -179,7 +205,7 @@ class TeXOCRWrapper:
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-                 length_alpha: float = 0.0, prefix=None, ingest: str = "host") -> tuple:
+                 length_alpha: float = 0.0, prefix=None, ingest: str = "host", fit: str = "none") -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
@@ -188,8 +214,10 @@ class TeXOCRWrapper:
         max_len is capped at the positional table; temp and seed play no part.
         prefix= (a LaTeX string or a token list): the decode continues it (BOS is put in front; OCRModel.generate(prefix=)); `tokens` (and
         logp) is the continuation, `latex` is decoded from prefix + continuation; max_len is capped so that both fit the positional table.
-        ingest='device': the image is preprocessed on the device (see batch); the result is identical."""
-        x = self._images([img], ingest)
+        ingest='device': the image is preprocessed on the device (see batch); the result is identical.
+        fit='canvas': an image beyond the canvas is downscaled to fit it first (see batch); the maps of return_align are then on the
+        fitted grid."""
+        x = self._images([img], ingest, fit)
         x = x.box if ingest == "device" else x[0][None]
         prow: List[int] = []
         gen_kw = {}
