@@ -76,8 +76,9 @@ struct EngineBase {
     virtual int decode_begin_ragged(const float* enc, int B, int Ns, const int32_t* n_tokens, int eos, hipStream_t s) = 0;
     virtual int score_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, const int64_t* tokens, const unsigned char* mask,
                              int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
-    virtual int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
-                                int* n_steps, float* logp_out, hipStream_t s) = 0;
+    // every txo_generate* but _beam (session.h).  Its slot here, where the first entry into the decode loop always stood, decides when the loop's
+    // template kernels are first used, and with it their order in the code object (see the kernel #include list)
+    virtual int generate(const DecodeReq& q, hipStream_t s) = 0;
     virtual int decode_step(const int64_t* tok_in, int t, float* logits_out, int64_t* tok_out, hipStream_t s) = 0;
     virtual int decode_prefill(const int64_t* tokens, int t, float* logits_out, hipStream_t s) = 0;
     virtual int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
@@ -86,18 +87,8 @@ struct EngineBase {
     virtual int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
                       int64_t* top1_out, float* top1_logp_out, hipStream_t s) = 0;
     virtual int decode_set_key_mask(const unsigned char* mask, int cols, hipStream_t s) = 0;
-    virtual int generate(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
-                         int64_t* tokens_out, int* n_steps, float* logits_out, float* logp_out, hipStream_t s) = 0;
-    // txo_generate_prefix (img, sizes null) / _from_enc (enc, N) / _ragged (img, sizes: the container is H x W)
-    virtual int generate_prefix(const float* img, const float* enc, const int32_t* sizes, int B, int C, int H, int W, int N, const int64_t* prefix,
-                                int P, const int32_t* prefix_len, int max_len, int eos, int64_t* tokens_out, int* n_steps, float* logp_out,
-                                float* prefix_logp_out, hipStream_t s) = 0;
-    virtual int generate_beam(const float* img, const float* enc, int B, int C, int H, int W, int N, int beams, int max_len,
-                              int eos, int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps,
-                              hipStream_t s) = 0;
-    // txo_beam_search (sizes null: B images of H x W) / txo_beam_search_ragged (sizes: the container is H x W)
-    virtual int beam_search(const float* img, int B, int C, int H, int W, const int32_t* sizes, int beams, int max_len, int eos,
-                            const txo_beam_out* out, int* n_steps, hipStream_t s) = 0;
+    // txo_generate_beam (sink.best) / txo_beam_search, txo_beam_search_ragged (sink.out)
+    virtual int beam_search(const DecodeSrc& src, int beams, int max_len, int eos, const BeamSink& sink, int* n_steps, hipStream_t s) = 0;
     int sample_mode = 0, sample_topk = 0; float sample_temp = 1.f; unsigned long long sample_seed = 0;
     size_t sample_lds_max = 65536;              // dynamic LDS the LDS-form sampler may ask for (init: the device's per-workgroup limit)
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
@@ -1116,19 +1107,68 @@ struct Engine : EngineBase {
                 return fail(TXO_E_INVALID, "ragged batches: n_tokens[" + std::to_string(b) + "] must be in [1, Ns]");
         return begin_session(enc, B, Ns, eos, s, true, KeyCounts{nullptr, n_tokens});
     }
-    int generate_ragged(const float* img, int B, int C, int Hc, int Wc, const int32_t* sizes, int max_len, int eos, int64_t* tokens_out,
-                        int* n_steps, float* logp_out, hipStream_t s) override {
-        if (int r = ragged_refusals()) return r;
-        if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
-        if (max_len > Tmax && !rag_fwd)
-            return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length (the sliding window of a ragged batch needs txo_set_ragged_forward(e, 1))");
-        // beyond the positional table the window slides through generate_window, under the fixed-shape call's two preconditions (generate())
-        if (max_len > Tmax && (V % 8 != 0 || (size_t)Tmax > (size_t)Bmax * Nmax))
-            return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a "
-                                       "vocabulary size that is a multiple of 8 and max_length <= max_batch * max_tokens");
+    // what a decode reads, checked: a fixed or ragged batch of images, or the caller's encoder rows as they are (begin_session checks those)
+    int resolve_source(const DecodeSrc& q, hipStream_t s, Source* src) {
         ImageBatch ib;
-        if (int r = ragged_batch(B, C, Hc, Wc, sizes, s, &ib)) return r;
-        return generate_common(&ib, img, B, ib.N, max_len, eos, tokens_out, n_steps, nullptr, logp_out, s);
+        if (q.img) { if (int r = q.sizes ? ragged_batch(q.B, q.C, q.H, q.W, q.sizes, s, &ib) : fixed_batch(q.B, q.C, q.H, q.W, &ib)) return r; }
+        *src = Source{ib, q.img != nullptr, q.img ? q.img : q.enc, q.B, q.img ? ib.N : q.N};
+        return 0;
+    }
+    // Every txo_generate* entry but txo_generate_beam (session.h: DecodeReq): from images, a ragged batch or encoder rows, with or without
+    // log-probabilities, from BOS or behind a caller's prefix (a prompted decode, texocr.h).  Everything is refused before anything is
+    // encoded, each family of entries in the order it always checked in.
+    // Per-row stop (stop_mode 1, a build extension: the reference has only the global break,
+    // decoder.py:115-116): the decode below is the same loop with the same break -- rows are independent, so every row's tokens up to its first eos
+    // are what the global-break run gives -- and every token BEHIND a row's first eos becomes cfg.pad (pad_after_eos_kernel); on the launch
+    // path the finished rows also stop costing work (compact_lane).
+    int generate(const DecodeReq& q, hipStream_t s) override {
+        const bool ragged = q.src.sizes != nullptr;
+        // results of THIS call, also when it is refused (txo_generate_ragged / _logp: only once the batch is accepted, generate_common)
+        if (q.prefix || !ragged) { last_compactions = 0; last_ragged = false; }
+        if (ragged) { if (int r = ragged_refusals()) return r; }
+        Decode d{q};
+        if (int r = q.prefix ? check_prefix(q, &d.m, &d.M) : check_length(q.max_len, ragged)) return r;
+        if (int r = resolve_source(q.src, s, &d.src)) return r;
+        if (q.prefix) {   // the lengths to the device, through the pinned staging of the ragged sizes (behind ragged_batch's own copy)
+            std::vector<int32_t> len((size_t)q.src.B, q.P);
+            if (q.prefix_len) len.assign(q.prefix_len, q.prefix_len + q.src.B);
+            if (int r = upload_i32(len.data(), flen, q.src.B, nullptr, 0, s)) return r;
+        }
+        return generate_common(d, s);
+    }
+    // max_len of a decode from BOS.  Beyond the positional table the window slides (generate_window), and its multi-position forward has two
+    // preconditions: refused BEFORE anything is decoded.  A ragged batch also needs the ragged forward for it, and says that first.
+    int check_length(int max_len, bool ragged) {
+        if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
+        if (max_len <= Tmax) return 0;
+        if (ragged && !rag_fwd)
+            return fail(TXO_E_INVALID, "ragged batches: max_len exceeds the decoder's max_length (the sliding window of a ragged batch needs txo_set_ragged_forward(e, 1))");
+        if (V % 8 == 0 && (size_t)Tmax <= (size_t)Bmax * Nmax) return 0;
+        return fail(TXO_E_INVALID, ragged ? "ragged batches: max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a "
+                                            "vocabulary size that is a multiple of 8 and max_length <= max_batch * max_tokens"
+                                          : "max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a vocabulary "
+                                            "size that is a multiple of 8 and max_length <= max_batch * max_tokens (use decoder.generate's stepwise loop)");
+    }
+    // a prompted decode's bounds; *m / *M: the shortest / longest prefix length
+    int check_prefix(const DecodeReq& q, int* m, int* M) {
+        const int B = q.src.B, P = q.P;
+        if (q.max_len < 1) return fail(TXO_E_INVALID, "prefix decode: max_len must be >= 1");
+        if (B < 1 || B > Bmax) return fail(TXO_E_INVALID, "prefix decode: batch exceeds engine max_batch");
+        if (P < 1) return fail(TXO_E_INVALID, "prefix decode: the prefix needs at least one column");
+        *m = *M = P;
+        if (q.prefix_len) {
+            *M = 1;
+            for (int b = 0; b < B; ++b) {
+                if (q.prefix_len[b] < 1 || q.prefix_len[b] > P)
+                    return fail(TXO_E_INVALID, "prefix decode: prefix_len[" + std::to_string(b) + "] must be in [1, P]");
+                *m = std::min(*m, (int)q.prefix_len[b]); *M = std::max(*M, (int)q.prefix_len[b]);
+            }
+        }
+        if ((long long)*M - 1 + q.max_len > Tmax)
+            return fail(TXO_E_INVALID, "prefix decode: the longest prefix - 1 + max_len exceeds the decoder's max_length (a prompted decode does not slide the window)");
+        if ((size_t)(*m - 1) > (size_t)Bmax * Nmax)
+            return fail(TXO_E_INVALID, "prefix decode: the shortest prefix does not fit the multi-position pass's workspace (max_batch * max_tokens rows)");
+        return 0;
     }
 
     // Opens the decode session on enc [B][N][D] (session.h), complete: no caller patches a field in behind this call.  kc: a ragged session's
@@ -1872,11 +1912,10 @@ struct Engine : EngineBase {
         return 0;
     }
     // returns 0 (done), TXO_E_STATE (the launch gave up: redo with launches), or an error
-    // n_pos positions are decoded; rows of tokens_out / logits_out are out_stride positions apart
+    // n_pos positions are decoded; rows of the request's outputs are its max_len positions apart
     // *broke: the reference's GLOBAL eos break fired inside these n_pos positions (possibly at the very last one)
-    int generate_persist(int B, int N, int n_pos, int out_stride, int eos, int64_t* tokens_out, float* logits_out, float* logp_out, int* n_steps, bool* broke,
-                         hipStream_t s) {
-        const int max_len = n_pos;
+    int generate_persist(const Decode& d, int n_pos, int* n_steps, bool* broke, hipStream_t s) {
+        const int B = d.src.B, N = d.src.N, eos = d.q.eos, max_len = n_pos;
         PersistArgs<T> pa{};
         pa.B = B; pa.N = N; pa.V = V; pa.Ld = cfg.dec_layers; pa.Tmax = Tmax; pa.max_len = max_len; pa.eos = eos; pa.bos = cfg.bos;
         for (int l = 0; l < cfg.dec_layers; ++l) {
@@ -1905,7 +1944,7 @@ struct Engine : EngineBase {
         pa.dx = dx; pa.dy = dy; pa.dq = dq; pa.dlogits = dlogits; pa.dao = dao; pa.dhid = dhid;
         pa.cur_tok = cur_tok; pa.eos_seen = eos_seen; pa.skv = skv; pa.ckv = ckv;
         pa.self_stride = (size_t)ses.rows * Id * Tmax; pa.cross_stride = (size_t)ses.images * N * Id;
-        pa.tokens_out = tokens_out; pa.out_stride = out_stride; pa.logits_out = logits_out; pa.logp_out = logp_out;
+        pa.tokens_out = d.q.tokens; pa.out_stride = d.q.max_len; pa.logits_out = d.q.logits; pa.logp_out = d.q.logp;
         pa.sample = sample_mode; pa.sample_topk = sample_topk; pa.inv_temp = 1.0f / sample_temp; pa.seed = sample_seed;
         pa.ctl = pctl; pa.stamps = pstamps;
         const char* stamp_file = knobs.run.pstamps ? knobs.run.pstamps_file.c_str() : nullptr;
@@ -1944,74 +1983,22 @@ struct Engine : EngineBase {
         *n_steps = steps;
         return 0;
     }
-    // txo_generate / txo_generate_from_enc.  Per-row stop (stop_mode 1, a build extension: the reference has only the global break,
-    // decoder.py:115-116): the decode below is the same loop with the same break -- rows are independent, so every row's tokens up to its first eos
-    // are what the global-break run gives -- and every token BEHIND a row's first eos becomes cfg.pad (pad_after_eos_kernel); on the launch
-    // path the finished rows also stop costing work (compact_lane).
-    int generate(const float* img, const float* enc, int B, int C, int H, int W, int N, int max_len, int eos,
-                 int64_t* tokens_out, int* n_steps, float* logits_out, float* logp_out, hipStream_t s) override {
-        last_compactions = 0; last_ragged = false;                // (results of THIS call, also when it is refused)
-        if (max_len < 1) return fail(TXO_E_INVALID, "max_len must be >= 1");
-        // the window's multi-position forward (generate_window) has two preconditions: refuse BEFORE decoding anything
-        if (max_len > Tmax && (V % 8 != 0 || (size_t)Tmax > (size_t)Bmax * Nmax))
-            return fail(TXO_E_INVALID, "max_len exceeds the decoder's max_length and the sliding window's multi-position forward needs a vocabulary "
-                                       "size that is a multiple of 8 and max_length <= max_batch * max_tokens (use decoder.generate's stepwise loop)");
-        ImageBatch ib;
-        if (img) if (int r = fixed_batch(B, C, H, W, &ib)) return r;
-        return generate_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, max_len, eos, tokens_out, n_steps, logits_out, logp_out, s);
-    }
-    // A prompted decode's prefix: tokens [B][P] on the device (its lengths are in flen already), m / M the shortest / longest length,
-    // logp_out [B][P] or null for the forced tokens' log-probabilities
-    struct PrefixIn { const int64_t* tokens; int P, m, M; float* logp_out; };
-    // txo_generate_prefix / _from_enc / _ragged: generate()'s loop continued behind a caller's prefix (texocr.h).  Everything is refused before
-    // anything is encoded.
-    int generate_prefix(const float* img, const float* enc, const int32_t* sizes, int B, int C, int H, int W, int N, const int64_t* prefix, int P,
-                        const int32_t* prefix_len, int max_len, int eos, int64_t* tokens_out, int* n_steps, float* logp_out, float* prefix_logp_out,
-                        hipStream_t s) override {
-        last_compactions = 0; last_ragged = false;
-        if (sizes) { if (int r = ragged_refusals()) return r; }
-        if (max_len < 1) return fail(TXO_E_INVALID, "prefix decode: max_len must be >= 1");
-        if (B < 1 || B > Bmax) return fail(TXO_E_INVALID, "prefix decode: batch exceeds engine max_batch");
-        if (P < 1) return fail(TXO_E_INVALID, "prefix decode: the prefix needs at least one column");
-        int m = P, M = P;
-        if (prefix_len) {
-            M = 1;
-            for (int b = 0; b < B; ++b) {
-                if (prefix_len[b] < 1 || prefix_len[b] > P)
-                    return fail(TXO_E_INVALID, "prefix decode: prefix_len[" + std::to_string(b) + "] must be in [1, P]");
-                m = std::min(m, (int)prefix_len[b]); M = std::max(M, (int)prefix_len[b]);
-            }
-        }
-        if ((long long)M - 1 + max_len > Tmax)
-            return fail(TXO_E_INVALID, "prefix decode: the longest prefix - 1 + max_len exceeds the decoder's max_length (a prompted decode does not slide the window)");
-        if ((size_t)(m - 1) > (size_t)Bmax * Nmax)
-            return fail(TXO_E_INVALID, "prefix decode: the shortest prefix does not fit the multi-position pass's workspace (max_batch * max_tokens rows)");
-        ImageBatch ib;
-        if (img) { if (int r = sizes ? ragged_batch(B, C, H, W, sizes, s, &ib) : fixed_batch(B, C, H, W, &ib)) return r; }
-        {   // the lengths to the device, through the pinned staging of the ragged sizes (behind ragged_batch's own copy)
-            std::vector<int32_t> len((size_t)B, P);
-            if (prefix_len) len.assign(prefix_len, prefix_len + B);
-            if (int r = upload_i32(len.data(), flen, B, nullptr, 0, s)) return r;
-        }
-        const PrefixIn px{prefix, P, m, M, prefix_logp_out};
-        return generate_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, max_len, eos, tokens_out, n_steps, nullptr, logp_out, s, &px);
-    }
-    // the common body of generate() / generate_ragged(): `ib` and its images, or (ib null) the caller's encoder rows src [B][N][D]
-    // logp_out [B][max_len] or null: log_softmax(logits)[token] of every returned position (txo_generate_logp), 0 behind a row's eos under the per-row stop
-    // px: a prompted decode (generate_prefix) -- the loop starts behind the shortest prefix and forces the rest (step_prefix.h)
-    int generate_common(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* n_steps,
-                        float* logits_out, float* logp_out, hipStream_t s, const PrefixIn* px = nullptr) {
+    // the decode itself and the state every call ends in.  q.logp [B][max_len] or null: log_softmax(logits)[token] of every returned position
+    // (txo_generate_logp), 0 behind a row's eos under the per-row stop.  A prompted decode starts behind the shortest prefix and forces the
+    // rest (step_prefix.h).
+    int generate_common(const Decode& d, hipStream_t s) {
+        const DecodeReq& q = d.q;
         int steps = 0; last_compactions = 0;
-        last_ragged = ib && ib->ragged;
-        const int rc = generate_impl(ib, src, B, N, max_len, eos, tokens_out, &steps, logits_out, logp_out, s, px);
+        last_ragged = d.src.ragged();
+        const int rc = generate_impl(d, &steps, s);
         ses.row_stop = false;                                     // the decode is over (a txo_decode_step behind it steps every row)
         ses.forced = false;                                       // ... and picks every row's token itself: the prefix table belongs to the finished call
         if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
-        if (n_steps) *n_steps = steps;
+        if (q.n_steps) *q.n_steps = steps;
         if (last_compactions > 0) ses.open = false;               // the session's rows are no longer the batch's: a new decode must begin
-        if (stop_mode == 1 && eos >= 0 && steps > 0 && !px) {      // (a prompted decode has padded already: prefix_finish_kernel)
-            hipLaunchKernelGGL(pad_after_eos_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tokens_out, logp_out, max_len, steps, B, eos, cfg.bos, cfg.pad);
+        if (stop_mode == 1 && q.eos >= 0 && steps > 0 && !d.prompted()) {   // (a prompted decode has padded already: prefix_finish_kernel)
+            hipLaunchKernelGGL(pad_after_eos_kernel, dim3((d.src.B + 255) / 256), dim3(256), 0, s, q.tokens, q.logp, q.max_len, steps, d.src.B, q.eos, cfg.bos, cfg.pad);
             HIP_TRY(hipStreamSynchronize(s));
             HIP_TRY(hipGetLastError());
         }
@@ -2042,20 +2029,22 @@ struct Engine : EngineBase {
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    int generate_impl(const ImageBatch* ib, const float* src, int B, int N, int max_len, int eos, int64_t* tokens_out, int* steps,
-                      float* logits_out, float* logp_out, hipStream_t s, const PrefixIn* px = nullptr) {
+    int generate_impl(const Decode& d, int* steps, hipStream_t s) {
+        const DecodeReq& q = d.q;
+        const int B = d.src.B, max_len = q.max_len, eos = q.eos;
         // max_len > decoder.max_len: the reference slides its window (decoder.py:99-100).  The first Tmax positions decode with the
         // KV cache as always (n_pos of them; rows of the outputs are max_len apart); every further token re-runs its window of the
         // last Tmax tokens, positions re-indexed from 0, through ONE multi-position forward (prefill) -- generate_window below.
-        // A prompted decode (px; generate_prefix checked that it stays inside the table): the loop decodes positions t0 = m-1 .. M+max_len-2.
-        const int t0 = px ? px->m - 1 : 0;
-        const int n_pos = px ? px->M + max_len - 1 : std::min(max_len, Tmax);
-        if (ib) { if (int r = encode_batch(*ib, src, eenc, s)) return r; src = eenc; }
+        // A prompted decode (check_prefix saw that it stays inside the table): the loop decodes positions t0 = m-1 .. M+max_len-2.
+        const int t0 = d.prompted() ? d.m - 1 : 0;
+        const int n_pos = d.prompted() ? d.M + max_len - 1 : std::min(max_len, Tmax);
+        const float* rows = d.src.data;
+        if (d.src.images) { if (int r = encode_batch(d.src.ib, rows, eenc, s)) return r; rows = eenc; }
         // (eos also decides whether the BOS column counts; a ragged session's key count per slot = the images' token counts)
-        if (int r = begin_session(src, B, N, eos, s, false, KeyCounts{ib && ib->ragged ? rag_ntok : nullptr})) return r;
-        ses.forced = px != nullptr;
-        if (px) {   // the prefix into the engine's table (lengths are in flen: generate_prefix), no forced token scored yet
-            hipLaunchKernelGGL(prefix_table_kernel, dim3((B * Tmax + 255) / 256), dim3(256), 0, s, ftab, Tmax, px->tokens, px->P, flen, B, V);
+        if (int r = begin_session(rows, B, d.src.N, eos, s, false, KeyCounts{d.src.ragged() ? rag_ntok : nullptr})) return r;
+        ses.forced = d.prompted();
+        if (d.prompted()) {   // the prefix into the engine's table (lengths are in flen: generate), no forced token scored yet
+            hipLaunchKernelGGL(prefix_table_kernel, dim3((B * Tmax + 255) / 256), dim3(256), 0, s, ftab, Tmax, q.prefix, q.P, flen, B, V);
             HIP_TRY(hipMemsetAsync(fplogp, 0, sizeof(float) * (size_t)B * Tmax, s));
         }
         last_persist = false;
@@ -2063,11 +2052,11 @@ struct Engine : EngineBase {
         if (persist_usable(B)) {
             ensure_ckv(s);                                        // (the persistent launch reads projected K/V panels: the session stays in the K/V form)
             bool broke = false;
-            const int pr = generate_persist(B, N, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, &broke, s);
+            const int pr = generate_persist(d, n_pos, steps, &broke, s);
             if (pr == 0) {
                 last_persist = true; persist_strikes = 0;
                 // (an eos break exactly at position n_pos - 1 also leaves steps == n_pos: the window must not start then)
-                if (!broke && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, s);
+                if (!broke && max_len > n_pos) return generate_window(d, n_pos, steps, s);
                 return 0;
             }
             if (pr != TXO_E_STATE) return pr;
@@ -2079,6 +2068,22 @@ struct Engine : EngineBase {
             lanes.split(ses.rows, 1, s);
             reset_lanes(s, eos);
         }
+        // the launch path, in three steps: how to run, the loop, the results to the caller
+        LoopPlan plan;
+        if (int r = plan_loop(d, s, &plan)) return r;
+        DonePoll poll{lanes, done_flag, Tmax, n_pos};              // GLOBAL eos break: poll.done = it fired inside the positional table
+        if (int r = run_loop(d, plan, t0, &poll, s)) return r;
+        if (int r = deliver(d, plan, poll, steps, s)) return r;
+        if (!d.prompted() && !poll.done && max_len > n_pos) return generate_window(d, n_pos, steps, s);
+        return 0;
+    }
+    // How the launch path runs a decode: replaying captured steps or with eager launches, and where its steps write -- a captured step the
+    // engine's own buffers (rows Tmax apart: graphs do not bake user pointers), an eager one the caller's
+    struct LoopPlan { bool use_graph; int64_t* tdst; float* ldst; int tstride; };
+    // Step 1: the session's form, graph or eager, the row ranges (reset, a prompted decode's history filled), the captured steps.
+    int plan_loop(const Decode& d, hipStream_t s, LoopPlan* plan) {
+        const DecodeReq& q = d.q;
+        const int B = d.src.B, max_len = q.max_len, eos = q.eos;
         // lanes: graphs + extra streams unless per-step logits were asked for or a debug/profiling mode is on
         // Measured on MI355X (B=64, 224x672, T=256): the step is bound by the GPU-side latency chain of its ~26
         // dependent launches, not by the host -- graph replay and 2-4 lanes give the same wall time as eager
@@ -2086,14 +2091,14 @@ struct Engine : EngineBase {
         // graph replay by default only for very small batches (B <= 4: there the host's enqueue rate bounds the step --
         // 34.2 vs 37.2 ms per generate at B = 1 -- from B = 8 on it is equal); TXO_GRAPH=1 / 0 forces it on / off
         // per-row stop with live-row compaction: inside the positional table, tokens only (a finished row's logits would be unspecified)
-        choose_form(stop_mode == 1 && eos >= 0 && logits_out == nullptr && max_len <= Tmax && knobs.stop_every > 0 && !prof && !prof_cross, s);
-        if (px) ses.lat_self = false;                              // (the multi-position pass fills the K/V history, not the z history)
+        choose_form(stop_mode == 1 && eos >= 0 && q.logits == nullptr && max_len <= Tmax && knobs.stop_every > 0 && !prof && !prof_cross, s);
+        if (d.prompted()) ses.lat_self = false;                    // (the multi-position pass fills the K/V history, not the z history)
         const bool want_graph = knobs.run.graph >= 0 ? knobs.run.graph != 0 : B <= 4;
         // per-row stop replays captured steps: as the ranges shrink a position's launches take less time than the host needs to enqueue them
         // (68 launches for two ranges: ~230 us per position on the host against 130 us on the device at 40 % of the rows), and a step
         // per row count (multiples of 16) is captured once and kept (lane_graph).  TXO_STOP_GRAPH=0: eager launches.
         const bool stop_graph = ses.row_stop && !sample_mode && knobs.stop_graph_on;
-        const bool eager = logits_out != nullptr || g_dbg || sample_mode || !(want_graph || stop_graph);
+        const bool eager = q.logits != nullptr || g_dbg || sample_mode || !(want_graph || stop_graph);
         // two row ranges on two streams for a WIDE decoder at >= 256 rows (BASELINE cfg 4): one range's latency-bound projection launches
         // run beside the other's HBM-bound attention launches (816 -> 834 images/s; four ranges: 765).  Greedy and sampled alike: a draw is keyed
         // by (seed; row of the batch, position), not by the range (step.h: StepArgs::row0)
@@ -2108,18 +2113,23 @@ struct Engine : EngineBase {
         if (want == 2 && knobs.tune_lanes && !lanes.tuned) { if (int r = lanes.tune(n_cus, knobs.tune_verbose)) return r; }
         lanes.split(ses.rows, want, s);
         last_ranges = lanes.n;
-        reset_lanes(s, eos, px ? px->m : 0);
+        reset_lanes(s, eos, d.prompted() ? d.m : 0);
         // a prompted decode: positions 0 .. m-2 of every row in ONE multi-position pass, no logits (it fills the K/V history the loop reads)
-        if (px && px->m > 1) { if (int r = prefill(ftab, Tmax, px->m - 1, nullptr, nullptr, s)) return r; }
-        bool use_graph = !eager && !prof && !prof_cross;   // event-carrying launches cannot be captured
+        if (d.prompted() && d.m > 1) { if (int r = prefill(ftab, Tmax, d.m - 1, nullptr, nullptr, s)) return r; }
+        const bool use_graph = !eager && !prof && !prof_cross;     // event-carrying launches cannot be captured
         prefix_cols = use_graph ? Tmax : max_len;                  // (a captured step writes the engine's buffers: every column of theirs exists)
-        const bool glogp = logp_out != nullptr;                    // a captured step carries the log-probabilities like the tokens: into the engine's buffer
-        if (use_graph) for (int i = 0; i < lanes.n; ++i) if (int r = lane_graph(i, eos, glogp)) return r;
+        // a captured step carries the log-probabilities like the tokens: into the engine's buffer
+        if (use_graph) for (int i = 0; i < lanes.n; ++i) if (int r = lane_graph(i, eos, q.logp != nullptr)) return r;
+        // (rows of q.tokens are max_len apart, of which only n_pos positions are decoded here)
+        *plan = use_graph ? LoopPlan{true, tok_buf, q.logp ? logp_buf : nullptr, Tmax} : LoopPlan{false, q.tokens, q.logp, max_len};
+        return 0;
+    }
+    // Step 2: positions t0 .. of the ranges, side by side, until the table ends or the global break fires (poll)
+    int run_loop(const Decode& d, const LoopPlan& plan, int t0, DonePoll* poll_, hipStream_t s) {
+        DonePoll& poll = *poll_;
+        const bool use_graph = plan.use_graph, glogp = d.q.logp != nullptr;
+        const int eos = d.q.eos, n_pos = poll.n_pos;
         if (int r = lanes.fork(s)) return r;
-        int64_t* tdst = use_graph ? tok_buf : tokens_out;
-        float* ldst = use_graph && logp_out ? logp_buf : logp_out;
-        const int tstride = use_graph ? Tmax : max_len;               // rows of tokens_out are max_len apart (only n_pos positions are decoded here)
-        DonePoll poll{lanes, done_flag, Tmax, n_pos};              // GLOBAL eos break: poll.done = it fired inside the positional table
         int live_pend = -1;                                        // per-row stop: position behind which the ranges' finished-row counts were requested
         const char* stamp_file = knobs.run.stamps ? knobs.run.stamps_file.c_str() : nullptr;
         if (stamp_file && !stamps.buf) { if (int r = dalloc(&stamps.buf, (size_t)Stamps::KERNELS * Stamps::BLOCKS * 3)) return r; }
@@ -2130,7 +2140,7 @@ struct Engine : EngineBase {
             else if (stamps.slot >= 0) stamps.dump(stamp_file, knobs.has_stamps_raw ? &knobs.stamps_raw : nullptr, s);
             for (int i = 0; i < lanes.n; ++i) {
                 if (use_graph) HIP_TRY(hipGraphLaunch(lanes[i].exec, lanes[i].stream));
-                else if (int r2 = enqueue_step(lanes[i].stream, i, tdst, tstride, logits_out, ldst, eos, nullptr, t)) return r2;
+                else if (int r2 = enqueue_step(lanes[i].stream, i, plan.tdst, plan.tstride, d.q.logits, plan.ldst, eos, nullptr, t)) return r2;
             }
             if (eos < 0) continue;
             if (ses.row_stop) {
@@ -2164,23 +2174,27 @@ struct Engine : EngineBase {
         return 0;
         };
         if (int r = decode_loop()) return abandon_lanes(s, r);
-        if (int r = lanes.join(s)) return r;
+        return lanes.join(s);
+    }
+    // Step 3: what the captured steps left in the engine's buffers to the caller's rows, a prompted decode's tail, the stream drained
+    int deliver(const Decode& d, const LoopPlan& plan, const DonePoll& poll, int* steps, hipStream_t s) {
+        const DecodeReq& q = d.q;
+        const int B = d.src.B, max_len = q.max_len;
         // a prompted decode returns min(max_len, t_last + 2 - m) columns: the shortest prefix's row wrote column t_last + 1 - m last
-        const int n_cols = px ? std::min(max_len, poll.steps + 1 - px->m) : n_pos;
-        if (use_graph) {
-            HIP_TRY(hipMemcpy2DAsync(tokens_out, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax,
+        const int n_cols = d.prompted() ? std::min(max_len, poll.steps + 1 - d.m) : poll.n_pos;
+        if (plan.use_graph) {
+            HIP_TRY(hipMemcpy2DAsync(q.tokens, sizeof(int64_t) * max_len, tok_buf, sizeof(int64_t) * Tmax,
                                      sizeof(int64_t) * n_cols, B, hipMemcpyDeviceToDevice, s));
-            if (logp_out)
-                HIP_TRY(hipMemcpy2DAsync(logp_out, sizeof(float) * max_len, logp_buf, sizeof(float) * Tmax, sizeof(float) * n_cols, B, hipMemcpyDeviceToDevice, s));
+            if (q.logp)
+                HIP_TRY(hipMemcpy2DAsync(q.logp, sizeof(float) * max_len, logp_buf, sizeof(float) * Tmax, sizeof(float) * n_cols, B, hipMemcpyDeviceToDevice, s));
         }
-        if (px)   // pad / 0.0 where a row did not get to (or is finished, per-row stop); the forced tokens' log-probabilities to the caller
-            hipLaunchKernelGGL(prefix_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tokens_out, logp_out, max_len, n_cols, B, poll.steps, eos,
-                               cfg.pad, stop_mode == 1 ? 1 : 0, ftab, Tmax, flen, px->m, fplogp, px->logp_out, px->P);
+        if (d.prompted())   // pad / 0.0 where a row did not get to (or is finished, per-row stop); the forced tokens' log-probabilities to the caller
+            hipLaunchKernelGGL(prefix_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, q.tokens, q.logp, max_len, n_cols, B, poll.steps, q.eos,
+                               cfg.pad, stop_mode == 1 ? 1 : 0, ftab, Tmax, flen, d.m, fplogp, q.prefix_logp, q.P);
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         lanes.split(ses.rows, 1, s);
-        *steps = px ? n_cols : poll.steps;
-        if (!px && !poll.done && max_len > n_pos) return generate_window(B, n_pos, max_len, eos, tokens_out, logits_out, logp_out, steps, s);
+        *steps = d.prompted() ? n_cols : poll.steps;
         return 0;
     }
 
@@ -2189,7 +2203,9 @@ struct Engine : EngineBase {
     // decoder, the last position's logits.  Nothing cached survives the shift, so every such token costs one multi-position
     // forward of Tmax rows per image (prefill) + the single-position final LayerNorm / logits / token selection of the step path.
     // The GLOBAL eos test still looks at the whole output (:115), i.e. the per-row "seen" state carries over.
-    int generate_window(int B, int n_pos, int max_len, int eos, int64_t* tokens_out, float* logits_out, float* logp_out, int* steps, hipStream_t s) {
+    int generate_window(const Decode& d, int n_pos, int* steps, hipStream_t s) {
+        const int B = d.src.B, max_len = d.q.max_len, eos = d.q.eos;
+        int64_t* tokens_out = d.q.tokens;
         lanes.split(ses.rows, 1, s);
         lanes[0].stream = s;
         // the launch path's eos bookkeeping, rebuilt from the tokens decoded so far (a persistent launch keeps its own)
@@ -2200,8 +2216,8 @@ struct Engine : EngineBase {
         for (int i = n_pos; i < max_len; ++i) {
             if (int r = prefill(tokens_out + (i - Tmax), max_len, Tmax, nullptr, dlogits, s)) return r;
             hipLaunchKernelGGL(set_position_kernel, dim3(1), dim3(1), 0, s, st, i);
-            StepArgs sa{dlogits, V, B, cur_tok, tokens_out, max_len, logits_out, st, eos_seen, flag - i, eos, sample_topk, 1.0f / sample_temp, sample_seed, 0,
-                        0, nullptr, logp_out};
+            StepArgs sa{dlogits, V, B, cur_tok, tokens_out, max_len, d.q.logits, st, eos_seen, flag - i, eos, sample_topk, 1.0f / sample_temp, sample_seed, 0,
+                        0, nullptr, d.q.logp};
             if (sample_mode) launch_sample_step(s, B, sa);
             else hipLaunchKernelGGL(argmax_step_kernel, dim3(B), dim3(64), 0, s, sa);
             *steps = i + 1;
@@ -2216,7 +2232,7 @@ struct Engine : EngineBase {
         return 0;
     }
 
-    // ---- beam search: txo_generate_beam, txo_beam_search, txo_beam_search_ragged -- one loop (beam_common), two tails ----
+    // ---- beam search: txo_generate_beam, txo_beam_search, txo_beam_search_ragged -- one loop (beam_impl), two tails ----
     // what all three refuse before anything is encoded or decoded
     int beam_refusals(int B, int beams, int max_len) {
         if (beams < 1 || beams > 8) return fail(TXO_E_INVALID, "beams must be in [1, 8]");
@@ -2226,42 +2242,28 @@ struct Engine : EngineBase {
         if (B < 1 || B * beams > Bmax || B * beams > 32767) return fail(TXO_E_INVALID, "images * beams exceeds engine max_batch");
         return 0;
     }
-    // where a search's results go: txo_generate_beam's three buffers (best beam [B][max_len], scores, every beam), or a txo_beam_out
-    struct BeamSink { int64_t* best; float* scores; int64_t* all; const txo_beam_out* out; };
-    int generate_beam(const float* img, const float* enc, int B, int C, int H, int W, int N, int beams, int max_len, int eos,
-                      int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int* n_steps, hipStream_t s) override {
-        if (int r = beam_refusals(B, beams, max_len)) return r;
-        ImageBatch ib;
-        if (img) if (int r = fixed_batch(B, C, H, W, &ib)) return r;
-        return beam_common(img ? &ib : nullptr, img ? img : enc, B, img ? ib.N : N, beams, max_len, eos,
-                           BeamSink{tokens_out, scores_out, all_tokens_out, nullptr}, n_steps, s);
-    }
-    int beam_search(const float* img, int B, int C, int H, int W, const int32_t* sizes, int beams, int max_len, int eos,
-                    const txo_beam_out* out, int* n_steps, hipStream_t s) override {
-        last_compactions = 0; last_ragged = false;                // (results of THIS call, also when it is refused, as generate(); txo_generate_beam
-                                                                  // leaves both as they were, as it always did)
-        if (int r = beam_refusals(B, beams, max_len)) return r;
-        if (!out || !out->tokens) return fail(TXO_E_INVALID, "beam search: null out / out->tokens");
-        {   // by its bits: the library is built with -fno-honor-nans, which lets a float comparison assume its operand is no NaN
-            uint32_t ab; memcpy(&ab, &out->length_alpha, sizeof ab);
+    int beam_search(const DecodeSrc& q, int beams, int max_len, int eos, const BeamSink& sink, int* n_steps, hipStream_t s) override {
+        const bool three = sink.best != nullptr;                  // txo_generate_beam: it leaves last_compactions / last_ragged as they were, as it
+        if (!three) { last_compactions = 0; last_ragged = false; }   // always did; the other two report THIS call, also when it is refused, as generate()
+        if (int r = beam_refusals(q.B, beams, max_len)) return r;
+        if (!three) {
+            if (!sink.out || !sink.out->tokens) return fail(TXO_E_INVALID, "beam search: null out / out->tokens");
+            // by its bits: the library is built with -fno-honor-nans, which lets a float comparison assume its operand is no NaN
+            uint32_t ab; memcpy(&ab, &sink.out->length_alpha, sizeof ab);
             const bool nonfinite = (ab & 0x7f800000u) == 0x7f800000u, negative = (ab >> 31) != 0 && (ab << 1) != 0;
             if (nonfinite || negative) return fail(TXO_E_INVALID, "beam search: length_alpha must be finite and >= 0");
         }
-        ImageBatch ib;
-        if (int r = sizes ? ragged_batch(B, C, H, W, sizes, s, &ib) : fixed_batch(B, C, H, W, &ib)) return r;
-        last_ragged = ib.ragged;
-        return beam_common(&ib, img, B, ib.N, beams, max_len, eos, BeamSink{nullptr, nullptr, nullptr, out}, n_steps, s);
-    }
-    // `ib` and its images, or (ib null) the caller's encoder rows src [B][N][D]
-    int beam_common(const ImageBatch* ib, const float* src, int B, int N, int beams, int max_len, int eos, const BeamSink& sink,
-                    int* n_steps, hipStream_t s) {
-        const int rc = beam_impl(ib, src, B, N, beams, max_len, eos, sink, n_steps, s);
-        if (ib && ib->ragged) ses.open = false;                        // nothing ragged outlives the call (generate_common)
+        Source src;
+        if (int r = resolve_source(q, s, &src)) return r;
+        if (!three) last_ragged = src.ragged();
+        const int rc = beam_impl(src, beams, max_len, eos, sink, n_steps, s);
+        if (src.ragged()) ses.open = false;                       // nothing ragged outlives the call (generate_common)
         return rc;
     }
-    int beam_impl(const ImageBatch* ib, const float* src, int B, int N, int beams, int max_len, int eos, const BeamSink& sink,
-                  int* n_steps, hipStream_t s) {
-        const int rows = B * beams;
+    int beam_impl(const Source& from, int beams, int max_len, int eos, const BeamSink& sink, int* n_steps, hipStream_t s) {
+        const int B = from.B, N = from.N, rows = B * beams;
+        const ImageBatch* ib = from.batch();
+        const float* src = from.data;
         if (ib) { if (int r = encode_batch(*ib, src, eenc, s)) return r; src = eenc; }
         // decode rows are (image, beam) slots for the length of this call: whatever way it ends, the session it leaves has one row per image
         struct Rows { Session& ses; ~Rows() { ses.rows = ses.images; } } restore{ses};
@@ -2523,13 +2525,15 @@ int txo_decode_begin_ragged(txo_engine* e, const float* enc, int32_t B, int32_t 
 int txo_generate_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, int32_t max_len,
                         int32_t eos, int64_t* tokens_out, int32_t* n_steps, void* stream) {
     if (!e || !img || !sizes || !tokens_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate_ragged(img, B, C, Hc, Wc, sizes, max_len, eos, tokens_out, n_steps, nullptr, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.img = img, .sizes = sizes, .B = B, .C = C, .H = Hc, .W = Wc}, .max_len = max_len, .eos = eos,
+                                       .tokens = tokens_out, .n_steps = n_steps}, (hipStream_t)stream);
 }
 
 int txo_generate_ragged_logp(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, int32_t max_len,
                              int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logp_out, void* stream) {
     if (!e || !img || !sizes || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate_ragged(img, B, C, Hc, Wc, sizes, max_len, eos, tokens_out, n_steps, logp_out, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.img = img, .sizes = sizes, .B = B, .C = C, .H = Hc, .W = Wc}, .max_len = max_len, .eos = eos,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logp = logp_out}, (hipStream_t)stream);
 }
 
 int txo_ingest_box(const int32_t* shapes, int32_t B, int32_t* Hc_out, int32_t* Wc_out) {
@@ -2653,68 +2657,76 @@ int txo_decode_set_key_mask(txo_engine* e, const uint8_t* mask, int32_t cols, vo
 int txo_generate(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t max_len,
                  int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logits_out, void* stream) {
     if (!e || !img || !tokens_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate(img, nullptr, B, C, H, W, 0, max_len, eos, tokens_out, n_steps, logits_out, nullptr, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.img = img, .B = B, .C = C, .H = H, .W = W}, .max_len = max_len, .eos = eos,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logits = logits_out}, (hipStream_t)stream);
 }
 
 int txo_generate_logp(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t max_len,
                       int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logits_out, float* logp_out, void* stream) {
     if (!e || !img || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate(img, nullptr, B, C, H, W, 0, max_len, eos, tokens_out, n_steps, logits_out, logp_out, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.img = img, .B = B, .C = C, .H = H, .W = W}, .max_len = max_len, .eos = eos,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logits = logits_out, .logp = logp_out}, (hipStream_t)stream);
 }
 
 int txo_generate_from_enc(txo_engine* e, const float* enc, int32_t B, int32_t N, int32_t max_len, int32_t eos,
                           int64_t* tokens_out, int32_t* n_steps, float* logits_out, void* stream) {
     if (!e || !enc || !tokens_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate(nullptr, enc, B, 0, 0, 0, N, max_len, eos, tokens_out, n_steps, logits_out, nullptr, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.enc = enc, .B = B, .N = N}, .max_len = max_len, .eos = eos,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logits = logits_out}, (hipStream_t)stream);
 }
 
 int txo_generate_from_enc_logp(txo_engine* e, const float* enc, int32_t B, int32_t N, int32_t max_len, int32_t eos,
                                int64_t* tokens_out, int32_t* n_steps, float* logits_out, float* logp_out, void* stream) {
     if (!e || !enc || !tokens_out || !logp_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate(nullptr, enc, B, 0, 0, 0, N, max_len, eos, tokens_out, n_steps, logits_out, logp_out, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.enc = enc, .B = B, .N = N}, .max_len = max_len, .eos = eos,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logits = logits_out, .logp = logp_out}, (hipStream_t)stream);
 }
 
 int txo_generate_prefix(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, const int64_t* prefix, int32_t P,
                         const int32_t* prefix_len, int32_t max_len, int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logp_out,
                         float* prefix_logp_out, void* stream) {
     if (!e || !img || !prefix || !tokens_out) return fail(TXO_E_INVALID, "prefix decode: null argument");
-    return e->impl->generate_prefix(img, nullptr, nullptr, B, C, H, W, 0, prefix, P, prefix_len, max_len, eos, tokens_out, n_steps, logp_out,
-                                    prefix_logp_out, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.img = img, .B = B, .C = C, .H = H, .W = W}, .max_len = max_len, .eos = eos,
+                                       .prefix = prefix, .P = P, .prefix_len = prefix_len,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logp = logp_out, .prefix_logp = prefix_logp_out}, (hipStream_t)stream);
 }
 
 int txo_generate_prefix_from_enc(txo_engine* e, const float* enc, int32_t B, int32_t N, const int64_t* prefix, int32_t P, const int32_t* prefix_len,
                                  int32_t max_len, int32_t eos, int64_t* tokens_out, int32_t* n_steps, float* logp_out, float* prefix_logp_out,
                                  void* stream) {
     if (!e || !enc || !prefix || !tokens_out) return fail(TXO_E_INVALID, "prefix decode: null argument");
-    return e->impl->generate_prefix(nullptr, enc, nullptr, B, 0, 0, 0, N, prefix, P, prefix_len, max_len, eos, tokens_out, n_steps, logp_out,
-                                    prefix_logp_out, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.enc = enc, .B = B, .N = N}, .max_len = max_len, .eos = eos,
+                                       .prefix = prefix, .P = P, .prefix_len = prefix_len,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logp = logp_out, .prefix_logp = prefix_logp_out}, (hipStream_t)stream);
 }
 
 int txo_generate_prefix_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes,
                                const int64_t* prefix, int32_t P, const int32_t* prefix_len, int32_t max_len, int32_t eos, int64_t* tokens_out,
                                int32_t* n_steps, float* logp_out, float* prefix_logp_out, void* stream) {
     if (!e || !img || !sizes || !prefix || !tokens_out) return fail(TXO_E_INVALID, "prefix decode: null argument");
-    return e->impl->generate_prefix(img, nullptr, sizes, B, C, Hc, Wc, 0, prefix, P, prefix_len, max_len, eos, tokens_out, n_steps, logp_out,
-                                    prefix_logp_out, (hipStream_t)stream);
+    return e->impl->generate(DecodeReq{.src = {.img = img, .sizes = sizes, .B = B, .C = C, .H = Hc, .W = Wc}, .max_len = max_len, .eos = eos,
+                                       .prefix = prefix, .P = P, .prefix_len = prefix_len,
+                                       .tokens = tokens_out, .n_steps = n_steps, .logp = logp_out, .prefix_logp = prefix_logp_out}, (hipStream_t)stream);
 }
 
 int txo_generate_beam(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t beams, int32_t max_len,
                       int32_t eos, int64_t* tokens_out, float* scores_out, int64_t* all_tokens_out, int32_t* n_steps, void* stream) {
     if (!e || !img || !tokens_out) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->generate_beam(img, nullptr, B, C, H, W, 0, beams, max_len, eos, tokens_out, scores_out, all_tokens_out, n_steps,
-                                  (hipStream_t)stream);
+    return e->impl->beam_search(DecodeSrc{.img = img, .B = B, .C = C, .H = H, .W = W}, beams, max_len, eos,
+                                BeamSink{.best = tokens_out, .scores = scores_out, .all = all_tokens_out}, n_steps, (hipStream_t)stream);
 }
 
 int txo_beam_search(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, int32_t beams, int32_t max_len,
                     int32_t eos, const txo_beam_out* out, int32_t* n_steps, void* stream) {
     if (!e || !img) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->beam_search(img, B, C, H, W, nullptr, beams, max_len, eos, out, n_steps, (hipStream_t)stream);
+    return e->impl->beam_search(DecodeSrc{.img = img, .B = B, .C = C, .H = H, .W = W}, beams, max_len, eos, BeamSink{.out = out}, n_steps, (hipStream_t)stream);
 }
 
 int txo_beam_search_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes,
                            int32_t beams, int32_t max_len, int32_t eos, const txo_beam_out* out, int32_t* n_steps, void* stream) {
     if (!e || !img || !sizes) return fail(TXO_E_INVALID, "null argument");
-    return e->impl->beam_search(img, B, C, Hc, Wc, sizes, beams, max_len, eos, out, n_steps, (hipStream_t)stream);
+    return e->impl->beam_search(DecodeSrc{.img = img, .sizes = sizes, .B = B, .C = C, .H = Hc, .W = Wc}, beams, max_len, eos, BeamSink{.out = out}, n_steps,
+                                (hipStream_t)stream);
 }
 
 int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint64_t seed) {

@@ -1,4 +1,5 @@
-// Session, the open decode session, and ImageBatch, what an encode is given, as values.  Host code, included by engine.hip only (after lanes.h).
+// Session, the open decode session, ImageBatch, what an encode is given, and DecodeReq, what a decode is asked for, as values.  Host code,
+// included by engine.hip only (after lanes.h).
 #pragma once
 
 namespace txo {
@@ -29,5 +30,37 @@ struct ImageBatch {
     size_t pixels() const { return (size_t)C * H * W; }   // of one image (slot)
     ImageBatch chunk(int b0, int nb) const { ImageBatch c = *this; c.first = first + b0; c.B = nb; return c; }
 };
+
+// What a decode is asked to read, as the caller gave it: img = B images [B][C][H][W] (with sizes [B][2] on the host a ragged batch whose
+// container is H x W), or enc = encoder rows [B][N][D].  Engine::resolve_source checks it.
+struct DecodeSrc {
+    const float* img = nullptr; const float* enc = nullptr; const int32_t* sizes = nullptr;
+    int B = 0, C = 0, H = 0, W = 0, N = 0;
+};
+// ... and checked: the images of `ib` (images) or the caller's encoder rows, B rows of N keys either way
+struct Source {
+    ImageBatch ib; bool images = false; const float* data = nullptr; int B = 0, N = 0;
+    const ImageBatch* batch() const { return images ? &ib : nullptr; }
+    bool ragged() const { return images && ib.ragged; }
+};
+
+// One token decode, what every txo_generate* entry asks for: the source, the loop's bounds, a prefix to force (prefix null: none; [B][P] on
+// the device, prefix_len [B] on the host or null = every row has P), where the results go (texocr.h says which may be null).
+struct DecodeReq {
+    DecodeSrc src;
+    int max_len = 0, eos = -1;
+    const int64_t* prefix = nullptr; int P = 0; const int32_t* prefix_len = nullptr;
+    int64_t* tokens = nullptr; int* n_steps = nullptr; float* logits = nullptr; float* logp = nullptr; float* prefix_logp = nullptr;
+};
+// The request behind Engine::generate's checks, what the decode loop and its two paths take.  m / M: the shortest / longest prefix
+// length of a prompted decode (the lengths themselves are in Engine::flen by then).
+struct Decode {
+    const DecodeReq& q; Source src; int m = 0, M = 0;
+    bool prompted() const { return q.prefix != nullptr; }
+};
+
+// Where a beam search's results go: txo_generate_beam's three buffers (best beam [B][max_len] -- never null there --, scores, every beam), or
+// the txo_beam_out of txo_beam_search / _ragged (best null)
+struct BeamSink { int64_t* best; float* scores; int64_t* all; const txo_beam_out* out; };
 
 }  // namespace txo

@@ -198,19 +198,26 @@ class HipEngine:
         if (img is None) == (enc is None):
             raise ValueError("pass exactly one of img / enc")
         self._ensure()
-        e = -1 if eos is None else int(eos)
-        if return_logp:
-            op = torch.ops.texocr.generate_logp if img is not None else torch.ops.texocr.generate_from_enc_logp
-            toks, n, logp, logits = op(img if img is not None else enc, self.id, int(max_len), e, bool(return_logits))
-            n = int(n.item())
-            return (toks[:, :n], logits[:, :n], logp[:, :n]) if return_logits else (toks[:, :n], logp[:, :n])
-        if img is not None:
-            toks, n, logits = torch.ops.texocr.generate(img, self.id, int(max_len), e, bool(return_logits))
+        o = self._generate_op("" if enc is None else "_from_enc", img if enc is None else enc, max_len, eos, logits=return_logits, logp=return_logp)
+        out = (o["toks"],) + ((o["logits"],) if return_logits else ()) + ((o["logp"],) if return_logp else ())
+        return out if len(out) > 1 else out[0]
+
+    def _generate_op(self, kind: str, src, max_len: int, eos: Optional[int], *, logits: bool = False, logp: bool = False, prefix=None,
+                     prefix_len=None) -> dict:
+        """The one place that picks among the nine texocr::generate* ops: by the source (kind "": a (B, C, H, W) tensor; "_from_enc": encoder
+        rows; "_ragged": images of different sizes), the prefix and the flags.  -> the op's outputs by name, cut to its n valid columns."""
+        head = ops.pack_ragged(src) if kind == "_ragged" else (src,)
+        tail = (self.id, int(max_len), -1 if eos is None else int(eos))
+        if prefix is not None:
+            names, name, args = ("toks", "n", "logp", "plogp"), "generate_prefix" + kind, (*head, prefix, prefix_len, *tail, bool(logp))
+        elif kind == "_ragged":
+            names, name, args = ("toks", "n", "logp"), "generate_ragged" + ("_logp" if logp else ""), (*head, *tail)
         else:
-            toks, n, logits = torch.ops.texocr.generate_from_enc(enc, self.id, int(max_len), e, bool(return_logits))
-        n = int(n.item())
-        toks = toks[:, :n]
-        return (toks, logits[:, :n]) if return_logits else toks
+            names = ("toks", "n", "logp", "logits") if logp else ("toks", "n", "logits")
+            name, args = "generate" + kind + ("_logp" if logp else ""), (*head, *tail, bool(logits))
+        o = dict(zip(names, getattr(torch.ops.texocr, name)(*args)))
+        n = int(o.pop("n").item())
+        return {k: v if k == "plogp" else v[:, :n] for k, v in o.items()}
 
     def generate_prefix(self, src, prefix: torch.Tensor, max_len: int, eos: Optional[int], prefix_len=None,
                         enc: Optional[torch.Tensor] = None, return_logp: bool = False):
@@ -224,17 +231,9 @@ class HipEngine:
             prefix_len = torch.as_tensor(prefix_len).to(device="cpu", dtype=torch.int32).reshape(-1).contiguous()
         ops.check_prefix(tuple(prefix.shape), prefix_len, max_len, self.dims.max_len, self.max_batch * self.max_tokens)   # before anything changes
         self._ensure()
-        e = -1 if eos is None else int(eos)
-        if enc is not None:
-            out = torch.ops.texocr.generate_prefix_from_enc(enc, prefix, prefix_len, self.id, int(max_len), e, bool(return_logp))
-        elif isinstance(src, torch.Tensor):
-            out = torch.ops.texocr.generate_prefix(src, prefix, prefix_len, self.id, int(max_len), e, bool(return_logp))
-        else:
-            box, sizes = ops.pack_ragged(src)
-            out = torch.ops.texocr.generate_prefix_ragged(box, sizes, prefix, prefix_len, self.id, int(max_len), e, bool(return_logp))
-        toks, n, logp, plogp = out
-        n = int(n.item())
-        return (toks[:, :n], logp[:, :n], plogp) if return_logp else toks[:, :n]
+        kind = "_from_enc" if enc is not None else "" if isinstance(src, torch.Tensor) else "_ragged"
+        o = self._generate_op(kind, src if enc is None else enc, max_len, eos, logp=return_logp, prefix=prefix, prefix_len=prefix_len)
+        return (o["toks"], o["logp"], o["plogp"]) if return_logp else o["toks"]
 
     # ---- ragged batches (build extension): images of different sizes in one call; `images` is a sequence of (C, H_b, W_b) tensors, or a
     # container that already exists (ops.PackedImages: what ingest returns) ----
@@ -263,14 +262,10 @@ class HipEngine:
 
     def generate_ragged(self, images, max_len: int, eos: Optional[int], return_logp: bool = False):
         self._ensure()
-        box, sizes = ops.pack_ragged(images)
         # beyond the positional table the window slides through the ragged multi-position forward
         with self.ragged_forward() if int(max_len) > self.dims.max_len else contextlib.nullcontext():
-            if return_logp:
-                toks, n, logp = torch.ops.texocr.generate_ragged_logp(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
-                return toks[:, :int(n.item())], logp[:, :int(n.item())]
-            toks, n = torch.ops.texocr.generate_ragged(box, sizes, self.id, int(max_len), -1 if eos is None else int(eos))
-            return toks[:, :int(n.item())]
+            o = self._generate_op("_ragged", images, max_len, eos, logp=return_logp)
+        return (o["toks"], o["logp"]) if return_logp else o["toks"]
 
     def generate_beam(self, img: torch.Tensor, beams: int, max_len: int, eos: Optional[int], return_beams: bool = False):
         """Beam search (build extension; the reference has none).  Returns the best beam's tokens (B, n), or with

@@ -38,7 +38,7 @@ import ctypes as C
 import os
 import weakref
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch.library import custom_op
@@ -302,47 +302,79 @@ def _(tokens, engine, want_logits, want_self, want_cross, want_mean):
     return tuple(tokens.new_empty(sh, dtype=torch.float32) for sh in shapes)
 
 
-def _gen_outputs(src, e, max_len, want_logits):
+class _Gen(NamedTuple):
+    """what a token decode returns; an output that was not asked for has no rows"""
+    toks: torch.Tensor          # (B, max_len) int64, of which the first n columns are valid
+    n: torch.Tensor             # int64 CPU tensor of shape (1,)
+    logp: torch.Tensor          # (B, max_len) float32
+    logits: torch.Tensor        # (B, max_len, V) float32
+    plogp: torch.Tensor         # (B, P) float32: the forced tokens of a prompted decode
+
+
+def _gen_shapes(src, vocab: int, max_len: int, want_logits: bool, want_logp: bool, prefix) -> _Gen:
+    """the outputs of every texocr::generate* op, real and fake alike (new_empty: on src's device, or meta)"""
     B = src.shape[0]
-    toks = torch.empty((B, max_len), device=src.device, dtype=torch.int64)
-    if os.environ.get("TXO_DEBUG_POISON"):      # tests: a column the engine returns as valid but never wrote shows as -7
-        toks.fill_(-7)
-    logits = torch.empty((B if want_logits else 0, max_len, e.dims.vocab), device=src.device, dtype=torch.float32)
-    return toks, logits
+    return _Gen(src.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
+                src.new_empty((B if want_logp else 0, max_len), dtype=torch.float32),
+                src.new_empty((B if want_logits else 0, max_len, vocab), dtype=torch.float32),
+                src.new_empty((B if want_logp and prefix is not None else 0, 0 if prefix is None else prefix.shape[1]), dtype=torch.float32))
+
+
+def _gen_fake(src, engine, max_len, want_logits=False, want_logp=False, prefix=None) -> _Gen:
+    return _gen_shapes(src, _eng(engine).dims.vocab, max_len, want_logits, want_logp, prefix)
+
+
+def _generate(src: torch.Tensor, engine: int, max_len: int, eos: int, *, kind: str = "", sizes=None, want_logits: bool = False,
+              want_logp: bool = False, prefix=None, prefix_len=None) -> _Gen:
+    """The body of the nine texocr::generate* ops: checks the source (kind "": images (B, C, H, W); "_from_enc": encoder rows (B, N, D);
+    "_ragged": a container + sizes) and the prefix, allocates the outputs, and makes the one call txo_generate[_prefix]<kind>[_logp]."""
+    e = _eng(engine, ready=True)
+    if kind == "_from_enc":
+        src = _enc_arg(src, e)
+        head = (src.data_ptr(), src.shape[0], src.shape[1])
+    else:
+        src, sizes = _ragged_args(src, sizes, e) if kind else (_img_arg(src, e), None)
+        head = (src.data_ptr(), *src.shape) + ((_i32p(sizes),) if kind else ())
+    B = src.shape[0]
+    if prefix is not None:
+        prefix, prefix_len = _prefix_args(prefix, prefix_len, e, B, max_len)
+    g = _gen_shapes(src, e.dims.vocab, max_len, want_logits, want_logp, prefix)
+    if os.environ.get("TXO_DEBUG_POISON"):      # tests: a column the engine returns as valid but never wrote shows as -7, a log-probability as nan
+        g.toks.fill_(-7)
+        g.logp.fill_(float("nan"))
+    n = C.c_int32(0)
+    ptr = lambda t, want: t.data_ptr() if want else None
+    if prefix is not None:
+        fn = "txo_generate_prefix" + kind
+        tail = (prefix.data_ptr(), int(prefix.shape[1]), None if prefix_len is None else _i32p(prefix_len), int(max_len), int(eos), g.toks.data_ptr(),
+                C.byref(n), ptr(g.logp, want_logp), ptr(g.plogp, want_logp))
+    else:
+        fn = "txo_generate" + kind + ("_logp" if want_logp else "")
+        tail = (int(max_len), int(eos), g.toks.data_ptr(), C.byref(n)) + (() if kind == "_ragged" else (ptr(g.logits, want_logits),)) \
+            + ((g.logp.data_ptr(),) if want_logp else ())
+    _call(e, fn, *head, *tail, leaves=() if kind == "_ragged" else (B, src))   # nothing ragged outlives the call (engine.hip: generate_common)
+    return g._replace(n=torch.tensor([n.value], dtype=torch.int64))
 
 
 @custom_op("texocr::generate", mutates_args=())
 def generate(img: torch.Tensor, engine: int, max_len: int, eos: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Greedy OCRModel.generate: (tokens (B, max_len) of which the first n are valid, n as an int64 CPU tensor of shape (1,),
     logits (B, max_len, V) or (0, max_len, V)).  eos < 0: no eos test (eos_tok=None)."""
-    e = _eng(engine, ready=True)
-    img = _img_arg(img, e)
-    B, Cc, H, W = img.shape
-    toks, logits = _gen_outputs(img, e, max_len, want_logits)
-    n = C.c_int32(0)
-    _call(e, "txo_generate", img.data_ptr(), B, Cc, H, W, int(max_len), int(eos), toks.data_ptr(), C.byref(n),
-          logits.data_ptr() if want_logits else None, leaves=(B, img))
-    return toks, torch.tensor([n.value], dtype=torch.int64), logits
+    g = _generate(img, engine, max_len, eos, want_logits=want_logits)
+    return g.toks, g.n, g.logits
 
 
 @custom_op("texocr::generate_from_enc", mutates_args=())
 def generate_from_enc(enc: torch.Tensor, engine: int, max_len: int, eos: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    e = _eng(engine, ready=True)
-    enc = _enc_arg(enc, e)
-    toks, logits = _gen_outputs(enc, e, max_len, want_logits)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_from_enc", enc.data_ptr(), enc.shape[0], enc.shape[1], int(max_len), int(eos), toks.data_ptr(), C.byref(n),
-          logits.data_ptr() if want_logits else None, leaves=(enc.shape[0], enc))
-    return toks, torch.tensor([n.value], dtype=torch.int64), logits
+    g = _generate(enc, engine, max_len, eos, kind="_from_enc", want_logits=want_logits)
+    return g.toks, g.n, g.logits
 
 
 @generate.register_fake
 @generate_from_enc.register_fake
 def _(src, engine, max_len, eos, want_logits):
-    d = _eng(engine).dims
-    B = src.shape[0]
-    return (src.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
-            src.new_empty((B if want_logits else 0, max_len, d.vocab), dtype=torch.float32))
+    g = _gen_fake(src, engine, max_len, want_logits)
+    return g.toks, g.n, g.logits
 
 
 def _logp_output(toks: torch.Tensor) -> torch.Tensor:
@@ -356,37 +388,21 @@ def _logp_output(toks: torch.Tensor) -> torch.Tensor:
 def generate_logp(img: torch.Tensor, engine: int, max_len: int, eos: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """texocr::generate plus logp (B, max_len) float32: log_softmax(logits)[token] of every valid position, at temperature 1 over the
     whole vocabulary whatever the token selection (txo_generate_logp) -> (tokens, n, logp, logits (B, max_len, V) or (0, max_len, V))."""
-    e = _eng(engine, ready=True)
-    img = _img_arg(img, e)
-    B, Cc, H, W = img.shape
-    toks, logits = _gen_outputs(img, e, max_len, want_logits)
-    logp = _logp_output(toks)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_logp", img.data_ptr(), B, Cc, H, W, int(max_len), int(eos), toks.data_ptr(), C.byref(n),
-          logits.data_ptr() if want_logits else None, logp.data_ptr(), leaves=(B, img))
-    return toks, torch.tensor([n.value], dtype=torch.int64), logp, logits
+    g = _generate(img, engine, max_len, eos, want_logits=want_logits, want_logp=True)
+    return g.toks, g.n, g.logp, g.logits
 
 
 @custom_op("texocr::generate_from_enc_logp", mutates_args=())
 def generate_from_enc_logp(enc: torch.Tensor, engine: int, max_len: int, eos: int, want_logits: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    e = _eng(engine, ready=True)
-    enc = _enc_arg(enc, e)
-    toks, logits = _gen_outputs(enc, e, max_len, want_logits)
-    logp = _logp_output(toks)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_from_enc_logp", enc.data_ptr(), enc.shape[0], enc.shape[1], int(max_len), int(eos), toks.data_ptr(), C.byref(n),
-          logits.data_ptr() if want_logits else None, logp.data_ptr(), leaves=(enc.shape[0], enc))
-    return toks, torch.tensor([n.value], dtype=torch.int64), logp, logits
+    g = _generate(enc, engine, max_len, eos, kind="_from_enc", want_logits=want_logits, want_logp=True)
+    return g.toks, g.n, g.logp, g.logits
 
 
 @generate_logp.register_fake
 @generate_from_enc_logp.register_fake
 def _(src, engine, max_len, eos, want_logits):
-    d = _eng(engine).dims
-    B = src.shape[0]
-    return (src.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
-            src.new_empty((B, max_len), dtype=torch.float32),
-            src.new_empty((B if want_logits else 0, max_len, d.vocab), dtype=torch.float32))
+    g = _gen_fake(src, engine, max_len, want_logits, True)
+    return g.toks, g.n, g.logp, g.logits
 
 
 @custom_op("texocr::generate_beam", mutates_args=())
@@ -557,19 +573,13 @@ def _(*args):
 @custom_op("texocr::generate_ragged", mutates_args=())
 def generate_ragged(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len: int, eos: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """txo_generate_ragged: (tokens (B, max_len) of which the first n are valid, n as an int64 CPU tensor of shape (1,))."""
-    e = _eng(engine, ready=True)
-    img, sizes = _ragged_args(img, sizes, e)
-    B, Cc, Hc, Wc = img.shape
-    toks, _ = _gen_outputs(img, e, max_len, False)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_ragged", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), int(max_len), int(eos), toks.data_ptr(), C.byref(n),
-          leaves=())                            # nothing ragged outlives the call (engine.hip: generate_common)
-    return toks, torch.tensor([n.value], dtype=torch.int64)
+    g = _generate(img, engine, max_len, eos, kind="_ragged", sizes=sizes)
+    return g.toks, g.n
 
 
 @generate_ragged.register_fake
 def _(img, sizes, engine, max_len, eos):
-    return img.new_empty((img.shape[0], max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu")
+    return _gen_fake(img, engine, max_len)[:2]
 
 
 def _beam_outputs(img: torch.Tensor, beams: int, max_len: int, want_logp: bool, length_alpha: float):
@@ -670,100 +680,57 @@ def _prefix_args(prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], e, B:
     return prefix, prefix_len
 
 
-def _prefix_outputs(prefix: torch.Tensor, e, max_len: int, want_logp: bool):
-    toks, _ = _gen_outputs(prefix, e, max_len, False)
-    logp = _logp_output(toks) if want_logp else torch.empty((0, max_len), device=prefix.device, dtype=torch.float32)
-    plogp = torch.empty((prefix.shape[0] if want_logp else 0, prefix.shape[1]), device=prefix.device, dtype=torch.float32)
-    return toks, logp, plogp
-
-
-def _prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp):
-    """the arguments every txo_generate_prefix* takes behind its images"""
-    return (prefix.data_ptr(), int(prefix.shape[1]), None if prefix_len is None else _i32p(prefix_len), int(max_len), int(eos), toks.data_ptr(),
-            C.byref(n), logp.data_ptr() if want_logp else None, plogp.data_ptr() if want_logp else None)
-
-
 @custom_op("texocr::generate_prefix", mutates_args=())
 def generate_prefix(img: torch.Tensor, prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], engine: int, max_len: int, eos: int,
                     want_logp: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """txo_generate_prefix: prefix (B, P) int64 on the GPU, prefix_len (B,) int32 CPU or None (every row has length P) -> (tokens (B, max_len)
     of which the first n are valid -- column j of row b is the j-th token behind row b's own prefix --, n as an int64 CPU tensor of shape
     (1,), logp (B, max_len) or (0, max_len), prefix_logp (B, P) or (0, P): the log-probabilities of the forced tokens)."""
-    e = _eng(engine, ready=True)
-    img = _img_arg(img, e)
-    B, Cc, H, W = img.shape
-    prefix, prefix_len = _prefix_args(prefix, prefix_len, e, B, max_len)
-    toks, logp, plogp = _prefix_outputs(prefix, e, max_len, want_logp)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_prefix", img.data_ptr(), B, Cc, H, W, *_prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp),
-          leaves=(B, img))
-    return toks, torch.tensor([n.value], dtype=torch.int64), logp, plogp
+    g = _generate(img, engine, max_len, eos, want_logp=want_logp, prefix=prefix, prefix_len=prefix_len)
+    return g.toks, g.n, g.logp, g.plogp
 
 
 @custom_op("texocr::generate_prefix_from_enc", mutates_args=())
 def generate_prefix_from_enc(enc: torch.Tensor, prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], engine: int, max_len: int, eos: int,
                              want_logp: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    e = _eng(engine, ready=True)
-    enc = _enc_arg(enc, e)
-    B = enc.shape[0]
-    prefix, prefix_len = _prefix_args(prefix, prefix_len, e, B, max_len)
-    toks, logp, plogp = _prefix_outputs(prefix, e, max_len, want_logp)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_prefix_from_enc", enc.data_ptr(), B, enc.shape[1], *_prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp),
-          leaves=(B, enc))
-    return toks, torch.tensor([n.value], dtype=torch.int64), logp, plogp
+    g = _generate(enc, engine, max_len, eos, kind="_from_enc", want_logp=want_logp, prefix=prefix, prefix_len=prefix_len)
+    return g.toks, g.n, g.logp, g.plogp
 
 
 @custom_op("texocr::generate_prefix_ragged", mutates_args=())
 def generate_prefix_ragged(img: torch.Tensor, sizes: torch.Tensor, prefix: torch.Tensor, prefix_len: Optional[torch.Tensor], engine: int,
                            max_len: int, eos: int, want_logp: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """txo_generate_prefix_ragged: texocr::generate_prefix over a container (B, C, Hc, Wc) + sizes (B, 2) int32 CPU."""
-    e = _eng(engine, ready=True)
-    img, sizes = _ragged_args(img, sizes, e)
-    B, Cc, Hc, Wc = img.shape
-    prefix, prefix_len = _prefix_args(prefix, prefix_len, e, B, max_len)
-    toks, logp, plogp = _prefix_outputs(prefix, e, max_len, want_logp)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_prefix_ragged", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes),
-          *_prefix_tail(prefix, prefix_len, max_len, eos, toks, n, logp, plogp, want_logp), leaves=())   # nothing ragged outlives the call
-    return toks, torch.tensor([n.value], dtype=torch.int64), logp, plogp
+    g = _generate(img, engine, max_len, eos, kind="_ragged", sizes=sizes, want_logp=want_logp, prefix=prefix, prefix_len=prefix_len)
+    return g.toks, g.n, g.logp, g.plogp
 
 
-def _prefix_fake(prefix, max_len, want_logp):
-    B, P = prefix.shape
-    return (prefix.new_empty((B, max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
-            prefix.new_empty((B if want_logp else 0, max_len), dtype=torch.float32), prefix.new_empty((B if want_logp else 0, P), dtype=torch.float32))
+def _prefix_fake(src, prefix, engine, max_len, want_logp):
+    g = _gen_fake(src, engine, max_len, False, want_logp, prefix)
+    return g.toks, g.n, g.logp, g.plogp
 
 
 @generate_prefix.register_fake
 @generate_prefix_from_enc.register_fake
 def _(src, prefix, prefix_len, engine, max_len, eos, want_logp):
-    return _prefix_fake(prefix, max_len, want_logp)
+    return _prefix_fake(src, prefix, engine, max_len, want_logp)
 
 
 @generate_prefix_ragged.register_fake
 def _(img, sizes, prefix, prefix_len, engine, max_len, eos, want_logp):
-    return _prefix_fake(prefix, max_len, want_logp)
+    return _prefix_fake(img, prefix, engine, max_len, want_logp)
 
 
 @custom_op("texocr::generate_ragged_logp", mutates_args=())
 def generate_ragged_logp(img: torch.Tensor, sizes: torch.Tensor, engine: int, max_len: int, eos: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """txo_generate_ragged_logp: texocr::generate_ragged plus logp (B, max_len) float32 -> (tokens, n, logp)."""
-    e = _eng(engine, ready=True)
-    img, sizes = _ragged_args(img, sizes, e)
-    B, Cc, Hc, Wc = img.shape
-    toks, _ = _gen_outputs(img, e, max_len, False)
-    logp = _logp_output(toks)
-    n = C.c_int32(0)
-    _call(e, "txo_generate_ragged_logp", img.data_ptr(), B, Cc, Hc, Wc, _i32p(sizes), int(max_len), int(eos), toks.data_ptr(), C.byref(n),
-          logp.data_ptr(), leaves=())
-    return toks, torch.tensor([n.value], dtype=torch.int64), logp
+    g = _generate(img, engine, max_len, eos, kind="_ragged", sizes=sizes, want_logp=True)
+    return g.toks, g.n, g.logp
 
 
 @generate_ragged_logp.register_fake
 def _(img, sizes, engine, max_len, eos):
-    return (img.new_empty((img.shape[0], max_len), dtype=torch.int64), torch.empty((1,), dtype=torch.int64, device="cpu"),
-            img.new_empty((img.shape[0], max_len), dtype=torch.float32))
+    return _gen_fake(img, engine, max_len, False, True)[:3]
 
 
 # ---- device-side image ingest (txo_ingest_u8): raw uint8 pixels -> the container of a ragged batch, one copy and one launch ----------
