@@ -392,6 +392,36 @@ int txo_ingest_u8_fit(txo_engine* e, const uint8_t* pix_dev, const int64_t* offs
                       int32_t Fh, int32_t Fw, int32_t Hc, int32_t Wc, float* box_out_dev, int32_t* sizes_out_host, void* scratch_dev,
                       int64_t scratch_bytes, void* stream);
 
+/* ---- Trim-to-ink and region ingest (a BUILD EXTENSION; opt-in: the calls above are unchanged and launch the kernels they always did) ----
+ * Ingest of a RECTANGLE of a source image, in front of the fit and the ingest arithmetic above: the rectangle -- the VIEW (y0, x0, h', w'),
+ * in source pixels -- takes the place of the image.  The fit rule applies to (h', w'), the pad to 16, the container and sizes_out_host come
+ * from the view, and what comes out is bit for bit txo_ingest_u8 / txo_ingest_u8_fit of a tightly packed copy of the view's pixels.  The
+ * order is always trim, then fit.  The caller names the views (boxes of a detector on a page that went up ONCE), or the engine finds them:
+ * Trim-to-ink (texocr_amd/csrc/ingest_trim.h).  Integer-only, on the bytes the ingest reads -- L as it is; R, G, B of RGB / RGBA; the alpha
+ * is never read.  A pixel is INK iff min(read channels) <= level, level in [0, 254] (127: the mid-grey convention).  margin >= 0 pixels are
+ * kept around the ink box and clamped to the image (2 keeps an anti-aliased rim lighter than level):
+ *   y0 = max(0, ymin_ink - margin), y1 = min(h, ymax_ink + 1 + margin), h' = y1 - y0; the same for x.
+ * An image with no ink keeps the whole-image view (0, 0, h, w).  Dark backgrounds and polarity detection are out of scope.
+ *   txo_ingest_trim_views  pix_dev / offsets_host / shapes_host / B as for txo_ingest_u8.  ONE launch reads every byte of every image once
+ *                          and leaves the ink extents; views_out_host int32 [B][4] = (y0, x0, h', w') by the rule above.  SYNCHRONOUS: it
+ *                          copies 16 B bytes back and WAITS on `stream` before it returns -- the container's size and sizes depend on the
+ *                          answer.  It is the one synchronisation of the path; every other ingest call stays asynchronous.  No allocation.
+ *                          Refused with TXO_E_INVALID before anything is enqueued: every refusal of txo_ingest_u8 about the list and the
+ *                          offsets, level outside [0, 254], margin < 0.  Under txo_profile_enable(e, 1) the launch carries events (kind 4).
+ *   txo_ingest_u8_view     shapes_host / offsets_host describe the FULL images; views_host int32 [B][4] = (y0, x0, h', w') one view per
+ *                          entry.  Several entries may name the same source bytes (the same offset) and their views may overlap.
+ *                          Fh = Fw = 0: txo_ingest_u8 on the views; otherwise txo_ingest_u8_fit on them under the target (Fh, Fw).
+ *                          txo_ingest_box, txo_ingest_fit and txo_ingest_fit_scratch compose unchanged: call them on shapes whose (h, w)
+ *                          are the views' (h', w').  Refused with TXO_E_INVALID and a message naming the image, nothing enqueued: a view
+ *                          with h' < 1 or w' < 1 or reaching outside its image, and every refusal of txo_ingest_u8 / txo_ingest_u8_fit,
+ *                          judged on the view's size.  Asynchronous; no allocation.  Views that all keep their images' widths run the very
+ *                          kernels of the calls above; others run their pitched forms (a source row is the image's width apart). */
+int txo_ingest_trim_views(txo_engine* e, const uint8_t* pix_dev, const int64_t* offsets_host, const int32_t* shapes_host, int32_t B, int32_t level,
+                          int32_t margin, int32_t* views_out_host, void* stream);
+int txo_ingest_u8_view(txo_engine* e, const uint8_t* pix_dev, const int64_t* offsets_host, const int32_t* shapes_host, const int32_t* views_host,
+                       int32_t B, int32_t C, int32_t Fh, int32_t Fw, int32_t Hc, int32_t Wc, float* box_out_dev, int32_t* sizes_out_host,
+                       void* scratch_dev, int64_t scratch_bytes, void* stream);
+
 /* Token selection for the following decode steps / generate calls.  mode 0 (default): greedy argmax.  mode 1:
  * the reference's sampler (decoder.py:104-108 + utils.topk, utils.py:85-91): keep the `topk` largest logits
  * (the reference uses int((1 - 0.9) * vocab) = 99 for vocab 1000), softmax(logits / temp), one multinomial draw,
@@ -418,7 +448,7 @@ int txo_set_stop_mode(txo_engine* e, int32_t mode);
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
  * enabled (txo_profile_enable(e, 1) also clears the previous samples); *count = number of launches averaged.  kind: 0 = cross-attention decode kernel,
- * 1 = encoder (whole txo_encode), 2 = whole decode step, 4 = the ingest kernel of txo_ingest_u8 and the launches of txo_ingest_u8_fit (events bound to the dispatch).
+ * 1 = encoder (whole txo_encode), 2 = whole decode step, 4 = the ingest kernel of txo_ingest_u8 and the launches of txo_ingest_u8_fit, txo_ingest_u8_view and txo_ingest_trim_views (events bound to the dispatch).
  * on = 1: everything above (adds marker commands around every encode and step -- use in a separate pass); on = 2: only every
  * fourth cross-attention dispatch carries events (bound to the dispatch, no extra commands; safe inside a timed region; samples are
  * kept for the first 16 generate() calls after enabling); on = 3: the persistent decode launch carries events (kind 3 =

@@ -71,6 +71,9 @@ SYMBOLS = {
     "txo_ingest_fit_coeffs": (C.c_int, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "txo_ingest_u8_fit": (C.c_int, [_P, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _I, _I, _I, _I, _I, _FP, C.POINTER(C.c_int32),
                                     C.c_void_p, C.c_int64, _P]),
+    "txo_ingest_trim_views": (C.c_int, [_P, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(C.c_int32), _P]),
+    "txo_ingest_u8_view": (C.c_int, [_P, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _I, _I, _I, _FP,
+                                     C.POINTER(C.c_int32), C.c_void_p, C.c_int64, _P]),
     "txo_set_sampling": (C.c_int, [_P, _I, _I, C.c_float, C.c_uint64]),
     "txo_set_stop_mode": (C.c_int, [_P, _I]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),

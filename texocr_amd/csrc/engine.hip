@@ -47,6 +47,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "step_prefix.h"   // (behind every other kernel: the kernels above keep their places in the code object)
 #include "ingest.h"        // (likewise: the newest kernel goes last)
 #include "ingest_fit.h"    // (the fit-to-canvas passes in front of it; uses ingest.h's per-pixel pieces)
+#include "ingest_trim.h"   // (the ink extents in front of both; reads ingest.h's descriptors)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -62,6 +63,15 @@ static void dbg(hipStream_t s, const char* what, int l = -1) {
 }
 
 struct HostTensor { std::vector<int64_t> shape; std::vector<float> data; };
+
+// The trim rule of texocr.h "Trim-to-ink ingest": ink extents (ymin, xmin, ymax, xmax; ymax < 0: no ink) of an image (h, w) and a margin ->
+// the view (y0, x0, h', w'): the ink box widened by the margin on every side and clamped to the image; the whole image where there is no ink
+static inline void trim_view_of(const int* ext, int h, int w, int margin, int32_t* view) {
+    if (ext[2] < 0) { view[0] = 0; view[1] = 0; view[2] = h; view[3] = w; return; }
+    const long long y0 = std::max(0LL, (long long)ext[0] - margin), y1 = std::min((long long)h, (long long)ext[2] + 1 + margin);
+    const long long x0 = std::max(0LL, (long long)ext[1] - margin), x1 = std::min((long long)w, (long long)ext[3] + 1 + margin);
+    view[0] = (int32_t)y0; view[1] = (int32_t)x0; view[2] = (int32_t)(y1 - y0); view[3] = (int32_t)(x1 - x0);
+}
 
 // -------------------------------------------------------------------------------------------------
 struct EngineBase {
@@ -94,12 +104,16 @@ struct EngineBase {
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
     bool rag_fwd = false;                       // txo_set_ragged_forward: the multi-position forward on ragged sessions and the ragged sliding window are accepted
     bool rag_hybrid = false;                    // txo_set_ragged_hybrid: ragged batches are accepted on the hybrid front end (conv.h: the RAGGED forms)
-    // txo_ingest_u8 behind its checks (ingest_check): descriptors up in one staged copy, one launch
-    virtual int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc, float* box,
-                          hipStream_t s) = 0;
+    // txo_ingest_u8 behind its checks (ingest_check): descriptors up in one staged copy, one launch.  pitch (here and below; null: rows are
+    // tightly packed, today's kernels): [B] pixels from one source row to the next -- (offsets, shapes) then describe VIEWS (txo_ingest_u8_view)
+    virtual int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int B, int C, int Hc, int Wc,
+                          float* box, hipStream_t s) = 0;
     // txo_ingest_u8_fit behind its checks, with at least one oversized image: fitted [B][2] from ingest_fit_sizes, scratch holds the intermediates
-    virtual int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* fitted, int B, int C, int Hc,
-                              int Wc, float* box, unsigned char* scratch, hipStream_t s) = 0;
+    virtual int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, const int32_t* fitted, int B,
+                              int C, int Hc, int Wc, float* box, unsigned char* scratch, hipStream_t s) = 0;
+    // txo_ingest_trim_views behind its checks: the ink extents of every image (ingest_trim.h) -> views [B][4]; waits on s
+    virtual int trim_views(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int level, int margin, int32_t* views,
+                           hipStream_t s) = 0;
     virtual int query(int what, int64_t* out) = 0;
     virtual int profile_enable(int on) = 0;
     virtual int profile_read(int kind, double* avg_ms, int64_t* count) = 0;
@@ -209,6 +223,8 @@ struct Engine : EngineBase {
     IngestDesc *ing_desc = nullptr, *ing_host = nullptr; hipEvent_t ing_ev = nullptr; bool ing_ev_pending = false;
     // fit-to-canvas ingest (ingest_fit.h): FitDesc [Bmax] followed by the list int [Bmax] of the images that need a horizontal pass; staged like ing_host
     char *fit_dev = nullptr, *fit_host = nullptr;
+    // trim-to-ink ingest (ingest_trim.h): the ink extents int [Bmax][4] on the device and where they are copied back to (pinned)
+    int *trim_rec = nullptr, *trim_host = nullptr;
     size_t fit_bytes(int B) const { return (sizeof(FitDesc) + sizeof(int)) * (size_t)B; }
     int rag_box[2] = {0, 0};          // the smallest H x W (multiples of 16) that holds every image of the last ragged batch
     // rag_fwd off (the default): these calls answer as they did before the forward had a ragged form
@@ -250,6 +266,7 @@ struct Engine : EngineBase {
         if (rag_ev) (void)hipEventDestroy(rag_ev);
         if (ing_host) (void)hipHostFree(ing_host);
         if (fit_host) (void)hipHostFree(fit_host);
+        if (trim_host) (void)hipHostFree(trim_host);
         if (ing_ev) (void)hipEventDestroy(ing_ev);
         for (void* p : allocs) (void)hipFree(p);
     }
@@ -594,6 +611,7 @@ struct Engine : EngineBase {
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ing_host), sizeof(IngestDesc) * (size_t)Bmax, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&ing_ev, hipEventDisableTiming));
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&fit_host), fit_bytes(Bmax), hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&trim_host), sizeof(int) * 4 * (size_t)Bmax, hipHostMallocDefault));
         return lanes.init(Tmax);
     }
     int init_buffers() {
@@ -704,6 +722,7 @@ struct Engine : EngineBase {
         if (int r = dalloc(&pstamps, (size_t)PS_TEAMS * PS_STAMP_RANKS * PS_MAX_STAGES * PS_STAMP_WORDS)) return r;
         if (int r = dalloc(&ing_desc, (size_t)Bmax)) return r;   // (last: no earlier buffer moves)
         if (int r = dalloc(&fit_dev, fit_bytes(Bmax))) return r;
+        if (int r = dalloc(&trim_rec, (size_t)4 * Bmax)) return r;
         return 0;
     }
 
@@ -988,30 +1007,32 @@ struct Engine : EngineBase {
     }
     // Device-side image ingest (ingest.h).  The list has passed ingest_check; works before the weights are finalized (it reads none).
     // The three host arrays go up as ONE staged copy of B descriptors, the way ragged_batch uploads its grids; no allocation.
-    int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc, float* box,
-                  hipStream_t s) override {
+    int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int B, int C, int Hc, int Wc,
+                  float* box, hipStream_t s) override {
         if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
         if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
-        for (int b = 0; b < B; ++b) ing_host[b] = IngestDesc{(long long)offsets[b], shapes[3 * b], shapes[3 * b + 1], shapes[3 * b + 2], 0};
+        for (int b = 0; b < B; ++b)
+            ing_host[b] = IngestDesc{(long long)offsets[b], shapes[3 * b], shapes[3 * b + 1], shapes[3 * b + 2], pitch ? pitch[b] : 0};
         HIP_TRY(hipMemcpyAsync(ing_desc, ing_host, sizeof(IngestDesc) * B, hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(ing_ev, s));
         ing_ev_pending = true;
         const dim3 grid((unsigned)((Wc + IG_BLOCK_W - 1) / IG_BLOCK_W), (unsigned)((Hc + IG_ROWS - 1) / IG_ROWS), (unsigned)B), blk(IG_LANES_X * IG_ROWS);
+        const auto kern = pitch ? ingest_u8_kernel<true> : ingest_u8_kernel<false>;
         if (prof) {                                           // txo_profile_read kind 4: events bound to the dispatch itself
             hipEvent_t e0 = pool.next(), e1 = pool.next();
             if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
-            hipExtLaunchKernelGGL(ingest_u8_kernel, grid, blk, 0, s, e0, e1, 0, pix, ing_desc, box, C, Hc, Wc);
+            hipExtLaunchKernelGGL(kern, grid, blk, 0, s, e0, e1, 0, pix, (const IngestDesc*)ing_desc, box, C, Hc, Wc);
             ev_ingest.push_back({e0, e1});
         } else {
-            hipLaunchKernelGGL(ingest_u8_kernel, grid, blk, 0, s, pix, ing_desc, box, C, Hc, Wc);
+            hipLaunchKernelGGL(kern, grid, blk, 0, s, pix, (const IngestDesc*)ing_desc, box, C, Hc, Wc);
         }
         HIP_TRY(hipGetLastError());
         return 0;
     }
     // Fit-to-canvas ingest (ingest_fit.h).  The list has passed ingest_fit_check and holds an oversized image.  One staged copy of the
     // descriptors and of the list of images with a horizontal pass, then that pass (if any image has one) and the fused vertical pass + ingest.
-    int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* fitted, int B, int C, int Hc, int Wc,
-                      float* box, unsigned char* scratch, hipStream_t s) override {
+    int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, const int32_t* fitted, int B, int C,
+                      int Hc, int Wc, float* box, unsigned char* scratch, hipStream_t s) override {
         if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
         if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
         FitDesc* fd = reinterpret_cast<FitDesc*>(fit_host);
@@ -1020,7 +1041,7 @@ struct Engine : EngineBase {
         int nh = 0, hmax = 0, wmax = 0;
         for (int b = 0; b < B; ++b) {
             const int h = shapes[3 * b], w = shapes[3 * b + 1], ch = shapes[3 * b + 2], fh = fitted[2 * b], fw = fitted[2 * b + 1];
-            fd[b] = FitDesc{(long long)offsets[b], -1, h, w, ch, fh, fw, 0};
+            fd[b] = FitDesc{(long long)offsets[b], -1, h, w, ch, fh, fw, pitch ? pitch[b] : 0};
             if (fw != w) {
                 fd[b].mid = mid;
                 mid += ingest_fit_mid_bytes(h, fw, ch);
@@ -1035,22 +1056,54 @@ struct Engine : EngineBase {
         const int* dl = reinterpret_cast<const int*>(fit_dev + sizeof(FitDesc) * (size_t)B);
         const dim3 hgrid((unsigned)((wmax + FR_COLS - 1) / FR_COLS), (unsigned)((hmax + FR_ROWS - 1) / FR_ROWS), (unsigned)nh), hblk(FR_COLS * FR_LANES_Y);
         const dim3 grid((unsigned)((Wc + IG_BLOCK_W - 1) / IG_BLOCK_W), (unsigned)((Hc + IG_ROWS - 1) / IG_ROWS), (unsigned)B), blk(IG_LANES_X * IG_ROWS);
+        const auto rows = pitch ? fit_rows_kernel<true> : fit_rows_kernel<false>;
+        const auto kern = pitch ? ingest_fit_kernel<true> : ingest_fit_kernel<false>;
         if (prof) {                                           // txo_profile_read kind 4: events bound to each dispatch
             if (nh) {
                 hipEvent_t h0 = pool.next(), h1 = pool.next();
                 if (!h0 || !h1) return fail(TXO_E_HIP, "hipEventCreate failed");
-                hipExtLaunchKernelGGL(fit_rows_kernel, hgrid, hblk, 0, s, h0, h1, 0, pix, dd, dl, scratch);
+                hipExtLaunchKernelGGL(rows, hgrid, hblk, 0, s, h0, h1, 0, pix, dd, dl, scratch);
                 ev_ingest.push_back({h0, h1});
             }
             hipEvent_t e0 = pool.next(), e1 = pool.next();
             if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
-            hipExtLaunchKernelGGL(ingest_fit_kernel, grid, blk, 0, s, e0, e1, 0, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
+            hipExtLaunchKernelGGL(kern, grid, blk, 0, s, e0, e1, 0, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
             ev_ingest.push_back({e0, e1});
         } else {
-            if (nh) hipLaunchKernelGGL(fit_rows_kernel, hgrid, hblk, 0, s, pix, dd, dl, scratch);
-            hipLaunchKernelGGL(ingest_fit_kernel, grid, blk, 0, s, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
+            if (nh) hipLaunchKernelGGL(rows, hgrid, hblk, 0, s, pix, dd, dl, scratch);
+            hipLaunchKernelGGL(kern, grid, blk, 0, s, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
         }
         HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    // Trim-to-ink ingest (ingest_trim.h).  The list, level and margin have passed txo_ingest_trim_views' checks.  The descriptors go up as in
+    // ingest_u8; a fill of the records, the one launch over every byte, 16 B bytes back and a wait on s: the container's size depends on them.
+    int trim_views(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int level, int margin, int32_t* views,
+                   hipStream_t s) override {
+        if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
+        if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
+        long long pieces = 1;                                 // of the largest image, whatever its first byte's alignment
+        for (int b = 0; b < B; ++b) {
+            ing_host[b] = IngestDesc{(long long)offsets[b], shapes[3 * b], shapes[3 * b + 1], shapes[3 * b + 2], 0};
+            pieces = std::max(pieces, ((long long)shapes[3 * b] * shapes[3 * b + 1] * shapes[3 * b + 2] + 30) / 16);
+        }
+        const long long tiles = (pieces + TB_TILE - 1) / TB_TILE;
+        if (tiles > 2147483647LL) return fail(TXO_E_INVALID, "ingest: an image exceeds the launch grid of the ink search");
+        HIP_TRY(hipMemcpyAsync(ing_desc, ing_host, sizeof(IngestDesc) * B, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(trim_fill_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, trim_rec, B);
+        const dim3 grid((unsigned)tiles, (unsigned)B), blk(TB_THREADS);
+        if (prof) {                                           // txo_profile_read kind 4
+            hipEvent_t e0 = pool.next(), e1 = pool.next();
+            if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
+            hipExtLaunchKernelGGL(trim_bbox_kernel, grid, blk, 0, s, e0, e1, 0, pix, (const IngestDesc*)ing_desc, trim_rec, level);
+            ev_ingest.push_back({e0, e1});
+        } else {
+            hipLaunchKernelGGL(trim_bbox_kernel, grid, blk, 0, s, pix, (const IngestDesc*)ing_desc, trim_rec, level);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(trim_host, trim_rec, sizeof(int) * 4 * (size_t)B, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));                     // (the staging is free again too: no event is left pending)
+        for (int b = 0; b < B; ++b) trim_view_of(trim_host + 4 * b, shapes[3 * b], shapes[3 * b + 1], margin, views + 4 * b);
         return 0;
     }
     int ragged_refusals() {
@@ -2545,14 +2598,20 @@ int txo_ingest_box(const int32_t* shapes, int32_t B, int32_t* Hc_out, int32_t* W
 }
 
 // (the list and the container are checked first: those refusals need neither an engine nor a device)
-int txo_ingest_u8(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Hc, int32_t Wc,
-                  float* box_out, int32_t* sizes_out, void* stream) {
+// pitch (null for txo_ingest_u8 itself): see EngineBase::ingest_u8 -- (offsets, shapes) are then the views of txo_ingest_u8_view
+static int ingest_u8_run(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int32_t B, int32_t C,
+                         int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* stream) {
     if (int r = ingest_check(offsets, shapes, B, C, Hc, Wc)) return r;
     if (!e || !pix || !box_out || !sizes_out) return fail(TXO_E_INVALID, "ingest: null argument");
     if (reinterpret_cast<uintptr_t>(box_out) % 16) return fail(TXO_E_INVALID, "ingest: the container must be 16-byte aligned (rows are written in 16-byte pieces)");
-    if (int r = e->impl->ingest_u8(pix, offsets, shapes, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
+    if (int r = e->impl->ingest_u8(pix, offsets, shapes, pitch, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
     for (int b = 0; b < B; ++b) { sizes_out[2 * b] = (int32_t)ingest_round16(shapes[3 * b]); sizes_out[2 * b + 1] = (int32_t)ingest_round16(shapes[3 * b + 1]); }
     return 0;
+}
+
+int txo_ingest_u8(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Hc, int32_t Wc,
+                  float* box_out, int32_t* sizes_out, void* stream) {
+    return ingest_u8_run(e, pix, offsets, shapes, nullptr, B, C, Hc, Wc, box_out, sizes_out, stream);
 }
 
 int txo_ingest_fit(const int32_t* shapes, int32_t B, int32_t Fh, int32_t Fw, int32_t* fitted_out) {
@@ -2588,8 +2647,9 @@ int txo_ingest_fit_coeffs(int32_t in, int32_t out, int32_t* xmin_out, int32_t* n
 }
 
 // (as txo_ingest_u8: the list, the target, the container and the scratch are checked before the engine or the device is looked at)
-int txo_ingest_u8_fit(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Fh, int32_t Fw,
-                      int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes, void* stream) {
+static int ingest_u8_fit_run(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int32_t B, int32_t C,
+                             int32_t Fh, int32_t Fw, int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes,
+                             void* stream) {
     std::vector<int32_t> fitted;
     long long need = 0;
     if (int r = ingest_fit_sizes(shapes, B, Fh, Fw, &fitted, &need)) return r;        // (the list is checked here, once)
@@ -2606,10 +2666,58 @@ int txo_ingest_u8_fit(txo_engine* e, const uint8_t* pix, const int64_t* offsets,
     if (!e || !pix || !box_out || !sizes_out) return fail(TXO_E_INVALID, "ingest: null argument");
     if (reinterpret_cast<uintptr_t>(box_out) % 16) return fail(TXO_E_INVALID, "ingest: the container must be 16-byte aligned (rows are written in 16-byte pieces)");
     // nothing oversized: txo_ingest_u8's own launch, its container bit for bit
-    if (int r = oversized ? e->impl->ingest_u8_fit(pix, offsets, shapes, fitted.data(), B, C, Hc, Wc, box_out, (unsigned char*)scratch, (hipStream_t)stream)
-                          : e->impl->ingest_u8(pix, offsets, shapes, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
+    if (int r = oversized ? e->impl->ingest_u8_fit(pix, offsets, shapes, pitch, fitted.data(), B, C, Hc, Wc, box_out, (unsigned char*)scratch, (hipStream_t)stream)
+                          : e->impl->ingest_u8(pix, offsets, shapes, pitch, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
     for (int b = 0; b < B; ++b) { sizes_out[2 * b] = (int32_t)ingest_round16(fitted[2 * b]); sizes_out[2 * b + 1] = (int32_t)ingest_round16(fitted[2 * b + 1]); }
     return 0;
+}
+
+int txo_ingest_u8_fit(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Fh, int32_t Fw,
+                      int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes, void* stream) {
+    return ingest_u8_fit_run(e, pix, offsets, shapes, nullptr, B, C, Fh, Fw, Hc, Wc, box_out, sizes_out, scratch, scratch_bytes, stream);
+}
+
+// (the list, the level and the margin are checked before the engine or the device is looked at)
+int txo_ingest_trim_views(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t level, int32_t margin,
+                          int32_t* views_out, void* stream) {
+    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+    if (!offsets) return fail(TXO_E_INVALID, "ingest: null offsets");
+    for (int b = 0; b < B; ++b)
+        if (offsets[b] < 0) return fail(TXO_E_INVALID, "ingest: image " + std::to_string(b) + " has a negative byte offset");
+    if (level < 0 || level > 254)
+        return fail(TXO_E_INVALID, "ingest: the trim level is " + std::to_string(level) + "; it must lie in [0, 254] (a pixel is ink where a channel is <= level)");
+    if (margin < 0) return fail(TXO_E_INVALID, "ingest: the trim margin is " + std::to_string(margin) + "; it must be >= 0");
+    if (!e || !pix || !views_out) return fail(TXO_E_INVALID, "ingest: null argument");
+    return e->impl->trim_views(pix, offsets, shapes, B, level, margin, views_out, (hipStream_t)stream);
+}
+
+// (the list and the views first, then everything txo_ingest_u8 / txo_ingest_u8_fit check, on the views: before the engine or the device is looked at)
+int txo_ingest_u8_view(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* views, int32_t B, int32_t C,
+                       int32_t Fh, int32_t Fw, int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes,
+                       void* stream) {
+    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+    if (!offsets) return fail(TXO_E_INVALID, "ingest: null offsets");
+    if (!views) return fail(TXO_E_INVALID, "ingest: null views");
+    std::vector<int32_t> vshapes((size_t)3 * B), pitch((size_t)B);
+    std::vector<int64_t> voff((size_t)B);
+    bool whole = true;                                                // every view spans its image's rows: nothing is pitched
+    for (int b = 0; b < B; ++b) {
+        const long long h = shapes[3 * b], w = shapes[3 * b + 1], ch = shapes[3 * b + 2];
+        const long long y0 = views[4 * b], x0 = views[4 * b + 1], vh = views[4 * b + 2], vw = views[4 * b + 3];
+        const std::string who = "ingest: image " + std::to_string(b) + " has the view " + std::to_string(vh) + "x" + std::to_string(vw) + " at (" +
+                                std::to_string(y0) + ", " + std::to_string(x0) + ")";
+        if (offsets[b] < 0) return fail(TXO_E_INVALID, "ingest: image " + std::to_string(b) + " has a negative byte offset");
+        if (vh < 1 || vw < 1) return fail(TXO_E_INVALID, who + "; both sides must be >= 1");
+        if (y0 < 0 || x0 < 0 || y0 + vh > h || x0 + vw > w)
+            return fail(TXO_E_INVALID, who + ", which reaches outside the image's " + std::to_string(h) + "x" + std::to_string(w));
+        vshapes[3 * b] = (int32_t)vh; vshapes[3 * b + 1] = (int32_t)vw; vshapes[3 * b + 2] = (int32_t)ch;
+        voff[b] = offsets[b] + (y0 * w + x0) * ch;                    // the origin folds into the offset; the rows stay w pixels apart
+        pitch[b] = (int32_t)w;
+        whole = whole && vw == w;
+    }
+    const int32_t* pp = whole ? nullptr : pitch.data();               // (views that keep their images' widths are tightly packed images: today's kernels)
+    if (Fh == 0 && Fw == 0) return ingest_u8_run(e, pix, voff.data(), vshapes.data(), pp, B, C, Hc, Wc, box_out, sizes_out, stream);
+    return ingest_u8_fit_run(e, pix, voff.data(), vshapes.data(), pp, B, C, Fh, Fw, Hc, Wc, box_out, sizes_out, scratch, scratch_bytes, stream);
 }
 
 int txo_decode_step(txo_engine* e, const int64_t* tok_in, int32_t t, float* logits_out, int64_t* tok_out, void* stream) {

@@ -25,6 +25,8 @@
 namespace txo {
 
 // one image of the list: where its first byte lies in the pixel buffer, and its shape.  ch: 1 = L, 3 = RGB, 4 = RGBA (alpha is not read)
+// reserved: 0, or -- for the PITCHED form of the kernel, which reads a VIEW of a larger image (ingest_trim.h, txo_ingest_u8_view) -- the pixels
+// from one source row to the next; (h, w) is then the view's shape and off the byte of its first pixel
 struct IngestDesc { long long off; int h, w, ch, reserved; };
 
 constexpr int IG_LANES_X = 64, IG_ROWS = 4, IG_PIECE = 4;        // block: 64 x 4 lanes, 4 floats per lane
@@ -38,6 +40,9 @@ __device__ __forceinline__ float ingest_luma_inv(float ar, float ag, float ab) {
     return __fsub_rn(1.0f, s);
 }
 
+// PITCHED: source rows are d.reserved pixels apart and not d.w (a view of a larger image).  A template parameter: the <false> form is the
+// kernel as it was, register for register (profiles/ingest_trim_resource_usage.txt).
+template <bool PITCHED>
 __global__ __launch_bounds__(IG_LANES_X * IG_ROWS) void ingest_u8_kernel(const unsigned char* __restrict__ pix, const IngestDesc* __restrict__ desc,
                                                                         float* __restrict__ box, int C, int Hc, int Wc) {
     __shared__ float unit[256];                                  // c / 255.0f for every byte value
@@ -52,7 +57,7 @@ __global__ __launch_bounds__(IG_LANES_X * IG_ROWS) void ingest_u8_kernel(const u
         // (ingest_fit.h: ingest_fit_kernel restates this block, statement for statement, for the images of a fitted batch that keep their
         // height; a change here goes there too, or a mixed batch stops being bit for bit this kernel's -- tests/test_gpu_ingest_fit.py)
         if (y < d.h && x0 < d.w) {
-            const unsigned char* p = pix + d.off + ((long long)y * d.w + x0) * d.ch;
+            const unsigned char* p = pix + d.off + ((long long)y * (PITCHED ? d.reserved : d.w) + x0) * d.ch;
             const int n = d.w - x0;                              // pixels of this row from x0 on: the piece reads min(n, 4) of them
             if (n >= IG_PIECE && d.ch == 1) {                    // a whole piece of L: four loads issued before the first use
                 unsigned char c[IG_PIECE];

@@ -102,6 +102,8 @@ __host__ __device__ inline void fit_size(long long h, long long w, long long Fh,
 
 // One image of the list.  off: its first byte in the pixel buffer; (h, w, ch) its source shape; (fh, fw) its fitted shape (= (h, w) when it
 // fits); mid: the byte offset of its horizontal pass's intermediate [h][fw][ch == 1 ? 1 : 3] in the scratch buffer, -1 when fw == w.
+// reserved: 0, or -- for the PITCHED forms of the kernels, which read a VIEW of a larger image (txo_ingest_u8_view) -- the pixels from one
+// source row to the next; (h, w) is then the view's shape and off the byte of its first pixel.  The intermediate is always fw wide.
 struct FitDesc { long long off, mid; int h, w, ch, fh, fw, reserved; };
 // bytes one intermediate takes in the scratch buffer (every one starts 16-byte aligned)
 inline long long ingest_fit_mid_bytes(long long h, long long fw, int ch) { return (h * fw * (ch == 1 ? 1 : 3) + 15) / 16 * 16; }
@@ -113,6 +115,8 @@ __device__ __forceinline__ int fit_byte(int acc) {               // acc starts a
 
 constexpr int FR_COLS = 64, FR_LANES_Y = 4, FR_ROWS = 32;        // fit_rows_kernel's block: 64 output columns x 4 lanes over 32 source rows
 
+// (PITCHED, here and in ingest_fit_kernel: as in ingest_u8_kernel; the <false> forms are the kernels as they were)
+template <bool PITCHED>
 __global__ __launch_bounds__(FR_COLS * FR_LANES_Y) void fit_rows_kernel(const unsigned char* __restrict__ pix, const FitDesc* __restrict__ desc,
                                                                        const int* __restrict__ hlist, unsigned char* __restrict__ scratch) {
     __shared__ int K[FIT_TAPS * FR_COLS];                        // [tap][column of the block]
@@ -127,7 +131,7 @@ __global__ __launch_bounds__(FR_COLS * FR_LANES_Y) void fit_rows_kernel(const un
     const int y1 = y0 + FR_ROWS < d.h ? y0 + FR_ROWS : d.h;
     const int mch = d.ch == 1 ? 1 : 3;
     for (int y = y0 + ty; y < y1; y += FR_LANES_Y) {
-        const unsigned char* p = pix + d.off + ((long long)y * d.w + xmin) * d.ch;            // xmin + n <= w: inside row y
+        const unsigned char* p = pix + d.off + ((long long)y * (PITCHED ? d.reserved : d.w) + xmin) * d.ch;   // xmin + n <= w: inside row y
         unsigned char* q = scratch + d.mid + ((long long)y * d.fw + xx) * mch;
         if (d.ch == 1) {
             int a = 1 << (FIT_BITS - 1);
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(FR_COLS * FR_LANES_Y) void fit_rows_kernel(const un
     }
 }
 
-// four consecutive fitted pixels (y, x0 .. x0 + 3) of the vertical pass over the view `img` (rows of sw pixels of sch bytes), of which NPX exist:
+// four consecutive fitted pixels (y, x0 .. x0 + 3) of the vertical pass over the view `img` (rows sw pixels apart, of sch bytes each), of which NPX exist:
 // the vertical taps in integers, then the ingest arithmetic; returned by value (pixels behind NPX are 0.0f)
 template <int NPX>
 __device__ __forceinline__ float4 fit_column_piece(const unsigned char* __restrict__ img, int sw, int sch, int x0, int ymin, int n, const int* Kr,
@@ -188,6 +192,7 @@ __device__ __forceinline__ float4 fit_column_piece(const unsigned char* __restri
 // The body between the table fill and the stores is ingest_u8_kernel's, statement for statement, on the view (img, fw, sch) -- restated here
 // and not shared, because that kernel is pinned register for register (profiles/ingest_resource_usage.txt) and taking its body out into a
 // function changed its allocation.
+template <bool PITCHED>
 __global__ __launch_bounds__(IG_LANES_X * IG_ROWS) void ingest_fit_kernel(const unsigned char* __restrict__ pix, const unsigned char* __restrict__ scratch,
                                                                          const FitDesc* __restrict__ desc, float* __restrict__ box, int C, int Hc, int Wc) {
     __shared__ float unit[256];                                  // c / 255.0f for every byte value
@@ -198,6 +203,7 @@ __global__ __launch_bounds__(IG_LANES_X * IG_ROWS) void ingest_fit_kernel(const 
     // what the vertical pass (or, without one, the pixel code) reads: the intermediate where a horizontal pass ran, else the source; fw wide
     const unsigned char* img = d.mid >= 0 ? scratch + d.mid : pix + d.off;
     const int sch = d.mid >= 0 ? (d.ch == 1 ? 1 : 3) : d.ch;
+    const int sw = PITCHED ? (d.mid >= 0 ? d.fw : d.reserved) : d.fw;   // pixels from one row of img to the next (only the source has a pitch)
     float o[IG_PIECE] = {0.0f, 0.0f, 0.0f, 0.0f};
     // (block-uniform, like the branch on fh == h below: a block that lies wholly outside the fitted image only writes zeros)
     if ((int)blockIdx.y * IG_ROWS < d.fh && (int)blockIdx.x * IG_BLOCK_W < d.fw) {
@@ -205,7 +211,7 @@ __global__ __launch_bounds__(IG_LANES_X * IG_ROWS) void ingest_fit_kernel(const 
         if (d.fh == d.h) {                                       // the height stays: an image that fits, or one with a horizontal pass only
             __syncthreads();
             if (y < d.fh && x0 < d.fw) {
-                const unsigned char* p = img + ((long long)y * d.fw + x0) * sch;
+                const unsigned char* p = img + ((long long)y * sw + x0) * sch;
                 const int n = d.fw - x0;                         // pixels of this row from x0 on: the piece reads min(n, 4) of them
                 if (n >= IG_PIECE && sch == 1) {                 // a whole piece of L: four loads issued before the first use
                     unsigned char c[IG_PIECE];
@@ -239,10 +245,10 @@ __global__ __launch_bounds__(IG_LANES_X * IG_ROWS) void ingest_fit_kernel(const 
             if (y < d.fh && x0 < d.fw) {
                 const int npx = d.fw - x0;
                 float4 v;
-                if (npx >= IG_PIECE) v = fit_column_piece<4>(img, d.fw, sch, x0, ymin, n, K[ty], unit);
-                else if (npx == 3) v = fit_column_piece<3>(img, d.fw, sch, x0, ymin, n, K[ty], unit);
-                else if (npx == 2) v = fit_column_piece<2>(img, d.fw, sch, x0, ymin, n, K[ty], unit);
-                else v = fit_column_piece<1>(img, d.fw, sch, x0, ymin, n, K[ty], unit);
+                if (npx >= IG_PIECE) v = fit_column_piece<4>(img, sw, sch, x0, ymin, n, K[ty], unit);
+                else if (npx == 3) v = fit_column_piece<3>(img, sw, sch, x0, ymin, n, K[ty], unit);
+                else if (npx == 2) v = fit_column_piece<2>(img, sw, sch, x0, ymin, n, K[ty], unit);
+                else v = fit_column_piece<1>(img, sw, sch, x0, ymin, n, K[ty], unit);
                 o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
             }
         }

@@ -237,12 +237,15 @@ class HipEngine:
 
     # ---- ragged batches (build extension): images of different sizes in one call; `images` is a sequence of (C, H_b, W_b) tensors, or a
     # container that already exists (ops.PackedImages: what ingest returns) ----
-    def ingest(self, images, fit: bool = False) -> "ops.PackedImages":
+    def ingest(self, images, fit: bool = False, trim=False, regions=None) -> "ops.PackedImages":
         """Device-side image ingest (txo_ingest_u8): raw uint8 images (PIL, numpy, uint8 tensors on the CPU or this device; L, RGB, RGBA) ->
         the container of a ragged batch, in one copy of the pixel bytes and one launch.  Needs no weights.  fit=True (txo_ingest_u8_fit): an
-        image beyond the canvas is downscaled on the device to fit it."""
+        image beyond the canvas is downscaled on the device to fit it.  trim=(level, margin) (True: the defaults) / regions=(B, 4): a
+        rectangle of every image -- its ink and a margin, or the caller's -- takes the image's place first (txo_ingest_u8_view)."""
+        if trim is True:
+            trim = (ops.TRIM_LEVEL, ops.TRIM_MARGIN)
         return ops.pack_u8(images, self.dims.in_channels, torch.device("cuda", self.device), engine=self.id,
-                           fit=self.dims.canvas_hw if fit else None)
+                           fit=self.dims.canvas_hw if fit else None, trim=trim or None, regions=regions)
 
     def encode_ragged(self, images):
         """-> (enc (B, Ns, D) with zero rows behind each image's own token count, n_tokens (B,) int32 CPU)"""
@@ -996,7 +999,7 @@ class OCRModel(nn.Module):
             return eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
 
     @torch.no_grad()
-    def ingest(self, images, fit: bool = False) -> "ops.PackedImages":
+    def ingest(self, images, fit: bool = False, trim=False, regions=None) -> "ops.PackedImages":
         """Build extension: device-side image ingest.  A list of raw uint8 images of any sizes -- PIL images, numpy arrays or uint8 tensors
         (on the CPU or the model's device) of shape (H, W), (H, W, 3) or (H, W, 4): L, RGB, RGBA with the alpha ignored -> PackedImages(box
         (B, in_channels, Hc, Wc) float32, sizes (B, 2) int32 CPU), from ONE copy of the pixel bytes and ONE launch (txo_ingest_u8).  box is
@@ -1008,8 +1011,15 @@ class OCRModel(nn.Module):
         side beyond the canvas (dims.canvas_hw) is downscaled on the device to fit it, aspect ratio kept (ops.fit_size; never upscaled), bit
         for bit PIL's Image.resize(..., BILINEAR) of its L / RGB channels -- an RGBA image is fitted on its RGB channels, the alpha is not
         read -- and `sizes` holds the fitted sizes.  Still one copy of the raw bytes.  An axis that would shrink by more than 32 times is a
-        ValueError naming the image."""
-        return self._engine.ingest(images, fit=fit)
+        ValueError naming the image.
+        trim=(level, margin), or True for (127, 2) (default False): every image is first cut to its ink on the device -- a pixel is ink iff
+        min(read channels) <= level; `margin` pixels are kept around the ink box, clamped to the image; an image without ink stays whole
+        (ops.trim_view is the rule) -- and the view takes the image's place in front of the fit and the ingest: an image beyond the canvas
+        whose ink fits is accepted without a fit.  regions=(B, 4) = (y0, x0, h, w): image b is cut to the caller's rectangle instead; pass
+        a page once per region and its bytes go up (or, on the device, are used) once.  trim and regions together are a ValueError.  Either
+        way the container is bit for bit that of contiguous copies of the views, the result's `views` (B, 4) int32 holds them in source
+        pixels, and the trim costs the one wait of the path (the container's size depends on its answer)."""
+        return self._engine.ingest(images, fit=fit, trim=trim, regions=regions)
 
     @torch.no_grad()
     def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0) -> Beams:

@@ -28,6 +28,10 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
                             the device in one launch, bit for bit what the host preprocessing makes of them (``pack_u8`` is its front end)
   texocr::ingest_u8_fit     (build extension) the same with every image beyond a target size downscaled to fit it first, bit for bit PIL's
                             BILINEAR resize (``pack_u8(..., fit=(Fh, Fw))``)
+  texocr::ingest_trim_views (build extension) the ink extents of every image, found on the device in one launch -> the views (y0, x0, h', w')
+                            that keep the ink and a margin (``trim_view`` is the rule on the host; ``pack_u8(..., trim=(level, margin))``)
+  texocr::ingest_u8_view    (build extension) ingest_u8 / ingest_u8_fit of a rectangle of every source image: the trimmed views, or the
+                            caller's regions of a page that went up once (``pack_u8(..., regions=...)``)
 
 An engine is named by an integer id (operators take tensors and scalars only); ``register_engine`` hands one out.
 There is no CPU implementation: calling an operator on CPU tensors raises.
@@ -433,9 +437,12 @@ def _(img, engine, beams, max_len, eos, want_all):
 class PackedImages:
     """A ragged batch that is already in its container -- what pack_u8 / OCRModel.ingest return, and what every *_ragged method takes in
     place of a sequence of (C, H_b, W_b) tensors: box (B, C, Hc, Wc) float32 on the device, image b in the top-left corner of slot b and
-    zeros around it; sizes (B, 2) int32 CPU = (H_b, W_b), multiples of 16.  len() is the number of images."""
+    zeros around it; sizes (B, 2) int32 CPU = (H_b, W_b), multiples of 16.  len() is the number of images.
+    views (pack_u8 with trim= / regions=; else None): (B, 4) int32 CPU = (y0, x0, h', w'), the rectangle of source image b that slot b holds, in
+    SOURCE pixels and before the fit: what maps a return_align map or a peak patch back to the source."""
     box: torch.Tensor
     sizes: torch.Tensor
+    views: Optional[torch.Tensor] = None
 
     def __len__(self) -> int:
         return int(self.box.shape[0])
@@ -763,22 +770,28 @@ def plan_u8(images: Sequence):
     staged: uint8 CPU tensor (n,), every HOST image of the list (PIL, numpy, CPU tensor) copied in at an offset aligned to 16, in list order;
     device_tensors: the uint8 device tensors of the list, contiguous, used where they lie;
     src: int64 CPU (B, 2) = (k, byte offset): image b starts `offset` bytes into the staged buffer (k = 0) or into device_tensors[k - 1];
-    shapes: int32 CPU (B, 3) = (h, w, ch), ch = 1 for an (H, W) image.  The channel count is the engine's to judge (txo_ingest_u8)."""
+    shapes: int32 CPU (B, 3) = (h, w, ch), ch = 1 for an (H, W) image.  The channel count is the engine's to judge (txo_ingest_u8).
+    An OBJECT that appears several times in the list (a page passed once per region: pack_u8(regions=)) is staged, or listed in
+    device_tensors, once; its entries of src name the same bytes."""
     import numpy as np
-    arrs = [_u8_array(im, i) for i, im in enumerate(images)]
-    src, shapes, dev, total = [], [], [], 0
-    for a in arrs:
+    seen = {}                                    # id(object of the list) -> (its array, its src entry)
+    arrs, src, shapes, dev, total = [], [], [], [], 0
+    for i, im in enumerate(images):
+        if id(im) not in seen:
+            a = _u8_array(im, i)
+            if isinstance(a, torch.Tensor):
+                dev.append(a)
+                seen[id(im)] = (a, [len(dev), 0])
+            else:
+                seen[id(im)] = (a, [0, total])
+                arrs.append((total, a))
+                total = (total + a.size + U8_ALIGN - 1) // U8_ALIGN * U8_ALIGN
+        a, where = seen[id(im)]
         shapes.append([a.shape[0], a.shape[1], a.shape[2] if a.ndim == 3 else 1])
-        if isinstance(a, torch.Tensor):
-            dev.append(a)
-            src.append([len(dev), 0])
-        else:
-            src.append([0, total])
-            total = (total + a.size + U8_ALIGN - 1) // U8_ALIGN * U8_ALIGN
+        src.append(list(where))
     staged = np.zeros((total,), dtype=np.uint8)
-    for (k, o), a in zip(src, arrs):
-        if k == 0:
-            staged[o:o + a.size] = a.reshape(-1)
+    for o, a in arrs:
+        staged[o:o + a.size] = a.reshape(-1)
     return (torch.from_numpy(staged), dev, torch.tensor(src, dtype=torch.int64).reshape(-1, 2),
             torch.tensor(shapes, dtype=torch.int32).reshape(-1, 3))
 
@@ -891,7 +904,100 @@ def _(bufs, src, shapes, engine, channels, Fh, Fw, Hc, Wc):
     return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
 
 
-def pack_u8(images: Sequence, in_channels: int, device, *, engine: int, fit: Optional[Tuple[int, int]] = None) -> PackedImages:
+# ---- trim-to-ink and region ingest (txo_ingest_trim_views / txo_ingest_u8_view): a rectangle of the source takes the image's place ----------
+TRIM_LEVEL, TRIM_MARGIN = 127, 2     # the defaults: the mid-grey convention; a rim that keeps anti-aliased pixels lighter than the level
+
+
+def _trim_args(level, margin) -> Tuple[int, int]:
+    """the refusals of txo_ingest_trim_views about the rule's two numbers, in its words"""
+    level, margin = int(level), int(margin)
+    if not 0 <= level <= 254:
+        raise ValueError(f"ingest: the trim level is {level}; it must lie in [0, 254] (a pixel is ink where a channel is <= level)")
+    if margin < 0:
+        raise ValueError(f"ingest: the trim margin is {margin}; it must be >= 0")
+    return level, margin
+
+
+def trim_view(arr, level: int = TRIM_LEVEL, margin: int = TRIM_MARGIN) -> Tuple[int, int, int, int]:
+    """The trim rule of texocr.h "Trim-to-ink ingest" in numpy, on the bytes the ingest reads: arr uint8 (H, W) or (H, W, ch) with ch = 1
+    (L), 3 (RGB) or 4 (RGBA: the alpha is not read) -> the view (y0, x0, h', w').  A pixel is ink iff min(read channels) <= level; the ink
+    box is widened by `margin` pixels on every side and clamped to the image; an image without ink keeps (0, 0, H, W).  Product code: the
+    wrapper's host path crops with it, and the engine's kernel (texocr::ingest_trim_views) gives the same four numbers."""
+    import numpy as np
+    level, margin = _trim_args(level, margin)
+    a = np.asarray(arr)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"trim_view: the image must be uint8 (H, W) or (H, W, ch) with H, W >= 1, got {a.dtype} {tuple(a.shape)}")
+    ink = (a if a.ndim == 2 else a[..., :3].min(axis=2)) <= level
+    h, w = ink.shape
+    ys, xs = np.flatnonzero(ink.any(axis=1)), np.flatnonzero(ink.any(axis=0))
+    if ys.size == 0:
+        return 0, 0, h, w
+    y0, y1 = max(0, int(ys[0]) - margin), min(h, int(ys[-1]) + 1 + margin)
+    x0, x1 = max(0, int(xs[0]) - margin), min(w, int(xs[-1]) + 1 + margin)
+    return y0, x0, y1 - y0, x1 - x0
+
+
+@custom_op("texocr::ingest_trim_views", mutates_args=())
+def ingest_trim_views(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Tensor, engine: int, level: int, margin: int) -> torch.Tensor:
+    """txo_ingest_trim_views: bufs / src / shapes as texocr::ingest_u8 takes them -> views (B, 4) int32 CPU = (y0, x0, h', w') by trim_view's
+    rule, from ONE launch over the bytes on the device.  SYNCHRONOUS (the one wait of the ingest path: the container's size depends on it)."""
+    e = _eng(engine)
+    base, offsets, shapes = _u8_source(bufs, src, shapes, e)
+    B = int(shapes.shape[0])
+    views = torch.zeros((B, 4), dtype=torch.int32)
+    _call(e, "txo_ingest_trim_views", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), B, int(level), int(margin), _i32p(views))
+    return views
+
+
+@ingest_trim_views.register_fake
+def _(bufs, src, shapes, engine, level, margin):
+    return torch.empty((shapes.shape[0], 4), dtype=torch.int32, device="cpu")
+
+
+def view_shapes(shapes: torch.Tensor, views: torch.Tensor) -> torch.Tensor:
+    """shapes (B, 3) = (h, w, ch), views (B, 4) = (y0, x0, h', w') -> (B, 3) = (h', w', ch): the list the container is sized from"""
+    out = shapes.clone()
+    out[:, :2] = views[:, 2:4]
+    return out
+
+
+def _views_inside(shapes: torch.Tensor, views: torch.Tensor) -> bool:
+    v, s = views.to(torch.int64), shapes.to(torch.int64)
+    return bool(((v[:, 2:] >= 1) & (v[:, :2] >= 0) & (v[:, :2] + v[:, 2:] <= s[:, :2])).all())
+
+
+@custom_op("texocr::ingest_u8_view", mutates_args=())
+def ingest_u8_view(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Tensor, views: torch.Tensor, engine: int, channels: int, Fh: int,
+                   Fw: int, Hc: int, Wc: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """txo_ingest_u8_view: texocr::ingest_u8 (Fh = Fw = 0) or texocr::ingest_u8_fit of the rectangle views[b] = (y0, x0, h', w') of every source
+    image (bufs / src / shapes describe the FULL images; entries may share bytes and views may overlap) -> (box, sizes) of the views, bit for
+    bit what contiguous copies of them give.  Asynchronous; the refusals are the engine's."""
+    e = _eng(engine)
+    base, offsets, shapes = _u8_source(bufs, src, shapes, e)      # (the bound check is on the full images)
+    B = int(shapes.shape[0])
+    if views.is_cuda or views.dtype != torch.int32 or tuple(views.shape) != (B, 4):
+        raise ValueError("views must be an int32 CPU tensor of shape (B, 4) = (y0, x0, h, w)")
+    views = views.contiguous()
+    need = C.c_int64(0)
+    if (Fh or Fw) and _views_inside(shapes, views):               # (a view the engine is about to refuse asks for no scratch)
+        vshapes = view_shapes(shapes, views).contiguous()         # (named: the pointer below must outlive the call)
+        _lib.check(_lib.load().txo_ingest_fit_scratch(_i32p(vshapes), B, int(Fh), int(Fw), C.byref(need)))
+    scratch = torch.empty((need.value,), dtype=torch.uint8, device=torch.device("cuda", e.device)) if need.value else None
+    box, sizes = _u8_outputs(e, B, channels, max(int(Hc), 0), max(int(Wc), 0))
+    _call(e, "txo_ingest_u8_view", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), _i32p(views), B, int(channels), int(Fh),
+          int(Fw), int(Hc), int(Wc), box.data_ptr(), _i32p(sizes), scratch.data_ptr() if scratch is not None else None, need.value)
+    return box, sizes
+
+
+@ingest_u8_view.register_fake
+def _(bufs, src, shapes, views, engine, channels, Fh, Fw, Hc, Wc):
+    B = shapes.shape[0]
+    return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
+
+
+def pack_u8(images: Sequence, in_channels: int, device, *, engine: int, fit: Optional[Tuple[int, int]] = None,
+            trim: Optional[Tuple[int, int]] = None, regions=None) -> PackedImages:
     """Raw uint8 pixels -> the container of a ragged batch, prepared on the DEVICE: the counterpart of
     pack_ragged([wrapper._tensor(im) for im in images]), bit for bit, with one host-to-device copy of the pixel BYTES and one launch
     (texocr::ingest_u8 on the engine `engine`) instead of a float32 conversion, a copy and a slice assignment per image.
@@ -899,9 +1005,30 @@ def pack_u8(images: Sequence, in_channels: int, device, *, engine: int, fit: Opt
     ignored); sizes need not be multiples of 16 (the pad is zero).  Host images are concatenated into one buffer (every offset aligned to
     16) and sent in one copy; device tensors are used where they lie if they are contiguous.
     fit=(Fh, Fw) (default None: today's path): an image with a side beyond it is downscaled on the device to fit_size(h, w, Fh, Fw) first
-    (texocr::ingest_u8_fit), bit for bit PIL's resize(..., BILINEAR) of its L / RGB channels; the container is sized by the fitted list."""
+    (texocr::ingest_u8_fit), bit for bit PIL's resize(..., BILINEAR) of its L / RGB channels; the container is sized by the fitted list.
+    trim=(level, margin) (default None): every image is first cut to its ink and a margin (trim_view's rule, found on the device by
+    texocr::ingest_trim_views -- the one wait of this call); regions=(B, 4) = (y0, x0, h, w): image b is cut to regions[b] -- pass a page
+    once per region, it is staged (or, on the device, used) once.  Either way the view takes the image's place in front of the fit and
+    the ingest, the result is bit for bit pack_u8 of contiguous copies a[y0:y0 + h, x0:x0 + w], and PackedImages.views holds the views in
+    source pixels.  trim and regions together are a ValueError."""
+    if trim is not None and regions is not None:
+        raise ValueError("pack_u8: trim and regions are two ways to name the views; pass one of them")
     staged, dev, src, shapes = plan_u8(images)
     device = torch.device(device)
+    if trim is not None or regions is not None:
+        bufs = [staged.to(device)] + dev
+        if trim is not None:
+            level, margin = _trim_args(*trim)
+            views = torch.ops.texocr.ingest_trim_views(bufs, src, shapes, int(engine), level, margin)
+        else:
+            views = torch.as_tensor(regions).to(device="cpu", dtype=torch.int32).reshape(-1, 4).contiguous()
+            if views.shape[0] != shapes.shape[0]:
+                raise ValueError(f"pack_u8: regions needs one (y0, x0, h, w) per image ({shapes.shape[0]}), got {views.shape[0]}")
+        vshapes = view_shapes(shapes, views)
+        Fh, Fw = (0, 0) if fit is None else (int(fit[0]), int(fit[1]))
+        Hc, Wc = box_u8(vshapes if fit is None else fit_shapes(vshapes, Fh, Fw))
+        box, sizes = torch.ops.texocr.ingest_u8_view(bufs, src, shapes, views, int(engine), int(in_channels), Fh, Fw, Hc, Wc)
+        return PackedImages(box, sizes, views)
     if fit is None:
         Hc, Wc = box_u8(shapes)
         box, sizes = torch.ops.texocr.ingest_u8([staged.to(device)] + dev, src, shapes, int(engine), int(in_channels), Hc, Wc)

@@ -104,17 +104,37 @@ class TeXOCRWrapper:
             raise ValueError(f"ingest: image {i} is {h}x{w}, {fh}x{fw} fitted to {Fh}x{Fw}: an axis shrinks by more than {ops.FIT_MAX_SCALE} times")
         return (img if img.mode == "L" else img.convert("RGB")).resize((fw, fh), Image.BILINEAR)
 
-    def _images(self, imgs: Sequence, ingest: str, fit: str = "none"):
+    @staticmethod
+    def _trim_rule(trim: str, level: int, margin: int):
+        """trim= / trim_level= / trim_margin= of batch and __call__ -> None ('none') or the rule's (level, margin), refused in the engine's words"""
+        from . import ops
+        if trim not in ("none", "ink"):
+            raise ValueError(f"trim must be 'none' or 'ink', got {trim!r}")
+        return ops._trim_args(level, margin) if trim == "ink" else None
+
+    @staticmethod
+    def _trimmed(img, rule):
+        """trim='ink' on the host path: a PIL image -> its crop to ops.trim_view of the bytes the ingest reads (L / RGB / RGBA as they are, any
+        other mode through convert('RGB')); an image whose view is the whole of it is returned untouched"""
+        from . import ops
+        y0, x0, h, w = ops.trim_view(ops._u8_array(img, 0), *rule)
+        return img if (w, h) == img.size else img.crop((x0, y0, x0 + w, y0 + h))
+
+    def _images(self, imgs: Sequence, ingest: str, fit: str = "none", trim=None):
         """imgs as one ragged call takes them -- ingest='host': a list of (C, H_b, W_b) tensors on the device, every image preprocessed
         on the host and copied on its own (the path that has always been there); 'device': ONE OCRModel.ingest over the raw pixels (a
         PackedImages, bit for bit the container the host path ends in).  fit='canvas': oversized images are downscaled to the canvas first,
-        by PIL on the host path and by the engine on the device path, to the same bytes."""
+        by PIL on the host path and by the engine on the device path, to the same bytes.  trim=(level, margin) (_trim_rule): every image is
+        cut to its ink first -- ops.trim_view and PIL's crop on the host path, OCRModel.ingest(trim=) on the device path."""
         if fit not in ("none", "canvas"):
             raise ValueError(f"fit must be 'none' or 'canvas', got {fit!r}")
         if ingest == "device":
-            return self.model.ingest(imgs, fit=True) if fit == "canvas" else self.model.ingest(imgs)
+            kw = {} if trim is None else dict(trim=trim)
+            return self.model.ingest(imgs, fit=True, **kw) if fit == "canvas" else self.model.ingest(imgs, **kw)
         if ingest != "host":
             raise ValueError(f"ingest must be 'host' or 'device', got {ingest!r}")
+        if trim is not None:
+            imgs = [self._trimmed(im, trim) for im in imgs]
         if fit == "canvas":
             imgs = [self._fitted(im, i) for i, im in enumerate(imgs)]
         return [self._tensor(im).cuda() for im in imgs]
@@ -147,7 +167,8 @@ class TeXOCRWrapper:
 
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-              length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host", fit: str = "none") -> List[tuple]:
+              length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host", fit: str = "none",
+              trim: str = "none", trim_level: int = 127, trim_margin: int = 2) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -169,7 +190,14 @@ class TeXOCRWrapper:
         resize(..., BILINEAR) -- by PIL itself with ingest='host', by the engine (OCRModel.ingest(fit=True)) with ingest='device', to the
         same bytes, so every result is identical by either ingest here too.  An RGBA image is fitted on its RGB channels (convert('RGB');
         the alpha is not read).  An axis that would shrink by more than 32 times is a ValueError.  return_align maps of a fitted image
-        are on the FITTED grid: (len(tokens), h'/16, w'/16) with (h', w') the fitted size rounded up to 16."""
+        are on the FITTED grid: (len(tokens), h'/16, w'/16) with (h', w') the fitted size rounded up to 16.
+        trim='ink' (build extension; default 'none'): every image is first cut to its ink -- a pixel is ink iff min(R, G, B) <= trim_level
+        (L: the byte itself; the alpha is not read), trim_margin pixels are kept around the ink box, clamped to the image, and an image
+        without ink stays whole (ops.trim_view) -- by numpy and PIL's crop with ingest='host', by the engine (OCRModel.ingest(trim=)) with
+        ingest='device', to the same pixels, so every result is identical by either ingest.  The cut comes BEFORE the fit: with
+        fit='none' an image beyond the canvas whose ink fits is accepted, and one whose ink does not fit is refused as ever, with the
+        trimmed size in the message.  return_align maps are on the grid of the trimmed (then fitted) image."""
+        rule = self._trim_rule(trim, trim_level, trim_margin)
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
         pre = plen = prows = None
@@ -179,9 +207,9 @@ class TeXOCRWrapper:
             pre, plen, prows, max_len = self._prefix_rows(prefix, decode, return_align, max_len)
         step = beam_chunk(eng.max_batch, beams) if decode == "beam" else eng.max_batch
         out: List[tuple] = []
-        xs = self._images(imgs, ingest, fit) if ingest != "device" else None
+        xs = self._images(imgs, ingest, fit, rule) if ingest != "device" else None
         for c0 in range(0, len(imgs), step):
-            chunk = xs[c0:c0 + step] if xs is not None else self._images(imgs[c0:c0 + step], ingest, fit)
+            chunk = xs[c0:c0 + step] if xs is not None else self._images(imgs[c0:c0 + step], ingest, fit, rule)
             if decode == "beam":
                 full, logp = self._best_beams(chunk, beams, max_len, length_alpha, return_logp)
             else:
@@ -205,7 +233,8 @@ class TeXOCRWrapper:
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
-                 length_alpha: float = 0.0, prefix=None, ingest: str = "host", fit: str = "none") -> tuple:
+                 length_alpha: float = 0.0, prefix=None, ingest: str = "host", fit: str = "none", trim: str = "none", trim_level: int = 127,
+                 trim_margin: int = 2) -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
@@ -216,8 +245,9 @@ class TeXOCRWrapper:
         logp) is the continuation, `latex` is decoded from prefix + continuation; max_len is capped so that both fit the positional table.
         ingest='device': the image is preprocessed on the device (see batch); the result is identical.
         fit='canvas': an image beyond the canvas is downscaled to fit it first (see batch); the maps of return_align are then on the
-        fitted grid."""
-        x = self._images([img], ingest, fit)
+        fitted grid.
+        trim='ink': the image is cut to its ink and a margin first (see batch), before the fit; the maps are on the trimmed image's grid."""
+        x = self._images([img], ingest, fit, self._trim_rule(trim, trim_level, trim_margin))
         x = x.box if ingest == "device" else x[0][None]
         prow: List[int] = []
         gen_kw = {}
