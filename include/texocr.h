@@ -445,6 +445,30 @@ int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint
 #define TXO_STOP_ROW 1
 int txo_set_stop_mode(txo_engine* e, int32_t mode);
 
+/* Constrained decode, a BUILD EXTENSION: which tokens the loop of the following txo_generate* calls may pick.  An engine knob like
+ * txo_set_sampling; rules_host == NULL switches the rules off (the default).
+ * A rule set is a table rules[S][V] of packed int32 on the host -- S states, 1 <= S <= 8; V = cfg.vocab -- and depth_max, 1 .. 255.  An entry packs
+ *   bits 0-7 need (unsigned)   bits 8-15 delta (signed)   bits 16-23 next   bit 24 BAN (TXO_RULE_BAN)   bit 25 ONLY_AT_ZERO (TXO_RULE_ONLY_AT_ZERO)
+ * Every row of the batch carries a state (s, depth), (0, 0) at the start.  In (s, depth) token v with r = rules[s][v] is ALLOWED iff BAN is not
+ * set, depth >= need, depth + delta <= depth_max, and ONLY_AT_ZERO is not set or depth == 0.  Committing a token -- picked or forced by a
+ * prefix -- moves the row to (next, clamp(depth + delta, 0, depth_max)).  A disallowed logit counts as -3.4e38f in the selection: greedy takes
+ * the arg-max of the masked row (ties to the lowest index), sampling runs txo_set_sampling's rule on the masked row (a masked entry inside the
+ * kept set has probability exactly 0 and is never drawn).  A forced prefix token is never masked, but advances the state.  logp_out keeps
+ * its meaning: log_softmax of the RAW logits over the whole vocabulary at the committed token, what txo_score reports -- a token the rules
+ * forced on a row shows its low probability; logits_out holds the raw logits.
+ * Refused with TXO_E_INVALID and a text that names the rule: S or depth_max out of range, V != cfg.vocab, an entry whose next >= S, a state
+ * without an always-allowed token (not BAN, not ONLY_AT_ZERO, need == 0, delta <= 0): so no row can ever face an empty allowed set.
+ * While rules are set every txo_generate* that decodes from BOS or from a prefix (image, _from_enc, _ragged, _logp, _prefix*) runs its loop
+ * with one launch per stage (TXO_Q_LAST_PERSISTENT reads 0) and otherwise as ever: captured steps, row ranges, TXO_STOP_ROW with live-row
+ * compaction, ragged batches, the sliding window, logp_out.  txo_generate_beam / txo_beam_search / txo_beam_search_ragged refuse.
+ * txo_decode_step picks without rules.  Closure is NOT guaranteed: a row that runs out of positions may end at depth > 0 --
+ * txo_last_rule_state: the (s, depth) of rows 0 .. B-1 behind the last position the last txo_generate* returned for them (under TXO_STOP_ROW:
+ * behind a finished row's first eos), int32 [B][2] on the device, ordered on `stream`. */
+#define TXO_RULE_BAN (1 << 24)
+#define TXO_RULE_ONLY_AT_ZERO (1 << 25)
+int txo_set_token_rules(txo_engine* e, const int32_t* rules_host, int32_t S, int32_t V, int32_t depth_max);
+int txo_last_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, void* stream);
+
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
  * enabled (txo_profile_enable(e, 1) also clears the previous samples); *count = number of launches averaged.  kind: 0 = cross-attention decode kernel,

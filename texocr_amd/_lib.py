@@ -76,6 +76,8 @@ SYMBOLS = {
                                      C.POINTER(C.c_int32), C.c_void_p, C.c_int64, _P]),
     "txo_set_sampling": (C.c_int, [_P, _I, _I, C.c_float, C.c_uint64]),
     "txo_set_stop_mode": (C.c_int, [_P, _I]),
+    "txo_set_token_rules": (C.c_int, [_P, C.c_void_p, _I, _I, _I]),
+    "txo_last_rule_state": (C.c_int, [_P, C.c_void_p, _I, _P]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),
     "txo_set_ragged_hybrid": (C.c_int, [_P, _I]),
     "txo_profile_enable": (C.c_int, [_P, _I]),

@@ -48,6 +48,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "ingest.h"        // (likewise: the newest kernel goes last)
 #include "ingest_fit.h"    // (the fit-to-canvas passes in front of it; uses ingest.h's per-pixel pieces)
 #include "ingest_trim.h"   // (the ink extents in front of both; reads ingest.h's descriptors)
+#include "step_rules.h"    // (the constrained token selection: step.h / step_prefix.h with a per-row automaton; last again)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -104,6 +105,11 @@ struct EngineBase {
     int stop_mode = 0;                          // txo_set_stop_mode: 0 = the reference's global eos break only, 1 = per-row stop (pad behind a row's first eos)
     bool rag_fwd = false;                       // txo_set_ragged_forward: the multi-position forward on ragged sessions and the ragged sliding window are accepted
     bool rag_hybrid = false;                    // txo_set_ragged_hybrid: ragged batches are accepted on the hybrid front end (conv.h: the RAGGED forms)
+    // txo_set_token_rules (step_rules.h): every generate from BOS or a prefix decodes on the launch path with the *_rules_step kernels while on
+    bool rules_on = false; int rules_S = 0, rules_dmax = 0;
+    int rules_rows = 0;                         // rows of the last constrained generate (txo_last_rule_state), 0: none since the rules were set
+    virtual int set_token_rules(const int32_t* table, int S, int depth_max) = 0;   // behind txo_set_token_rules's checks; table null: off
+    virtual int last_rule_state(int32_t* out, int B, hipStream_t s) = 0;
     // txo_ingest_u8 behind its checks (ingest_check): descriptors up in one staged copy, one launch.  pitch (here and below; null: rows are
     // tightly packed, today's kernels): [B] pixels from one source row to the next -- (offsets, shapes) then describe VIEWS (txo_ingest_u8_view)
     virtual int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int B, int C, int Hc, int Wc,
@@ -238,6 +244,9 @@ struct Engine : EngineBase {
     // tokens' log-probabilities [Bmax][Tmax] -- engine-owned, so that a captured step can carry them
     int64_t* ftab = nullptr; int* flen = nullptr; float* fplogp = nullptr;
     int prefix_cols = 0;                   // StepArgs::out_cols of the running prompted decode
+    // constrained decode (step_rules.h): the packed table [RULES_MAX_STATES][V], every row's (state, depth) [Bmax] and the state behind every
+    // position [Bmax][Tmax] -- engine-owned, so that a captured step can carry them
+    int* rules_dev = nullptr; int2* rule_state = nullptr; int2* rule_hist = nullptr;
     Session ses;                           // the open decode session (session.h)
     // persistent decode launch (persist.h): control block (device + pinned host copy), per-stage stamps of one position
     PersistCtl* pctl = nullptr; PersistCtl* pctl_host = nullptr; unsigned long long* pstamps = nullptr;
@@ -723,6 +732,9 @@ struct Engine : EngineBase {
         if (int r = dalloc(&ing_desc, (size_t)Bmax)) return r;   // (last: no earlier buffer moves)
         if (int r = dalloc(&fit_dev, fit_bytes(Bmax))) return r;
         if (int r = dalloc(&trim_rec, (size_t)4 * Bmax)) return r;
+        if (int r = dalloc(&rules_dev, (size_t)RULES_MAX_STATES * V)) return r;
+        if (int r = dalloc(&rule_state, (size_t)Bmax)) return r;
+        if (int r = dalloc(&rule_hist, (size_t)Bmax * Tmax)) return r;
         return 0;
     }
 
@@ -1676,12 +1688,17 @@ struct Engine : EngineBase {
         if (ses.forced) {   // prompted decode: the range's slices of the prefix table, indexed through row_map like the outputs
             sa.forced = ftab + r0 * Tmax; sa.forced_stride = Tmax; sa.forced_len = flen + r0; sa.out_cols = prefix_cols; sa.prefix_logp = fplogp + r0 * Tmax;
         }
+        if (ses.ruled) {    // constrained decode: the table, and the range's slices of the states (through row_map like the outputs)
+            sa.rules = rules_dev; sa.n_states = rules_S; sa.depth_max = rules_dmax; sa.rule_state = rule_state + r0;
+            sa.rule_hist = rule_hist + r0 * Tmax; sa.rule_hist_stride = Tmax;
+        }
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
             if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
             else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba);
-        } else if (ses.forced) launch_prefix_step(s, nb, sa, sample_mode != 0);
+        } else if (ses.ruled) launch_rules_step(s, nb, sa, sample_mode != 0);
+        else if (ses.forced) launch_prefix_step(s, nb, sa, sample_mode != 0);
         else if (sample_mode) launch_sample_step(s, nb, sa);
         else hipLaunchKernelGGL(argmax_step_kernel, dim3(nb), dim3(64), 0, s, sa);
         dbg(s, "argmax");
@@ -1693,7 +1710,7 @@ struct Engine : EngineBase {
     // logp: the step also writes its log-probabilities, into the engine-owned logp_buf (part of the key: it is another StepArgs)
     int lane_graph(int li, int eos, bool logp) {
         const auto& ln = lanes[li];
-        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode, logp);
+        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode, logp, rules_S * 256 + rules_dmax);
         if (lanes.cached(li, key)) return 0;
         hipStream_t cs = lanes.cap_stream;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -1932,6 +1949,7 @@ struct Engine : EngineBase {
         if (prof || prof_cross || g_dbg || knobs.run.stamps || knobs.run.graph >= 0 || knobs.run.lanes > 0) return false;
         if (ses.ragged) return false;                                 // a ragged batch decodes with launches (persist.h has no per-row key count)
         if (ses.forced) return false;                                 // so does a prompted decode (persist.h starts at BOS and forces nothing)
+        if (ses.ruled) return false;                                  // and a constrained one (persist.h picks without rules)
         if (cfg.dec_exp != 4 || cfg.dec_layers > PS_MAXLD) return false;
         const bool exists = (D == 256 && cfg.dec_heads == 8) || (D == 768 && cfg.dec_heads == 12 && sizeof(T) == 2);
         if (!exists) return false;
@@ -2046,6 +2064,8 @@ struct Engine : EngineBase {
         const int rc = generate_impl(d, &steps, s);
         ses.row_stop = false;                                     // the decode is over (a txo_decode_step behind it steps every row)
         ses.forced = false;                                       // ... and picks every row's token itself: the prefix table belongs to the finished call
+        ses.ruled = false;                                        // ... without rules: they bind the generate family only
+        rules_rows = (rules_on && rc == 0) ? d.src.B : 0;         // what txo_last_rule_state may read
         if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
         if (q.n_steps) *q.n_steps = steps;
@@ -2096,6 +2116,7 @@ struct Engine : EngineBase {
         // (eos also decides whether the BOS column counts; a ragged session's key count per slot = the images' token counts)
         if (int r = begin_session(rows, B, d.src.N, eos, s, false, KeyCounts{d.src.ragged() ? rag_ntok : nullptr})) return r;
         ses.forced = d.prompted();
+        ses.ruled = rules_on;
         if (d.prompted()) {   // the prefix into the engine's table (lengths are in flen: generate), no forced token scored yet
             hipLaunchKernelGGL(prefix_table_kernel, dim3((B * Tmax + 255) / 256), dim3(256), 0, s, ftab, Tmax, q.prefix, q.P, flen, B, V);
             HIP_TRY(hipMemsetAsync(fplogp, 0, sizeof(float) * (size_t)B * Tmax, s));
@@ -2167,6 +2188,9 @@ struct Engine : EngineBase {
         lanes.split(ses.rows, want, s);
         last_ranges = lanes.n;
         reset_lanes(s, eos, d.prompted() ? d.m : 0);
+        if (ses.ruled)   // every row's automaton at its start, run over the prefix columns the multi-position pass consumes
+            hipLaunchKernelGGL(rules_start_kernel, dim3((B + 255) / 256), dim3(256), 0, s, rule_state, B, rules_dev, V, rules_S, rules_dmax, ftab, Tmax,
+                               d.prompted() ? d.m : 0);
         // a prompted decode: positions 0 .. m-2 of every row in ONE multi-position pass, no logits (it fills the K/V history the loop reads)
         if (d.prompted() && d.m > 1) { if (int r = prefill(ftab, Tmax, d.m - 1, nullptr, nullptr, s)) return r; }
         const bool use_graph = !eager && !prof && !prof_cross;     // event-carrying launches cannot be captured
@@ -2244,6 +2268,11 @@ struct Engine : EngineBase {
         if (d.prompted())   // pad / 0.0 where a row did not get to (or is finished, per-row stop); the forced tokens' log-probabilities to the caller
             hipLaunchKernelGGL(prefix_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, q.tokens, q.logp, max_len, n_cols, B, poll.steps, q.eos,
                                cfg.pad, stop_mode == 1 ? 1 : 0, ftab, Tmax, flen, d.m, fplogp, q.prefix_logp, q.P);
+        // the rules' states behind the last RETURNED position of every row (the loop may have run ahead of the eos break; a prompted row stops
+        // counting at its last returned column).  Under the per-row stop a finished row froze its state itself.
+        if (ses.ruled && !ses.row_stop && poll.steps >= 1)
+            hipLaunchKernelGGL(rules_settle_kernel, dim3((B + 255) / 256), dim3(256), 0, s, rule_state, rule_hist, Tmax, B, std::min(poll.steps, Tmax) - 1,
+                               d.prompted() ? flen : nullptr, n_cols);
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         lanes.split(ses.rows, 1, s);
@@ -2271,6 +2300,10 @@ struct Engine : EngineBase {
             hipLaunchKernelGGL(set_position_kernel, dim3(1), dim3(1), 0, s, st, i);
             StepArgs sa{dlogits, V, B, cur_tok, tokens_out, max_len, d.q.logits, st, eos_seen, flag - i, eos, sample_topk, 1.0f / sample_temp, sample_seed, 0,
                         0, nullptr, d.q.logp};
+            if (ses.ruled) {   // the loop's states carry over (no history beyond the table: the host looks at every token here, nothing runs ahead)
+                sa.rules = rules_dev; sa.n_states = rules_S; sa.depth_max = rules_dmax; sa.rule_state = rule_state;
+                launch_rules_step(s, B, sa, sample_mode != 0);
+            } else
             if (sample_mode) launch_sample_step(s, B, sa);
             else hipLaunchKernelGGL(argmax_step_kernel, dim3(B), dim3(64), 0, s, sa);
             *steps = i + 1;
@@ -2309,6 +2342,8 @@ struct Engine : EngineBase {
         Source src;
         if (int r = resolve_source(q, s, &src)) return r;
         if (!three) last_ragged = src.ragged();
+        if (rules_on)   // (last: every other refusal of the three entries keeps its place)
+            return fail(TXO_E_INVALID, "beam search: not available while token rules are set (txo_set_token_rules with rules_host == NULL switches them off)");
         const int rc = beam_impl(src, beams, max_len, eos, sink, n_steps, s);
         if (src.ragged()) ses.open = false;                       // nothing ragged outlives the call (generate_common)
         return rc;
@@ -2380,6 +2415,25 @@ struct Engine : EngineBase {
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         if (n_steps) *n_steps = steps;
+        return 0;
+    }
+
+    // txo_set_token_rules behind its checks: the table to the device (nothing of the engine is in flight between two calls: every generate drains
+    // its stream).  table null: off.
+    int set_token_rules(const int32_t* table, int S, int depth_max) override {
+        rules_rows = 0;
+        if (!table) { rules_on = false; rules_S = 0; rules_dmax = 0; return 0; }
+        HIP_TRY(hipMemcpy(rules_dev, table, sizeof(int32_t) * (size_t)S * V, hipMemcpyHostToDevice));
+        rules_on = true; rules_S = S; rules_dmax = depth_max;
+        return 0;
+    }
+    int last_rule_state(int32_t* out, int B, hipStream_t s) override {
+        if (!rules_on) return fail(TXO_E_STATE, "txo_last_rule_state: no token rules are set");
+        if (rules_rows < 1) return fail(TXO_E_STATE, "txo_last_rule_state: no generate has run since the token rules were set");
+        if (B < 1 || B > rules_rows)
+            return fail(TXO_E_INVALID, "txo_last_rule_state: B must be in [1, " + std::to_string(rules_rows) + "], the rows of the last constrained generate");
+        hipLaunchKernelGGL(rules_state_out_kernel, dim3((B + 255) / 256), dim3(256), 0, s, out, rule_state, B);
+        HIP_TRY(hipGetLastError());
         return 0;
     }
 
@@ -2847,6 +2901,42 @@ int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint
                                    "TXO_Q_SAMPLE_VOCAB_MAX)");
     e->impl->sample_mode = mode; e->impl->sample_topk = topk; e->impl->sample_temp = mode ? temp : 1.f; e->impl->sample_seed = seed;
     return 0;
+}
+
+// (the table is checked first: those refusals need neither an engine nor a device)
+int txo_set_token_rules(txo_engine* e, const int32_t* rules_host, int32_t S, int32_t V, int32_t depth_max) {
+    if (!rules_host) {
+        if (!e) return fail(TXO_E_INVALID, "null engine");
+        return e->impl->set_token_rules(nullptr, 0, 0);
+    }
+    if (S < 1 || S > RULES_MAX_STATES)
+        return fail(TXO_E_INVALID, "token rules: S is " + std::to_string(S) + "; the number of states must be in [1, " + std::to_string(RULES_MAX_STATES) + "]");
+    if (depth_max < 1 || depth_max > 255)
+        return fail(TXO_E_INVALID, "token rules: depth_max is " + std::to_string(depth_max) + "; it must be in [1, 255]");
+    if (V < 1) return fail(TXO_E_INVALID, "token rules: V must be >= 1");
+    for (int s = 0; s < S; ++s) {
+        bool always = false;                                          // a token this state allows at every depth
+        for (int v = 0; v < V; ++v) {
+            const int r = rules_host[(size_t)s * V + v];
+            if (rule_next(r) >= S)
+                return fail(TXO_E_INVALID, "token rules: rules[" + std::to_string(s) + "][" + std::to_string(v) + "] has next = " + std::to_string(rule_next(r)) +
+                                               ", not a state below S = " + std::to_string(S));
+            always = always || (!(r & (RULE_BAN | RULE_ONLY_AT_ZERO)) && rule_need(r) == 0 && rule_delta(r) <= 0);
+        }
+        if (!always)
+            return fail(TXO_E_INVALID, "token rules: state " + std::to_string(s) + " has no always-allowed token (not BAN, not ONLY_AT_ZERO, need == 0, delta <= 0): "
+                                       "a row could face an empty allowed set");
+    }
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (V != e->impl->cfg.vocab)
+        return fail(TXO_E_INVALID, "token rules: V is " + std::to_string(V) + " but the engine's vocabulary has " + std::to_string(e->impl->cfg.vocab) + " entries");
+    if (!e->impl->ready) return fail(TXO_E_STATE, "weights not finalized");
+    return e->impl->set_token_rules(rules_host, S, depth_max);
+}
+
+int txo_last_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, void* stream) {
+    if (!e || !state_out_dev) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->last_rule_state(state_out_dev, B, (hipStream_t)stream);
 }
 
 int txo_set_ragged_hybrid(txo_engine* e, int32_t on) {

@@ -14,10 +14,12 @@ struct Session {
     bool kmask_on = false;                // padding mask over the decoded positions (txo_decode_set_key_mask)
     bool row_stop = false;                // this generate compacts the live rows of its row ranges (launch path, stop_mode 1)
     bool forced = false;                  // a prompted decode: the steps force the caller's prefix (step_prefix.h; launch path only)
+    bool ruled = false;                   // a constrained decode: the steps pick under the engine's token rules (step_rules.h; launch path only)
     // what a captured step was built for (lanes.h): every field a step's launches depend on (strides and row count are baked into them)
-    LaneSet::GraphKey graph_key(const LaneSet::Lane& ln, int eos, int sample_mode, bool logp) const {
+    // rules: what a constrained step bakes of the rule set (states * 256 + depth cap; the table itself stays in the engine's buffer)
+    LaneSet::GraphKey graph_key(const LaneSet::Lane& ln, int eos, int sample_mode, bool logp, int rules = 0) const {
         return {ln.b0, ln.nb, keys, eos, rows, images,
-                (int)latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)ragged + 32 * (int)logp + 64 * (int)forced};
+                (int)latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)ragged + 32 * (int)logp + 64 * (int)forced + 128 * (ruled ? rules : 0)};
     }
 };
 struct KeyCounts { const int* dev = nullptr; const int32_t* host = nullptr; };   // a ragged session's key count per image: a device array or the caller's host array (staged)

@@ -44,6 +44,11 @@ struct StepArgs {
     const int64_t* forced; int forced_stride; const int* forced_len;
     int out_cols;               // output columns of a row (max_len): a pick whose column lies beyond is committed but not written
     float* prefix_logp;         // [rows][forced_stride] or null: log-probability of the forced token forced[r][t + 1], at column t + 1
+    // constrained decode (txo_set_token_rules; the *_rules_step kernels of step_rules.h, null / 0 for every other step): the packed table
+    // [n_states][V], its depth cap, and every row's (state, depth) -- indexed by row of the BATCH like outputs and sampler keys (the range's
+    // slice, through out_row); rule_hist [rows][rule_hist_stride]: the state behind every position (null: not kept)
+    const int* rules; int n_states; int depth_max; int2* rule_state;
+    int2* rule_hist; int rule_hist_stride;
 };
 // row of the range (relative to row0) whose outputs slot `row` produces
 __device__ inline int out_row(const StepArgs& a, int row) { return a.row_map ? a.row_map[row] - a.row0 : row; }

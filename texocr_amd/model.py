@@ -98,6 +98,7 @@ class HipEngine:
             _lib.check(self.lib.txo_engine_create(C.byref(cfg), C.byref(h)))
         self.handle = h
         self.loaded = False
+        self.token_rules = None                      # (a new handle has no token rules: a set installed by hand goes with the old one)
         if getattr(self, "_ragged_hybrid", False):   # (a reload of the weights makes a new handle: the switch follows the engine object)
             _lib.check(self.lib.txo_set_ragged_hybrid(h, 1))
         self._env_seen = self._txo_env()             # what the engine saw when it read its knobs
@@ -312,17 +313,35 @@ class HipEngine:
         self._ensure()
         _lib.check(self.lib.txo_set_stop_mode(self.handle, 1 if stop == "row" else 0))
 
+    def set_token_rules(self, rules) -> None:
+        """txo_set_token_rules: a texocr_amd.rules.TokenRules (checked on the host first: the same refusals, before the engine is touched), or
+        None = off.  While set, every generate from BOS or a prefix picks under the rules, on the launch path; beam search raises."""
+        self._ensure()
+        if rules is None:
+            torch.ops.texocr.set_token_rules(None, self.id, 0)
+            return
+        rules.validate(self.dims.vocab)
+        torch.ops.texocr.set_token_rules(torch.from_numpy(rules.table), self.id, rules.depth_max)
+
+    def last_rule_state(self, tokens: torch.Tensor) -> torch.Tensor:
+        """(B, 2) int32: the (state, depth) of every row behind the last constrained generate, beside its tokens (B, n)"""
+        return torch.ops.texocr.last_rule_state(tokens if tokens.ndim == 2 else tokens[None, :], self.id)
+
     @contextlib.contextmanager
-    def modes(self, sample: Optional[Tuple[float, Optional[int]]] = None, stop: str = "global", decode: Optional[str] = None):
-        """The engine's two global switches around the calls of one generate: sampling with sample = (temp, seed) -- a seed of None is
-        drawn from torch's generator; decode='greedy' overrides it -- and per-row stop.  Nothing else in this module turns either on,
-        and both are off again behind every exit.  Yields (temp, seed) as set, or None."""
+    def modes(self, sample: Optional[Tuple[float, Optional[int]]] = None, stop: str = "global", decode: Optional[str] = None, rules=None):
+        """The engine's global switches around the calls of one generate: sampling with sample = (temp, seed) -- a seed of None is
+        drawn from torch's generator; decode='greedy' overrides it --, per-row stop, and token rules (rules=: a TokenRules installed for the
+        scope; the set that was installed before, or none, is back behind every exit).  Nothing else in this module turns sampling or the
+        per-row stop on, and both are off again behind every exit.  Yields (temp, seed) as set, or None."""
         _check_modes(stop, decode or "greedy")
         if decode == "greedy":
             sample = None
         if sample is not None and sample[1] is None:
             sample = (sample[0], int(torch.randint(0, 2**62, (1,)).item()))
+        before = getattr(self, "token_rules", None)                # what ops.set_token_rules recorded: (table, depth_max) or None
         try:
+            if rules is not None:
+                self.set_token_rules(rules)
             if sample is not None:
                 self.set_sampling(True, temp=sample[0], seed=sample[1])
             if stop == "row":
@@ -333,6 +352,11 @@ class HipEngine:
                 self.set_sampling(False)
             if stop == "row":
                 self.set_stop_mode("global")
+            if rules is not None:
+                if before is None:
+                    torch.ops.texocr.set_token_rules(None, self.id, 0)
+                else:
+                    torch.ops.texocr.set_token_rules(before[0], self.id, before[1])
 
     @property
     def ragged_hybrid(self) -> bool:
@@ -744,6 +768,10 @@ class AutoRegressiveDecoder(nn.Module):
         # build extension: (B,) lengths of the rows of start_tokens (columns at and behind a row's length are never read); the result's
         # column j of row b is then the j-th token behind row b's own start.  Needs the engine's prompted loop (see below).
         prefix_len = kwargs.pop("prefix_len", None)
+        # build extension: a texocr_amd.rules.TokenRules the loop picks under (installed for this call); the result gains rule_state (B, 2)
+        # int32 as its last element.  Needs the engine's own loop: a BOS start or the prompted route, not the stepwise one.
+        rules = kwargs.pop("rules", None)
+        rstate = None
         if kwargs:
             raise ValueError(f"unsupported arguments: {sorted(kwargs)}")
         _need_enc(enc)
@@ -775,27 +803,37 @@ class AutoRegressiveDecoder(nn.Module):
             prompted = True
             if return_logits:
                 raise ValueError("return_logits is not available with prefix_len (a prompted decode keeps no logits)")
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode) as sample:
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules) as sample:
             if prompted:
                 out = eng.generate_prefix(None, st.to(enc.device), max_len, eos_tok, prefix_len=prefix_len, enc=enc, return_logp=return_logp)
+                if rules is not None:
+                    rstate = eng.last_rule_state(out[0] if return_logp else out)
                 # stop='row': the engine has padded with its own pad id, by each row's own prefix; a caller's pad= is put in its place -- every
                 # column the engine padded lies behind the row's first eos (the loop breaks only once every row holds one)
                 if stop == "row" and eos_tok is not None and pad is not None and int(pad) != eng.dims.pad:
                     toks = out[0] if return_logp else out
                     toks = _pad_after_eos(toks, _inside_lengths(st, prefix_len, -1).to(toks.device), eos_tok, int(pad))
                     out = (toks, *out[1:]) if return_logp else toks
-                if return_logp:
+                if rules is not None:
+                    out = (*out, rstate) if return_logp else (out, rstate)
+                if return_logp or rules is not None:
                     return tuple(o.squeeze(0) for o in out) if squeeze else out
                 return out.squeeze(0) if squeeze else out
             # beyond the positional table the engine slides the window with its multi-position forward, which needs a vocabulary
             # that is a multiple of 8 and a table that fits its workspace -- else the general stepwise loop below
             window_ok = max_len <= self.max_len or (eng.dims.vocab % 8 == 0 and self.max_len <= eng.max_batch * eng.max_tokens)
+            engine_loop = not padded and T0 == 1 and bool((st == eng.dims.bos).all()) and (window_ok or return_logits)
+            if rules is not None and not engine_loop:
+                raise ValueError("rules= needs the engine's own loop: a start the prompted decode or a BOS start can take (no padding mask; beyond "
+                                 "decoder.max_len a vocabulary that is a multiple of 8 and max_length <= max_batch * max_tokens)")
             if padded:
                 if return_logits or return_logp:
                     raise ValueError("return_logits / return_logp are not available with a padding mask")
                 out = self._generate_stepwise(st, eos_tok, max_len, enc, sample, mask=mask)
             elif T0 == 1 and bool((st == eng.dims.bos).all()) and (window_ok or return_logits):
                 out = eng.generate(None, max_len, eos_tok, enc=enc, return_logits=return_logits, return_logp=return_logp)
+                if rules is not None:
+                    rstate = eng.last_rule_state(out[0] if (return_logits or return_logp) else out)
             elif return_logits:
                 raise ValueError("return_logits needs a BOS start inside the positional table (max_len <= decoder.max_len)")
             elif return_logp:
@@ -812,7 +850,9 @@ class AutoRegressiveDecoder(nn.Module):
                 out = (_pad_after_eos(out[0], st.to(out[0].device), eos_tok, p_id), *out[1:])
             else:
                 out = _pad_after_eos(out, st.to(out.device), eos_tok, p_id)
-        if return_logits or return_logp:
+        if rules is not None:
+            out = (*out, rstate) if (return_logits or return_logp) else (out, rstate)
+        if return_logits or return_logp or rules is not None:
             return tuple(o.squeeze(0) for o in out) if squeeze else out
         return out.squeeze(0) if squeeze else out
 
@@ -945,8 +985,13 @@ class OCRModel(nn.Module):
     def generate(self, src: torch.Tensor, max_len: int, temp: float = 0.3, *, decode: str = "greedy",
                  generator: Optional[torch.Generator] = None, seed: Optional[int] = None, return_logits: bool = False,
                  beam: int = 0, return_beams: bool = False, stop: str = "global", return_logp: bool = False,
-                 prefix: Optional[torch.Tensor] = None, prefix_len=None):
-        """return_logp=True (build extension): (tokens, logp), both (B, n_steps) -- logp[b, t] = log_softmax(logits[b, t])[tokens[b, t]],
+                 prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None):
+        """rules= (build extension): a texocr_amd.rules.TokenRules -- which tokens the loop may pick (vocabulary bans, brace balance:
+        rules.ban / rules.brace_rules) -- installed for this call; the result gains rule_state (B, 2) int32 = every row's (state, depth)
+        behind its last returned token as its LAST element.  The decode then runs on the launch path (not the persistent launch); logp and
+        logits stay those of the raw logits.  No closure guarantee: a row that runs out of positions may end at depth > 0.  With beam=:
+        the engine's refusal (ValueError).
+        return_logp=True (build extension): (tokens, logp), both (B, n_steps) -- logp[b, t] = log_softmax(logits[b, t])[tokens[b, t]],
         what score(src, cat([bos], tokens)).logp reports, taken from the token selection itself: temperature 1 and the whole vocabulary
         also with decode='sample' (not the sampler's top-k / temperature distribution); stop='row': 0 behind a row's first eos, so
         logp.sum(1) is the sequence log-probability.  With return_logits: (tokens, logits, logp).
@@ -956,7 +1001,7 @@ class OCRModel(nn.Module):
         0.0 elsewhere.  Needs (longest prefix - 1) + max_len <= decoder.max_len; not with beam= or return_logits."""
         _check_modes(stop)
         if prefix is not None:
-            return self._generate_prefix(src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len)
+            return self._generate_prefix(src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
         if beam and return_logp:
@@ -964,19 +1009,24 @@ class OCRModel(nn.Module):
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
             if max_len > self.decoder.max_len:
                 raise ValueError(f"beam search needs max_len <= decoder.max_len ({self.decoder.max_len})")
-            return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
+            with self._engine.modes(rules=rules):                  # (with rules the engine refuses: beam search has no constrained form)
+                return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
         if decode == "greedy" and self.bos_token == self._engine.dims.bos:
             # (max_len > decoder.max_len: txo_generate slides the window like the reference, decoder.py:99-100)
             # (stop='row' with return_logits: the engine does not compact -- a finished row's logits would be missing -- and only pads)
-            with self._engine.modes(stop=stop):
-                return self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits, return_logp=return_logp)
+            with self._engine.modes(stop=stop, rules=rules):
+                out = self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits, return_logp=return_logp)
+                if rules is None:
+                    return out
+                out = out if isinstance(out, tuple) else (out,)
+                return (*out, self._engine.last_rule_state(out[0]))
         enc = self.encoder(src)
         start = torch.full((src.shape[0], 1), self.bos_token, dtype=torch.int64, device=src.device)   # ocr_model.py:57
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
-                                     stop=stop, pad=self.trg_pad_idx, return_logp=return_logp)
+                                     stop=stop, pad=self.trg_pad_idx, return_logp=return_logp, **({} if rules is None else {"rules": rules}))
 
-    def _generate_prefix(self, src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len):
+    def _generate_prefix(self, src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules=None):
         """generate(prefix=) / generate_ragged(prefix=): src a (B, C, H, W) tensor or a sequence of images.  Every refusal comes before
         the engine is touched."""
         if beam:
@@ -995,8 +1045,12 @@ class OCRModel(nn.Module):
         if seed is None and generator is not None:
             seed = generator.initial_seed()
         dev = src[0].device if isinstance(src, (list, tuple)) else src.device           # (a tensor or a PackedImages says it itself)
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode):
-            return eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules):
+            out = eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
+            if rules is None:
+                return out
+            out = out if isinstance(out, tuple) else (out,)
+            return (*out, eng.last_rule_state(out[0]))
 
     @torch.no_grad()
     def ingest(self, images, fit: bool = False, trim=False, regions=None) -> "ops.PackedImages":
@@ -1022,7 +1076,7 @@ class OCRModel(nn.Module):
         return self._engine.ingest(images, fit=fit, trim=trim, regions=regions)
 
     @torch.no_grad()
-    def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0) -> Beams:
+    def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0, rules=None) -> Beams:
         """Build extension: the k = beams best sequences of every image, with score, length and (return_logp=True) the log-probability of
         every token -> Beams.  src is a (B, C, H, W) tensor, or a sequence of (C, H_b, W_b) tensors of different sizes: those go
         through ONE ragged encode and ONE decode, and the beams of image b are what beam_search(src[b][None]) returns, over the batch's n.
@@ -1038,22 +1092,28 @@ class OCRModel(nn.Module):
         else:
             raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
         check_beam_args(beams, max_len, length_alpha, n_images, self.decoder.max_len, self._engine.max_batch)
-        return Beams(*self._engine.beam_search(src, beams, max_len, self.eos_token, return_logp=return_logp, length_alpha=length_alpha))
+        with self._engine.modes(rules=rules):                      # rules=: the engine refuses (ValueError) -- beam search has no constrained form
+            return Beams(*self._engine.beam_search(src, beams, max_len, self.eos_token, return_logp=return_logp, length_alpha=length_alpha))
 
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
-                        stop: str = "global", return_logp: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len=None):
+                        stop: str = "global", return_logp: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None):
         """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
         is keyed by the row of the batch).  max_len may exceed decoder.max_len: the window slides as in generate(), under the engine's
         two preconditions (a vocabulary that is a multiple of 8, max_length <= max_batch * max_tokens; ValueError before anything is
-        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them.  prefix= / prefix_len=: as generate() takes them."""
+        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them.  prefix= / prefix_len= / rules=: as generate() takes
+        them (rules=: rule_state (B, 2) is the result's last element)."""
         if prefix is not None:
-            return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len)
+            return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len, rules)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
-        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode):
-            return self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
+        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules):
+            out = self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
+            if rules is None:
+                return out
+            out = out if isinstance(out, tuple) else (out,)
+            return (*out, self._engine.last_rule_state(out[0]))
 
     @torch.no_grad()
     def score(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:

@@ -740,6 +740,46 @@ def _(img, sizes, engine, max_len, eos):
     return _gen_fake(img, engine, max_len, False, True)[:3]
 
 
+# ---- constrained decode (txo_set_token_rules): which tokens the loop of the generate family may pick (texocr_amd/rules.py builds the tables) ----
+@custom_op("texocr::set_token_rules", mutates_args=())
+def set_token_rules(table: Optional[torch.Tensor], engine: int, depth_max: int) -> None:
+    """txo_set_token_rules: table (S, V) int32 on the CPU, packed as texocr_amd.rules.pack packs an entry, and its depth cap; None: off (the
+    default).  The engine checks the table and names what it refuses (ValueError).  ``engine.token_rules`` records what is installed."""
+    e = _eng(engine, ready=True)
+    if table is None:
+        with torch.cuda.device(e.device):
+            _lib.check(e.lib.txo_set_token_rules(e.handle, None, 0, 0, 0))
+        e.token_rules = None
+        return
+    if table.is_cuda or table.dtype != torch.int32 or table.ndim != 2:
+        raise ValueError("token rules: table must be an int32 CPU tensor of shape (S, V)")
+    table = table.contiguous()
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_set_token_rules(e.handle, table.data_ptr(), int(table.shape[0]), int(table.shape[1]), int(depth_max)))
+    e.token_rules = (table, int(depth_max))
+
+
+@custom_op("texocr::last_rule_state", mutates_args=())
+def last_rule_state(tokens: torch.Tensor, engine: int) -> torch.Tensor:
+    """txo_last_rule_state: the (state, depth) of every row of the last constrained generate -> (B, 2) int32 beside its `tokens` (B, n)"""
+    e = _eng(engine)
+    if not tokens.is_cuda or tokens.ndim != 2 or tokens.device.index != e.device:
+        raise ValueError("last_rule_state: tokens must be the (B, n) GPU tensor the constrained generate returned")
+    out = torch.empty((tokens.shape[0], 2), device=tokens.device, dtype=torch.int32)
+    _call(e, "txo_last_rule_state", out.data_ptr(), int(tokens.shape[0]))
+    return out
+
+
+@set_token_rules.register_fake
+def _(table, engine, depth_max):
+    return None
+
+
+@last_rule_state.register_fake
+def _(tokens, engine):
+    return tokens.new_empty((tokens.shape[0], 2), dtype=torch.int32)
+
+
 # ---- device-side image ingest (txo_ingest_u8): raw uint8 pixels -> the container of a ragged batch, one copy and one launch ----------
 U8_ALIGN = 16        # byte alignment of every host image inside the staged buffer
 

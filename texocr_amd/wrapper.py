@@ -64,8 +64,12 @@ def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.T
 
 
 class TeXOCRWrapper:
-    def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False):
-        """ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)"""
+    def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False, balanced: bool = False):
+        """ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)
+        balanced=True (build extension): every __call__ / batch decodes under the brace rule of this tokenizer unless the call says otherwise
+        (see batch)"""
+        self.balanced = bool(balanced)
+        self._brace_rules = None
         self.tokenizer = RegExTokenizer()
         self.tokenizer.load(config["tokenizer_path"])                                # ocr_model.py:74-75
         config = dict(config)
@@ -82,6 +86,18 @@ class TeXOCRWrapper:
         if sd is not None:
             self.model.load_state_dict(sd)
         self.dims: Dims = self.model._engine.dims
+
+    def _rules(self, balanced: Optional[bool], decode: str):
+        """the rules= of a call: rules.brace_rules of the wrapper's tokenizer (built once) where balanced, else None"""
+        if not (self.balanced if balanced is None else balanced):
+            return None
+        if decode == "beam":
+            raise ValueError("balanced=True is not available with decode='beam' (beam search has no constrained form)")
+        if self._brace_rules is None:
+            from .rules import brace_rules
+            self._brace_rules = brace_rules(self.tokenizer, vocab=self.dims.vocab, eos=self.model.eos_token,
+                                            ban=(self.model.bos_token, self.model.trg_pad_idx)).validate(self.dims.vocab)
+        return self._brace_rules
 
     def _tensor(self, img) -> torch.Tensor:
         x = preprocess_image(img, self.dims.patch)
@@ -168,7 +184,7 @@ class TeXOCRWrapper:
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
               length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host", fit: str = "none",
-              trim: str = "none", trim_level: int = 127, trim_margin: int = 2) -> List[tuple]:
+              trim: str = "none", trim_level: int = 127, trim_margin: int = 2, balanced: Optional[bool] = None) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -196,7 +212,11 @@ class TeXOCRWrapper:
         without ink stays whole (ops.trim_view) -- by numpy and PIL's crop with ingest='host', by the engine (OCRModel.ingest(trim=)) with
         ingest='device', to the same pixels, so every result is identical by either ingest.  The cut comes BEFORE the fit: with
         fit='none' an image beyond the canvas whose ink fits is accepted, and one whose ink does not fit is refused as ever, with the
-        trimmed size in the message.  return_align maps are on the grid of the trimmed (then fitted) image."""
+        trimmed size in the message.  return_align maps are on the grid of the trimmed (then fitted) image.
+        balanced=True (build extension; default: the wrapper's own setting): the decode picks under rules.brace_rules of the tokenizer
+        (OCRModel.generate_ragged(rules=)): no token closes a group that is not open, eos comes only at depth 0, <BOS> / <PAD> never.  A
+        row that runs out of positions may still end open; logp stays the raw model's.  Not with decode='beam'."""
+        rules = self._rules(balanced, decode)
         rule = self._trim_rule(trim, trim_level, trim_margin)
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
@@ -216,7 +236,9 @@ class TeXOCRWrapper:
                 chunk_seed = None if seed is None else int(seed) + c0 // step
                 kw = {} if pre is None else dict(prefix=pre[c0:c0 + step].cuda(), prefix_len=plen[c0:c0 + step])
                 toks = self.model.generate_ragged(chunk, max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
-                                                  return_logp=return_logp, **kw)
+                                                  return_logp=return_logp, **kw, **({} if rules is None else {"rules": rules}))
+                if rules is not None:
+                    toks = toks[:-1] if return_logp else toks[0]                       # (without the rule states)
                 toks, logp = toks[:2] if return_logp else (toks, None)
                 full = [cut_at_eos(row, self.model.eos_token) for row in toks.tolist()]
                 logp = logp.tolist() if return_logp else None
@@ -234,7 +256,7 @@ class TeXOCRWrapper:
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
                  length_alpha: float = 0.0, prefix=None, ingest: str = "host", fit: str = "none", trim: str = "none", trim_level: int = 127,
-                 trim_margin: int = 2) -> tuple:
+                 trim_margin: int = 2, balanced: Optional[bool] = None) -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
@@ -246,7 +268,9 @@ class TeXOCRWrapper:
         ingest='device': the image is preprocessed on the device (see batch); the result is identical.
         fit='canvas': an image beyond the canvas is downscaled to fit it first (see batch); the maps of return_align are then on the
         fitted grid.
-        trim='ink': the image is cut to its ink and a margin first (see batch), before the fit; the maps are on the trimmed image's grid."""
+        trim='ink': the image is cut to its ink and a margin first (see batch), before the fit; the maps are on the trimmed image's grid.
+        balanced=True: the decode picks under the tokenizer's brace rule (see batch)."""
+        rules = self._rules(balanced, decode)
         x = self._images([img], ingest, fit, self._trim_rule(trim, trim_level, trim_margin))
         x = x.box if ingest == "device" else x[0][None]
         prow: List[int] = []
@@ -262,7 +286,10 @@ class TeXOCRWrapper:
         else:
             # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
             # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
-            toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp, **gen_kw)
+            toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp, **gen_kw,
+                                       **({} if rules is None else {"rules": rules}))
+            if rules is not None:
+                toks = toks[:-1] if return_logp else toks[0]                           # (without the rule states)
             toks, logp = toks[:2] if return_logp else (toks, None)
         out_tokens = toks.squeeze(0).tolist()[:-1]                                   # ocr_model.py:104 (drops the EOS)
         latex = process_output(self.tokenizer.decode(prow + out_tokens))             # :105-108
