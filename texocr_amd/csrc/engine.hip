@@ -53,6 +53,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "lanes.h"
 #include "session.h"
 #include "stamps.h"
+#include "ingest_req.h"
 
 namespace txo {
 
@@ -64,15 +65,6 @@ static void dbg(hipStream_t s, const char* what, int l = -1) {
 }
 
 struct HostTensor { std::vector<int64_t> shape; std::vector<float> data; };
-
-// The trim rule of texocr.h "Trim-to-ink ingest": ink extents (ymin, xmin, ymax, xmax; ymax < 0: no ink) of an image (h, w) and a margin ->
-// the view (y0, x0, h', w'): the ink box widened by the margin on every side and clamped to the image; the whole image where there is no ink
-static inline void trim_view_of(const int* ext, int h, int w, int margin, int32_t* view) {
-    if (ext[2] < 0) { view[0] = 0; view[1] = 0; view[2] = h; view[3] = w; return; }
-    const long long y0 = std::max(0LL, (long long)ext[0] - margin), y1 = std::min((long long)h, (long long)ext[2] + 1 + margin);
-    const long long x0 = std::max(0LL, (long long)ext[1] - margin), x1 = std::min((long long)w, (long long)ext[3] + 1 + margin);
-    view[0] = (int32_t)y0; view[1] = (int32_t)x0; view[2] = (int32_t)(y1 - y0); view[3] = (int32_t)(x1 - x0);
-}
 
 // -------------------------------------------------------------------------------------------------
 struct EngineBase {
@@ -110,16 +102,11 @@ struct EngineBase {
     int rules_rows = 0;                         // rows of the last constrained generate (txo_last_rule_state), 0: none since the rules were set
     virtual int set_token_rules(const int32_t* table, int S, int depth_max) = 0;   // behind txo_set_token_rules's checks; table null: off
     virtual int last_rule_state(int32_t* out, int B, hipStream_t s) = 0;
-    // txo_ingest_u8 behind its checks (ingest_check): descriptors up in one staged copy, one launch.  pitch (here and below; null: rows are
-    // tightly packed, today's kernels): [B] pixels from one source row to the next -- (offsets, shapes) then describe VIEWS (txo_ingest_u8_view)
-    virtual int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int B, int C, int Hc, int Wc,
-                          float* box, hipStream_t s) = 0;
-    // txo_ingest_u8_fit behind its checks, with at least one oversized image: fitted [B][2] from ingest_fit_sizes, scratch holds the intermediates
-    virtual int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, const int32_t* fitted, int B,
-                              int C, int Hc, int Wc, float* box, unsigned char* scratch, hipStream_t s) = 0;
+    // txo_ingest_u8 / _fit / _view behind their checks (ingest_req.h: ingest_plan): descriptors up in one staged copy, then one launch -- or,
+    // where an image is downscaled, the horizontal pass of those that need one and the fused vertical pass + ingest
+    virtual int ingest(const IngestPlan& p, const IngestReq& q, hipStream_t s) = 0;
     // txo_ingest_trim_views behind its checks: the ink extents of every image (ingest_trim.h) -> views [B][4]; waits on s
-    virtual int trim_views(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int level, int margin, int32_t* views,
-                           hipStream_t s) = 0;
+    virtual int trim_views(const IngestList& l, int level, int margin, int32_t* views, hipStream_t s) = 0;
     virtual int query(int what, int64_t* out) = 0;
     virtual int profile_enable(int on) = 0;
     virtual int profile_read(int kind, double* avg_ms, int64_t* count) = 0;
@@ -1017,105 +1004,92 @@ struct Engine : EngineBase {
         rag_ev_pending = true;
         return 0;
     }
-    // Device-side image ingest (ingest.h).  The list has passed ingest_check; works before the weights are finalized (it reads none).
-    // The three host arrays go up as ONE staged copy of B descriptors, the way ragged_batch uploads its grids; no allocation.
-    int ingest_u8(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int B, int C, int Hc, int Wc,
-                  float* box, hipStream_t s) override {
+    // ---- device-side image ingest (ingest.h, ingest_fit.h, ingest_trim.h); works before the weights are finalized (it reads none) -----------
+    // What the three calls below share: the staging is free once its last copy has left it; `fill` then writes the descriptors of the B images
+    // into it (non-zero: its refusal), and they go up as ONE staged copy, the way ragged_batch uploads its grids; no allocation.
+    // pending: the copy's event is left for the next call to wait on (trim_views waits on the stream itself instead)
+    struct Staging { void* dev; const void* host; size_t bytes; };
+    template <typename Fill> int ingest_stage(int B, Staging st, hipStream_t s, bool pending, Fill fill) {
         if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
         if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
-        for (int b = 0; b < B; ++b)
-            ing_host[b] = IngestDesc{(long long)offsets[b], shapes[3 * b], shapes[3 * b + 1], shapes[3 * b + 2], pitch ? pitch[b] : 0};
-        HIP_TRY(hipMemcpyAsync(ing_desc, ing_host, sizeof(IngestDesc) * B, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ing_ev, s));
-        ing_ev_pending = true;
-        const dim3 grid((unsigned)((Wc + IG_BLOCK_W - 1) / IG_BLOCK_W), (unsigned)((Hc + IG_ROWS - 1) / IG_ROWS), (unsigned)B), blk(IG_LANES_X * IG_ROWS);
-        const auto kern = pitch ? ingest_u8_kernel<true> : ingest_u8_kernel<false>;
-        if (prof) {                                           // txo_profile_read kind 4: events bound to the dispatch itself
-            hipEvent_t e0 = pool.next(), e1 = pool.next();
-            if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
-            hipExtLaunchKernelGGL(kern, grid, blk, 0, s, e0, e1, 0, pix, (const IngestDesc*)ing_desc, box, C, Hc, Wc);
-            ev_ingest.push_back({e0, e1});
-        } else {
-            hipLaunchKernelGGL(kern, grid, blk, 0, s, pix, (const IngestDesc*)ing_desc, box, C, Hc, Wc);
-        }
-        HIP_TRY(hipGetLastError());
+        if (int r = fill()) return r;
+        HIP_TRY(hipMemcpyAsync(st.dev, st.host, st.bytes, hipMemcpyHostToDevice, s));
+        if (pending) { HIP_TRY(hipEventRecord(ing_ev, s)); ing_ev_pending = true; }
         return 0;
     }
-    // Fit-to-canvas ingest (ingest_fit.h).  The list has passed ingest_fit_check and holds an oversized image.  One staged copy of the
-    // descriptors and of the list of images with a horizontal pass, then that pass (if any image has one) and the fused vertical pass + ingest.
-    int ingest_u8_fit(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, const int32_t* fitted, int B, int C,
-                      int Hc, int Wc, float* box, unsigned char* scratch, hipStream_t s) override {
-        if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
-        if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
-        FitDesc* fd = reinterpret_cast<FitDesc*>(fit_host);
-        int* hl = reinterpret_cast<int*>(fit_host + sizeof(FitDesc) * (size_t)B);
-        long long mid = 0;
-        int nh = 0, hmax = 0, wmax = 0;
-        for (int b = 0; b < B; ++b) {
-            const int h = shapes[3 * b], w = shapes[3 * b + 1], ch = shapes[3 * b + 2], fh = fitted[2 * b], fw = fitted[2 * b + 1];
-            fd[b] = FitDesc{(long long)offsets[b], -1, h, w, ch, fh, fw, pitch ? pitch[b] : 0};
-            if (fw != w) {
-                fd[b].mid = mid;
-                mid += ingest_fit_mid_bytes(h, fw, ch);
-                hl[nh++] = b;
-                hmax = std::max(hmax, h); wmax = std::max(wmax, fw);
-            }
+    // one dispatch of an ingest kernel; profiling on (txo_profile_read kind 4): with a pair of pooled events bound to the dispatch itself
+    template <typename... P> int ingest_launch(void (*kern)(P...), dim3 grid, dim3 blk, hipStream_t s, typename std::common_type<P>::type... args) {
+        if (!prof) { hipLaunchKernelGGL(kern, grid, blk, 0, s, args...); return 0; }
+        hipEvent_t e0 = pool.next(), e1 = pool.next();
+        if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
+        hipExtLaunchKernelGGL(kern, grid, blk, 0, s, e0, e1, 0, args...);
+        ev_ingest.push_back({e0, e1});
+        return 0;
+    }
+    int ingest(const IngestPlan& p, const IngestReq& q, hipStream_t s) override {
+        const int B = q.src.B;
+        const unsigned char* pix = q.src.pix;
+        const dim3 grid((unsigned)((q.Wc + IG_BLOCK_W - 1) / IG_BLOCK_W), (unsigned)((q.Hc + IG_ROWS - 1) / IG_ROWS), (unsigned)B), blk(IG_LANES_X * IG_ROWS);
+        if (!p.oversized) {                                   // nothing to downscale: txo_ingest_u8's own launch, its container bit for bit
+            if (int r = ingest_stage(B, {ing_desc, ing_host, sizeof(IngestDesc) * B}, s, true, [&] {
+                    for (int b = 0; b < B; ++b)
+                        ing_host[b] = IngestDesc{(long long)p.off[b], p.shapes[3 * b], p.shapes[3 * b + 1], p.shapes[3 * b + 2], p.pitch ? p.pitch[b] : 0};
+                    return 0;
+                })) return r;
+            if (int r = ingest_launch(p.pitch ? ingest_u8_kernel<true> : ingest_u8_kernel<false>, grid, blk, s, pix, ing_desc, q.box, q.C, q.Hc, q.Wc)) return r;
+            HIP_TRY(hipGetLastError());
+            return 0;
         }
-        HIP_TRY(hipMemcpyAsync(fit_dev, fit_host, fit_bytes(B), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ing_ev, s));
-        ing_ev_pending = true;
+        // Fit-to-canvas (ingest_fit.h): the descriptors and the list of the images with a horizontal pass in one staged copy, then that pass (if
+        // any image has one) and the fused vertical pass + ingest
+        int nh = 0, hmax = 0, wmax = 0;
+        if (int r = ingest_stage(B, {fit_dev, fit_host, fit_bytes(B)}, s, true, [&] {
+                FitDesc* fd = reinterpret_cast<FitDesc*>(fit_host);
+                int* hl = reinterpret_cast<int*>(fit_host + sizeof(FitDesc) * (size_t)B);
+                long long mid = 0;
+                for (int b = 0; b < B; ++b) {
+                    const int h = p.shapes[3 * b], w = p.shapes[3 * b + 1], ch = p.shapes[3 * b + 2], fh = p.fitted[2 * b], fw = p.fitted[2 * b + 1];
+                    fd[b] = FitDesc{(long long)p.off[b], -1, h, w, ch, fh, fw, p.pitch ? p.pitch[b] : 0};
+                    if (fw != w) {
+                        fd[b].mid = mid;
+                        mid += ingest_fit_mid_bytes(h, fw, ch);
+                        hl[nh++] = b;
+                        hmax = std::max(hmax, h); wmax = std::max(wmax, fw);
+                    }
+                }
+                return 0;
+            })) return r;
         const FitDesc* dd = reinterpret_cast<const FitDesc*>(fit_dev);
         const int* dl = reinterpret_cast<const int*>(fit_dev + sizeof(FitDesc) * (size_t)B);
+        unsigned char* scratch = static_cast<unsigned char*>(q.scratch);
         const dim3 hgrid((unsigned)((wmax + FR_COLS - 1) / FR_COLS), (unsigned)((hmax + FR_ROWS - 1) / FR_ROWS), (unsigned)nh), hblk(FR_COLS * FR_LANES_Y);
-        const dim3 grid((unsigned)((Wc + IG_BLOCK_W - 1) / IG_BLOCK_W), (unsigned)((Hc + IG_ROWS - 1) / IG_ROWS), (unsigned)B), blk(IG_LANES_X * IG_ROWS);
-        const auto rows = pitch ? fit_rows_kernel<true> : fit_rows_kernel<false>;
-        const auto kern = pitch ? ingest_fit_kernel<true> : ingest_fit_kernel<false>;
-        if (prof) {                                           // txo_profile_read kind 4: events bound to each dispatch
-            if (nh) {
-                hipEvent_t h0 = pool.next(), h1 = pool.next();
-                if (!h0 || !h1) return fail(TXO_E_HIP, "hipEventCreate failed");
-                hipExtLaunchKernelGGL(rows, hgrid, hblk, 0, s, h0, h1, 0, pix, dd, dl, scratch);
-                ev_ingest.push_back({h0, h1});
-            }
-            hipEvent_t e0 = pool.next(), e1 = pool.next();
-            if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
-            hipExtLaunchKernelGGL(kern, grid, blk, 0, s, e0, e1, 0, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
-            ev_ingest.push_back({e0, e1});
-        } else {
-            if (nh) hipLaunchKernelGGL(rows, hgrid, hblk, 0, s, pix, dd, dl, scratch);
-            hipLaunchKernelGGL(kern, grid, blk, 0, s, pix, (const unsigned char*)scratch, dd, box, C, Hc, Wc);
-        }
+        const auto rows = p.pitch ? fit_rows_kernel<true> : fit_rows_kernel<false>;
+        const auto kern = p.pitch ? ingest_fit_kernel<true> : ingest_fit_kernel<false>;
+        if (nh) if (int r = ingest_launch(rows, hgrid, hblk, s, pix, dd, dl, scratch)) return r;
+        if (int r = ingest_launch(kern, grid, blk, s, pix, scratch, dd, q.box, q.C, q.Hc, q.Wc)) return r;
         HIP_TRY(hipGetLastError());
         return 0;
     }
     // Trim-to-ink ingest (ingest_trim.h).  The list, level and margin have passed txo_ingest_trim_views' checks.  The descriptors go up as in
-    // ingest_u8; a fill of the records, the one launch over every byte, 16 B bytes back and a wait on s: the container's size depends on them.
-    int trim_views(const unsigned char* pix, const int64_t* offsets, const int32_t* shapes, int B, int level, int margin, int32_t* views,
-                   hipStream_t s) override {
-        if (B > Bmax) return fail(TXO_E_INVALID, "ingest: batch exceeds engine max_batch (the descriptor staging holds max_batch images)");
-        if (ing_ev_pending) { HIP_TRY(hipEventSynchronize(ing_ev)); ing_ev_pending = false; }
-        long long pieces = 1;                                 // of the largest image, whatever its first byte's alignment
-        for (int b = 0; b < B; ++b) {
-            ing_host[b] = IngestDesc{(long long)offsets[b], shapes[3 * b], shapes[3 * b + 1], shapes[3 * b + 2], 0};
-            pieces = std::max(pieces, ((long long)shapes[3 * b] * shapes[3 * b + 1] * shapes[3 * b + 2] + 30) / 16);
-        }
-        const long long tiles = (pieces + TB_TILE - 1) / TB_TILE;
-        if (tiles > 2147483647LL) return fail(TXO_E_INVALID, "ingest: an image exceeds the launch grid of the ink search");
-        HIP_TRY(hipMemcpyAsync(ing_desc, ing_host, sizeof(IngestDesc) * B, hipMemcpyHostToDevice, s));
+    // ingest; a fill of the records, the one launch over every byte, 16 B bytes back and a wait on s: the container's size depends on them.
+    int trim_views(const IngestList& l, int level, int margin, int32_t* views, hipStream_t s) override {
+        const int B = l.B;
+        long long tiles = 0;
+        if (int r = ingest_stage(B, {ing_desc, ing_host, sizeof(IngestDesc) * B}, s, false, [&] {
+                long long pieces = 1;                         // of the largest image, whatever its first byte's alignment
+                for (int b = 0; b < B; ++b) {
+                    ing_host[b] = IngestDesc{(long long)l.offsets[b], l.shapes[3 * b], l.shapes[3 * b + 1], l.shapes[3 * b + 2], 0};
+                    pieces = std::max(pieces, ((long long)l.shapes[3 * b] * l.shapes[3 * b + 1] * l.shapes[3 * b + 2] + 30) / 16);
+                }
+                tiles = (pieces + TB_TILE - 1) / TB_TILE;
+                return tiles > 2147483647LL ? fail(TXO_E_INVALID, "ingest: an image exceeds the launch grid of the ink search") : 0;
+            })) return r;
         hipLaunchKernelGGL(trim_fill_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, trim_rec, B);
-        const dim3 grid((unsigned)tiles, (unsigned)B), blk(TB_THREADS);
-        if (prof) {                                           // txo_profile_read kind 4
-            hipEvent_t e0 = pool.next(), e1 = pool.next();
-            if (!e0 || !e1) return fail(TXO_E_HIP, "hipEventCreate failed");
-            hipExtLaunchKernelGGL(trim_bbox_kernel, grid, blk, 0, s, e0, e1, 0, pix, (const IngestDesc*)ing_desc, trim_rec, level);
-            ev_ingest.push_back({e0, e1});
-        } else {
-            hipLaunchKernelGGL(trim_bbox_kernel, grid, blk, 0, s, pix, (const IngestDesc*)ing_desc, trim_rec, level);
-        }
+        if (int r = ingest_launch(trim_bbox_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(TB_THREADS), s, l.pix, ing_desc, trim_rec, level)) return r;
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(trim_host, trim_rec, sizeof(int) * 4 * (size_t)B, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));                     // (the staging is free again too: no event is left pending)
-        for (int b = 0; b < B; ++b) trim_view_of(trim_host + 4 * b, shapes[3 * b], shapes[3 * b + 1], margin, views + 4 * b);
+        for (int b = 0; b < B; ++b) trim_view_of(trim_host + 4 * b, l.shapes[3 * b], l.shapes[3 * b + 1], margin, views + 4 * b);
         return 0;
     }
     int ragged_refusals() {
@@ -2496,78 +2470,6 @@ static int validate(const txo_config& c) {
     return 0;
 }
 
-// ---- device-side image ingest: the refusals that need no engine (texocr.h: txo_ingest_u8 / txo_ingest_box) -------------------------------
-static long long ingest_round16(long long v) { return (v + 15) / 16 * 16; }
-
-// shapes int32 [B][3] = (h, w, ch); every message names the image.  box (may be null): the largest rounded-up height / width
-static int ingest_check_shapes(const int32_t* shapes, int B, long long* box) {
-    if (B < 1) return fail(TXO_E_INVALID, "ingest: no images (B must be >= 1)");
-    if (!shapes) return fail(TXO_E_INVALID, "ingest: null shapes");
-    if (B > 65535) return fail(TXO_E_INVALID, "ingest: more than 65535 images in one call");
-    long long H = 0, W = 0;
-    for (int b = 0; b < B; ++b) {
-        const int h = shapes[3 * b], w = shapes[3 * b + 1], ch = shapes[3 * b + 2];
-        const std::string who = "ingest: image " + std::to_string(b);
-        if (ch != 1 && ch != 3 && ch != 4)
-            return fail(TXO_E_INVALID, who + " has ch = " + std::to_string(ch) + "; the channel count must be 1 (L), 3 (RGB) or 4 (RGBA)");
-        if (h < 1 || w < 1) return fail(TXO_E_INVALID, who + " is " + std::to_string(h) + "x" + std::to_string(w) + "; both sides must be >= 1");
-        H = std::max(H, ingest_round16(h)); W = std::max(W, ingest_round16(w));
-    }
-    if (box) { box[0] = H; box[1] = W; }
-    return 0;
-}
-
-// what txo_ingest_u8 refuses about the offsets and the container, for a list that has passed ingest_check_shapes
-static int ingest_check_container(const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc) {
-    if (!offsets) return fail(TXO_E_INVALID, "ingest: null offsets");
-    if (C < 1) return fail(TXO_E_INVALID, "ingest: the container's channel count must be >= 1");
-    if (Hc < 1 || Wc < 1) return fail(TXO_E_INVALID, "ingest: the container's height/width must be positive");
-    if (Wc % 4) return fail(TXO_E_INVALID, "ingest: the container's width must be a multiple of 4 (rows are written in 16-byte pieces)");
-    if ((Hc + IG_ROWS - 1) / IG_ROWS > 65535) return fail(TXO_E_INVALID, "ingest: the container's height exceeds the launch grid");
-    for (int b = 0; b < B; ++b) {
-        const long long h16 = ingest_round16(shapes[3 * b]), w16 = ingest_round16(shapes[3 * b + 1]);
-        const std::string who = "ingest: image " + std::to_string(b);
-        if (offsets[b] < 0) return fail(TXO_E_INVALID, who + " has a negative byte offset");
-        if (h16 > Hc || w16 > Wc)
-            return fail(TXO_E_INVALID, who + " is " + std::to_string(shapes[3 * b]) + "x" + std::to_string(shapes[3 * b + 1]) + ", " + std::to_string(h16) + "x" +
-                                           std::to_string(w16) + " rounded up to multiples of 16: it does not fit the container's " + std::to_string(Hc) + "x" +
-                                           std::to_string(Wc));
-    }
-    return 0;
-}
-
-// everything txo_ingest_u8 refuses about the list and the container, before the engine or the device is looked at
-static int ingest_check(const int64_t* offsets, const int32_t* shapes, int B, int C, int Hc, int Wc) {
-    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
-    return ingest_check_container(offsets, shapes, B, C, Hc, Wc);
-}
-
-// ---- fit-to-canvas ingest: the rule, the scratch and the refusals, none of which needs an engine (texocr.h: txo_ingest_fit ...) -----------
-// *fitted (may be null; sized here, once the list has passed) [B][2] = (h', w') of every image under the target (Fh, Fw); *scratch (may be
-// null): the bytes of the horizontal passes' intermediates
-static_assert(TXO_FIT_TAPS == FIT_TAPS, "texocr.h and ingest_fit.h disagree on the taps per output pixel");
-static int ingest_fit_sizes(const int32_t* shapes, int B, int Fh, int Fw, std::vector<int32_t>* fitted, long long* scratch) {
-    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
-    if (fitted) fitted->assign((size_t)2 * B, 0);
-    if (Fh < 16 || Fh % 16 || Fw < 16 || Fw % 16)
-        return fail(TXO_E_INVALID, "ingest: the fit target is " + std::to_string(Fh) + "x" + std::to_string(Fw) + "; both sides must be positive multiples of 16");
-    if ((32LL * Fh + FR_ROWS - 1) / FR_ROWS > 65535) return fail(TXO_E_INVALID, "ingest: the fit target's height exceeds the launch grid");
-    long long need = 0;
-    for (int b = 0; b < B; ++b) {
-        const int h = shapes[3 * b], w = shapes[3 * b + 1];
-        int fh, fw;
-        fit_size(h, w, Fh, Fw, &fh, &fw);
-        if ((long long)h > (long long)FIT_MAX_SCALE * fh || (long long)w > (long long)FIT_MAX_SCALE * fw)
-            return fail(TXO_E_INVALID, "ingest: image " + std::to_string(b) + " is " + std::to_string(h) + "x" + std::to_string(w) + ", " + std::to_string(fh) + "x" +
-                                           std::to_string(fw) + " fitted to " + std::to_string(Fh) + "x" + std::to_string(Fw) + ": an axis shrinks by more than " +
-                                           std::to_string(FIT_MAX_SCALE) + " times");
-        if (fitted) { (*fitted)[2 * b] = fh; (*fitted)[2 * b + 1] = fw; }
-        if (fw != w) need += ingest_fit_mid_bytes(h, fw, shapes[3 * b + 2]);
-    }
-    if (scratch) *scratch = need;
-    return 0;
-}
-
 }  // namespace txo
 
 using namespace txo;
@@ -2651,27 +2553,26 @@ int txo_ingest_box(const int32_t* shapes, int32_t B, int32_t* Hc_out, int32_t* W
     return 0;
 }
 
-// (the list and the container are checked first: those refusals need neither an engine nor a device)
-// pitch (null for txo_ingest_u8 itself): see EngineBase::ingest_u8 -- (offsets, shapes) are then the views of txo_ingest_u8_view
-static int ingest_u8_run(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int32_t B, int32_t C,
-                         int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* stream) {
-    if (int r = ingest_check(offsets, shapes, B, C, Hc, Wc)) return r;
-    if (!e || !pix || !box_out || !sizes_out) return fail(TXO_E_INVALID, "ingest: null argument");
-    if (reinterpret_cast<uintptr_t>(box_out) % 16) return fail(TXO_E_INVALID, "ingest: the container must be 16-byte aligned (rows are written in 16-byte pieces)");
-    if (int r = e->impl->ingest_u8(pix, offsets, shapes, pitch, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
-    for (int b = 0; b < B; ++b) { sizes_out[2 * b] = (int32_t)ingest_round16(shapes[3 * b]); sizes_out[2 * b + 1] = (int32_t)ingest_round16(shapes[3 * b + 1]); }
+// txo_ingest_u8 / _fit / _view: every refusal that needs neither an engine nor a device (ingest_plan), the engine's one entry, the sizes
+static int ingest_run(const IngestReq& q, void* stream) {
+    IngestPlan p;
+    if (int r = ingest_plan(q, &p)) return r;
+    if (int r = q.engine->impl->ingest(p, q, (hipStream_t)stream)) return r;
+    for (int b = 0; b < q.src.B; ++b) { q.sizes_out[2 * b] = (int32_t)ingest_round16(p.out_h(b)); q.sizes_out[2 * b + 1] = (int32_t)ingest_round16(p.out_w(b)); }
     return 0;
 }
 
 int txo_ingest_u8(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Hc, int32_t Wc,
                   float* box_out, int32_t* sizes_out, void* stream) {
-    return ingest_u8_run(e, pix, offsets, shapes, nullptr, B, C, Hc, Wc, box_out, sizes_out, stream);
+    return ingest_run(IngestReq{.engine = e, .src = {.pix = pix, .offsets = offsets, .shapes = shapes, .B = B}, .C = C, .Hc = Hc, .Wc = Wc,
+                                .box = box_out, .sizes_out = sizes_out}, stream);
 }
 
 int txo_ingest_fit(const int32_t* shapes, int32_t B, int32_t Fh, int32_t Fw, int32_t* fitted_out) {
     if (!fitted_out) return fail(TXO_E_INVALID, "ingest: null argument");
-    std::vector<int32_t> fitted;                                      // (nothing is written on a refusal)
-    if (int r = ingest_fit_sizes(shapes, B, Fh, Fw, &fitted, nullptr)) return r;
+    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+    std::vector<int32_t> fitted((size_t)2 * B);                       // (nothing is written on a refusal)
+    if (int r = ingest_fit_sizes(shapes, B, {Fh, Fw}, fitted.data(), nullptr)) return r;
     memcpy(fitted_out, fitted.data(), sizeof(int32_t) * 2 * (size_t)B);
     return 0;
 }
@@ -2679,7 +2580,8 @@ int txo_ingest_fit(const int32_t* shapes, int32_t B, int32_t Fh, int32_t Fw, int
 int txo_ingest_fit_scratch(const int32_t* shapes, int32_t B, int32_t Fh, int32_t Fw, int64_t* bytes_out) {
     if (!bytes_out) return fail(TXO_E_INVALID, "ingest: null argument");
     long long need = 0;
-    if (int r = ingest_fit_sizes(shapes, B, Fh, Fw, nullptr, &need)) return r;
+    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
+    if (int r = ingest_fit_sizes(shapes, B, {Fh, Fw}, nullptr, &need)) return r;
     *bytes_out = need;
     return 0;
 }
@@ -2700,35 +2602,10 @@ int txo_ingest_fit_coeffs(int32_t in, int32_t out, int32_t* xmin_out, int32_t* n
     return 0;
 }
 
-// (as txo_ingest_u8: the list, the target, the container and the scratch are checked before the engine or the device is looked at)
-static int ingest_u8_fit_run(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* pitch, int32_t B, int32_t C,
-                             int32_t Fh, int32_t Fw, int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes,
-                             void* stream) {
-    std::vector<int32_t> fitted;
-    long long need = 0;
-    if (int r = ingest_fit_sizes(shapes, B, Fh, Fw, &fitted, &need)) return r;        // (the list is checked here, once)
-    std::vector<int32_t> fshapes((size_t)3 * B);
-    bool oversized = false;
-    for (int b = 0; b < B; ++b) {
-        fshapes[3 * b] = fitted[2 * b]; fshapes[3 * b + 1] = fitted[2 * b + 1]; fshapes[3 * b + 2] = shapes[3 * b + 2];
-        oversized = oversized || fitted[2 * b] != shapes[3 * b] || fitted[2 * b + 1] != shapes[3 * b + 1];
-    }
-    if (int r = ingest_check_container(offsets, fshapes.data(), B, C, Hc, Wc)) return r;   // (the container holds the FITTED sizes)
-    if (need > 0 && (!scratch || scratch_bytes < need))
-        return fail(TXO_E_INVALID, "ingest: the fit scratch is " + (scratch ? std::to_string((long long)scratch_bytes) + " bytes" : std::string("null")) +
-                                       "; the horizontal passes of this list need " + std::to_string(need) + " bytes (txo_ingest_fit_scratch)");
-    if (!e || !pix || !box_out || !sizes_out) return fail(TXO_E_INVALID, "ingest: null argument");
-    if (reinterpret_cast<uintptr_t>(box_out) % 16) return fail(TXO_E_INVALID, "ingest: the container must be 16-byte aligned (rows are written in 16-byte pieces)");
-    // nothing oversized: txo_ingest_u8's own launch, its container bit for bit
-    if (int r = oversized ? e->impl->ingest_u8_fit(pix, offsets, shapes, pitch, fitted.data(), B, C, Hc, Wc, box_out, (unsigned char*)scratch, (hipStream_t)stream)
-                          : e->impl->ingest_u8(pix, offsets, shapes, pitch, B, C, Hc, Wc, box_out, (hipStream_t)stream)) return r;
-    for (int b = 0; b < B; ++b) { sizes_out[2 * b] = (int32_t)ingest_round16(fitted[2 * b]); sizes_out[2 * b + 1] = (int32_t)ingest_round16(fitted[2 * b + 1]); }
-    return 0;
-}
-
 int txo_ingest_u8_fit(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, int32_t B, int32_t C, int32_t Fh, int32_t Fw,
                       int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes, void* stream) {
-    return ingest_u8_fit_run(e, pix, offsets, shapes, nullptr, B, C, Fh, Fw, Hc, Wc, box_out, sizes_out, scratch, scratch_bytes, stream);
+    return ingest_run(IngestReq{.engine = e, .src = {.pix = pix, .offsets = offsets, .shapes = shapes, .B = B}, .fit = true, .Fh = Fh, .Fw = Fw,
+                                .C = C, .Hc = Hc, .Wc = Wc, .box = box_out, .sizes_out = sizes_out, .scratch = scratch, .scratch_bytes = scratch_bytes}, stream);
 }
 
 // (the list, the level and the margin are checked before the engine or the device is looked at)
@@ -2737,41 +2614,21 @@ int txo_ingest_trim_views(txo_engine* e, const uint8_t* pix, const int64_t* offs
     if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
     if (!offsets) return fail(TXO_E_INVALID, "ingest: null offsets");
     for (int b = 0; b < B; ++b)
-        if (offsets[b] < 0) return fail(TXO_E_INVALID, "ingest: image " + std::to_string(b) + " has a negative byte offset");
+        if (int r = ingest_check_offset(offsets[b], b)) return r;
     if (level < 0 || level > 254)
         return fail(TXO_E_INVALID, "ingest: the trim level is " + std::to_string(level) + "; it must lie in [0, 254] (a pixel is ink where a channel is <= level)");
     if (margin < 0) return fail(TXO_E_INVALID, "ingest: the trim margin is " + std::to_string(margin) + "; it must be >= 0");
     if (!e || !pix || !views_out) return fail(TXO_E_INVALID, "ingest: null argument");
-    return e->impl->trim_views(pix, offsets, shapes, B, level, margin, views_out, (hipStream_t)stream);
+    return e->impl->trim_views(IngestList{pix, offsets, shapes, B}, level, margin, views_out, (hipStream_t)stream);
 }
 
 // (the list and the views first, then everything txo_ingest_u8 / txo_ingest_u8_fit check, on the views: before the engine or the device is looked at)
 int txo_ingest_u8_view(txo_engine* e, const uint8_t* pix, const int64_t* offsets, const int32_t* shapes, const int32_t* views, int32_t B, int32_t C,
                        int32_t Fh, int32_t Fw, int32_t Hc, int32_t Wc, float* box_out, int32_t* sizes_out, void* scratch, int64_t scratch_bytes,
                        void* stream) {
-    if (int r = ingest_check_shapes(shapes, B, nullptr)) return r;
-    if (!offsets) return fail(TXO_E_INVALID, "ingest: null offsets");
-    if (!views) return fail(TXO_E_INVALID, "ingest: null views");
-    std::vector<int32_t> vshapes((size_t)3 * B), pitch((size_t)B);
-    std::vector<int64_t> voff((size_t)B);
-    bool whole = true;                                                // every view spans its image's rows: nothing is pitched
-    for (int b = 0; b < B; ++b) {
-        const long long h = shapes[3 * b], w = shapes[3 * b + 1], ch = shapes[3 * b + 2];
-        const long long y0 = views[4 * b], x0 = views[4 * b + 1], vh = views[4 * b + 2], vw = views[4 * b + 3];
-        const std::string who = "ingest: image " + std::to_string(b) + " has the view " + std::to_string(vh) + "x" + std::to_string(vw) + " at (" +
-                                std::to_string(y0) + ", " + std::to_string(x0) + ")";
-        if (offsets[b] < 0) return fail(TXO_E_INVALID, "ingest: image " + std::to_string(b) + " has a negative byte offset");
-        if (vh < 1 || vw < 1) return fail(TXO_E_INVALID, who + "; both sides must be >= 1");
-        if (y0 < 0 || x0 < 0 || y0 + vh > h || x0 + vw > w)
-            return fail(TXO_E_INVALID, who + ", which reaches outside the image's " + std::to_string(h) + "x" + std::to_string(w));
-        vshapes[3 * b] = (int32_t)vh; vshapes[3 * b + 1] = (int32_t)vw; vshapes[3 * b + 2] = (int32_t)ch;
-        voff[b] = offsets[b] + (y0 * w + x0) * ch;                    // the origin folds into the offset; the rows stay w pixels apart
-        pitch[b] = (int32_t)w;
-        whole = whole && vw == w;
-    }
-    const int32_t* pp = whole ? nullptr : pitch.data();               // (views that keep their images' widths are tightly packed images: today's kernels)
-    if (Fh == 0 && Fw == 0) return ingest_u8_run(e, pix, voff.data(), vshapes.data(), pp, B, C, Hc, Wc, box_out, sizes_out, stream);
-    return ingest_u8_fit_run(e, pix, voff.data(), vshapes.data(), pp, B, C, Fh, Fw, Hc, Wc, box_out, sizes_out, scratch, scratch_bytes, stream);
+    return ingest_run(IngestReq{.engine = e, .src = {.pix = pix, .offsets = offsets, .shapes = shapes, .B = B}, .view = true, .views = views,
+                                .fit = Fh != 0 || Fw != 0, .Fh = Fh, .Fw = Fw, .C = C, .Hc = Hc, .Wc = Wc, .box = box_out, .sizes_out = sizes_out,
+                                .scratch = scratch, .scratch_bytes = scratch_bytes}, stream);
 }
 
 int txo_decode_step(txo_engine* e, const int64_t* tok_in, int32_t t, float* logits_out, int64_t* tok_out, void* stream) {

@@ -850,13 +850,7 @@ def ingest_u8(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Ten
     """txo_ingest_u8: bufs = uint8 device tensors that hold the pixels (contiguous), src (B, 2) int64 CPU = (index into bufs, byte offset),
     shapes (B, 3) int32 CPU = (h, w, ch) -> (box (B, channels, Hc, Wc) float32 with every element written, sizes (B, 2) int32 CPU = (h, w)
     rounded up to 16).  One launch; the refusals are the engine's (ValueError with its message)."""
-    e = _eng(engine)
-    base, offsets, shapes = _u8_source(bufs, src, shapes, e)
-    B = int(shapes.shape[0])
-    box, sizes = _u8_outputs(e, B, channels, Hc, Wc)
-    _call(e, "txo_ingest_u8", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), B, int(channels), int(Hc), int(Wc),
-          box.data_ptr(), _i32p(sizes))
-    return box, sizes
+    return _ingest_container("txo_ingest_u8", bufs, src, shapes, engine=engine, channels=channels, box=(Hc, Wc))
 
 
 def _u8_source(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Tensor, e):
@@ -883,16 +877,42 @@ def _u8_source(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch.Te
     return base, torch.tensor([p - base for p in first], dtype=torch.int64), shapes
 
 
-def _u8_outputs(e, B: int, channels: int, Hc: int, Wc: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    box = torch.empty((B, int(channels), int(Hc), int(Wc)), device=torch.device("cuda", e.device), dtype=torch.float32)
+def _ingest_container(entry: str, bufs, src, shapes, *, engine: int, channels: int, box: Tuple[int, int], views=None,
+                      fit: Optional[Tuple[int, int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The one body of texocr::ingest_u8 / ingest_u8_fit / ingest_u8_view, each on its own C entry point `entry`: the source checks, the view
+    check (views given), the scratch of the horizontal passes (fit given; txo_ingest_fit_scratch, a tensor of this call: nothing is
+    allocated when no image is oversized), the outputs and the one call.  box = (Hc, Wc); a view op without a fit passes the target 0 x 0."""
+    e = _eng(engine)
+    base, offsets, shapes = _u8_source(bufs, src, shapes, e)      # (the bound check is on the full images)
+    dev = torch.device("cuda", e.device)
+    B, Hc, Wc = int(shapes.shape[0]), int(box[0]), int(box[1])
+    Fh, Fw = (0, 0) if fit is None else (int(fit[0]), int(fit[1]))
+    fitted = shapes if fit is not None else None                  # the list the fit is applied to
+    if views is not None:
+        if views.is_cuda or views.dtype != torch.int32 or tuple(views.shape) != (B, 4):
+            raise ValueError("views must be an int32 CPU tensor of shape (B, 4) = (y0, x0, h, w)")
+        views = views.contiguous()
+        if fit is not None:                                       # (a view the engine is about to refuse asks for no scratch)
+            fitted = view_shapes(shapes, views).contiguous() if _views_inside(shapes, views) else None
+    need = C.c_int64(0)
+    if fitted is not None:
+        _lib.check(_lib.load().txo_ingest_fit_scratch(_i32p(fitted), B, Fh, Fw, C.byref(need)))
+    scratch = torch.empty((need.value,), dtype=torch.uint8, device=dev) if need.value else None
+    # (a view op sizes the container from its views: where they are about to be refused, the engine is still given the box as it came)
+    out = torch.empty((B, int(channels)) + ((Hc, Wc) if views is None else (max(Hc, 0), max(Wc, 0))), device=dev, dtype=torch.float32)
     if os.environ.get("TXO_DEBUG_POISON"):      # tests: an element the kernel left unwritten shows as nan
-        box.fill_(float("nan"))
-    return box, torch.zeros((B, 2), dtype=torch.int32)
+        out.fill_(float("nan"))
+    sizes = torch.zeros((B, 2), dtype=torch.int32)
+    args = [base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes)] + ([] if views is None else [_i32p(views)]) + [B, int(channels)]
+    args += [Hc, Wc, out.data_ptr(), _i32p(sizes)] if entry == "txo_ingest_u8" else \
+            [Fh, Fw, Hc, Wc, out.data_ptr(), _i32p(sizes), scratch.data_ptr() if scratch is not None else None, need.value]
+    _call(e, entry, *args)
+    return out, sizes
 
 
-@ingest_u8.register_fake
-def _(bufs, src, shapes, engine, channels, Hc, Wc):
-    B = shapes.shape[0]
+def _ingest_container_fake(bufs, src, shapes, *rest):
+    """the outputs of the three container ops, whose arguments end in channels, [Fh, Fw,] Hc, Wc"""
+    B, channels, (Hc, Wc) = shapes.shape[0], rest[-3 if len(rest) == 4 else -5], rest[-2:]
     return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
 
 
@@ -926,22 +946,7 @@ def ingest_u8_fit(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torch
     """txo_ingest_u8_fit: texocr::ingest_u8 with every image that exceeds (Fh, Fw) downscaled to fit it first (fit_size; bit for bit PIL's
     BILINEAR resize of its L / RGB channels) -> (box (B, channels, Hc, Wc), sizes (B, 2) int32 CPU = the FITTED sizes rounded up to 16).
     The scratch of the horizontal passes (txo_ingest_fit_scratch) is a tensor of this call; nothing is allocated when no image is oversized."""
-    e = _eng(engine)
-    base, offsets, shapes = _u8_source(bufs, src, shapes, e)
-    B = int(shapes.shape[0])
-    need = C.c_int64(0)
-    _lib.check(_lib.load().txo_ingest_fit_scratch(_i32p(shapes), B, int(Fh), int(Fw), C.byref(need)))
-    scratch = torch.empty((need.value,), dtype=torch.uint8, device=torch.device("cuda", e.device)) if need.value else None
-    box, sizes = _u8_outputs(e, B, channels, Hc, Wc)
-    _call(e, "txo_ingest_u8_fit", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), B, int(channels), int(Fh), int(Fw),
-          int(Hc), int(Wc), box.data_ptr(), _i32p(sizes), scratch.data_ptr() if scratch is not None else None, need.value)
-    return box, sizes
-
-
-@ingest_u8_fit.register_fake
-def _(bufs, src, shapes, engine, channels, Fh, Fw, Hc, Wc):
-    B = shapes.shape[0]
-    return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
+    return _ingest_container("txo_ingest_u8_fit", bufs, src, shapes, engine=engine, channels=channels, box=(Hc, Wc), fit=(Fh, Fw))
 
 
 # ---- trim-to-ink and region ingest (txo_ingest_trim_views / txo_ingest_u8_view): a rectangle of the source takes the image's place ----------
@@ -1013,27 +1018,12 @@ def ingest_u8_view(bufs: Sequence[torch.Tensor], src: torch.Tensor, shapes: torc
     """txo_ingest_u8_view: texocr::ingest_u8 (Fh = Fw = 0) or texocr::ingest_u8_fit of the rectangle views[b] = (y0, x0, h', w') of every source
     image (bufs / src / shapes describe the FULL images; entries may share bytes and views may overlap) -> (box, sizes) of the views, bit for
     bit what contiguous copies of them give.  Asynchronous; the refusals are the engine's."""
-    e = _eng(engine)
-    base, offsets, shapes = _u8_source(bufs, src, shapes, e)      # (the bound check is on the full images)
-    B = int(shapes.shape[0])
-    if views.is_cuda or views.dtype != torch.int32 or tuple(views.shape) != (B, 4):
-        raise ValueError("views must be an int32 CPU tensor of shape (B, 4) = (y0, x0, h, w)")
-    views = views.contiguous()
-    need = C.c_int64(0)
-    if (Fh or Fw) and _views_inside(shapes, views):               # (a view the engine is about to refuse asks for no scratch)
-        vshapes = view_shapes(shapes, views).contiguous()         # (named: the pointer below must outlive the call)
-        _lib.check(_lib.load().txo_ingest_fit_scratch(_i32p(vshapes), B, int(Fh), int(Fw), C.byref(need)))
-    scratch = torch.empty((need.value,), dtype=torch.uint8, device=torch.device("cuda", e.device)) if need.value else None
-    box, sizes = _u8_outputs(e, B, channels, max(int(Hc), 0), max(int(Wc), 0))
-    _call(e, "txo_ingest_u8_view", base, C.cast(offsets.data_ptr(), C.POINTER(C.c_int64)), _i32p(shapes), _i32p(views), B, int(channels), int(Fh),
-          int(Fw), int(Hc), int(Wc), box.data_ptr(), _i32p(sizes), scratch.data_ptr() if scratch is not None else None, need.value)
-    return box, sizes
+    return _ingest_container("txo_ingest_u8_view", bufs, src, shapes, engine=engine, channels=channels, box=(Hc, Wc), views=views,
+                             fit=(Fh, Fw) if Fh or Fw else None)
 
 
-@ingest_u8_view.register_fake
-def _(bufs, src, shapes, views, engine, channels, Fh, Fw, Hc, Wc):
-    B = shapes.shape[0]
-    return bufs[0].new_empty((B, channels, Hc, Wc), dtype=torch.float32), torch.empty((B, 2), dtype=torch.int32, device="cpu")
+for _op in (ingest_u8, ingest_u8_fit, ingest_u8_view):
+    _op.register_fake(_ingest_container_fake)
 
 
 def pack_u8(images: Sequence, in_channels: int, device, *, engine: int, fit: Optional[Tuple[int, int]] = None,
@@ -1054,26 +1044,22 @@ def pack_u8(images: Sequence, in_channels: int, device, *, engine: int, fit: Opt
     if trim is not None and regions is not None:
         raise ValueError("pack_u8: trim and regions are two ways to name the views; pass one of them")
     staged, dev, src, shapes = plan_u8(images)
-    device = torch.device(device)
-    if trim is not None or regions is not None:
-        bufs = [staged.to(device)] + dev
-        if trim is not None:
-            level, margin = _trim_args(*trim)
-            views = torch.ops.texocr.ingest_trim_views(bufs, src, shapes, int(engine), level, margin)
-        else:
-            views = torch.as_tensor(regions).to(device="cpu", dtype=torch.int32).reshape(-1, 4).contiguous()
-            if views.shape[0] != shapes.shape[0]:
-                raise ValueError(f"pack_u8: regions needs one (y0, x0, h, w) per image ({shapes.shape[0]}), got {views.shape[0]}")
-        vshapes = view_shapes(shapes, views)
-        Fh, Fw = (0, 0) if fit is None else (int(fit[0]), int(fit[1]))
-        Hc, Wc = box_u8(vshapes if fit is None else fit_shapes(vshapes, Fh, Fw))
+    bufs = [staged.to(torch.device(device))] + dev
+    views = None
+    if trim is not None:
+        level, margin = _trim_args(*trim)
+        views = torch.ops.texocr.ingest_trim_views(bufs, src, shapes, int(engine), level, margin)
+    elif regions is not None:
+        views = torch.as_tensor(regions).to(device="cpu", dtype=torch.int32).reshape(-1, 4).contiguous()
+        if views.shape[0] != shapes.shape[0]:
+            raise ValueError(f"pack_u8: regions needs one (y0, x0, h, w) per image ({shapes.shape[0]}), got {views.shape[0]}")
+    Fh, Fw = (0, 0) if fit is None else (int(fit[0]), int(fit[1]))
+    sized = shapes if views is None else view_shapes(shapes, views)          # what the container holds: the images or their views, fitted
+    Hc, Wc = box_u8(sized if fit is None else fit_shapes(sized, Fh, Fw))
+    if views is not None:
         box, sizes = torch.ops.texocr.ingest_u8_view(bufs, src, shapes, views, int(engine), int(in_channels), Fh, Fw, Hc, Wc)
-        return PackedImages(box, sizes, views)
-    if fit is None:
-        Hc, Wc = box_u8(shapes)
-        box, sizes = torch.ops.texocr.ingest_u8([staged.to(device)] + dev, src, shapes, int(engine), int(in_channels), Hc, Wc)
+    elif fit is not None:
+        box, sizes = torch.ops.texocr.ingest_u8_fit(bufs, src, shapes, int(engine), int(in_channels), Fh, Fw, Hc, Wc)
     else:
-        Fh, Fw = int(fit[0]), int(fit[1])
-        Hc, Wc = box_u8(fit_shapes(shapes, Fh, Fw))
-        box, sizes = torch.ops.texocr.ingest_u8_fit([staged.to(device)] + dev, src, shapes, int(engine), int(in_channels), Fh, Fw, Hc, Wc)
-    return PackedImages(box, sizes)
+        box, sizes = torch.ops.texocr.ingest_u8(bufs, src, shapes, int(engine), int(in_channels), Hc, Wc)
+    return PackedImages(box, sizes, views)
