@@ -460,7 +460,8 @@ int txo_set_stop_mode(txo_engine* e, int32_t mode);
  * without an always-allowed token (not BAN, not ONLY_AT_ZERO, need == 0, delta <= 0): so no row can ever face an empty allowed set.
  * While rules are set every txo_generate* that decodes from BOS or from a prefix (image, _from_enc, _ragged, _logp, _prefix*) runs its loop
  * with one launch per stage (TXO_Q_LAST_PERSISTENT reads 0) and otherwise as ever: captured steps, row ranges, TXO_STOP_ROW with live-row
- * compaction, ragged batches, the sliding window, logp_out.  txo_generate_beam / txo_beam_search / txo_beam_search_ragged refuse.
+ * compaction, ragged batches, the sliding window, logp_out.  txo_generate_beam / txo_beam_search / txo_beam_search_ragged refuse, unless
+ * txo_set_rules_beam(e, 1) is in effect (below).
  * txo_decode_step picks without rules.  Closure is NOT guaranteed: a row that runs out of positions may end at depth > 0 --
  * txo_last_rule_state: the (s, depth) of rows 0 .. B-1 behind the last position the last txo_generate* returned for them (under TXO_STOP_ROW:
  * behind a finished row's first eos), int32 [B][2] on the device, ordered on `stream`. */
@@ -468,6 +469,29 @@ int txo_set_stop_mode(txo_engine* e, int32_t mode);
 #define TXO_RULE_ONLY_AT_ZERO (1 << 25)
 int txo_set_token_rules(txo_engine* e, const int32_t* rules_host, int32_t S, int32_t V, int32_t depth_max);
 int txo_last_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, void* stream);
+
+/* Constrained beam search, a BUILD EXTENSION and opt-in: txo_set_rules_beam(e, 1) (default 0; TXO_E_INVALID unless on is 0 or 1).  Off, the
+ * three beam entries refuse while token rules are set, word for word as before the search had a constrained form.  On, and with rules set,
+ * they run the search with the rules inside the beam selection; on, without rules, they run as ever.
+ * Every (image, beam) slot carries a state (s, depth); all k slots of an image start at (0, 0) and only slot 0 is live, as ever.  For a live
+ * parent j in (s_j, d_j) the candidate (j, v) is score[j] + (logit[j][v] - lse[j]) iff rules[s_j][v] allows v at d_j, and -inf otherwise --
+ * the beam search's own dead marker, not the -3.4e38f of the single-row pick.  lse[j] is the log-sum-exp of the RAW row: nothing is
+ * renormalised, a beam's score stays the sum of the raw model's log-probabilities of its tokens and txo_beam_out.logp means what logp_out of a
+ * constrained txo_generate_logp means.  A finished parent offers eos at + 0 and nothing else, unmasked, and its state is frozen.  A slot takes
+ * its parent's state advanced by its token, (next, clamp(depth + delta, 0, depth_max)): the eos that finishes a beam advances the state once,
+ * its later repeats do not.  Ranking, the tie order (lower parent * V + token) and *n_steps_out are the unconstrained search's.
+ * Fewer than k allowed candidates is a normal case (a state that allows two tokens, k = 5, position 0): the surplus beams are DEAD -- score
+ * -inf, like beams 1 .. k-1 before position 0 --, and a dead beam is outside every guarantee: its tokens and its state are unspecified
+ * (tokens inside the vocabulary).  A live beam always has an allowed token (txo_set_token_rules has checked the table).  A dead beam does not
+ * keep the search running: it ends when every live beam of every image is finished.
+ * Closure is NOT guaranteed: a beam that runs out of positions may end at depth > 0 (its state shows it); with ONLY_AT_ZERO on eos a FINISHED
+ * beam is at depth 0 by construction.  Works with out->logp, row ranges, ragged batches and all three entries; txo_beam_out keeps its layout.
+ * txo_last_beam_rule_state: the (s, depth) of every beam of the last constrained beam search, int32 [B][beams][2] on the device, ordered on
+ * `stream`, in the order of that call's outputs (txo_beam_search*: the final order, length_alpha included; txo_generate_beam: the order of
+ * all_tokens_out and scores_out).  Refused with TXO_E_STATE: no token rules are set; no constrained beam search has run since the token rules
+ * were set; B / beams are not that search's. */
+int txo_set_rules_beam(txo_engine* e, int32_t on);
+int txo_last_beam_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, int32_t beams, void* stream);
 
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last

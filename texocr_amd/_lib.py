@@ -78,6 +78,8 @@ SYMBOLS = {
     "txo_set_stop_mode": (C.c_int, [_P, _I]),
     "txo_set_token_rules": (C.c_int, [_P, C.c_void_p, _I, _I, _I]),
     "txo_last_rule_state": (C.c_int, [_P, C.c_void_p, _I, _P]),
+    "txo_set_rules_beam": (C.c_int, [_P, _I]),
+    "txo_last_beam_rule_state": (C.c_int, [_P, C.c_void_p, _I, _I, _P]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),
     "txo_set_ragged_hybrid": (C.c_int, [_P, _I]),
     "txo_profile_enable": (C.c_int, [_P, _I]),

@@ -49,6 +49,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "ingest_fit.h"    // (the fit-to-canvas passes in front of it; uses ingest.h's per-pixel pieces)
 #include "ingest_trim.h"   // (the ink extents in front of both; reads ingest.h's descriptors)
 #include "step_rules.h"    // (the constrained token selection: step.h / step_prefix.h with a per-row automaton; last again)
+#include "beam_rules.h"    // (the constrained beam selection: step.h's beam kernels with that automaton; last again)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -102,6 +103,10 @@ struct EngineBase {
     int rules_rows = 0;                         // rows of the last constrained generate (txo_last_rule_state), 0: none since the rules were set
     virtual int set_token_rules(const int32_t* table, int S, int depth_max) = 0;   // behind txo_set_token_rules's checks; table null: off
     virtual int last_rule_state(int32_t* out, int B, hipStream_t s) = 0;
+    // txo_set_rules_beam (beam_rules.h): while on, a beam search under token rules runs the constrained selection instead of being refused
+    bool rules_beam = false;
+    int brule_B = 0, brule_k = 0;               // images / beams of the last constrained beam search (txo_last_beam_rule_state), 0: none since the rules were set
+    virtual int last_beam_rule_state(int32_t* out, int B, int beams, hipStream_t s) = 0;
     // txo_ingest_u8 / _fit / _view behind their checks (ingest_req.h: ingest_plan): descriptors up in one staged copy, then one launch -- or,
     // where an image is downscaled, the horizontal pass of those that need one and the fused vertical pass + ingest
     virtual int ingest(const IngestPlan& p, const IngestReq& q, hipStream_t s) = 0;
@@ -244,7 +249,8 @@ struct Engine : EngineBase {
     // beam search state (rows = images * beams)
     float* bscore = nullptr; int* bfin = nullptr; short* bpath[2] = {nullptr, nullptr}; short* bparent = nullptr; int* btok = nullptr;
     float* blogp = nullptr;                // [Tmax][Bmax] beside btok: the selected candidates' increments (txo_beam_search with logp)
-    struct BeamCtx { int k; const short* path_cur; short* path_nxt; bool logp = false; };   // logp: the step also records blogp
+    int2* brule_state = nullptr;           // [Bmax] constrained beam search (beam_rules.h): the (state, depth) of every (image, beam) slot
+    struct BeamCtx { int k; const short* path_cur; short* path_nxt; bool logp = false; bool ruled = false; };   // logp: the step also records blogp; ruled: beam_rules.h's selection
     // ----- profiling -----
     bool prof = false;                // full: per-launch cross-attention events + markers around every encode and step
     bool prof_cross = false;          // light: only the cross-attention dispatches carry events (no extra packets)
@@ -722,6 +728,7 @@ struct Engine : EngineBase {
         if (int r = dalloc(&rules_dev, (size_t)RULES_MAX_STATES * V)) return r;
         if (int r = dalloc(&rule_state, (size_t)Bmax)) return r;
         if (int r = dalloc(&rule_hist, (size_t)Bmax * Tmax)) return r;
+        if (int r = dalloc(&brule_state, (size_t)Bmax)) return r;
         return 0;
     }
 
@@ -1669,7 +1676,11 @@ struct Engine : EngineBase {
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
-            if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
+            if (bm->ruled) {   // constrained beam search: the table, and the range's slice of the slots' states (range-local, like every pointer of ba)
+                const BeamRuleArgs ra{rules_dev, rules_S, rules_dmax, brule_state + r0};
+                if (bm->logp) hipLaunchKernelGGL(beam_select_rules_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
+                else hipLaunchKernelGGL(beam_select_rules_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
+            } else if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
             else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba);
         } else if (ses.ruled) launch_rules_step(s, nb, sa, sample_mode != 0);
         else if (ses.forced) launch_prefix_step(s, nb, sa, sample_mode != 0);
@@ -2316,9 +2327,11 @@ struct Engine : EngineBase {
         Source src;
         if (int r = resolve_source(q, s, &src)) return r;
         if (!three) last_ragged = src.ragged();
-        if (rules_on)   // (last: every other refusal of the three entries keeps its place)
+        if (rules_on && !rules_beam)   // (last: every other refusal of the three entries keeps its place; txo_set_rules_beam lifts it)
             return fail(TXO_E_INVALID, "beam search: not available while token rules are set (txo_set_token_rules with rules_host == NULL switches them off)");
+        brule_B = brule_k = 0;
         const int rc = beam_impl(src, beams, max_len, eos, sink, n_steps, s);
+        if (rules_on && rc == 0) { brule_B = src.B; brule_k = beams; }   // what txo_last_beam_rule_state may read
         if (src.ragged()) ses.open = false;                       // nothing ragged outlives the call (generate_common)
         return rc;
     }
@@ -2344,18 +2357,22 @@ struct Engine : EngineBase {
         const int n = std::max(rows, Tmax);
         hipLaunchKernelGGL(beam_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st, cur_tok, bscore, bfin, done_flag, rows,
                            beams, Tmax, cfg.bos);
+        const bool ruled = rules_on;                                  // (beam_search has refused unless txo_set_rules_beam is on) every slot starts at (0, 0)
+        if (ruled) HIP_TRY(hipMemsetAsync(brule_state, 0, sizeof(int2) * (size_t)rows, s));
         for (int i = 1; i < lanes.n; ++i)                             // the other ranges' step state and flags (no rows: they were reset above)
             hipLaunchKernelGGL(beam_reset_kernel, dim3((Tmax + 255) / 256), dim3(256), 0, s, st + i, cur_tok, bscore, bfin,
                                done_flag + (size_t)i * Tmax, 0, beams, Tmax, cfg.bos);
         if (int r = lanes.fork(s)) return r;
         // same non-draining eos look as generate(): once every beam is finished further steps only repeat eos at no cost
-        // (beam_select_kernel), so the few steps enqueued ahead of the look change neither scores nor slots.
+        // (beam_select_kernel), so the few steps enqueued ahead of the look change neither scores nor slots.  Nor do they change a
+        // constrained search's states -- a finished beam's state is frozen (beam_rules.h) --, so those need no history behind every
+        // position the way a constrained generate's do (rule_hist).
         DonePoll poll{lanes, done_flag, Tmax, max_len};
         const bool want_logp = sink.out && sink.out->logp;
         int cur = 0;
         auto beam_loop = [&]() -> int {
         for (int t = 0; t < max_len; ++t) {
-            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1], want_logp};
+            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1], want_logp, ruled};
             for (int i = 0; i < lanes.n; ++i)
                 if (int r2 = enqueue_step(lanes[i].stream, i, nullptr, 0, nullptr, nullptr, eos, &bm, t)) return r2;
             cur ^= 1;
@@ -2374,7 +2391,8 @@ struct Engine : EngineBase {
             const txo_beam_out& o = *sink.out;
             BeamFinishArgs fa{bparent, btok, want_logp ? blogp : nullptr, Bmax, bscore, steps, beams, eos, o.length_alpha,
                               o.tokens, o.logp, o.scores, o.lengths, max_len};
-            hipLaunchKernelGGL(beam_finish_kernel, dim3(B), dim3(64), 0, s, fa);
+            if (ruled) hipLaunchKernelGGL(beam_finish_rules_kernel, dim3(B), dim3(64), 0, s, fa, brule_state);   // ... and the states into that order
+            else hipLaunchKernelGGL(beam_finish_kernel, dim3(B), dim3(64), 0, s, fa);
         } else {
             // backtrack every beam into tok_buf rows, then hand out the best beam (slot 0: selection order is by score)
             hipLaunchKernelGGL(beam_backtrack_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, bparent, btok, Bmax, steps, rows,
@@ -2395,7 +2413,7 @@ struct Engine : EngineBase {
     // txo_set_token_rules behind its checks: the table to the device (nothing of the engine is in flight between two calls: every generate drains
     // its stream).  table null: off.
     int set_token_rules(const int32_t* table, int S, int depth_max) override {
-        rules_rows = 0;
+        rules_rows = 0; brule_B = brule_k = 0;
         if (!table) { rules_on = false; rules_S = 0; rules_dmax = 0; return 0; }
         HIP_TRY(hipMemcpy(rules_dev, table, sizeof(int32_t) * (size_t)S * V, hipMemcpyHostToDevice));
         rules_on = true; rules_S = S; rules_dmax = depth_max;
@@ -2407,6 +2425,19 @@ struct Engine : EngineBase {
         if (B < 1 || B > rules_rows)
             return fail(TXO_E_INVALID, "txo_last_rule_state: B must be in [1, " + std::to_string(rules_rows) + "], the rows of the last constrained generate");
         hipLaunchKernelGGL(rules_state_out_kernel, dim3((B + 255) / 256), dim3(256), 0, s, out, rule_state, B);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+
+    // txo_last_beam_rule_state: the slots' states in the order of the last beam call's outputs (beam_finish_rules_kernel; txo_generate_beam: slot order)
+    int last_beam_rule_state(int32_t* out, int B, int beams, hipStream_t s) override {
+        if (!rules_on) return fail(TXO_E_STATE, "txo_last_beam_rule_state: no token rules are set");
+        if (brule_B < 1) return fail(TXO_E_STATE, "txo_last_beam_rule_state: no constrained beam search has run since the token rules were set");
+        if (B != brule_B || beams != brule_k)
+            return fail(TXO_E_STATE, "txo_last_beam_rule_state: B and beams must be " + std::to_string(brule_B) + " and " + std::to_string(brule_k) +
+                                     ", the images and beams of the last constrained beam search");
+        const int rows = B * beams;
+        hipLaunchKernelGGL(rules_state_out_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, out, brule_state, rows);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -2794,6 +2825,18 @@ int txo_set_token_rules(txo_engine* e, const int32_t* rules_host, int32_t S, int
 int txo_last_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, void* stream) {
     if (!e || !state_out_dev) return fail(TXO_E_INVALID, "null argument");
     return e->impl->last_rule_state(state_out_dev, B, (hipStream_t)stream);
+}
+
+int txo_set_rules_beam(txo_engine* e, int32_t on) {
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (on != 0 && on != 1) return fail(TXO_E_INVALID, "txo_set_rules_beam: on must be 0 or 1");
+    e->impl->rules_beam = on != 0;
+    return 0;
+}
+
+int txo_last_beam_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, int32_t beams, void* stream) {
+    if (!e || !state_out_dev) return fail(TXO_E_INVALID, "null argument");
+    return e->impl->last_beam_rule_state(state_out_dev, B, beams, (hipStream_t)stream);
 }
 
 int txo_set_ragged_hybrid(txo_engine* e, int32_t on) {

@@ -101,6 +101,8 @@ class HipEngine:
         self.token_rules = None                      # (a new handle has no token rules: a set installed by hand goes with the old one)
         if getattr(self, "_ragged_hybrid", False):   # (a reload of the weights makes a new handle: the switch follows the engine object)
             _lib.check(self.lib.txo_set_ragged_hybrid(h, 1))
+        if getattr(self, "_rules_beam", False):
+            _lib.check(self.lib.txo_set_rules_beam(h, 1))
         self._env_seen = self._txo_env()             # what the engine saw when it read its knobs
 
     @staticmethod
@@ -315,7 +317,8 @@ class HipEngine:
 
     def set_token_rules(self, rules) -> None:
         """txo_set_token_rules: a texocr_amd.rules.TokenRules (checked on the host first: the same refusals, before the engine is touched), or
-        None = off.  While set, every generate from BOS or a prefix picks under the rules, on the launch path; beam search raises."""
+        None = off.  While set, every generate from BOS or a prefix picks under the rules, on the launch path; beam search raises unless
+        rules_beam is on."""
         self._ensure()
         if rules is None:
             torch.ops.texocr.set_token_rules(None, self.id, 0)
@@ -371,6 +374,24 @@ class HipEngine:
             raise ValueError("ragged_hybrid must be False or True")
         _lib.check(self.lib.txo_set_ragged_hybrid(self.handle, 1 if on else 0))
         self._ragged_hybrid = bool(on)
+
+    @property
+    def rules_beam(self) -> bool:
+        """txo_set_rules_beam: beam search under token rules.  False (the default): every beam call raises ValueError while token rules are
+        set, as before the search had a constrained form.  True: it runs with the rules inside the beam selection (csrc/beam_rules.h).
+        No effect on a beam search without rules."""
+        return getattr(self, "_rules_beam", False)
+
+    @rules_beam.setter
+    def rules_beam(self, on) -> None:
+        if on not in (False, True, 0, 1):
+            raise ValueError("rules_beam must be False or True")
+        torch.ops.texocr.set_rules_beam(self.id, bool(on))
+        self._rules_beam = bool(on)
+
+    def last_beam_rule_state(self, tokens: torch.Tensor) -> torch.Tensor:
+        """(B, beams, 2) int32: the (state, depth) of every beam of the last constrained beam search, beside its tokens (B, beams, n)"""
+        return torch.ops.texocr.last_beam_rule_state(tokens, self.id)
 
     @contextlib.contextmanager
     def ragged_forward(self):
@@ -559,15 +580,29 @@ def score_summary(logp: torch.Tensor, top1: torch.Tensor, top1_logp: torch.Tenso
     return Score(logp, top1, top1_logp, valid, nll64.float(), (nll64.sum() / n).float(), (hit.sum().double() / n).float())
 
 
-class Beams(NamedTuple):
-    """What OCRModel.beam_search returns, the beams of every image best first: tokens (B, beams, n) int64; scores (B, beams) the sum of a
-    beam's log-probabilities; lengths (B, beams) int32, the index of the beam's first eos + 1, or n without one; logp (B, beams, n)
-    float32 or None, the log-probability of every token at the beam's own prefix -- the floats the search summed, left to right, into
-    scores.  Behind a beam's length tokens hold eos and logp holds 0."""
+class _BeamFields(NamedTuple):
     tokens: torch.Tensor
     scores: torch.Tensor
     lengths: torch.Tensor
     logp: Optional[torch.Tensor]
+
+
+class Beams(_BeamFields):
+    """What OCRModel.beam_search returns, the beams of every image best first: tokens (B, beams, n) int64; scores (B, beams) the sum of a
+    beam's log-probabilities; lengths (B, beams) int32, the index of the beam's first eos + 1, or n without one; logp (B, beams, n)
+    float32 or None, the log-probability of every token at the beam's own prefix -- the floats the search summed, left to right, into
+    scores.  Behind a beam's length tokens hold eos and logp holds 0.
+    rule_state, the last field: (B, beams, 2) int32 under rules= (with OCRModel.rules_beam on), every beam's (state, depth) behind its last
+    token that counts -- its first eos, or n --, and None without rules.  It is read by name: as a tuple a Beams stays the four fields
+    above, so code that unpacks or iterates one keeps working.
+    Under rules= an image may have fewer than `beams` allowed sequences: the surplus beams are DEAD -- score -inf -- and outside every
+    guarantee: their tokens, lengths and rule_state are unspecified.  Look at scores before anything else of a beam."""
+    rule_state: Optional[torch.Tensor] = None
+
+    def __new__(cls, tokens, scores, lengths, logp, rule_state=None):
+        self = super().__new__(cls, tokens, scores, lengths, logp)
+        self.rule_state = rule_state
+        return self
 
 
 def check_beam_args(beams, max_len, length_alpha, n_images: int, table: int, max_batch: int) -> None:
@@ -946,6 +981,15 @@ class OCRModel(nn.Module):
     def ragged_hybrid(self, on) -> None:
         self._engine.ragged_hybrid = on
 
+    @property
+    def rules_beam(self) -> bool:
+        """Build extension: accept rules= in beam_search and generate(beam=k) (HipEngine.rules_beam); off by default."""
+        return self._engine.rules_beam
+
+    @rules_beam.setter
+    def rules_beam(self, on) -> None:
+        self._engine.rules_beam = on
+
     # ---- weights: the reference's state_dict layout, aliases included ----
     def _export_weights(self) -> Dict[str, torch.Tensor]:
         return dict(self.state_dict())
@@ -990,7 +1034,8 @@ class OCRModel(nn.Module):
         rules.ban / rules.brace_rules) -- installed for this call; the result gains rule_state (B, 2) int32 = every row's (state, depth)
         behind its last returned token as its LAST element.  The decode then runs on the launch path (not the persistent launch); logp and
         logits stay those of the raw logits.  No closure guarantee: a row that runs out of positions may end at depth > 0.  With beam=:
-        the engine's refusal (ValueError).
+        the engine's refusal (ValueError) unless rules_beam is on; then the rules bind inside the beam selection (see beam_search) and
+        rule_state (B, beam, 2), the state of every beam in the order of return_beams' tokens, is appended to the result.
         return_logp=True (build extension): (tokens, logp), both (B, n_steps) -- logp[b, t] = log_softmax(logits[b, t])[tokens[b, t]],
         what score(src, cat([bos], tokens)).logp reports, taken from the token selection itself: temperature 1 and the whole vocabulary
         also with decode='sample' (not the sampler's top-k / temperature distribution); stop='row': 0 behind a row's first eos, so
@@ -1009,8 +1054,12 @@ class OCRModel(nn.Module):
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
             if max_len > self.decoder.max_len:
                 raise ValueError(f"beam search needs max_len <= decoder.max_len ({self.decoder.max_len})")
-            with self._engine.modes(rules=rules):                  # (with rules the engine refuses: beam search has no constrained form)
-                return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
+            with self._engine.modes(rules=rules):                  # (with rules the engine refuses unless rules_beam is on)
+                if rules is None:
+                    return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
+                toks, scores = self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=True)
+                state = self._engine.last_beam_rule_state(toks)
+            return (toks, scores, state) if return_beams else (toks[:, 0], state)
         if decode == "greedy" and self.bos_token == self._engine.dims.bos:
             # (max_len > decoder.max_len: txo_generate slides the window like the reference, decoder.py:99-100)
             # (stop='row' with return_logits: the engine does not compact -- a finished row's logits would be missing -- and only pads)
@@ -1082,7 +1131,11 @@ class OCRModel(nn.Module):
         through ONE ragged encode and ONE decode, and the beams of image b are what beam_search(src[b][None]) returns, over the batch's n.
         The search is generate(beam=k)'s (same tokens and scores); eos is the model's eos_token.  length_alpha > 0 orders an image's beams
         by score / length ** length_alpha instead of by score -- the final order only, the set of beams does not depend on it.
-        Needs beams in [1, 8], max_len <= decoder.max_len and images * beams <= the engine's max_batch (ValueError otherwise)."""
+        Needs beams in [1, 8], max_len <= decoder.max_len and images * beams <= the engine's max_batch (ValueError otherwise).
+        rules= (build extension): a texocr_amd.rules.TokenRules installed for this call.  With rules_beam off (the default) the engine
+        refuses (ValueError).  On: a candidate the rules disallow in its parent's state counts as -inf in the selection, so no disallowed
+        hypothesis ever holds a slot; scores and logp stay sums of the RAW model's log-probabilities (nothing is renormalised), and
+        Beams.rule_state holds every beam's state.  No closure guarantee: a beam that runs out of positions may end at depth > 0."""
         if isinstance(src, torch.Tensor):
             if src.ndim != 4:
                 raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
@@ -1092,8 +1145,9 @@ class OCRModel(nn.Module):
         else:
             raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
         check_beam_args(beams, max_len, length_alpha, n_images, self.decoder.max_len, self._engine.max_batch)
-        with self._engine.modes(rules=rules):                      # rules=: the engine refuses (ValueError) -- beam search has no constrained form
-            return Beams(*self._engine.beam_search(src, beams, max_len, self.eos_token, return_logp=return_logp, length_alpha=length_alpha))
+        with self._engine.modes(rules=rules):                      # rules=: the engine refuses (ValueError) unless rules_beam is on
+            out = self._engine.beam_search(src, beams, max_len, self.eos_token, return_logp=return_logp, length_alpha=length_alpha)
+            return Beams(*out, self._engine.last_beam_rule_state(out[0]) if rules is not None else None)
 
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
@@ -1178,23 +1232,27 @@ class OCRModel(nn.Module):
                                   "implements the generate() inference path only")
 
 
-def _assemble(dims: Dims, dtype: str, max_batch: int, max_tokens: int, device: torch.device, ragged_hybrid: bool = False) -> OCRModel:
+def _assemble(dims: Dims, dtype: str, max_batch: int, max_tokens: int, device: torch.device, ragged_hybrid: bool = False,
+              rules_beam: bool = False) -> OCRModel:
     eng = HipEngine(dims, dtype=dtype, max_batch=max_batch, max_tokens=max_tokens)
     if ragged_hybrid:
         eng.ragged_hybrid = True
+    if rules_beam:
+        eng.rules_beam = True
     shared: Dict[str, nn.Parameter] = {}
     return OCRModel(VisionEncoder(eng, shared), AutoRegressiveDecoder(eng, shared), dims.bos, dims.eos, dims.pad, device)
 
 
-def create_model(config: dict, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0, ragged_hybrid: bool = False) -> OCRModel:
+def create_model(config: dict, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0, ragged_hybrid: bool = False,
+                 rules_beam: bool = False) -> OCRModel:
     """create_model(config) (ocr_model.py:113-130).  As in the reference the model comes back with default-initialised
     parameters; load_state_dict replaces them.  ragged_hybrid=True (build extension): the model's ragged calls work on the hybrid
-    front end (OCRModel.ragged_hybrid)."""
+    front end (OCRModel.ragged_hybrid).  rules_beam=True (build extension): beam search accepts rules= (OCRModel.rules_beam)."""
     dims = Dims.from_config(config)
     device = torch.device(config.get("device", "cuda"))
     if device.type != "cuda":
         device = torch.device("cuda")
-    return _assemble(dims, dtype, max_batch, max_tokens, device, ragged_hybrid)
+    return _assemble(dims, dtype, max_batch, max_tokens, device, ragged_hybrid, rules_beam)
 
 
 def model_from_dims(dims: Dims, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0) -> OCRModel:

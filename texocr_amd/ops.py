@@ -20,6 +20,8 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::generate_logp / generate_from_enc_logp / generate_ragged_logp
                             (build extension) generate / generate_from_enc / generate_ragged that also return the log-probability
                             of every produced token, taken from the token selection itself (no second pass, no (B, T, V) tensor)
+  texocr::set_rules_beam / last_beam_rule_state
+                            (build extension, opt-in) beam search under token rules (texocr::set_token_rules) and the beams' rule states
   texocr::encode_ragged / decode_begin_ragged / generate_ragged / score_ragged
                             (build extension) the same callables over a RAGGED batch: B images of different sizes in one
                             container, every image computed as if it had been passed on its own (``pack_ragged`` builds the container);
@@ -778,6 +780,37 @@ def _(table, engine, depth_max):
 @last_rule_state.register_fake
 def _(tokens, engine):
     return tokens.new_empty((tokens.shape[0], 2), dtype=torch.int32)
+
+
+# ---- constrained beam search (txo_set_rules_beam): the opt-in that lets the beam entries run under token rules -----------------------------
+@custom_op("texocr::set_rules_beam", mutates_args=())
+def set_rules_beam(engine: int, on: bool) -> None:
+    """txo_set_rules_beam: on=True, a beam search under token rules runs the constrained selection; False (the default), it is refused"""
+    e = _eng(engine)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_set_rules_beam(e.handle, 1 if on else 0))
+
+
+@custom_op("texocr::last_beam_rule_state", mutates_args=())
+def last_beam_rule_state(tokens: torch.Tensor, engine: int) -> torch.Tensor:
+    """txo_last_beam_rule_state: the (state, depth) of every beam of the last constrained beam search -> (B, beams, 2) int32 beside its
+    `tokens` (B, beams, n), in their order"""
+    e = _eng(engine)
+    if not tokens.is_cuda or tokens.ndim != 3 or tokens.device.index != e.device:
+        raise ValueError("last_beam_rule_state: tokens must be the (B, beams, n) GPU tensor the constrained beam search returned")
+    out = torch.empty((tokens.shape[0], tokens.shape[1], 2), device=tokens.device, dtype=torch.int32)
+    _call(e, "txo_last_beam_rule_state", out.data_ptr(), int(tokens.shape[0]), int(tokens.shape[1]))
+    return out
+
+
+@set_rules_beam.register_fake
+def _(engine, on):
+    return None
+
+
+@last_beam_rule_state.register_fake
+def _(tokens, engine):
+    return tokens.new_empty((tokens.shape[0], tokens.shape[1], 2), dtype=torch.int32)
 
 
 # ---- device-side image ingest (txo_ingest_u8): raw uint8 pixels -> the container of a ragged batch, one copy and one launch ----------

@@ -64,10 +64,13 @@ def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.T
 
 
 class TeXOCRWrapper:
-    def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False, balanced: bool = False):
+    def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False, balanced: bool = False,
+                 rules_beam: bool = False):
         """ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)
         balanced=True (build extension): every __call__ / batch decodes under the brace rule of this tokenizer unless the call says otherwise
-        (see batch)"""
+        (see batch)
+        rules_beam=True (build extension): decode='beam' accepts balanced=True -- the brace rule inside the beam selection
+        (OCRModel.rules_beam); off, the default, the two together are a ValueError"""
         self.balanced = bool(balanced)
         self._brace_rules = None
         self.tokenizer = RegExTokenizer()
@@ -82,7 +85,7 @@ class TeXOCRWrapper:
             key = "decoder.net.pos_embedding.embedding.weight"
             if key in sd:                                                            # ocr_model.py:84-88: the checkpoint decides
                 config["max_length"] = int(sd[key].shape[0])
-        self.model: OCRModel = create_model(config, dtype=dtype, max_batch=max_batch, ragged_hybrid=ragged_hybrid)
+        self.model: OCRModel = create_model(config, dtype=dtype, max_batch=max_batch, ragged_hybrid=ragged_hybrid, rules_beam=rules_beam)
         if sd is not None:
             self.model.load_state_dict(sd)
         self.dims: Dims = self.model._engine.dims
@@ -91,7 +94,7 @@ class TeXOCRWrapper:
         """the rules= of a call: rules.brace_rules of the wrapper's tokenizer (built once) where balanced, else None"""
         if not (self.balanced if balanced is None else balanced):
             return None
-        if decode == "beam":
+        if decode == "beam" and not self.model.rules_beam:
             raise ValueError("balanced=True is not available with decode='beam' (beam search has no constrained form)")
         if self._brace_rules is None:
             from .rules import brace_rules
@@ -155,10 +158,10 @@ class TeXOCRWrapper:
             imgs = [self._fitted(im, i) for i, im in enumerate(imgs)]
         return [self._tensor(im).cuda() for im in imgs]
 
-    def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool):
+    def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool, rules=None):
         """decode='beam': one OCRModel.beam_search over the images xs (a (B, C, H, W) tensor or a list of (C, H_b, W_b)) -> per image
         (the best beam's tokens up to and including its eos, their log-probabilities or None)"""
-        res = self.model.beam_search(xs, beams, max_len, return_logp=return_logp, length_alpha=length_alpha)
+        res = self.model.beam_search(xs, beams, max_len, return_logp=return_logp, length_alpha=length_alpha, **({} if rules is None else {"rules": rules}))
         lengths = res.lengths[:, 0].tolist()
         rows = [res.tokens[b, 0, :n].tolist() for b, n in enumerate(lengths)]
         logp = [res.logp[b, 0, :n].tolist() for b, n in enumerate(lengths)] if return_logp else [None] * len(rows)
@@ -215,7 +218,8 @@ class TeXOCRWrapper:
         trimmed size in the message.  return_align maps are on the grid of the trimmed (then fitted) image.
         balanced=True (build extension; default: the wrapper's own setting): the decode picks under rules.brace_rules of the tokenizer
         (OCRModel.generate_ragged(rules=)): no token closes a group that is not open, eos comes only at depth 0, <BOS> / <PAD> never.  A
-        row that runs out of positions may still end open; logp stays the raw model's.  Not with decode='beam'."""
+        row that runs out of positions may still end open; logp stays the raw model's.  With decode='beam' only on a wrapper built with
+        rules_beam=True: the rule then binds inside the beam selection, and a best beam that finished is balanced by construction."""
         rules = self._rules(balanced, decode)
         rule = self._trim_rule(trim, trim_level, trim_margin)
         eng = self.model._engine
@@ -231,7 +235,7 @@ class TeXOCRWrapper:
         for c0 in range(0, len(imgs), step):
             chunk = xs[c0:c0 + step] if xs is not None else self._images(imgs[c0:c0 + step], ingest, fit, rule)
             if decode == "beam":
-                full, logp = self._best_beams(chunk, beams, max_len, length_alpha, return_logp)
+                full, logp = self._best_beams(chunk, beams, max_len, length_alpha, return_logp, rules)
             else:
                 chunk_seed = None if seed is None else int(seed) + c0 // step
                 kw = {} if pre is None else dict(prefix=pre[c0:c0 + step].cuda(), prefix_len=plen[c0:c0 + step])
@@ -280,7 +284,7 @@ class TeXOCRWrapper:
             gen_kw = dict(prefix=pre.cuda())
         if decode == "beam":
             beam_chunk(self.model._engine.max_batch, beams)
-            rows, lps = self._best_beams(x, beams, min(int(max_len), self.dims.max_len), length_alpha, return_logp)
+            rows, lps = self._best_beams(x, beams, min(int(max_len), self.dims.max_len), length_alpha, return_logp, rules)
             toks = torch.tensor(rows, dtype=torch.int64, device=x.device)
             logp = torch.tensor(lps, dtype=torch.float32) if return_logp else None   # (every float32 is exact in the list's doubles)
         else:
