@@ -493,6 +493,33 @@ int txo_last_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, void* 
 int txo_set_rules_beam(txo_engine* e, int32_t on);
 int txo_last_beam_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, int32_t beams, void* stream);
 
+/* Closing decode, a BUILD EXTENSION and opt-in: txo_set_rules_close(e, 1) (default 0; TXO_E_INVALID unless on is 0 or 1).  Off, every call
+ * does what it did.  On, and with token rules set, a row may only pick a token from which its automaton can still reach eos (cfg.eos) in the
+ * positions the call has left, so every constrained row ends at an eos its rules allow -- with ONLY_AT_ZERO on eos: at depth 0, inside max_len.
+ * The rule.  dist[s][d], s < S, 0 <= d <= depth_max, is the least number of picks, the eos included, that takes a row from (s, d) to a
+ * committed eos when every pick is allowed by the rule set and every move is its own (next, clamp(d + delta, 0, depth_max));
+ * TXO_CLOSE_INF: no path.  It is computed on the host whenever rules and switch are both set, in either order.  At a pick, a row in (s, d)
+ * that has not yet committed an eos has R picks left in what the call returns, this one included (max_len minus the tokens it has picked;
+ * behind a prefix each row counts for itself), and D = dist[s][d].  If D is finite, token v is allowed iff txo_set_token_rules' rule allows it
+ * AND (v == eos OR dist[next][depth after v] <= max(R, D) - 1).  The allowed set is never empty.  If D <= R at a row's first pick the row
+ * commits an allowed eos within its R picks.  D > R, which only a forced prefix can cause, is the one exception for a row: it takes
+ * distance-reducing tokens only and ends open, and txo_last_rule_state shows it.  A row where D is TXO_CLOSE_INF (only a prefix leads there)
+ * and a row that has committed its eos (the rest of a TXO_STOP_GLOBAL decode) run the plain rule.  While R - 1 >= the largest finite entry
+ * and no entry is TXO_CLOSE_INF, the picks are those of the plain constrained decode, bit for bit.  Everything else keeps its meaning: the
+ * masked value, raw logp_out / logits_out, forced tokens (never masked, they advance the state), tie order, the sampler's draws.
+ * Beam search (with txo_set_rules_beam): for a live unfinished parent the candidate (j, v) is finite iff the rule above holds with the
+ * parent's state and R = max_len - position.  Finished parents and dead slots are untouched.  So every LIVE beam of a closing search is
+ * finished; dead beams (score -inf) remain the other exception.
+ * Refused with TXO_E_INVALID, behind every other refusal of the entry: by txo_set_rules_close / txo_set_token_rules (nothing changes) when
+ * switch and rules would both be set and eos is unreachable from the start state (cfg.eos outside the vocabulary, or dist[0][0] is
+ * TXO_CLOSE_INF); by txo_generate* / the beam entries when the call's eos is not cfg.eos, and, from BOS, when dist[0][0] exceeds max_len (the
+ * text gives both numbers).
+ * txo_rules_close_dist: the table the engine computed, int32 [S][D] on the HOST, D = depth_max + 1.  TXO_E_STATE unless rules and switch are
+ * both set; TXO_E_INVALID unless S and D are the installed rules'. */
+#define TXO_CLOSE_INF 0x7fffffff
+int txo_set_rules_close(txo_engine* e, int32_t on);
+int txo_rules_close_dist(txo_engine* e, int32_t* out_host, int32_t S, int32_t D);
+
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
  * enabled (txo_profile_enable(e, 1) also clears the previous samples); *count = number of launches averaged.  kind: 0 = cross-attention decode kernel,

@@ -80,6 +80,8 @@ SYMBOLS = {
     "txo_last_rule_state": (C.c_int, [_P, C.c_void_p, _I, _P]),
     "txo_set_rules_beam": (C.c_int, [_P, _I]),
     "txo_last_beam_rule_state": (C.c_int, [_P, C.c_void_p, _I, _I, _P]),
+    "txo_set_rules_close": (C.c_int, [_P, _I]),
+    "txo_rules_close_dist": (C.c_int, [_P, C.c_void_p, _I, _I]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),
     "txo_set_ragged_hybrid": (C.c_int, [_P, _I]),
     "txo_profile_enable": (C.c_int, [_P, _I]),

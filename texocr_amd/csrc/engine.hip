@@ -50,6 +50,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "ingest_trim.h"   // (the ink extents in front of both; reads ingest.h's descriptors)
 #include "step_rules.h"    // (the constrained token selection: step.h / step_prefix.h with a per-row automaton; last again)
 #include "beam_rules.h"    // (the constrained beam selection: step.h's beam kernels with that automaton; last again)
+#include "rules_close.h"   // (host only: the closing decode's distance table)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -107,6 +108,12 @@ struct EngineBase {
     bool rules_beam = false;
     int brule_B = 0, brule_k = 0;               // images / beams of the last constrained beam search (txo_last_beam_rule_state), 0: none since the rules were set
     virtual int last_beam_rule_state(int32_t* out, int B, int beams, hipStream_t s) = 0;
+    // txo_set_rules_close (rules_close.h; the closing kernels of step_rules.h / beam_rules.h): while on, a constrained decode or beam search
+    // picks under the budget that ends every row at an allowed eos.  close_dist [S][depth_max + 1]: the table while rules and switch are both set
+    bool rules_close = false;
+    std::vector<int32_t> close_dist; int close_dist_max = 0;
+    bool closing() const { return rules_on && rules_close; }
+    virtual int set_rules_close(bool on) = 0;
     // txo_ingest_u8 / _fit / _view behind their checks (ingest_req.h: ingest_plan): descriptors up in one staged copy, then one launch -- or,
     // where an image is downscaled, the horizontal pass of those that need one and the fused vertical pass + ingest
     virtual int ingest(const IngestPlan& p, const IngestReq& q, hipStream_t s) = 0;
@@ -239,6 +246,9 @@ struct Engine : EngineBase {
     // constrained decode (step_rules.h): the packed table [RULES_MAX_STATES][V], every row's (state, depth) [Bmax] and the state behind every
     // position [Bmax][Tmax] -- engine-owned, so that a captured step can carry them
     int* rules_dev = nullptr; int2* rule_state = nullptr; int2* rule_hist = nullptr;
+    // closing decode (txo_set_rules_close): the host copy of the installed table (the switch may come after the rules), the distance table on
+    // the device, and every row's (end position, has committed eos) [Bmax]
+    std::vector<int32_t> rules_host; CloseTable* close_dev = nullptr; int2* rule_close = nullptr;
     Session ses;                           // the open decode session (session.h)
     // persistent decode launch (persist.h): control block (device + pinned host copy), per-stage stamps of one position
     PersistCtl* pctl = nullptr; PersistCtl* pctl_host = nullptr; unsigned long long* pstamps = nullptr;
@@ -250,7 +260,8 @@ struct Engine : EngineBase {
     float* bscore = nullptr; int* bfin = nullptr; short* bpath[2] = {nullptr, nullptr}; short* bparent = nullptr; int* btok = nullptr;
     float* blogp = nullptr;                // [Tmax][Bmax] beside btok: the selected candidates' increments (txo_beam_search with logp)
     int2* brule_state = nullptr;           // [Bmax] constrained beam search (beam_rules.h): the (state, depth) of every (image, beam) slot
-    struct BeamCtx { int k; const short* path_cur; short* path_nxt; bool logp = false; bool ruled = false; };   // logp: the step also records blogp; ruled: beam_rules.h's selection
+    // logp: the step also records blogp; ruled: beam_rules.h's selection; closing: its closing form over `positions` positions
+    struct BeamCtx { int k; const short* path_cur; short* path_nxt; bool logp = false; bool ruled = false; bool closing = false; int positions = 0; };
     // ----- profiling -----
     bool prof = false;                // full: per-launch cross-attention events + markers around every encode and step
     bool prof_cross = false;          // light: only the cross-attention dispatches carry events (no extra packets)
@@ -729,6 +740,8 @@ struct Engine : EngineBase {
         if (int r = dalloc(&rule_state, (size_t)Bmax)) return r;
         if (int r = dalloc(&rule_hist, (size_t)Bmax * Tmax)) return r;
         if (int r = dalloc(&brule_state, (size_t)Bmax)) return r;
+        if (int r = dalloc(&close_dev, (size_t)1)) return r;
+        if (int r = dalloc(&rule_close, (size_t)Bmax)) return r;
         return 0;
     }
 
@@ -1175,6 +1188,7 @@ struct Engine : EngineBase {
         Decode d{q};
         if (int r = q.prefix ? check_prefix(q, &d.m, &d.M) : check_length(q.max_len, ragged)) return r;
         if (int r = resolve_source(q.src, s, &d.src)) return r;
+        if (int r = close_refusals("generate", q.eos, q.max_len, !q.prefix)) return r;   // (behind every other refusal of the entry)
         if (q.prefix) {   // the lengths to the device, through the pinned staging of the ragged sizes (behind ragged_batch's own copy)
             std::vector<int32_t> len((size_t)q.src.B, q.P);
             if (q.prefix_len) len.assign(q.prefix_len, q.prefix_len + q.src.B);
@@ -1672,17 +1686,22 @@ struct Engine : EngineBase {
         if (ses.ruled) {    // constrained decode: the table, and the range's slices of the states (through row_map like the outputs)
             sa.rules = rules_dev; sa.n_states = rules_S; sa.depth_max = rules_dmax; sa.rule_state = rule_state + r0;
             sa.rule_hist = rule_hist + r0 * Tmax; sa.rule_hist_stride = Tmax;
+            if (ses.closing) { sa.close_tab = close_dev; sa.rule_close = rule_close + r0; }
         }
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
             if (bm->ruled) {   // constrained beam search: the table, and the range's slice of the slots' states (range-local, like every pointer of ba)
                 const BeamRuleArgs ra{rules_dev, rules_S, rules_dmax, brule_state + r0};
-                if (bm->logp) hipLaunchKernelGGL(beam_select_rules_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
+                const BeamCloseArgs ca{close_dev, bm->positions};
+                if (bm->closing && bm->logp) hipLaunchKernelGGL(beam_select_close_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra, ca);
+                else if (bm->closing) hipLaunchKernelGGL(beam_select_close_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra, ca);
+                else if (bm->logp) hipLaunchKernelGGL(beam_select_rules_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
                 else hipLaunchKernelGGL(beam_select_rules_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
             } else if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
             else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba);
-        } else if (ses.ruled) launch_rules_step(s, nb, sa, sample_mode != 0);
+        } else if (ses.closing) launch_rules_close_step(s, nb, sa, sample_mode != 0);
+        else if (ses.ruled) launch_rules_step(s, nb, sa, sample_mode != 0);
         else if (ses.forced) launch_prefix_step(s, nb, sa, sample_mode != 0);
         else if (sample_mode) launch_sample_step(s, nb, sa);
         else hipLaunchKernelGGL(argmax_step_kernel, dim3(nb), dim3(64), 0, s, sa);
@@ -1695,7 +1714,7 @@ struct Engine : EngineBase {
     // logp: the step also writes its log-probabilities, into the engine-owned logp_buf (part of the key: it is another StepArgs)
     int lane_graph(int li, int eos, bool logp) {
         const auto& ln = lanes[li];
-        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode, logp, rules_S * 256 + rules_dmax);
+        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode, logp, rules_S * 256 + rules_dmax + (ses.closing ? 4096 : 0));   // (S * 256 + depth cap < 4096)
         if (lanes.cached(li, key)) return 0;
         hipStream_t cs = lanes.cap_stream;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -2050,6 +2069,7 @@ struct Engine : EngineBase {
         ses.row_stop = false;                                     // the decode is over (a txo_decode_step behind it steps every row)
         ses.forced = false;                                       // ... and picks every row's token itself: the prefix table belongs to the finished call
         ses.ruled = false;                                        // ... without rules: they bind the generate family only
+        ses.closing = false;
         rules_rows = (rules_on && rc == 0) ? d.src.B : 0;         // what txo_last_rule_state may read
         if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
@@ -2102,6 +2122,7 @@ struct Engine : EngineBase {
         if (int r = begin_session(rows, B, d.src.N, eos, s, false, KeyCounts{d.src.ragged() ? rag_ntok : nullptr})) return r;
         ses.forced = d.prompted();
         ses.ruled = rules_on;
+        ses.closing = closing();
         if (d.prompted()) {   // the prefix into the engine's table (lengths are in flen: generate), no forced token scored yet
             hipLaunchKernelGGL(prefix_table_kernel, dim3((B * Tmax + 255) / 256), dim3(256), 0, s, ftab, Tmax, q.prefix, q.P, flen, B, V);
             HIP_TRY(hipMemsetAsync(fplogp, 0, sizeof(float) * (size_t)B * Tmax, s));
@@ -2176,6 +2197,9 @@ struct Engine : EngineBase {
         if (ses.ruled)   // every row's automaton at its start, run over the prefix columns the multi-position pass consumes
             hipLaunchKernelGGL(rules_start_kernel, dim3((B + 255) / 256), dim3(256), 0, s, rule_state, B, rules_dev, V, rules_S, rules_dmax, ftab, Tmax,
                                d.prompted() ? d.m : 0);
+        if (ses.closing)   // ... and its end position and "has committed eos" (a captured step reads both from here: it bakes no position)
+            hipLaunchKernelGGL(rules_close_start_kernel, dim3((B + 255) / 256), dim3(256), 0, s, rule_close, B, d.prompted() ? flen : nullptr, max_len, eos,
+                               ftab, Tmax, d.prompted() ? d.m : 0);
         // a prompted decode: positions 0 .. m-2 of every row in ONE multi-position pass, no logits (it fills the K/V history the loop reads)
         if (d.prompted() && d.m > 1) { if (int r = prefill(ftab, Tmax, d.m - 1, nullptr, nullptr, s)) return r; }
         const bool use_graph = !eager && !prof && !prof_cross;     // event-carrying launches cannot be captured
@@ -2287,7 +2311,8 @@ struct Engine : EngineBase {
                         0, nullptr, d.q.logp};
             if (ses.ruled) {   // the loop's states carry over (no history beyond the table: the host looks at every token here, nothing runs ahead)
                 sa.rules = rules_dev; sa.n_states = rules_S; sa.depth_max = rules_dmax; sa.rule_state = rule_state;
-                launch_rules_step(s, B, sa, sample_mode != 0);
+                if (ses.closing) { sa.close_tab = close_dev; sa.rule_close = rule_close; launch_rules_close_step(s, B, sa, sample_mode != 0); }
+                else launch_rules_step(s, B, sa, sample_mode != 0);
             } else
             if (sample_mode) launch_sample_step(s, B, sa);
             else hipLaunchKernelGGL(argmax_step_kernel, dim3(B), dim3(64), 0, s, sa);
@@ -2329,6 +2354,7 @@ struct Engine : EngineBase {
         if (!three) last_ragged = src.ragged();
         if (rules_on && !rules_beam)   // (last: every other refusal of the three entries keeps its place; txo_set_rules_beam lifts it)
             return fail(TXO_E_INVALID, "beam search: not available while token rules are set (txo_set_token_rules with rules_host == NULL switches them off)");
+        if (int r = close_refusals("beam search", eos, max_len, true)) return r;   // (behind every other refusal, like the one above)
         brule_B = brule_k = 0;
         const int rc = beam_impl(src, beams, max_len, eos, sink, n_steps, s);
         if (rules_on && rc == 0) { brule_B = src.B; brule_k = beams; }   // what txo_last_beam_rule_state may read
@@ -2372,7 +2398,7 @@ struct Engine : EngineBase {
         int cur = 0;
         auto beam_loop = [&]() -> int {
         for (int t = 0; t < max_len; ++t) {
-            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1], want_logp, ruled};
+            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1], want_logp, ruled, ruled && rules_close, max_len};
             for (int i = 0; i < lanes.n; ++i)
                 if (int r2 = enqueue_step(lanes[i].stream, i, nullptr, 0, nullptr, nullptr, eos, &bm, t)) return r2;
             cur ^= 1;
@@ -2413,10 +2439,47 @@ struct Engine : EngineBase {
     // txo_set_token_rules behind its checks: the table to the device (nothing of the engine is in flight between two calls: every generate drains
     // its stream).  table null: off.
     int set_token_rules(const int32_t* table, int S, int depth_max) override {
+        if (table && rules_close) { if (int r = close_install(table, S, depth_max)) return r; }   // (a refused table leaves the installed one in place)
         rules_rows = 0; brule_B = brule_k = 0;
-        if (!table) { rules_on = false; rules_S = 0; rules_dmax = 0; return 0; }
+        if (!table) { rules_on = false; rules_S = 0; rules_dmax = 0; rules_host.clear(); close_dist.clear(); close_dist_max = 0; return 0; }
         HIP_TRY(hipMemcpy(rules_dev, table, sizeof(int32_t) * (size_t)S * V, hipMemcpyHostToDevice));
+        rules_host.assign(table, table + (size_t)S * V);
         rules_on = true; rules_S = S; rules_dmax = depth_max;
+        return 0;
+    }
+    // txo_set_rules_close behind its check.  The table is (re)computed whenever rules and switch are both set, in either order
+    int set_rules_close(bool on) override {
+        if (on && rules_on) { if (int r = close_install(rules_host.data(), rules_S, rules_dmax)) return r; }   // (refused: the switch stays as it was)
+        if (!on) { close_dist.clear(); close_dist_max = 0; }
+        rules_close = on;
+        return 0;
+    }
+    // the distance table of a rule set (rules_close.h) to the host copy and, packed to 16 bits, to the device beside rules_dev.  Refused, with
+    // nothing changed: the engine has no eos, or eos cannot be reached from the start state
+    int close_install(const int32_t* table, int S, int depth_max) {
+        std::vector<int32_t> dist; bool any_inf = false;
+        const int dmax = rules_close_dist(table, S, V, depth_max, cfg.eos, dist, &any_inf);
+        if (cfg.eos < 0 || cfg.eos >= V || dist[0] == CLOSE_INF)
+            return fail(TXO_E_INVALID, "closing decode: eos is unreachable from the start state (the engine's eos id is " + std::to_string(cfg.eos) +
+                                       "; the rules must allow a path from state 0, depth 0 to it)");
+        std::vector<CloseTable> tab(1);
+        for (int i = 0; i < CLOSE_NODES; ++i)
+            tab[0].dist[i] = (unsigned short)((size_t)i < dist.size() && dist[(size_t)i] != CLOSE_INF ? dist[(size_t)i] : CLOSE_FAR);
+        tab[0].slack = any_inf ? 0x7fffffff : dmax; tab[0].dist_max = dmax; tab[0].pad[0] = tab[0].pad[1] = 0;
+        HIP_TRY(hipMemcpy(close_dev, tab.data(), sizeof(CloseTable), hipMemcpyHostToDevice));
+        close_dist.swap(dist); close_dist_max = dmax;
+        return 0;
+    }
+    // what a closing call refuses, behind every other refusal of its entry: an eos other than the engine's (the table was computed for that
+    // one), and from BOS a call too short to reach eos at all
+    int close_refusals(const char* what, int eos, int picks, bool from_bos) {
+        if (!closing()) return 0;
+        if (eos != cfg.eos)
+            return fail(TXO_E_INVALID, std::string(what) + ": a closing decode (txo_set_rules_close) needs eos = " + std::to_string(cfg.eos) + ", the engine's eos id; got " +
+                                       std::to_string(eos));
+        if (from_bos && close_dist[0] > picks)
+            return fail(TXO_E_INVALID, std::string(what) + ": a closing decode needs " + std::to_string(close_dist[0]) + " picks to reach eos from the start state, but the call has " +
+                                       std::to_string(picks));
         return 0;
     }
     int last_rule_state(int32_t* out, int B, hipStream_t s) override {
@@ -2837,6 +2900,22 @@ int txo_set_rules_beam(txo_engine* e, int32_t on) {
 int txo_last_beam_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, int32_t beams, void* stream) {
     if (!e || !state_out_dev) return fail(TXO_E_INVALID, "null argument");
     return e->impl->last_beam_rule_state(state_out_dev, B, beams, (hipStream_t)stream);
+}
+
+int txo_set_rules_close(txo_engine* e, int32_t on) {
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (on != 0 && on != 1) return fail(TXO_E_INVALID, "txo_set_rules_close: on must be 0 or 1");
+    return e->impl->set_rules_close(on != 0);
+}
+
+int txo_rules_close_dist(txo_engine* e, int32_t* out_host, int32_t S, int32_t D) {
+    if (!e || !out_host) return fail(TXO_E_INVALID, "null argument");
+    if (!e->impl->closing()) return fail(TXO_E_STATE, "txo_rules_close_dist: no table -- token rules and txo_set_rules_close must both be set");
+    if (S != e->impl->rules_S || D != e->impl->rules_dmax + 1)
+        return fail(TXO_E_INVALID, "txo_rules_close_dist: S and D must be " + std::to_string(e->impl->rules_S) + " and " + std::to_string(e->impl->rules_dmax + 1) +
+                                   ", the states and depth_max + 1 of the installed rules");
+    std::copy(e->impl->close_dist.begin(), e->impl->close_dist.end(), out_host);
+    return 0;
 }
 
 int txo_set_ragged_hybrid(txo_engine* e, int32_t on) {

@@ -15,8 +15,10 @@ struct Session {
     bool row_stop = false;                // this generate compacts the live rows of its row ranges (launch path, stop_mode 1)
     bool forced = false;                  // a prompted decode: the steps force the caller's prefix (step_prefix.h; launch path only)
     bool ruled = false;                   // a constrained decode: the steps pick under the engine's token rules (step_rules.h; launch path only)
+    bool closing = false;                 // ... and under the closing budget (txo_set_rules_close; implies ruled)
     // what a captured step was built for (lanes.h): every field a step's launches depend on (strides and row count are baked into them)
-    // rules: what a constrained step bakes of the rule set (states * 256 + depth cap; the table itself stays in the engine's buffer)
+    // rules: what a constrained step bakes of the rule set (states * 256 + depth cap, + 4096 for a closing decode's kernels; the tables
+    // themselves stay in the engine's buffers)
     LaneSet::GraphKey graph_key(const LaneSet::Lane& ln, int eos, int sample_mode, bool logp, int rules = 0) const {
         return {ln.b0, ln.nb, keys, eos, rows, images,
                 (int)latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)ragged + 32 * (int)logp + 64 * (int)forced + 128 * (ruled ? rules : 0)};

@@ -49,6 +49,9 @@ struct StepArgs {
     // slice, through out_row); rule_hist [rows][rule_hist_stride]: the state behind every position (null: not kept)
     const int* rules; int n_states; int depth_max; int2* rule_state;
     int2* rule_hist; int rule_hist_stride;
+    // closing decode (txo_set_rules_close; the *_rules_close_step kernels of step_rules.h, null for every other step): the distance table
+    // (step_rules.h: CloseTable) and every row's (end position, has committed eos) -- by row of the BATCH, like rule_state
+    const void* close_tab; int2* rule_close;
 };
 // row of the range (relative to row0) whose outputs slot `row` produces
 __device__ inline int out_row(const StepArgs& a, int row) { return a.row_map ? a.row_map[row] - a.row0 : row; }

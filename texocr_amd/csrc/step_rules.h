@@ -218,4 +218,209 @@ __global__ void rules_state_out_kernel(int* out, const int2* state, int rows) {
     if (i < rows) { out[2 * i] = state[i].x; out[2 * i + 1] = state[i].y; }
 }
 
+// ---- closing decode (texocr.h: txo_set_rules_close) -----------------------------------------------------------------------------------------
+// The rules above with a budget: a row may only pick a token from which its automaton can still reach eos in the positions the call has left.
+// dist[s][d] (rules_close.h, computed on the host at installation) is the least number of picks, the eos included, from (s, d) to a committed
+// eos.  A row in (s, d) that has not committed an eos, with R picks left in what the call returns (this one included) and D = dist[s][d]
+// finite, may pick v iff the rule allows it AND (v == eos OR dist[next][depth after v] <= max(R, D) - 1).  Some allowed token always leads to
+// D - 1, so the set is never empty; D <= R at a row's first pick ends the row at an allowed eos inside its R picks; D > R (a forced prefix)
+// takes distance-reducing tokens only and ends open.  A row that has committed its eos, or stands where D is infinite, runs the plain rule.
+//
+// R comes from device-side state: the position word every step reads and the row's end position rule_close[row].x (the position behind its
+// last returned one: prefix length + max_len - 1, so R = end - t), written once per call by rules_close_start_kernel -- a captured step bakes
+// neither.  rule_close[row].y: the row has committed an eos.  Both by row of the BATCH, like the state.
+//
+// While R - 1 >= slack no token can be budgeted away (every move lands within dist_max <= R - 1) and the wave runs the plain kernels' masking
+// code: the picks are theirs bit for bit.  A table with an infinite entry has no such slack -- a token may lead to a node that cannot close at
+// all -- and its rows are budgeted at every position (slack = INT_MAX).  The budgeted branch costs one more dependent look-up per vocabulary
+// entry, at an index every lane computes from its own entry: not a scalar load.  The table (at most 8 * 256 nodes of 16 bits = 4 KB) is staged
+// into LDS with 16-byte loads first -- one wave's 64 look-ups per instruction is what LDS serves, and only the last dist_max positions of a row
+// pay the staging.
+constexpr int CLOSE_NODES = RULES_MAX_STATES * 256;
+constexpr int CLOSE_FAR = 0xffff;                                  // an entry without a path (CLOSE_INF of rules_close.h)
+struct CloseTable {
+    unsigned short dist[CLOSE_NODES];                              // [n_states][depth_max + 1], CLOSE_FAR behind it: whole 16-byte pieces are read
+    int slack, dist_max, pad[2];
+};
+struct CloseRow { bool bind; int lim; };                           // (lane-uniform) budgeted: a non-eos token must land at a distance <= lim
+__device__ inline CloseRow close_row(const CloseTable* ct, int2 ce, int t, int s, int depth, int depth_max) {
+    const int R = ce.x - t;
+    if (ce.y || R - 1 >= ct->slack) return {false, 0};
+    const int D = ct->dist[(s * (depth_max + 1) + min(max(depth, 0), depth_max)) & (CLOSE_NODES - 1)];
+    if (D == CLOSE_FAR) return {false, 0};
+    return {true, min(max(R, D) - 1, CLOSE_FAR - 1)};
+}
+// the first `nodes` entries into LDS, in 16-byte pieces, by the workgroup's `threads` threads; a barrier behind it
+__device__ inline void close_stage(unsigned short* cl, const CloseTable* ct, int nodes, int tid, int threads) {
+    const int n16 = (nodes * 2 + 15) >> 4;
+    for (int i = tid; i < n16; i += threads) reinterpret_cast<uint4*>(cl)[i] = reinterpret_cast<const uint4*>(ct->dist)[i];
+    __syncthreads();
+}
+__device__ inline bool close_allows(const unsigned short* cl, int r, int v, int depth, int depth_max, int eos, int lim) {
+    if (!rule_allows(r, depth, depth_max)) return false;
+    return v == eos || (int)cl[(rule_next(r) * (depth_max + 1) + rule_depth_after(r, depth, depth_max)) & (CLOSE_NODES - 1)] <= lim;
+}
+__device__ inline float close_mask(const unsigned short* cl, float x, int r, int v, int depth, int depth_max, int eos, int lim) {
+    return close_allows(cl, r, v, depth, depth_max, eos, lim) ? x : -3.4e38f;
+}
+// stream_row_rules with the budgeted mask: the same requests, the same log-sum-exp calls in the same order, best / bi over the budgeted row
+__device__ inline void stream_row_close(const float* lg, const int* rl, const unsigned short* cl, int depth, int depth_max, int eos, int lim, int V,
+                                        int lane, bool lp, float* lo, float& best, int& bi, float& lm, float& ls) {
+    best = -3.4e38f; bi = 0x7fffffff; lm = -3.4e38f; ls = 0.f;
+    if ((V & 3) == 0) {
+        const int n4 = V >> 2;
+        for (int base = 0; base < n4; base += 256) {
+            float4 v[4]; int4 r[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j4 = base + u * 64 + lane;
+                v[u] = j4 < n4 ? reinterpret_cast<const float4*>(lg)[j4] : make_float4(-3.4e38f, -3.4e38f, -3.4e38f, -3.4e38f);
+                r[u] = j4 < n4 ? reinterpret_cast<const int4*>(rl)[j4] : make_int4(RULE_BAN, RULE_BAN, RULE_BAN, RULE_BAN);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j4 = base + u * 64 + lane;
+                if (j4 >= n4) continue;
+                if (lo) reinterpret_cast<float4*>(lo)[j4] = v[u];
+                if (lp) lse_push4(lm, ls, v[u]);
+                const int j = j4 * 4;
+                const float mx = close_mask(cl, v[u].x, r[u].x, j, depth, depth_max, eos, lim), my = close_mask(cl, v[u].y, r[u].y, j + 1, depth, depth_max, eos, lim);
+                const float mz = close_mask(cl, v[u].z, r[u].z, j + 2, depth, depth_max, eos, lim), mw = close_mask(cl, v[u].w, r[u].w, j + 3, depth, depth_max, eos, lim);
+                if (mx > best) { best = mx; bi = j; }
+                if (my > best) { best = my; bi = j + 1; }
+                if (mz > best) { best = mz; bi = j + 2; }
+                if (mw > best) { best = mw; bi = j + 3; }
+            }
+        }
+    } else {
+        for (int j = lane; j < V; j += 64) {
+            const float v = lg[j];
+            const int r = rl[j];
+            if (lo) lo[j] = v;
+            if (lp) lse_push(lm, ls, v);
+            const float m = close_mask(cl, v, r, j, depth, depth_max, eos, lim);
+            if (m > best) { best = m; bi = j; }
+        }
+    }
+    wave_argmax(best, bi);
+}
+// commit_rules, then the row's "has committed eos" (picked or forced; a row the per-row stop froze committed one long ago)
+__device__ inline void commit_close(const StepArgs& a, int row, int orow, int t, const RuleRow& rr, int tok, float logp, bool forced, int len) {
+    commit_rules(a, row, orow, t, rr, tok, logp, forced, len);
+    if (a.eos >= 0 && in_vocab(tok, a.V) == a.eos) a.rule_close[orow].y = 1;
+}
+
+__global__ __launch_bounds__(64) void argmax_rules_close_step_kernel(StepArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned short cl[CLOSE_NODES];
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int t = a.st->t;
+    const int orow = out_row(a, row);
+    int len = 0;
+    const int ftok = a.forced ? forced_token(a, orow, t, len) : -1;
+    const bool forced = ftok >= 0;
+    const bool lp = forced ? a.prefix_logp != nullptr : a.logp_out != nullptr;
+    const RuleRow rr = rule_row(a, orow);
+    const CloseTable* ct = static_cast<const CloseTable*>(a.close_tab);
+    const CloseRow cr = forced ? CloseRow{false, 0} : close_row(ct, a.rule_close[orow], t, rr.s, rr.depth, a.depth_max);
+    const float* lg = a.logits + (size_t)row * a.V;
+    float* lo = (a.logits_out && !a.forced) ? a.logits_out + ((size_t)orow * a.out_stride + t) * a.V : nullptr;
+    float best, lm, ls; int bi;
+    if (!cr.bind) {                                                            // (wave-uniform) slack, an ended row, a forced token: the plain rule's code
+        stream_row_rules(lg, rr.rl, rr.depth, a.depth_max, a.V, lane, lp, lo, best, bi, lm, ls);
+    } else {
+        close_stage(cl, ct, a.n_states * (a.depth_max + 1), lane, 64);
+        stream_row_close(lg, rr.rl, cl, rr.depth, a.depth_max, a.eos, cr.lim, a.V, lane, lp, lo, best, bi, lm, ls);
+    }
+    const int tok = forced ? ftok : bi;
+    float logp = 0.f;
+    if (lp) logp = raw_logp(lg, a.V, tok, lm, ls);
+    if (lane == 0) commit_close(a, row, orow, t, rr, tok, logp, forced, len);
+}
+
+template <bool REGS>
+__global__ __launch_bounds__(64) void sample_rules_close_step_kernel(StepArgs a) {
+    extern __shared__ float row_lds[];
+    __shared__ __attribute__((aligned(16))) unsigned short cl[CLOSE_NODES];
+    const int row = blockIdx.x, lane = threadIdx.x, V = a.V;
+    const int t = a.st->t;
+    const float* lg = a.logits + (size_t)row * V;
+    const int orow = out_row(a, row);
+    int len = 0;
+    const int ftok = a.forced ? forced_token(a, orow, t, len) : -1;
+    const RuleRow rr = rule_row(a, orow);
+    if (ftok >= 0) {                                                           // (wave-uniform: one row per wave)
+        float logp = 0.f;
+        if (a.prefix_logp) {
+            float best, lm, ls, wv; int bi;
+            stream_row(lg, V, lane, true, ftok, best, bi, lm, ls, wv);
+            logp = forced_logp(best, lm, ls, wv);
+        }
+        if (lane == 0) commit_close(a, row, orow, t, rr, ftok, logp, true, len);
+        return;
+    }
+    const CloseTable* ct = static_cast<const CloseTable*>(a.close_tab);
+    const CloseRow cr = close_row(ct, a.rule_close[orow], t, rr.s, rr.depth, a.depth_max);
+    const int* rl = rr.rl;
+    const int depth = rr.depth, dmax = a.depth_max, eos = a.eos, lim = cr.lim;
+    const unsigned NO = __float_as_uint(-3.4e38f);
+    int pick; float unused = 0.f;
+    if (!cr.bind) {                                                            // (wave-uniform) the plain rule's loads
+        auto load = [&](int j) { return rule_mask(lg[j], rl[j], depth, dmax); };
+        if constexpr (REGS) {
+            auto load4 = [&](int j) {
+                u32x4 w = ld16(lg + j);
+                const u32x4 r = ld16(rl + j);
+                w.x = rule_allows((int)r.x, depth, dmax) ? w.x : NO; w.y = rule_allows((int)r.y, depth, dmax) ? w.y : NO;
+                w.z = rule_allows((int)r.z, depth, dmax) ? w.z : NO; w.w = rule_allows((int)r.w, depth, dmax) ? w.w : NO;
+                return w;
+            };
+            pick = sample_row_regs(load, load4, nullptr, V, lane, a.topk, a.inv_temp, a.seed, (unsigned)(a.row0 + orow), (unsigned)t, false, unused);
+        } else {
+            pick = sample_row_lds(load, row_lds, nullptr, V, lane, a.topk, a.inv_temp, a.seed, (unsigned)(a.row0 + orow), (unsigned)t, false, unused);
+        }
+    } else {
+        close_stage(cl, ct, a.n_states * (dmax + 1), lane, 64);
+        auto load = [&](int j) { return close_mask(cl, lg[j], rl[j], j, depth, dmax, eos, lim); };
+        if constexpr (REGS) {
+            auto load4 = [&](int j) {
+                u32x4 w = ld16(lg + j);
+                const u32x4 r = ld16(rl + j);
+                w.x = close_allows(cl, (int)r.x, j, depth, dmax, eos, lim) ? w.x : NO; w.y = close_allows(cl, (int)r.y, j + 1, depth, dmax, eos, lim) ? w.y : NO;
+                w.z = close_allows(cl, (int)r.z, j + 2, depth, dmax, eos, lim) ? w.z : NO; w.w = close_allows(cl, (int)r.w, j + 3, depth, dmax, eos, lim) ? w.w : NO;
+                return w;
+            };
+            pick = sample_row_regs(load, load4, nullptr, V, lane, a.topk, a.inv_temp, a.seed, (unsigned)(a.row0 + orow), (unsigned)t, false, unused);
+        } else {
+            pick = sample_row_lds(load, row_lds, nullptr, V, lane, a.topk, a.inv_temp, a.seed, (unsigned)(a.row0 + orow), (unsigned)t, false, unused);
+        }
+    }
+    float* lo = (a.logits_out && !a.forced) ? a.logits_out + ((size_t)orow * a.out_stride + t) * V : nullptr;
+    const bool lp = a.logp_out != nullptr;
+    float logp = 0.f;
+    if (lp || lo) {                                                            // (wave-uniform) the raw row once more
+        float lm = -3.4e38f, ls = 0.f;
+        for (int j = lane; j < V; j += 64) {
+            const float v = lg[j];
+            if (lo) lo[j] = v;
+            if (lp) lse_push(lm, ls, v);
+        }
+        if (lp) logp = raw_logp(lg, V, pick, lm, ls);
+    }
+    if (lane == 0) commit_close(a, row, orow, t, rr, pick, logp, false, len);
+}
+inline void launch_rules_close_step(hipStream_t s, int rows, const StepArgs& sa, bool sample) {
+    if (!sample) hipLaunchKernelGGL(argmax_rules_close_step_kernel, dim3(rows), dim3(64), 0, s, sa);
+    else if (sample_in_regs(sa.V)) hipLaunchKernelGGL(sample_rules_close_step_kernel<true>, dim3(rows), dim3(64), 0, s, sa);
+    else hipLaunchKernelGGL(sample_rules_close_step_kernel<false>, dim3(rows), dim3(64), (size_t)sa.V * sizeof(float), s, sa);
+}
+// beside rules_start_kernel: every row's end position -- the position behind the last one the call returns for it, prefix length (len null: 1,
+// the BOS column) + max_len - 1 -- and whether the prefix columns the multi-position pass consumed (1 .. m-1) hold an eos
+__global__ void rules_close_start_kernel(int2* close, int rows, const int* len, int max_len, int eos, const int64_t* table, int stride, int m) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    int ended = 0;
+    if (eos >= 0) for (int c = 1; c < m; ++c) ended |= table[(size_t)i * stride + c] == eos ? 1 : 0;
+    close[i] = make_int2((len ? len[i] : 1) + max_len - 1, ended);
+}
+
 }  // namespace txo

@@ -331,12 +331,18 @@ class HipEngine:
         return torch.ops.texocr.last_rule_state(tokens if tokens.ndim == 2 else tokens[None, :], self.id)
 
     @contextlib.contextmanager
-    def modes(self, sample: Optional[Tuple[float, Optional[int]]] = None, stop: str = "global", decode: Optional[str] = None, rules=None):
+    def modes(self, sample: Optional[Tuple[float, Optional[int]]] = None, stop: str = "global", decode: Optional[str] = None, rules=None,
+              close: bool = False):
         """The engine's global switches around the calls of one generate: sampling with sample = (temp, seed) -- a seed of None is
         drawn from torch's generator; decode='greedy' overrides it --, per-row stop, and token rules (rules=: a TokenRules installed for the
         scope; the set that was installed before, or none, is back behind every exit).  Nothing else in this module turns sampling or the
-        per-row stop on, and both are off again behind every exit.  Yields (temp, seed) as set, or None."""
+        per-row stop on, and both are off again behind every exit.  Yields (temp, seed) as set, or None.
+        close=True (only with rules=, ValueError otherwise): the closing decode (txo_set_rules_close) for the scope, off again behind it."""
         _check_modes(stop, decode or "greedy")
+        if close not in (False, True, 0, 1):
+            raise ValueError("close must be False or True")
+        if close and rules is None:
+            raise ValueError("close=True needs rules=: the closing decode is a budget on top of a rule set")
         if decode == "greedy":
             sample = None
         if sample is not None and sample[1] is None:
@@ -345,6 +351,8 @@ class HipEngine:
         try:
             if rules is not None:
                 self.set_token_rules(rules)
+            if close:                                              # (behind the rules: the engine computes its table here, or refuses)
+                torch.ops.texocr.set_rules_close(self.id, True)
             if sample is not None:
                 self.set_sampling(True, temp=sample[0], seed=sample[1])
             if stop == "row":
@@ -355,6 +363,8 @@ class HipEngine:
                 self.set_sampling(False)
             if stop == "row":
                 self.set_stop_mode("global")
+            if close:
+                torch.ops.texocr.set_rules_close(self.id, False)
             if rules is not None:
                 if before is None:
                     torch.ops.texocr.set_token_rules(None, self.id, 0)
@@ -392,6 +402,12 @@ class HipEngine:
     def last_beam_rule_state(self, tokens: torch.Tensor) -> torch.Tensor:
         """(B, beams, 2) int32: the (state, depth) of every beam of the last constrained beam search, beside its tokens (B, beams, n)"""
         return torch.ops.texocr.last_beam_rule_state(tokens, self.id)
+
+    def rules_close_dist(self, rules) -> torch.Tensor:
+        """txo_rules_close_dist: the closing decode's distance table as the ENGINE computes it for `rules` (installed with the switch on for
+        the length of this call) -> (S, depth_max + 1) int32 on the CPU; rules.close_dist(dims.eos) is the host's restatement"""
+        with self.modes(rules=rules, close=True):
+            return ops.rules_close_dist(self.id, rules.n_states, rules.depth_max)
 
     @contextlib.contextmanager
     def ragged_forward(self):
@@ -806,6 +822,7 @@ class AutoRegressiveDecoder(nn.Module):
         # build extension: a texocr_amd.rules.TokenRules the loop picks under (installed for this call); the result gains rule_state (B, 2)
         # int32 as its last element.  Needs the engine's own loop: a BOS start or the prompted route, not the stepwise one.
         rules = kwargs.pop("rules", None)
+        close = kwargs.pop("close", False)                         # build extension, with rules=: the closing decode (OCRModel.generate)
         rstate = None
         if kwargs:
             raise ValueError(f"unsupported arguments: {sorted(kwargs)}")
@@ -838,7 +855,7 @@ class AutoRegressiveDecoder(nn.Module):
             prompted = True
             if return_logits:
                 raise ValueError("return_logits is not available with prefix_len (a prompted decode keeps no logits)")
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules) as sample:
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close) as sample:
             if prompted:
                 out = eng.generate_prefix(None, st.to(enc.device), max_len, eos_tok, prefix_len=prefix_len, enc=enc, return_logp=return_logp)
                 if rules is not None:
@@ -1029,8 +1046,14 @@ class OCRModel(nn.Module):
     def generate(self, src: torch.Tensor, max_len: int, temp: float = 0.3, *, decode: str = "greedy",
                  generator: Optional[torch.Generator] = None, seed: Optional[int] = None, return_logits: bool = False,
                  beam: int = 0, return_beams: bool = False, stop: str = "global", return_logp: bool = False,
-                 prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None):
-        """rules= (build extension): a texocr_amd.rules.TokenRules -- which tokens the loop may pick (vocabulary bans, brace balance:
+                 prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None, close: bool = False):
+        """close=True (build extension, only with rules=; ValueError otherwise): the closing decode, for this call.  A row may only pick a
+        token from which its rules can still reach eos in the positions it has left (rules.TokenRules.allowed(remaining=) is the rule), so
+        every row ends at an eos its rules allow -- under rules.brace_rules: balanced and finished inside max_len.  The one exception of a
+        row is a forced prefix too deep to close in max_len: it closes as far as it gets and rule_state shows the rest.  Refused
+        (ValueError) when the rules cannot reach eos from the start, or not within max_len.  With beam= (and rules_beam): every live beam
+        ends finished; dead beams (score -inf) stay outside every guarantee.
+        rules= (build extension): a texocr_amd.rules.TokenRules -- which tokens the loop may pick (vocabulary bans, brace balance:
         rules.ban / rules.brace_rules) -- installed for this call; the result gains rule_state (B, 2) int32 = every row's (state, depth)
         behind its last returned token as its LAST element.  The decode then runs on the launch path (not the persistent launch); logp and
         logits stay those of the raw logits.  No closure guarantee: a row that runs out of positions may end at depth > 0.  With beam=:
@@ -1046,7 +1069,8 @@ class OCRModel(nn.Module):
         0.0 elsewhere.  Needs (longest prefix - 1) + max_len <= decoder.max_len; not with beam= or return_logits."""
         _check_modes(stop)
         if prefix is not None:
-            return self._generate_prefix(src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules)
+            return self._generate_prefix(src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules,
+                                         close)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
         if beam and return_logp:
@@ -1054,7 +1078,7 @@ class OCRModel(nn.Module):
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
             if max_len > self.decoder.max_len:
                 raise ValueError(f"beam search needs max_len <= decoder.max_len ({self.decoder.max_len})")
-            with self._engine.modes(rules=rules):                  # (with rules the engine refuses unless rules_beam is on)
+            with self._engine.modes(rules=rules, close=close):     # (with rules the engine refuses unless rules_beam is on)
                 if rules is None:
                     return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
                 toks, scores = self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=True)
@@ -1063,7 +1087,7 @@ class OCRModel(nn.Module):
         if decode == "greedy" and self.bos_token == self._engine.dims.bos:
             # (max_len > decoder.max_len: txo_generate slides the window like the reference, decoder.py:99-100)
             # (stop='row' with return_logits: the engine does not compact -- a finished row's logits would be missing -- and only pads)
-            with self._engine.modes(stop=stop, rules=rules):
+            with self._engine.modes(stop=stop, rules=rules, close=close):
                 out = self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits, return_logp=return_logp)
                 if rules is None:
                     return out
@@ -1073,9 +1097,11 @@ class OCRModel(nn.Module):
         start = torch.full((src.shape[0], 1), self.bos_token, dtype=torch.int64, device=src.device)   # ocr_model.py:57
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
-                                     stop=stop, pad=self.trg_pad_idx, return_logp=return_logp, **({} if rules is None else {"rules": rules}))
+                                     stop=stop, pad=self.trg_pad_idx, return_logp=return_logp,
+                                     **({} if rules is None and not close else {"rules": rules, "close": close}))
 
-    def _generate_prefix(self, src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules=None):
+    def _generate_prefix(self, src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules=None,
+                         close=False):
         """generate(prefix=) / generate_ragged(prefix=): src a (B, C, H, W) tensor or a sequence of images.  Every refusal comes before
         the engine is touched."""
         if beam:
@@ -1094,7 +1120,7 @@ class OCRModel(nn.Module):
         if seed is None and generator is not None:
             seed = generator.initial_seed()
         dev = src[0].device if isinstance(src, (list, tuple)) else src.device           # (a tensor or a PackedImages says it itself)
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules):
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close):
             out = eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
             if rules is None:
                 return out
@@ -1125,7 +1151,8 @@ class OCRModel(nn.Module):
         return self._engine.ingest(images, fit=fit, trim=trim, regions=regions)
 
     @torch.no_grad()
-    def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0, rules=None) -> Beams:
+    def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0, rules=None,
+                    close: bool = False) -> Beams:
         """Build extension: the k = beams best sequences of every image, with score, length and (return_logp=True) the log-probability of
         every token -> Beams.  src is a (B, C, H, W) tensor, or a sequence of (C, H_b, W_b) tensors of different sizes: those go
         through ONE ragged encode and ONE decode, and the beams of image b are what beam_search(src[b][None]) returns, over the batch's n.
@@ -1135,7 +1162,10 @@ class OCRModel(nn.Module):
         rules= (build extension): a texocr_amd.rules.TokenRules installed for this call.  With rules_beam off (the default) the engine
         refuses (ValueError).  On: a candidate the rules disallow in its parent's state counts as -inf in the selection, so no disallowed
         hypothesis ever holds a slot; scores and logp stay sums of the RAW model's log-probabilities (nothing is renormalised), and
-        Beams.rule_state holds every beam's state.  No closure guarantee: a beam that runs out of positions may end at depth > 0."""
+        Beams.rule_state holds every beam's state.  No closure guarantee: a beam that runs out of positions may end at depth > 0.
+        close=True (only with rules=): the closing search, generate(close=True)'s budget inside the selection with R = max_len - position: a
+        hypothesis that could no longer reach eos never holds a slot, so every LIVE beam ends finished (under brace_rules: balanced) and
+        lengths <= max_len; dead beams stay outside every guarantee."""
         if isinstance(src, torch.Tensor):
             if src.ndim != 4:
                 raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
@@ -1145,24 +1175,25 @@ class OCRModel(nn.Module):
         else:
             raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
         check_beam_args(beams, max_len, length_alpha, n_images, self.decoder.max_len, self._engine.max_batch)
-        with self._engine.modes(rules=rules):                      # rules=: the engine refuses (ValueError) unless rules_beam is on
+        with self._engine.modes(rules=rules, close=close):         # rules=: the engine refuses (ValueError) unless rules_beam is on
             out = self._engine.beam_search(src, beams, max_len, self.eos_token, return_logp=return_logp, length_alpha=length_alpha)
             return Beams(*out, self._engine.last_beam_rule_state(out[0]) if rules is not None else None)
 
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
-                        stop: str = "global", return_logp: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None):
+                        stop: str = "global", return_logp: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None,
+                        close: bool = False):
         """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
         is keyed by the row of the batch).  max_len may exceed decoder.max_len: the window slides as in generate(), under the engine's
         two preconditions (a vocabulary that is a multiple of 8, max_length <= max_batch * max_tokens; ValueError before anything is
-        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them.  prefix= / prefix_len= / rules=: as generate() takes
-        them (rules=: rule_state (B, 2) is the result's last element)."""
+        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them.  prefix= / prefix_len= / rules= / close=: as generate()
+        takes them (rules=: rule_state (B, 2) is the result's last element)."""
         if prefix is not None:
-            return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len, rules)
+            return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len, rules, close)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
-        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules):
+        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close):
             out = self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
             if rules is None:
                 return out

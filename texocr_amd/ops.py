@@ -22,6 +22,8 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
                             of every produced token, taken from the token selection itself (no second pass, no (B, T, V) tensor)
   texocr::set_rules_beam / last_beam_rule_state
                             (build extension, opt-in) beam search under token rules (texocr::set_token_rules) and the beams' rule states
+  texocr::set_rules_close   (build extension, opt-in) the closing decode: a constrained decode or beam search only picks tokens from which
+                            eos can still be reached in the positions left (``rules_close_dist`` reads the engine's distance table)
   texocr::encode_ragged / decode_begin_ragged / generate_ragged / score_ragged
                             (build extension) the same callables over a RAGGED batch: B images of different sizes in one
                             container, every image computed as if it had been passed on its own (``pack_ragged`` builds the container);
@@ -806,6 +808,29 @@ def last_beam_rule_state(tokens: torch.Tensor, engine: int) -> torch.Tensor:
 @set_rules_beam.register_fake
 def _(engine, on):
     return None
+
+
+# ---- closing decode (txo_set_rules_close): the budget that ends every constrained row at an allowed eos inside the call's positions --------
+@custom_op("texocr::set_rules_close", mutates_args=())
+def set_rules_close(engine: int, on: bool) -> None:
+    """txo_set_rules_close: on=True, a constrained decode / beam search only picks tokens from which eos can still be reached in the positions
+    left; False (the default): the plain rules.  The engine refuses (ValueError) when rules are set and eos is unreachable from the start."""
+    e = _eng(engine)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_set_rules_close(e.handle, 1 if on else 0))
+
+
+@set_rules_close.register_fake
+def _(engine, on):
+    return None
+
+
+def rules_close_dist(engine: int, n_states: int, depth_max: int) -> torch.Tensor:
+    """txo_rules_close_dist: the distance table the engine computed for the installed rules -> (S, depth_max + 1) int32 on the CPU"""
+    e = _eng(engine)
+    out = torch.empty((int(n_states), int(depth_max) + 1), dtype=torch.int32)
+    _lib.check(e.lib.txo_rules_close_dist(e.handle, out.data_ptr(), int(n_states), int(depth_max) + 1))
+    return out
 
 
 @last_beam_rule_state.register_fake

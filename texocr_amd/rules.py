@@ -19,6 +19,7 @@ import numpy as np
 BAN, ONLY_AT_ZERO = 1, 2            # the flag bits of an entry (bits 24 and 25 of the packed word)
 MAX_STATES = 8
 MASKED = np.float32(-3.4e38)        # what a disallowed logit counts as
+CLOSE_INF = np.int32(0x7fffffff)    # a close_dist entry without a path to eos (include/texocr.h: TXO_CLOSE_INF)
 
 
 def pack(need=0, delta=0, next=0, flags=0) -> np.ndarray:
@@ -35,6 +36,18 @@ def unpack(entry) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
     delta = (e >> 8) & 0xff
     return ((e & 0xff).astype(np.int32), np.where(delta >= 128, delta - 256, delta).astype(np.int32), ((e >> 16) & 0xff).astype(np.int32),
             ((e >> 24) & 0xff).astype(np.int32))
+
+
+class CloseDist(np.ndarray):
+    """TokenRules.close_dist's table: int32 (S, depth_max + 1), CLOSE_INF where eos cannot be reached, with the eos id it was computed for
+    (``eos``), its largest finite entry (``dist_max``, 0: none) and ``any_inf``"""
+    eos: int = -1
+    dist_max: int = 0
+    any_inf: bool = True
+
+    def __array_finalize__(self, obj):
+        if obj is not None:
+            self.eos, self.dist_max, self.any_inf = getattr(obj, "eos", -1), getattr(obj, "dist_max", 0), getattr(obj, "any_inf", True)
 
 
 class TokenRules:
@@ -79,16 +92,64 @@ class TokenRules:
     def start(self, rows: int) -> np.ndarray:
         return np.zeros((int(rows), 2), dtype=np.int32)
 
-    def allowed(self, state) -> np.ndarray:
-        """state (n, 2) of (s, depth) -> (n, V) bool: the tokens every row may pick"""
+    def allowed(self, state, remaining=None, ended=None, dist=None) -> np.ndarray:
+        """state (n, 2) of (s, depth) -> (n, V) bool: the tokens every row may pick.
+        remaining= (n,) or a scalar: the closing decode's rule (txo_set_rules_close) -- R, the picks every row has left in what the call
+        returns, this one included; dist= the CloseDist of close_dist(eos) (needed then); ended= (n,) bool, rows that have committed an eos
+        (default: none).  A row that has not ended, with D = dist[s][depth] finite, may pick v iff the rule allows it and (v == eos or
+        dist[next][depth after v] <= max(R, D) - 1); an ended row and a row with D infinite keep the plain rule."""
         state = np.asarray(state, dtype=np.int32).reshape(-1, 2)
-        need, delta, _, flags = unpack(self.table[state[:, 0]])
+        need, delta, nxt, flags = unpack(self.table[state[:, 0]])
         depth = state[:, 1:2]
-        return ((flags & BAN) == 0) & (depth >= need) & (depth + delta <= self.depth_max) & (((flags & ONLY_AT_ZERO) == 0) | (depth == 0))
+        ok = ((flags & BAN) == 0) & (depth >= need) & (depth + delta <= self.depth_max) & (((flags & ONLY_AT_ZERO) == 0) | (depth == 0))
+        if remaining is None:
+            if ended is not None or dist is not None:
+                raise ValueError("token rules: ended= and dist= belong to remaining= (the closing decode's rule)")
+            return ok
+        if not isinstance(dist, CloseDist) or dist.shape != (self.n_states, self.depth_max + 1):
+            raise ValueError("token rules: remaining= needs dist=, the table close_dist(eos) returned for these rules")
+        n = state.shape[0]
+        R = np.broadcast_to(np.asarray(remaining, dtype=np.int64).reshape(-1), (n,))
+        done = np.zeros(n, dtype=bool) if ended is None else np.broadcast_to(np.asarray(ended, dtype=bool).reshape(-1), (n,))
+        d64 = np.asarray(dist, dtype=np.int64)
+        D = d64[state[:, 0], state[:, 1]]
+        bind = ~done & (D != int(CLOSE_INF))
+        lim = np.maximum(R, D) - 1
+        after = d64[np.minimum(nxt, self.n_states - 1), np.clip(depth + delta, 0, self.depth_max)]
+        close = after <= lim[:, None]                              # (CLOSE_INF never is: lim is finite where the row binds)
+        close[:, dist.eos] = True
+        return np.where(bind[:, None], ok & close, ok)
 
-    def mask(self, state, logits) -> np.ndarray:
-        """the float32 rows the selection sees: logits (n, V) with MASKED where a token is disallowed"""
-        return np.where(self.allowed(state), np.asarray(logits, dtype=np.float32), MASKED)
+    def mask(self, state, logits, remaining=None, ended=None, dist=None) -> np.ndarray:
+        """the float32 rows the selection sees: logits (n, V) with MASKED where a token is disallowed (remaining / ended / dist: as allowed)"""
+        return np.where(self.allowed(state, remaining, ended, dist), np.asarray(logits, dtype=np.float32), MASKED)
+
+    def close_dist(self, eos: int) -> CloseDist:
+        """The closing decode's table (csrc/rules_close.h restated): dist[s][d] = the least number of picks, the eos included, that takes a
+        row from (s, d) to a committed eos with every pick allowed and every move the rule's own; CLOSE_INF: no path."""
+        S, W = self.n_states, self.depth_max + 1
+        out = np.full((S, W), int(CLOSE_INF), dtype=np.int64)
+        eos = int(eos)
+        if 0 <= eos < self.vocab:
+            depths = np.arange(W)
+            edges = []                                             # per state: its distinct words' (allowed at d, node behind it at d), eos apart
+            for s in range(S):
+                words = np.unique(np.delete(self.table[s], eos))
+                need, delta, nxt, flags = unpack(words[:, None])
+                ok = ((flags & BAN) == 0) & (depths >= need) & (depths + delta <= self.depth_max) & (((flags & ONLY_AT_ZERO) == 0) | (depths == 0))
+                edges.append((ok & (nxt < S), np.minimum(nxt, S - 1) + 0 * depths, np.clip(depths + delta, 0, self.depth_max)))
+            out[self.allowed(np.stack([np.repeat(np.arange(S), W), np.tile(depths, S)], 1))[:, eos].reshape(S, W)] = 1
+            for level in range(2, S * W + 1):
+                new = np.zeros((S, W), dtype=bool)
+                for s, (ok, ns, nd) in enumerate(edges):
+                    new[s] = (ok & (out[ns, nd] == level - 1)).any(0) & (out[s] == int(CLOSE_INF))
+                if not new.any():
+                    break
+                out[new] = level
+        res = out.astype(np.int32).view(CloseDist)
+        finite = out[out != int(CLOSE_INF)]
+        res.eos, res.dist_max, res.any_inf = eos, int(finite.max()) if finite.size else 0, bool((out == int(CLOSE_INF)).any())
+        return res
 
     def step(self, state, tokens) -> Tuple[np.ndarray, np.ndarray]:
         """state (n, 2), tokens (n,) committed in it -> (next state (n, 2) int32, allowed (n,) bool: would the rules have let the row pick it)"""

@@ -65,13 +65,15 @@ def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.T
 
 class TeXOCRWrapper:
     def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False, balanced: bool = False,
-                 rules_beam: bool = False):
+                 rules_beam: bool = False, close: bool = False):
         """ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)
         balanced=True (build extension): every __call__ / batch decodes under the brace rule of this tokenizer unless the call says otherwise
         (see batch)
         rules_beam=True (build extension): decode='beam' accepts balanced=True -- the brace rule inside the beam selection
-        (OCRModel.rules_beam); off, the default, the two together are a ValueError"""
+        (OCRModel.rules_beam); off, the default, the two together are a ValueError
+        close=True (build extension; only together with balanced): balanced decodes are closing decodes unless the call says otherwise (see batch)"""
         self.balanced = bool(balanced)
+        self.close = bool(close)
         self._brace_rules = None
         self.tokenizer = RegExTokenizer()
         self.tokenizer.load(config["tokenizer_path"])                                # ocr_model.py:74-75
@@ -101,6 +103,13 @@ class TeXOCRWrapper:
             self._brace_rules = brace_rules(self.tokenizer, vocab=self.dims.vocab, eos=self.model.eos_token,
                                             ban=(self.model.bos_token, self.model.trg_pad_idx)).validate(self.dims.vocab)
         return self._brace_rules
+
+    def _close(self, close: Optional[bool], rules) -> dict:
+        """the close= of a call as keyword arguments: the call's own setting, else the wrapper's where the call is balanced"""
+        on = bool(self.close and rules is not None) if close is None else bool(close)
+        if on and rules is None:
+            raise ValueError("close=True needs balanced=True: the closing decode is a budget on top of the brace rule")
+        return {"close": True} if on else {}
 
     def _tensor(self, img) -> torch.Tensor:
         x = preprocess_image(img, self.dims.patch)
@@ -158,10 +167,11 @@ class TeXOCRWrapper:
             imgs = [self._fitted(im, i) for i, im in enumerate(imgs)]
         return [self._tensor(im).cuda() for im in imgs]
 
-    def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool, rules=None):
+    def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool, rules=None, close: bool = False):
         """decode='beam': one OCRModel.beam_search over the images xs (a (B, C, H, W) tensor or a list of (C, H_b, W_b)) -> per image
         (the best beam's tokens up to and including its eos, their log-probabilities or None)"""
-        res = self.model.beam_search(xs, beams, max_len, return_logp=return_logp, length_alpha=length_alpha, **({} if rules is None else {"rules": rules}))
+        res = self.model.beam_search(xs, beams, max_len, return_logp=return_logp, length_alpha=length_alpha,
+                                     **({} if rules is None else {"rules": rules, "close": close}))
         lengths = res.lengths[:, 0].tolist()
         rows = [res.tokens[b, 0, :n].tolist() for b, n in enumerate(lengths)]
         logp = [res.logp[b, 0, :n].tolist() for b, n in enumerate(lengths)] if return_logp else [None] * len(rows)
@@ -187,7 +197,8 @@ class TeXOCRWrapper:
     def batch(self, imgs: Sequence, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
               length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host", fit: str = "none",
-              trim: str = "none", trim_level: int = 127, trim_margin: int = 2, balanced: Optional[bool] = None) -> List[tuple]:
+              trim: str = "none", trim_level: int = 127, trim_margin: int = 2, balanced: Optional[bool] = None,
+              close: Optional[bool] = None) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -219,8 +230,12 @@ class TeXOCRWrapper:
         balanced=True (build extension; default: the wrapper's own setting): the decode picks under rules.brace_rules of the tokenizer
         (OCRModel.generate_ragged(rules=)): no token closes a group that is not open, eos comes only at depth 0, <BOS> / <PAD> never.  A
         row that runs out of positions may still end open; logp stays the raw model's.  With decode='beam' only on a wrapper built with
-        rules_beam=True: the rule then binds inside the beam selection, and a best beam that finished is balanced by construction."""
+        rules_beam=True: the rule then binds inside the beam selection, and a best beam that finished is balanced by construction.
+        close=True (build extension; with balanced=True only; default: the wrapper's own setting): the closing decode
+        (OCRModel.generate_ragged(close=True)) -- a row only picks tokens from which it can still close its groups and reach eos inside
+        max_len, so every row ends balanced and finished; with a prefix too deep to close in max_len it closes as far as it gets."""
         rules = self._rules(balanced, decode)
+        ckw = self._close(close, rules)
         rule = self._trim_rule(trim, trim_level, trim_margin)
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
@@ -235,12 +250,12 @@ class TeXOCRWrapper:
         for c0 in range(0, len(imgs), step):
             chunk = xs[c0:c0 + step] if xs is not None else self._images(imgs[c0:c0 + step], ingest, fit, rule)
             if decode == "beam":
-                full, logp = self._best_beams(chunk, beams, max_len, length_alpha, return_logp, rules)
+                full, logp = self._best_beams(chunk, beams, max_len, length_alpha, return_logp, rules, **ckw)
             else:
                 chunk_seed = None if seed is None else int(seed) + c0 // step
                 kw = {} if pre is None else dict(prefix=pre[c0:c0 + step].cuda(), prefix_len=plen[c0:c0 + step])
                 toks = self.model.generate_ragged(chunk, max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
-                                                  return_logp=return_logp, **kw, **({} if rules is None else {"rules": rules}))
+                                                  return_logp=return_logp, **kw, **({} if rules is None else {"rules": rules}), **ckw)
                 if rules is not None:
                     toks = toks[:-1] if return_logp else toks[0]                       # (without the rule states)
                 toks, logp = toks[:2] if return_logp else (toks, None)
@@ -260,7 +275,7 @@ class TeXOCRWrapper:
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
                  length_alpha: float = 0.0, prefix=None, ingest: str = "host", fit: str = "none", trim: str = "none", trim_level: int = 127,
-                 trim_margin: int = 2, balanced: Optional[bool] = None) -> tuple:
+                 trim_margin: int = 2, balanced: Optional[bool] = None, close: Optional[bool] = None) -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
@@ -273,8 +288,9 @@ class TeXOCRWrapper:
         fit='canvas': an image beyond the canvas is downscaled to fit it first (see batch); the maps of return_align are then on the
         fitted grid.
         trim='ink': the image is cut to its ink and a margin first (see batch), before the fit; the maps are on the trimmed image's grid.
-        balanced=True: the decode picks under the tokenizer's brace rule (see batch)."""
+        balanced=True: the decode picks under the tokenizer's brace rule (see batch).  close=True: as a closing decode (see batch)."""
         rules = self._rules(balanced, decode)
+        ckw = self._close(close, rules)
         x = self._images([img], ingest, fit, self._trim_rule(trim, trim_level, trim_margin))
         x = x.box if ingest == "device" else x[0][None]
         prow: List[int] = []
@@ -284,14 +300,14 @@ class TeXOCRWrapper:
             gen_kw = dict(prefix=pre.cuda())
         if decode == "beam":
             beam_chunk(self.model._engine.max_batch, beams)
-            rows, lps = self._best_beams(x, beams, min(int(max_len), self.dims.max_len), length_alpha, return_logp, rules)
+            rows, lps = self._best_beams(x, beams, min(int(max_len), self.dims.max_len), length_alpha, return_logp, rules, **ckw)
             toks = torch.tensor(rows, dtype=torch.int64, device=x.device)
             logp = torch.tensor(lps, dtype=torch.float32) if return_logp else None   # (every float32 is exact in the list's doubles)
         else:
             # max_len may exceed the positional table (the reference's default 350 does for short tables): the model then
             # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
             toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp, **gen_kw,
-                                       **({} if rules is None else {"rules": rules}))
+                                       **({} if rules is None else {"rules": rules}), **ckw)
             if rules is not None:
                 toks = toks[:-1] if return_logp else toks[0]                           # (without the rule states)
             toks, logp = toks[:2] if return_logp else (toks, None)
