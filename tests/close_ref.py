@@ -36,7 +36,8 @@ def brute_dist(rules, eos):
 def closing_counter_rules(V, eos, depth_max, banned=()):
     """tests/test_gpu_rules.py's counter_rules (ids % 5 == 0 open, ids % 5 == 1 close with need 1, two states with next = id & 1, `banned`
     banned) with eos enabled: its entry is (need 0, delta 0, ONLY_AT_ZERO) whatever eos % 5 is -- at V = 64 the eos id 61 would otherwise
-    be a close token that needs depth 1 and is allowed at depth 0 only, i.e. never"""
+    be a close token that needs depth 1 and is allowed at depth 0 only, i.e. never.  The two states are copies on purpose (the counter
+    isolates the depth); tests/rule_zoo.py holds the rule sets whose states differ."""
     ids = np.arange(V)
     flags = np.zeros(V, dtype=np.int64)
     flags[np.asarray(sorted(banned), dtype=np.int64)] |= R.BAN

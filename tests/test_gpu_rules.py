@@ -37,7 +37,8 @@ def _tiny(vocab, max_len=24):
 
 def counter_rules(V, eos, depth_max, banned=(), eos_at_zero=True):
     """the synthetic counter: ids % 5 == 0 open, ids % 5 == 1 close (need 1), eos only at depth 0, two states with next = id & 1, and
-    `banned` ids banned"""
+    `banned` ids banned.  The two states are copies on purpose (the counter isolates the depth); tests/rule_zoo.py holds the rule sets whose
+    states differ."""
     ids = np.arange(V)
     flags = np.zeros(V, dtype=np.int64)
     if eos_at_zero:
