@@ -520,6 +520,28 @@ int txo_last_beam_rule_state(txo_engine* e, int32_t* state_out_dev, int32_t B, i
 int txo_set_rules_close(txo_engine* e, int32_t on);
 int txo_rules_close_dist(txo_engine* e, int32_t* out_host, int32_t S, int32_t D);
 
+/* Repeat guard, a BUILD EXTENSION: stops a row of the following txo_generate* calls from looping on a short block of tokens.  An engine
+ * knob like txo_set_token_rules; (0, 0) switches it off (the default).  Two integers: max_period P, 1 <= P <= 16, and max_repeats R,
+ * 1 <= R <= 16.
+ * A row's HISTORY at a pick is h[0 .. n-1]: every token the row has committed after its start token, in order -- forced prefix tokens first,
+ * then the row's own picks.  For a period p in 1 .. P with p <= n, m_p is the number of trailing positions i with i - p >= 0 and
+ * h[i] == h[i - p], counted back from n - 1 and stopping at the first mismatch.  Token h[n - p] is BANNED at this pick iff m_p >= R * p - 1:
+ * committing it would make the row end in R + 1 consecutive copies of one p-token block.  So a block may stand R times in a row, never R + 1.
+ * The eos token (the call's eos) is never banned.  A forced prefix token is never masked.  A banned logit counts as -3.4e38f in the selection,
+ * exactly as a rule-disallowed one: greedy takes the arg-max of the masked row (ties to the lowest index), sampling runs txo_set_sampling's
+ * rule on the masked row.  logp_out and logits_out stay the RAW row's: nothing is renormalised, a pick the guard forced shows its low
+ * probability.  The ban set is computed from the committed tokens at every pick; the engine keeps no per-row counters.
+ * With token rules: a token must be rule-allowed AND unbanned.  If no token is both, the ban is dropped for that pick and the rules alone
+ * decide.  The automaton advances on the committed token as ever; txo_last_rule_state keeps its meaning.
+ * While a guard is set every txo_generate* that decodes from BOS or from a prefix runs its loop with one launch per stage
+ * (TXO_Q_LAST_PERSISTENT reads 0, TXO_Q_LAST_GUARDED reads 1) and otherwise as ever: captured steps, row ranges, TXO_STOP_ROW with live-row
+ * compaction, ragged batches, the sliding window, logp_out.  txo_decode_step picks without it.
+ * Refused with TXO_E_INVALID: max_period or max_repeats out of range; cfg.vocab <= max_period + 1 (the guard may ban max_period tokens at a
+ * pick); by txo_generate*, behind every other refusal of the entry, while the closing decode is in effect (token rules and
+ * txo_set_rules_close: its guarantee and the guard's ban can conflict), and in sampling mode when vocab * 4 + vocab / 8 bytes exceed the
+ * 64 KB of LDS the guarded LDS-form sampler may use; by txo_generate_beam / txo_beam_search / txo_beam_search_ragged while a guard is set. */
+int txo_set_repeat_guard(txo_engine* e, int32_t max_period, int32_t max_repeats);
+
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
  * enabled (txo_profile_enable(e, 1) also clears the previous samples); *count = number of launches averaged.  kind: 0 = cross-attention decode kernel,
@@ -548,6 +570,7 @@ int txo_profile_read(txo_engine* e, int32_t kind, double* avg_ms, int64_t* count
 #define TXO_Q_LAST_RAGGED 7        /* 1 if the last generate decoded a ragged batch (per-image encoder token counts), 0 otherwise */
 #define TXO_Q_LAST_LATENT_SELF 8   /* 1 if the last generate's SELF attention ran in latent form too (TXO_LATENT_SELF=1: the history is z, not k / v);
                                     * 0 where the engine declined it (no latent form, per-row stop, a positional table beyond the beam slot table) */
+#define TXO_Q_LAST_GUARDED 9       /* 1 if the last txo_generate* picked under a repeat guard (txo_set_repeat_guard), 0 otherwise */
 int txo_engine_query(txo_engine* e, int32_t what, int64_t* out);
 
 const char* txo_last_error(void);

@@ -49,6 +49,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "ingest_fit.h"    // (the fit-to-canvas passes in front of it; uses ingest.h's per-pixel pieces)
 #include "ingest_trim.h"   // (the ink extents in front of both; reads ingest.h's descriptors)
 #include "step_rules.h"    // (the constrained token selection: step.h / step_prefix.h with a per-row automaton; last again)
+#include "step_guard.h"    // (the repeat guard's token selection: step_rules.h with a ban on the block a row has just repeated; last again)
 #include "beam_rules.h"    // (the constrained beam selection: step.h's beam kernels with that automaton; last again)
 #include "rules_close.h"   // (host only: the closing decode's distance table)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
@@ -114,6 +115,9 @@ struct EngineBase {
     std::vector<int32_t> close_dist; int close_dist_max = 0;
     bool closing() const { return rules_on && rules_close; }
     virtual int set_rules_close(bool on) = 0;
+    // txo_set_repeat_guard (step_guard.h): while set (max_period > 0), every generate from BOS or a prefix decodes on the launch path with the
+    // *_guard_step kernels; last_guarded: the last txo_generate* ran them (TXO_Q_LAST_GUARDED)
+    int guard_p = 0, guard_r = 0; bool last_guarded = false;
     // txo_ingest_u8 / _fit / _view behind their checks (ingest_req.h: ingest_plan): descriptors up in one staged copy, then one launch -- or,
     // where an image is downscaled, the horizontal pass of those that need one and the fused vertical pass + ingest
     virtual int ingest(const IngestPlan& p, const IngestReq& q, hipStream_t s) = 0;
@@ -1184,11 +1188,19 @@ struct Engine : EngineBase {
         const bool ragged = q.src.sizes != nullptr;
         // results of THIS call, also when it is refused (txo_generate_ragged / _logp: only once the batch is accepted, generate_common)
         if (q.prefix || !ragged) { last_compactions = 0; last_ragged = false; }
+        last_guarded = false;
         if (ragged) { if (int r = ragged_refusals()) return r; }
         Decode d{q};
         if (int r = q.prefix ? check_prefix(q, &d.m, &d.M) : check_length(q.max_len, ragged)) return r;
         if (int r = resolve_source(q.src, s, &d.src)) return r;
         if (int r = close_refusals("generate", q.eos, q.max_len, !q.prefix)) return r;   // (behind every other refusal of the entry)
+        if (guard_p > 0) {                                         // ... and the repeat guard's behind those
+            if (closing())
+                return fail(TXO_E_INVALID, "repeat guard: not available with a closing decode (txo_set_rules_close): the budget's guarantee and the guard's ban can "
+                                           "conflict (txo_set_repeat_guard(e, 0, 0) switches the guard off)");
+            if (sample_mode && !sample_in_regs(V) && (size_t)V * sizeof(float) + guard_map_bytes(V) > 65536)
+                return fail(TXO_E_INVALID, "repeat guard: the vocabulary does not fit the guarded sampler's LDS (vocab * 4 bytes + vocab / 8 bytes per workgroup, 64 KB)");
+        }
         if (q.prefix) {   // the lengths to the device, through the pinned staging of the ragged sizes (behind ragged_batch's own copy)
             std::vector<int32_t> len((size_t)q.src.B, q.P);
             if (q.prefix_len) len.assign(q.prefix_len, q.prefix_len + q.src.B);
@@ -1688,6 +1700,7 @@ struct Engine : EngineBase {
             sa.rule_hist = rule_hist + r0 * Tmax; sa.rule_hist_stride = Tmax;
             if (ses.closing) { sa.close_tab = close_dev; sa.rule_close = rule_close + r0; }
         }
+        sa.guard_p = ses.guard_p; sa.guard_r = ses.guard_r;
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
@@ -1700,7 +1713,8 @@ struct Engine : EngineBase {
                 else hipLaunchKernelGGL(beam_select_rules_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
             } else if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
             else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba);
-        } else if (ses.closing) launch_rules_close_step(s, nb, sa, sample_mode != 0);
+        } else if (ses.guarded()) launch_guard_step(s, nb, sa, sample_mode != 0);   // (with or without rules; never closing: generate refuses)
+        else if (ses.closing) launch_rules_close_step(s, nb, sa, sample_mode != 0);
         else if (ses.ruled) launch_rules_step(s, nb, sa, sample_mode != 0);
         else if (ses.forced) launch_prefix_step(s, nb, sa, sample_mode != 0);
         else if (sample_mode) launch_sample_step(s, nb, sa);
@@ -1954,6 +1968,7 @@ struct Engine : EngineBase {
         if (ses.ragged) return false;                                 // a ragged batch decodes with launches (persist.h has no per-row key count)
         if (ses.forced) return false;                                 // so does a prompted decode (persist.h starts at BOS and forces nothing)
         if (ses.ruled) return false;                                  // and a constrained one (persist.h picks without rules)
+        if (ses.guarded()) return false;                              // and a guarded one (persist.h keeps no ban set)
         if (cfg.dec_exp != 4 || cfg.dec_layers > PS_MAXLD) return false;
         const bool exists = (D == 256 && cfg.dec_heads == 8) || (D == 768 && cfg.dec_heads == 12 && sizeof(T) == 2);
         if (!exists) return false;
@@ -2070,6 +2085,7 @@ struct Engine : EngineBase {
         ses.forced = false;                                       // ... and picks every row's token itself: the prefix table belongs to the finished call
         ses.ruled = false;                                        // ... without rules: they bind the generate family only
         ses.closing = false;
+        ses.guard_p = ses.guard_r = 0;                            // ... nor a repeat guard
         rules_rows = (rules_on && rc == 0) ? d.src.B : 0;         // what txo_last_rule_state may read
         if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
@@ -2123,6 +2139,8 @@ struct Engine : EngineBase {
         ses.forced = d.prompted();
         ses.ruled = rules_on;
         ses.closing = closing();
+        ses.guard_p = guard_p; ses.guard_r = guard_r;
+        last_guarded = guard_p > 0;
         if (d.prompted()) {   // the prefix into the engine's table (lengths are in flen: generate), no forced token scored yet
             hipLaunchKernelGGL(prefix_table_kernel, dim3((B * Tmax + 255) / 256), dim3(256), 0, s, ftab, Tmax, q.prefix, q.P, flen, B, V);
             HIP_TRY(hipMemsetAsync(fplogp, 0, sizeof(float) * (size_t)B * Tmax, s));
@@ -2309,8 +2327,11 @@ struct Engine : EngineBase {
             hipLaunchKernelGGL(set_position_kernel, dim3(1), dim3(1), 0, s, st, i);
             StepArgs sa{dlogits, V, B, cur_tok, tokens_out, max_len, d.q.logits, st, eos_seen, flag - i, eos, sample_topk, 1.0f / sample_temp, sample_seed, 0,
                         0, nullptr, d.q.logp};
+            sa.guard_p = ses.guard_p; sa.guard_r = ses.guard_r;
+            if (ses.ruled) { sa.rules = rules_dev; sa.n_states = rules_S; sa.depth_max = rules_dmax; sa.rule_state = rule_state; }
+            if (ses.guarded()) launch_guard_step(s, B, sa, sample_mode != 0);   // (the history is the caller's rows: every token so far stands there)
+            else
             if (ses.ruled) {   // the loop's states carry over (no history beyond the table: the host looks at every token here, nothing runs ahead)
-                sa.rules = rules_dev; sa.n_states = rules_S; sa.depth_max = rules_dmax; sa.rule_state = rule_state;
                 if (ses.closing) { sa.close_tab = close_dev; sa.rule_close = rule_close; launch_rules_close_step(s, B, sa, sample_mode != 0); }
                 else launch_rules_step(s, B, sa, sample_mode != 0);
             } else
@@ -2355,6 +2376,8 @@ struct Engine : EngineBase {
         if (rules_on && !rules_beam)   // (last: every other refusal of the three entries keeps its place; txo_set_rules_beam lifts it)
             return fail(TXO_E_INVALID, "beam search: not available while token rules are set (txo_set_token_rules with rules_host == NULL switches them off)");
         if (int r = close_refusals("beam search", eos, max_len, true)) return r;   // (behind every other refusal, like the one above)
+        if (guard_p > 0)
+            return fail(TXO_E_INVALID, "beam search: not available while a repeat guard is set (txo_set_repeat_guard(e, 0, 0) switches it off)");
         brule_B = brule_k = 0;
         const int rc = beam_impl(src, beams, max_len, eos, sink, n_steps, s);
         if (rules_on && rc == 0) { brule_B = src.B; brule_k = beams; }   // what txo_last_beam_rule_state may read
@@ -2514,6 +2537,7 @@ struct Engine : EngineBase {
         else if (what == TXO_Q_LAST_COMPACTIONS) *out = last_compactions;
         else if (what == TXO_Q_LAST_RAGGED) *out = last_ragged ? 1 : 0;
         else if (what == TXO_Q_LAST_LATENT_SELF) *out = (!last_persist && ses.latent && ses.lat_self) ? 1 : 0;
+        else if (what == TXO_Q_LAST_GUARDED) *out = last_guarded ? 1 : 0;
         else if (what == TXO_Q_SAMPLE_VOCAB_MAX) *out = std::max<int64_t>(64 * SR_PER, (int64_t)(sample_lds_max / sizeof(float)));
         else return fail(TXO_E_INVALID, "unknown query");
         return 0;
@@ -2906,6 +2930,24 @@ int txo_set_rules_close(txo_engine* e, int32_t on) {
     if (!e) return fail(TXO_E_INVALID, "null engine");
     if (on != 0 && on != 1) return fail(TXO_E_INVALID, "txo_set_rules_close: on must be 0 or 1");
     return e->impl->set_rules_close(on != 0);
+}
+
+int txo_set_repeat_guard(txo_engine* e, int32_t max_period, int32_t max_repeats) {
+    if (max_period == 0 && max_repeats == 0) {
+        if (!e) return fail(TXO_E_INVALID, "null engine");
+        e->impl->guard_p = e->impl->guard_r = 0;
+        return 0;
+    }
+    if (max_period < 1 || max_period > GUARD_MAX)
+        return fail(TXO_E_INVALID, "repeat guard: max_period is " + std::to_string(max_period) + "; it must be in [1, " + std::to_string(GUARD_MAX) + "] (0, 0 switches the guard off)");
+    if (max_repeats < 1 || max_repeats > GUARD_MAX)
+        return fail(TXO_E_INVALID, "repeat guard: max_repeats is " + std::to_string(max_repeats) + "; it must be in [1, " + std::to_string(GUARD_MAX) + "] (0, 0 switches the guard off)");
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (e->impl->cfg.vocab <= max_period + 1)
+        return fail(TXO_E_INVALID, "repeat guard: the vocabulary has " + std::to_string(e->impl->cfg.vocab) + " entries; it needs more than max_period + 1 = " +
+                                   std::to_string(max_period + 1) + " (the guard may ban max_period tokens at a pick)");
+    e->impl->guard_p = max_period; e->impl->guard_r = max_repeats;
+    return 0;
 }
 
 int txo_rules_close_dist(txo_engine* e, int32_t* out_host, int32_t S, int32_t D) {

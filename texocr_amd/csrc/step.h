@@ -52,6 +52,8 @@ struct StepArgs {
     // closing decode (txo_set_rules_close; the *_rules_close_step kernels of step_rules.h, null for every other step): the distance table
     // (step_rules.h: CloseTable) and every row's (end position, has committed eos) -- by row of the BATCH, like rule_state
     const void* close_tab; int2* rule_close;
+    // repeat guard (txo_set_repeat_guard; the *_guard_step kernels of step_guard.h, 0 for every other step): max_period and max_repeats
+    int guard_p, guard_r;
 };
 // row of the range (relative to row0) whose outputs slot `row` produces
 __device__ inline int out_row(const StepArgs& a, int row) { return a.row_map ? a.row_map[row] - a.row0 : row; }

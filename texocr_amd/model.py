@@ -40,7 +40,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import _lib, guard, ops
 from .config import Dims
 from .synth import state_dict_layout
 
@@ -99,6 +99,7 @@ class HipEngine:
         self.handle = h
         self.loaded = False
         self.token_rules = None                      # (a new handle has no token rules: a set installed by hand goes with the old one)
+        self.repeat_guard = None                     # (... and no repeat guard)
         if getattr(self, "_ragged_hybrid", False):   # (a reload of the weights makes a new handle: the switch follows the engine object)
             _lib.check(self.lib.txo_set_ragged_hybrid(h, 1))
         if getattr(self, "_rules_beam", False):
@@ -330,14 +331,23 @@ class HipEngine:
         """(B, 2) int32: the (state, depth) of every row behind the last constrained generate, beside its tokens (B, n)"""
         return torch.ops.texocr.last_rule_state(tokens if tokens.ndim == 2 else tokens[None, :], self.id)
 
+    def set_repeat_guard(self, repeat_guard) -> None:
+        """txo_set_repeat_guard: (max_period, max_repeats) (checked on the host first, texocr_amd.guard.check: the same refusals), or None =
+        off.  While set, every generate from BOS or a prefix picks under the guard, on the launch path; beam search and close=True raise."""
+        self._ensure()
+        g = guard.check(repeat_guard, self.dims.vocab)
+        torch.ops.texocr.set_repeat_guard(self.id, *(g or (0, 0)))
+
     @contextlib.contextmanager
     def modes(self, sample: Optional[Tuple[float, Optional[int]]] = None, stop: str = "global", decode: Optional[str] = None, rules=None,
-              close: bool = False):
+              close: bool = False, repeat_guard=None):
         """The engine's global switches around the calls of one generate: sampling with sample = (temp, seed) -- a seed of None is
         drawn from torch's generator; decode='greedy' overrides it --, per-row stop, and token rules (rules=: a TokenRules installed for the
         scope; the set that was installed before, or none, is back behind every exit).  Nothing else in this module turns sampling or the
         per-row stop on, and both are off again behind every exit.  Yields (temp, seed) as set, or None.
-        close=True (only with rules=, ValueError otherwise): the closing decode (txo_set_rules_close) for the scope, off again behind it."""
+        close=True (only with rules=, ValueError otherwise): the closing decode (txo_set_rules_close) for the scope, off again behind it.
+        repeat_guard=(max_period, max_repeats): the repeat guard (txo_set_repeat_guard) for the scope; the one set before, or none, is back
+        behind every exit."""
         _check_modes(stop, decode or "greedy")
         if close not in (False, True, 0, 1):
             raise ValueError("close must be False or True")
@@ -348,7 +358,10 @@ class HipEngine:
         if sample is not None and sample[1] is None:
             sample = (sample[0], int(torch.randint(0, 2**62, (1,)).item()))
         before = getattr(self, "token_rules", None)                # what ops.set_token_rules recorded: (table, depth_max) or None
+        guard_before = getattr(self, "repeat_guard", None)         # what ops.set_repeat_guard recorded: (P, R) or None
         try:
+            if repeat_guard is not None:
+                self.set_repeat_guard(repeat_guard)
             if rules is not None:
                 self.set_token_rules(rules)
             if close:                                              # (behind the rules: the engine computes its table here, or refuses)
@@ -359,6 +372,8 @@ class HipEngine:
                 self.set_stop_mode("row")
             yield sample
         finally:
+            if repeat_guard is not None:
+                torch.ops.texocr.set_repeat_guard(self.id, *(guard_before or (0, 0)))
             if sample is not None:
                 self.set_sampling(False)
             if stop == "row":
@@ -823,6 +838,8 @@ class AutoRegressiveDecoder(nn.Module):
         # int32 as its last element.  Needs the engine's own loop: a BOS start or the prompted route, not the stepwise one.
         rules = kwargs.pop("rules", None)
         close = kwargs.pop("close", False)                         # build extension, with rules=: the closing decode (OCRModel.generate)
+        # build extension: (max_period, max_repeats), the repeat guard (OCRModel.generate).  Needs the engine's own loop, like rules=
+        repeat_guard = kwargs.pop("repeat_guard", None)
         rstate = None
         if kwargs:
             raise ValueError(f"unsupported arguments: {sorted(kwargs)}")
@@ -855,7 +872,7 @@ class AutoRegressiveDecoder(nn.Module):
             prompted = True
             if return_logits:
                 raise ValueError("return_logits is not available with prefix_len (a prompted decode keeps no logits)")
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close) as sample:
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard) as sample:
             if prompted:
                 out = eng.generate_prefix(None, st.to(enc.device), max_len, eos_tok, prefix_len=prefix_len, enc=enc, return_logp=return_logp)
                 if rules is not None:
@@ -878,6 +895,9 @@ class AutoRegressiveDecoder(nn.Module):
             if rules is not None and not engine_loop:
                 raise ValueError("rules= needs the engine's own loop: a start the prompted decode or a BOS start can take (no padding mask; beyond "
                                  "decoder.max_len a vocabulary that is a multiple of 8 and max_length <= max_batch * max_tokens)")
+            if repeat_guard is not None and not engine_loop:
+                raise ValueError("repeat_guard= needs the engine's own loop: a start the prompted decode or a BOS start can take (no padding mask; "
+                                 "beyond decoder.max_len a vocabulary that is a multiple of 8 and max_length <= max_batch * max_tokens)")
             if padded:
                 if return_logits or return_logp:
                     raise ValueError("return_logits / return_logp are not available with a padding mask")
@@ -1046,8 +1066,14 @@ class OCRModel(nn.Module):
     def generate(self, src: torch.Tensor, max_len: int, temp: float = 0.3, *, decode: str = "greedy",
                  generator: Optional[torch.Generator] = None, seed: Optional[int] = None, return_logits: bool = False,
                  beam: int = 0, return_beams: bool = False, stop: str = "global", return_logp: bool = False,
-                 prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None, close: bool = False):
-        """close=True (build extension, only with rules=; ValueError otherwise): the closing decode, for this call.  A row may only pick a
+                 prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None, close: bool = False, repeat_guard=None):
+        """repeat_guard=(max_period, max_repeats) (build extension; both in [1, 16]): the repeat guard, for this call.  No row may end in
+        max_repeats + 1 consecutive copies of a block of at most max_period tokens: the token that would complete such a run is masked in
+        the selection like a rule-disallowed one (texocr_amd.guard.banned is the rule; the history is the prefix's tokens behind its start
+        token, then the row's picks).  eos is never banned, a prefix token never masked; logp and logits stay those of the raw logits.  With
+        rules=: a token must be allowed and unbanned, and where none is the ban is dropped for that pick.  The decode runs on the launch
+        path.  Refused (ValueError): with close=True, with beam=, out-of-range values, a vocabulary of at most max_period + 1 entries.
+        close=True (build extension, only with rules=; ValueError otherwise): the closing decode, for this call.  A row may only pick a
         token from which its rules can still reach eos in the positions it has left (rules.TokenRules.allowed(remaining=) is the rule), so
         every row ends at an eos its rules allow -- under rules.brace_rules: balanced and finished inside max_len.  The one exception of a
         row is a forced prefix too deep to close in max_len: it closes as far as it gets and rule_state shows the rest.  Refused
@@ -1070,7 +1096,7 @@ class OCRModel(nn.Module):
         _check_modes(stop)
         if prefix is not None:
             return self._generate_prefix(src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules,
-                                         close)
+                                         close, repeat_guard)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
         if beam and return_logp:
@@ -1078,7 +1104,7 @@ class OCRModel(nn.Module):
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
             if max_len > self.decoder.max_len:
                 raise ValueError(f"beam search needs max_len <= decoder.max_len ({self.decoder.max_len})")
-            with self._engine.modes(rules=rules, close=close):     # (with rules the engine refuses unless rules_beam is on)
+            with self._engine.modes(rules=rules, close=close, repeat_guard=repeat_guard):   # (with rules the engine refuses unless rules_beam is on; with a guard, always)
                 if rules is None:
                     return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
                 toks, scores = self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=True)
@@ -1087,7 +1113,7 @@ class OCRModel(nn.Module):
         if decode == "greedy" and self.bos_token == self._engine.dims.bos:
             # (max_len > decoder.max_len: txo_generate slides the window like the reference, decoder.py:99-100)
             # (stop='row' with return_logits: the engine does not compact -- a finished row's logits would be missing -- and only pads)
-            with self._engine.modes(stop=stop, rules=rules, close=close):
+            with self._engine.modes(stop=stop, rules=rules, close=close, repeat_guard=repeat_guard):
                 out = self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits, return_logp=return_logp)
                 if rules is None:
                     return out
@@ -1098,10 +1124,11 @@ class OCRModel(nn.Module):
         return self.decoder.generate(start_tokens=start, eos_tok=self.eos_token, max_len=max_len, temp=temp,
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
                                      stop=stop, pad=self.trg_pad_idx, return_logp=return_logp,
-                                     **({} if rules is None and not close else {"rules": rules, "close": close}))
+                                     **({} if rules is None and not close else {"rules": rules, "close": close}),
+                                     **({} if repeat_guard is None else {"repeat_guard": repeat_guard}))
 
     def _generate_prefix(self, src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules=None,
-                         close=False):
+                         close=False, repeat_guard=None):
         """generate(prefix=) / generate_ragged(prefix=): src a (B, C, H, W) tensor or a sequence of images.  Every refusal comes before
         the engine is touched."""
         if beam:
@@ -1120,7 +1147,7 @@ class OCRModel(nn.Module):
         if seed is None and generator is not None:
             seed = generator.initial_seed()
         dev = src[0].device if isinstance(src, (list, tuple)) else src.device           # (a tensor or a PackedImages says it itself)
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close):
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard):
             out = eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
             if rules is None:
                 return out
@@ -1152,7 +1179,7 @@ class OCRModel(nn.Module):
 
     @torch.no_grad()
     def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0, rules=None,
-                    close: bool = False) -> Beams:
+                    close: bool = False, repeat_guard=None) -> Beams:
         """Build extension: the k = beams best sequences of every image, with score, length and (return_logp=True) the log-probability of
         every token -> Beams.  src is a (B, C, H, W) tensor, or a sequence of (C, H_b, W_b) tensors of different sizes: those go
         through ONE ragged encode and ONE decode, and the beams of image b are what beam_search(src[b][None]) returns, over the batch's n.
@@ -1165,7 +1192,8 @@ class OCRModel(nn.Module):
         Beams.rule_state holds every beam's state.  No closure guarantee: a beam that runs out of positions may end at depth > 0.
         close=True (only with rules=): the closing search, generate(close=True)'s budget inside the selection with R = max_len - position: a
         hypothesis that could no longer reach eos never holds a slot, so every LIVE beam ends finished (under brace_rules: balanced) and
-        lengths <= max_len; dead beams stay outside every guarantee."""
+        lengths <= max_len; dead beams stay outside every guarantee.
+        repeat_guard=: refused (ValueError) -- the repeat guard binds generate() only."""
         if isinstance(src, torch.Tensor):
             if src.ndim != 4:
                 raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
@@ -1175,25 +1203,26 @@ class OCRModel(nn.Module):
         else:
             raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
         check_beam_args(beams, max_len, length_alpha, n_images, self.decoder.max_len, self._engine.max_batch)
-        with self._engine.modes(rules=rules, close=close):         # rules=: the engine refuses (ValueError) unless rules_beam is on
+        with self._engine.modes(rules=rules, close=close, repeat_guard=repeat_guard):   # rules=: the engine refuses (ValueError) unless rules_beam is on
             out = self._engine.beam_search(src, beams, max_len, self.eos_token, return_logp=return_logp, length_alpha=length_alpha)
             return Beams(*out, self._engine.last_beam_rule_state(out[0]) if rules is not None else None)
 
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
                         stop: str = "global", return_logp: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None,
-                        close: bool = False):
+                        close: bool = False, repeat_guard=None):
         """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
         is keyed by the row of the batch).  max_len may exceed decoder.max_len: the window slides as in generate(), under the engine's
         two preconditions (a vocabulary that is a multiple of 8, max_length <= max_batch * max_tokens; ValueError before anything is
-        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them.  prefix= / prefix_len= / rules= / close=: as generate()
-        takes them (rules=: rule_state (B, 2) is the result's last element)."""
+        decoded otherwise).  return_logp=True: (tokens, logp) as generate() returns them.  prefix= / prefix_len= / rules= / close= /
+        repeat_guard=: as generate() takes them (rules=: rule_state (B, 2) is the result's last element)."""
         if prefix is not None:
-            return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len, rules, close)
+            return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len, rules, close,
+                                         repeat_guard)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
-        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close):
+        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard):
             out = self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
             if rules is None:
                 return out

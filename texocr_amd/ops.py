@@ -22,6 +22,8 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
                             of every produced token, taken from the token selection itself (no second pass, no (B, T, V) tensor)
   texocr::set_rules_beam / last_beam_rule_state
                             (build extension, opt-in) beam search under token rules (texocr::set_token_rules) and the beams' rule states
+  texocr::set_repeat_guard  (build extension, opt-in) the repeat guard: a row of the generate family may not end in max_repeats + 1 copies of a
+                            block of at most max_period tokens (texocr_amd/guard.py is the rule in numpy)
   texocr::set_rules_close   (build extension, opt-in) the closing decode: a constrained decode or beam search only picks tokens from which
                             eos can still be reached in the positions left (``rules_close_dist`` reads the engine's distance table)
   texocr::encode_ragged / decode_begin_ragged / generate_ragged / score_ragged
@@ -822,6 +824,22 @@ def set_rules_close(engine: int, on: bool) -> None:
 
 @set_rules_close.register_fake
 def _(engine, on):
+    return None
+
+
+# ---- repeat guard (txo_set_repeat_guard): no row of the generate family ends in max_repeats + 1 copies of a block of <= max_period tokens ----
+@custom_op("texocr::set_repeat_guard", mutates_args=())
+def set_repeat_guard(engine: int, max_period: int, max_repeats: int) -> None:
+    """txo_set_repeat_guard: (max_period, max_repeats), both in [1, 16]; (0, 0): off (the default).  The engine names what it refuses
+    (ValueError).  ``engine.repeat_guard`` records what is set."""
+    e = _eng(engine)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_set_repeat_guard(e.handle, int(max_period), int(max_repeats)))
+    e.repeat_guard = (int(max_period), int(max_repeats)) if max_period or max_repeats else None
+
+
+@set_repeat_guard.register_fake
+def _(engine, max_period, max_repeats):
     return None
 
 

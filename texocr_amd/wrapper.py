@@ -65,8 +65,10 @@ def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.T
 
 class TeXOCRWrapper:
     def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False, balanced: bool = False,
-                 rules_beam: bool = False, close: bool = False):
-        """ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)
+                 rules_beam: bool = False, close: bool = False, repeat_guard=None):
+        """repeat_guard=(max_period, max_repeats) (build extension): every __call__ / batch decodes under the repeat guard unless the call says
+        otherwise (see batch)
+        ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)
         balanced=True (build extension): every __call__ / batch decodes under the brace rule of this tokenizer unless the call says otherwise
         (see batch)
         rules_beam=True (build extension): decode='beam' accepts balanced=True -- the brace rule inside the beam selection
@@ -74,6 +76,8 @@ class TeXOCRWrapper:
         close=True (build extension; only together with balanced): balanced decodes are closing decodes unless the call says otherwise (see batch)"""
         self.balanced = bool(balanced)
         self.close = bool(close)
+        from . import guard
+        self.repeat_guard = guard.check(repeat_guard)
         self._brace_rules = None
         self.tokenizer = RegExTokenizer()
         self.tokenizer.load(config["tokenizer_path"])                                # ocr_model.py:74-75
@@ -110,6 +114,15 @@ class TeXOCRWrapper:
         if on and rules is None:
             raise ValueError("close=True needs balanced=True: the closing decode is a budget on top of the brace rule")
         return {"close": True} if on else {}
+
+    def _guard(self, repeat_guard, decode: str) -> dict:
+        """the repeat_guard= of a call as keyword arguments: the call's own (False: none), else the wrapper's"""
+        g = self.repeat_guard if repeat_guard is None else (repeat_guard or None)
+        if g is None:
+            return {}
+        if decode == "beam":
+            raise ValueError("repeat_guard is not available with decode='beam' (the repeat guard binds generate() only)")
+        return {"repeat_guard": g}
 
     def _tensor(self, img) -> torch.Tensor:
         x = preprocess_image(img, self.dims.patch)
@@ -198,7 +211,7 @@ class TeXOCRWrapper:
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
               length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host", fit: str = "none",
               trim: str = "none", trim_level: int = 127, trim_margin: int = 2, balanced: Optional[bool] = None,
-              close: Optional[bool] = None) -> List[tuple]:
+              close: Optional[bool] = None, repeat_guard=None) -> List[tuple]:
         """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
@@ -233,9 +246,12 @@ class TeXOCRWrapper:
         rules_beam=True: the rule then binds inside the beam selection, and a best beam that finished is balanced by construction.
         close=True (build extension; with balanced=True only; default: the wrapper's own setting): the closing decode
         (OCRModel.generate_ragged(close=True)) -- a row only picks tokens from which it can still close its groups and reach eos inside
-        max_len, so every row ends balanced and finished; with a prefix too deep to close in max_len it closes as far as it gets."""
+        max_len, so every row ends balanced and finished; with a prefix too deep to close in max_len it closes as far as it gets.
+        repeat_guard=(max_period, max_repeats) (build extension; default: the wrapper's own setting; False: none): the repeat guard
+        (OCRModel.generate_ragged(repeat_guard=)) -- no row ends in max_repeats + 1 consecutive copies of a block of at most max_period
+        tokens; texocr_amd.guard.hits flags the rows of an unguarded decode that looped.  Not with decode='beam' or close=True."""
         rules = self._rules(balanced, decode)
-        ckw = self._close(close, rules)
+        ckw = {**self._close(close, rules), **self._guard(repeat_guard, decode)}
         rule = self._trim_rule(trim, trim_level, trim_margin)
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
@@ -275,7 +291,7 @@ class TeXOCRWrapper:
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
                  length_alpha: float = 0.0, prefix=None, ingest: str = "host", fit: str = "none", trim: str = "none", trim_level: int = 127,
-                 trim_margin: int = 2, balanced: Optional[bool] = None, close: Optional[bool] = None) -> tuple:
+                 trim_margin: int = 2, balanced: Optional[bool] = None, close: Optional[bool] = None, repeat_guard=None) -> tuple:
         """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
@@ -288,9 +304,10 @@ class TeXOCRWrapper:
         fit='canvas': an image beyond the canvas is downscaled to fit it first (see batch); the maps of return_align are then on the
         fitted grid.
         trim='ink': the image is cut to its ink and a margin first (see batch), before the fit; the maps are on the trimmed image's grid.
-        balanced=True: the decode picks under the tokenizer's brace rule (see batch).  close=True: as a closing decode (see batch)."""
+        balanced=True: the decode picks under the tokenizer's brace rule (see batch).  close=True: as a closing decode (see batch).
+        repeat_guard=(max_period, max_repeats): under the repeat guard (see batch)."""
         rules = self._rules(balanced, decode)
-        ckw = self._close(close, rules)
+        ckw = {**self._close(close, rules), **self._guard(repeat_guard, decode)}
         x = self._images([img], ingest, fit, self._trim_rule(trim, trim_level, trim_margin))
         x = x.box if ingest == "device" else x[0][None]
         prow: List[int] = []
