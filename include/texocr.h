@@ -539,8 +539,25 @@ int txo_rules_close_dist(txo_engine* e, int32_t* out_host, int32_t S, int32_t D)
  * Refused with TXO_E_INVALID: max_period or max_repeats out of range; cfg.vocab <= max_period + 1 (the guard may ban max_period tokens at a
  * pick); by txo_generate*, behind every other refusal of the entry, while the closing decode is in effect (token rules and
  * txo_set_rules_close: its guarantee and the guard's ban can conflict), and in sampling mode when vocab * 4 + vocab / 8 bytes exceed the
- * 64 KB of LDS the guarded LDS-form sampler may use; by txo_generate_beam / txo_beam_search / txo_beam_search_ragged while a guard is set. */
+ * 64 KB of LDS the guarded LDS-form sampler may use; by txo_generate_beam / txo_beam_search / txo_beam_search_ragged while a guard is set,
+ * unless txo_set_guard_beam(e, 1) is in effect (below). */
 int txo_set_repeat_guard(txo_engine* e, int32_t max_period, int32_t max_repeats);
+
+/* Repeat guard inside beam search, a BUILD EXTENSION and opt-in: txo_set_guard_beam(e, 1) (default 0; TXO_E_INVALID unless on is 0 or 1).  Off,
+ * the three beam entries refuse while a guard is set, as above and in the same words.  On, they run the guarded selection
+ * (texocr_amd/csrc/beam_guard.h) and TXO_Q_LAST_GUARDED reads 1 behind them (0 behind a beam entry without a guard).
+ * Slot j of an image at position t has the history h[0 .. t-1] of the tokens its ancestry committed, and its ban set is the rule above on
+ * that history.  For a live, unfinished parent j the candidate (j, v) is score[j] + (logit[j][v] - lse[j]) iff v is allowed and not
+ * banned for j, -INFINITY otherwise.  "Allowed": every token without rules; the rule of txo_set_token_rules under rules (which need
+ * txo_set_rules_beam as ever); the budgeted rule under txo_set_rules_close.  THE YIELD RULE: a parent with no token both allowed and unbanned
+ * drops its ban at that pick, and the rules, or the budget, decide alone.  The guard therefore only shrinks a non-empty allowed set to a
+ * non-empty one: a closing beam search keeps its guarantee (every live beam ends finished and balanced), which is why the guard is accepted
+ * there while txo_generate* with a closing decode still refuses it.  eos is never banned; a finished parent offers eos at + 0, unmasked;
+ * scores and logp stay sums of the RAW row's log-probabilities; dead slots, tie order and txo_last_beam_rule_state are the constrained
+ * search's.  With the guard off, or the switch off, a beam search runs the kernels it ran before.
+ * Refused with TXO_E_INVALID, behind every other refusal of the entry: beams * (vocab / 8 + ((max_repeats + 1) * max_period - 1) * 4) bytes
+ * beyond the 56 KB of LDS the guarded selection may use (the message names the vocabulary). */
+int txo_set_guard_beam(txo_engine* e, int32_t on);
 
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
@@ -570,7 +587,8 @@ int txo_profile_read(txo_engine* e, int32_t kind, double* avg_ms, int64_t* count
 #define TXO_Q_LAST_RAGGED 7        /* 1 if the last generate decoded a ragged batch (per-image encoder token counts), 0 otherwise */
 #define TXO_Q_LAST_LATENT_SELF 8   /* 1 if the last generate's SELF attention ran in latent form too (TXO_LATENT_SELF=1: the history is z, not k / v);
                                     * 0 where the engine declined it (no latent form, per-row stop, a positional table beyond the beam slot table) */
-#define TXO_Q_LAST_GUARDED 9       /* 1 if the last txo_generate* picked under a repeat guard (txo_set_repeat_guard), 0 otherwise */
+#define TXO_Q_LAST_GUARDED 9       /* 1 if the last txo_generate* picked under a repeat guard (txo_set_repeat_guard), 0 otherwise; with txo_set_guard_beam on,
+                                    * also set by the beam entries: 1 behind a guarded beam search, 0 behind one without a guard */
 int txo_engine_query(txo_engine* e, int32_t what, int64_t* out);
 
 const char* txo_last_error(void);

@@ -83,6 +83,7 @@ SYMBOLS = {
     "txo_set_rules_close": (C.c_int, [_P, _I]),
     "txo_rules_close_dist": (C.c_int, [_P, C.c_void_p, _I, _I]),
     "txo_set_repeat_guard": (C.c_int, [_P, _I, _I]),
+    "txo_set_guard_beam": (C.c_int, [_P, _I]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),
     "txo_set_ragged_hybrid": (C.c_int, [_P, _I]),
     "txo_profile_enable": (C.c_int, [_P, _I]),

@@ -52,6 +52,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "step_guard.h"    // (the repeat guard's token selection: step_rules.h with a ban on the block a row has just repeated; last again)
 #include "beam_rules.h"    // (the constrained beam selection: step.h's beam kernels with that automaton; last again)
 #include "rules_close.h"   // (host only: the closing decode's distance table)
+#include "beam_guard.h"    // (the repeat guard inside the beam selection: beam_rules.h with step_guard.h's ban; last again)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -107,6 +108,8 @@ struct EngineBase {
     virtual int last_rule_state(int32_t* out, int B, hipStream_t s) = 0;
     // txo_set_rules_beam (beam_rules.h): while on, a beam search under token rules runs the constrained selection instead of being refused
     bool rules_beam = false;
+    // txo_set_guard_beam (beam_guard.h): while on, a beam search under a repeat guard runs the guarded selection instead of being refused
+    bool guard_beam = false;
     int brule_B = 0, brule_k = 0;               // images / beams of the last constrained beam search (txo_last_beam_rule_state), 0: none since the rules were set
     virtual int last_beam_rule_state(int32_t* out, int B, int beams, hipStream_t s) = 0;
     // txo_set_rules_close (rules_close.h; the closing kernels of step_rules.h / beam_rules.h): while on, a constrained decode or beam search
@@ -265,7 +268,7 @@ struct Engine : EngineBase {
     float* blogp = nullptr;                // [Tmax][Bmax] beside btok: the selected candidates' increments (txo_beam_search with logp)
     int2* brule_state = nullptr;           // [Bmax] constrained beam search (beam_rules.h): the (state, depth) of every (image, beam) slot
     // logp: the step also records blogp; ruled: beam_rules.h's selection; closing: its closing form over `positions` positions
-    struct BeamCtx { int k; const short* path_cur; short* path_nxt; bool logp = false; bool ruled = false; bool closing = false; int positions = 0; };
+    struct BeamCtx { int k; const short* path_cur; short* path_nxt; bool logp = false; bool ruled = false; bool closing = false; int positions = 0; int guard_p = 0, guard_r = 0; };
     // ----- profiling -----
     bool prof = false;                // full: per-launch cross-attention events + markers around every encode and step
     bool prof_cross = false;          // light: only the cross-attention dispatches carry events (no extra packets)
@@ -1704,7 +1707,11 @@ struct Engine : EngineBase {
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
-            if (bm->ruled) {   // constrained beam search: the table, and the range's slice of the slots' states (range-local, like every pointer of ba)
+            if (bm->guard_p > 0) {   // guarded beam search (beam_guard.h): one kernel, with or without the rules and the budget
+                const BeamRuleArgs ra{bm->ruled ? rules_dev : nullptr, bm->ruled ? rules_S : 0, bm->ruled ? rules_dmax : 0, bm->ruled ? brule_state + r0 : nullptr};
+                const BeamCloseArgs ca{bm->closing ? close_dev : nullptr, bm->positions};
+                launch_beam_guard(s, ba, ra, ca, BeamGuardArgs{bm->guard_p, bm->guard_r}, bm->logp);
+            } else if (bm->ruled) {   // constrained beam search: the table, and the range's slice of the slots' states (range-local, like every pointer of ba)
                 const BeamRuleArgs ra{rules_dev, rules_S, rules_dmax, brule_state + r0};
                 const BeamCloseArgs ca{close_dev, bm->positions};
                 if (bm->closing && bm->logp) hipLaunchKernelGGL(beam_select_close_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra, ca);
@@ -2376,8 +2383,12 @@ struct Engine : EngineBase {
         if (rules_on && !rules_beam)   // (last: every other refusal of the three entries keeps its place; txo_set_rules_beam lifts it)
             return fail(TXO_E_INVALID, "beam search: not available while token rules are set (txo_set_token_rules with rules_host == NULL switches them off)");
         if (int r = close_refusals("beam search", eos, max_len, true)) return r;   // (behind every other refusal, like the one above)
-        if (guard_p > 0)
+        if (guard_p > 0 && !guard_beam)   // (txo_set_guard_beam lifts it)
             return fail(TXO_E_INVALID, "beam search: not available while a repeat guard is set (txo_set_repeat_guard(e, 0, 0) switches it off)");
+        if (guard_p > 0 && beam_guard_lds_bytes(beams, V, guard_p, guard_r) > BEAM_GUARD_LDS_MAX)
+            return fail(TXO_E_INVALID, "beam search: the vocabulary does not fit the guarded selection's LDS (beams * (vocab / 8 bytes + ((max_repeats + 1) * max_period - 1) * 4 bytes) "
+                                       "per workgroup, 56 KB; the vocabulary has " + std::to_string(V) + " entries)");
+        if (guard_beam) last_guarded = guard_p > 0;               // (off: a beam entry leaves TXO_Q_LAST_GUARDED as it was, as it always did)
         brule_B = brule_k = 0;
         const int rc = beam_impl(src, beams, max_len, eos, sink, n_steps, s);
         if (rules_on && rc == 0) { brule_B = src.B; brule_k = beams; }   // what txo_last_beam_rule_state may read
@@ -2421,7 +2432,7 @@ struct Engine : EngineBase {
         int cur = 0;
         auto beam_loop = [&]() -> int {
         for (int t = 0; t < max_len; ++t) {
-            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1], want_logp, ruled, ruled && rules_close, max_len};
+            BeamCtx bm{beams, bpath[cur], bpath[cur ^ 1], want_logp, ruled, ruled && rules_close, max_len, guard_p, guard_r};   // (a guard set here has passed beam_search: txo_set_guard_beam is on)
             for (int i = 0; i < lanes.n; ++i)
                 if (int r2 = enqueue_step(lanes[i].stream, i, nullptr, 0, nullptr, nullptr, eos, &bm, t)) return r2;
             cur ^= 1;
@@ -2918,6 +2929,13 @@ int txo_set_rules_beam(txo_engine* e, int32_t on) {
     if (!e) return fail(TXO_E_INVALID, "null engine");
     if (on != 0 && on != 1) return fail(TXO_E_INVALID, "txo_set_rules_beam: on must be 0 or 1");
     e->impl->rules_beam = on != 0;
+    return 0;
+}
+
+int txo_set_guard_beam(txo_engine* e, int32_t on) {
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (on != 0 && on != 1) return fail(TXO_E_INVALID, "txo_set_guard_beam: on must be 0 or 1");
+    e->impl->guard_beam = on != 0;
     return 0;
 }
 

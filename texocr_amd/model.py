@@ -104,6 +104,8 @@ class HipEngine:
             _lib.check(self.lib.txo_set_ragged_hybrid(h, 1))
         if getattr(self, "_rules_beam", False):
             _lib.check(self.lib.txo_set_rules_beam(h, 1))
+        if getattr(self, "_guard_beam", False):
+            _lib.check(self.lib.txo_set_guard_beam(h, 1))
         self._env_seen = self._txo_env()             # what the engine saw when it read its knobs
 
     @staticmethod
@@ -333,7 +335,7 @@ class HipEngine:
 
     def set_repeat_guard(self, repeat_guard) -> None:
         """txo_set_repeat_guard: (max_period, max_repeats) (checked on the host first, texocr_amd.guard.check: the same refusals), or None =
-        off.  While set, every generate from BOS or a prefix picks under the guard, on the launch path; beam search and close=True raise."""
+        off.  While set, every generate from BOS or a prefix picks under the guard, on the launch path; close=True raises there, and beam search raises unless guard_beam is on."""
         self._ensure()
         g = guard.check(repeat_guard, self.dims.vocab)
         torch.ops.texocr.set_repeat_guard(self.id, *(g or (0, 0)))
@@ -413,6 +415,20 @@ class HipEngine:
             raise ValueError("rules_beam must be False or True")
         torch.ops.texocr.set_rules_beam(self.id, bool(on))
         self._rules_beam = bool(on)
+
+    @property
+    def guard_beam(self) -> bool:
+        """txo_set_guard_beam: beam search under a repeat guard.  False (the default): every beam call raises ValueError while a guard is
+        set, as before the search had a guarded form.  True: it runs with the ban inside the beam selection (csrc/beam_guard.h).
+        No effect on a beam search without a guard."""
+        return getattr(self, "_guard_beam", False)
+
+    @guard_beam.setter
+    def guard_beam(self, on) -> None:
+        if on not in (False, True, 0, 1):
+            raise ValueError("guard_beam must be False or True")
+        torch.ops.texocr.set_guard_beam(self.id, bool(on))
+        self._guard_beam = bool(on)
 
     def last_beam_rule_state(self, tokens: torch.Tensor) -> torch.Tensor:
         """(B, beams, 2) int32: the (state, depth) of every beam of the last constrained beam search, beside its tokens (B, beams, n)"""
@@ -1027,6 +1043,15 @@ class OCRModel(nn.Module):
     def rules_beam(self, on) -> None:
         self._engine.rules_beam = on
 
+    @property
+    def guard_beam(self) -> bool:
+        """Build extension: accept repeat_guard= in beam_search and generate(beam=k) (HipEngine.guard_beam); off by default."""
+        return self._engine.guard_beam
+
+    @guard_beam.setter
+    def guard_beam(self, on) -> None:
+        self._engine.guard_beam = on
+
     # ---- weights: the reference's state_dict layout, aliases included ----
     def _export_weights(self) -> Dict[str, torch.Tensor]:
         return dict(self.state_dict())
@@ -1072,7 +1097,9 @@ class OCRModel(nn.Module):
         the selection like a rule-disallowed one (texocr_amd.guard.banned is the rule; the history is the prefix's tokens behind its start
         token, then the row's picks).  eos is never banned, a prefix token never masked; logp and logits stay those of the raw logits.  With
         rules=: a token must be allowed and unbanned, and where none is the ban is dropped for that pick.  The decode runs on the launch
-        path.  Refused (ValueError): with close=True, with beam=, out-of-range values, a vocabulary of at most max_period + 1 entries.
+        path.  Refused (ValueError): with close=True outside beam search, out-of-range values, a vocabulary of at most max_period + 1
+        entries.  With beam=: the engine's refusal (ValueError) unless guard_beam is on; then every beam is held to the guard on its own
+        history inside the beam selection, also beside close=True (see beam_search).
         close=True (build extension, only with rules=; ValueError otherwise): the closing decode, for this call.  A row may only pick a
         token from which its rules can still reach eos in the positions it has left (rules.TokenRules.allowed(remaining=) is the rule), so
         every row ends at an eos its rules allow -- under rules.brace_rules: balanced and finished inside max_len.  The one exception of a
@@ -1104,7 +1131,7 @@ class OCRModel(nn.Module):
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
             if max_len > self.decoder.max_len:
                 raise ValueError(f"beam search needs max_len <= decoder.max_len ({self.decoder.max_len})")
-            with self._engine.modes(rules=rules, close=close, repeat_guard=repeat_guard):   # (with rules the engine refuses unless rules_beam is on; with a guard, always)
+            with self._engine.modes(rules=rules, close=close, repeat_guard=repeat_guard):   # (with rules the engine refuses unless rules_beam is on; with a guard, unless guard_beam is)
                 if rules is None:
                     return self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=return_beams)
                 toks, scores = self._engine.generate_beam(src, beam, max_len, self.eos_token, return_beams=True)
@@ -1193,7 +1220,11 @@ class OCRModel(nn.Module):
         close=True (only with rules=): the closing search, generate(close=True)'s budget inside the selection with R = max_len - position: a
         hypothesis that could no longer reach eos never holds a slot, so every LIVE beam ends finished (under brace_rules: balanced) and
         lengths <= max_len; dead beams stay outside every guarantee.
-        repeat_guard=: refused (ValueError) -- the repeat guard binds generate() only."""
+        repeat_guard=(max_period, max_repeats) (build extension): with guard_beam off (the default) the engine refuses (ValueError).  On: the
+        repeat guard inside the selection.  Every beam's ban set is texocr_amd.guard.banned on the tokens ITS ancestry committed; a banned
+        candidate counts as -inf like a rule-disallowed one, eos is never banned, scores and logp stay sums of the raw log-probabilities.
+        Beside rules= (rules_beam on as well) a candidate must be allowed and unbanned; a beam that has no such token drops its ban at that
+        pick (the yield rule), so with close=True every live beam still ends finished."""
         if isinstance(src, torch.Tensor):
             if src.ndim != 4:
                 raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
@@ -1293,26 +1324,29 @@ class OCRModel(nn.Module):
 
 
 def _assemble(dims: Dims, dtype: str, max_batch: int, max_tokens: int, device: torch.device, ragged_hybrid: bool = False,
-              rules_beam: bool = False) -> OCRModel:
+              rules_beam: bool = False, guard_beam: bool = False) -> OCRModel:
     eng = HipEngine(dims, dtype=dtype, max_batch=max_batch, max_tokens=max_tokens)
     if ragged_hybrid:
         eng.ragged_hybrid = True
     if rules_beam:
         eng.rules_beam = True
+    if guard_beam:
+        eng.guard_beam = True
     shared: Dict[str, nn.Parameter] = {}
     return OCRModel(VisionEncoder(eng, shared), AutoRegressiveDecoder(eng, shared), dims.bos, dims.eos, dims.pad, device)
 
 
 def create_model(config: dict, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0, ragged_hybrid: bool = False,
-                 rules_beam: bool = False) -> OCRModel:
+                 rules_beam: bool = False, guard_beam: bool = False) -> OCRModel:
     """create_model(config) (ocr_model.py:113-130).  As in the reference the model comes back with default-initialised
     parameters; load_state_dict replaces them.  ragged_hybrid=True (build extension): the model's ragged calls work on the hybrid
-    front end (OCRModel.ragged_hybrid).  rules_beam=True (build extension): beam search accepts rules= (OCRModel.rules_beam)."""
+    front end (OCRModel.ragged_hybrid).  rules_beam=True (build extension): beam search accepts rules= (OCRModel.rules_beam).
+    guard_beam=True (build extension): beam search accepts repeat_guard= (OCRModel.guard_beam)."""
     dims = Dims.from_config(config)
     device = torch.device(config.get("device", "cuda"))
     if device.type != "cuda":
         device = torch.device("cuda")
-    return _assemble(dims, dtype, max_batch, max_tokens, device, ragged_hybrid, rules_beam)
+    return _assemble(dims, dtype, max_batch, max_tokens, device, ragged_hybrid, rules_beam, guard_beam)
 
 
 def model_from_dims(dims: Dims, dtype: str = "fp32", max_batch: int = 64, max_tokens: int = 0) -> OCRModel:

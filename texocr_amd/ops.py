@@ -22,6 +22,7 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
                             of every produced token, taken from the token selection itself (no second pass, no (B, T, V) tensor)
   texocr::set_rules_beam / last_beam_rule_state
                             (build extension, opt-in) beam search under token rules (texocr::set_token_rules) and the beams' rule states
+  texocr::set_guard_beam    (build extension, opt-in) the repeat guard inside the beam selection: the beam entries accept a guard
   texocr::set_repeat_guard  (build extension, opt-in) the repeat guard: a row of the generate family may not end in max_repeats + 1 copies of a
                             block of at most max_period tokens (texocr_amd/guard.py is the rule in numpy)
   texocr::set_rules_close   (build extension, opt-in) the closing decode: a constrained decode or beam search only picks tokens from which
@@ -840,6 +841,20 @@ def set_repeat_guard(engine: int, max_period: int, max_repeats: int) -> None:
 
 @set_repeat_guard.register_fake
 def _(engine, max_period, max_repeats):
+    return None
+
+
+# ---- repeat guard inside beam search (txo_set_guard_beam): the opt-in that lets the beam entries run under a repeat guard --------------------
+@custom_op("texocr::set_guard_beam", mutates_args=())
+def set_guard_beam(engine: int, on: bool) -> None:
+    """txo_set_guard_beam: on=True, a beam search under a repeat guard runs the guarded selection; False (the default), it is refused"""
+    e = _eng(engine)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_set_guard_beam(e.handle, 1 if on else 0))
+
+
+@set_guard_beam.register_fake
+def _(engine, on):
     return None
 
 

@@ -65,9 +65,11 @@ def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.T
 
 class TeXOCRWrapper:
     def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False, balanced: bool = False,
-                 rules_beam: bool = False, close: bool = False, repeat_guard=None):
+                 rules_beam: bool = False, close: bool = False, repeat_guard=None, guard_beam: bool = False):
         """repeat_guard=(max_period, max_repeats) (build extension): every __call__ / batch decodes under the repeat guard unless the call says
         otherwise (see batch)
+        guard_beam=True (build extension): decode='beam' accepts a repeat guard -- the ban inside the beam selection (OCRModel.guard_beam);
+        off, the default, the two together are a ValueError
         ragged_hybrid=True (build extension): batch() also works when config builds the hybrid ResNetV2 front end (OCRModel.ragged_hybrid)
         balanced=True (build extension): every __call__ / batch decodes under the brace rule of this tokenizer unless the call says otherwise
         (see batch)
@@ -91,7 +93,8 @@ class TeXOCRWrapper:
             key = "decoder.net.pos_embedding.embedding.weight"
             if key in sd:                                                            # ocr_model.py:84-88: the checkpoint decides
                 config["max_length"] = int(sd[key].shape[0])
-        self.model: OCRModel = create_model(config, dtype=dtype, max_batch=max_batch, ragged_hybrid=ragged_hybrid, rules_beam=rules_beam)
+        self.model: OCRModel = create_model(config, dtype=dtype, max_batch=max_batch, ragged_hybrid=ragged_hybrid, rules_beam=rules_beam,
+                                             guard_beam=guard_beam)
         if sd is not None:
             self.model.load_state_dict(sd)
         self.dims: Dims = self.model._engine.dims
@@ -120,7 +123,7 @@ class TeXOCRWrapper:
         g = self.repeat_guard if repeat_guard is None else (repeat_guard or None)
         if g is None:
             return {}
-        if decode == "beam":
+        if decode == "beam" and not self.model.guard_beam:
             raise ValueError("repeat_guard is not available with decode='beam' (the repeat guard binds generate() only)")
         return {"repeat_guard": g}
 
@@ -180,11 +183,13 @@ class TeXOCRWrapper:
             imgs = [self._fitted(im, i) for i, im in enumerate(imgs)]
         return [self._tensor(im).cuda() for im in imgs]
 
-    def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool, rules=None, close: bool = False):
+    def _best_beams(self, xs, beams: int, max_len: int, length_alpha: float, return_logp: bool, rules=None, close: bool = False,
+                    repeat_guard=None):
         """decode='beam': one OCRModel.beam_search over the images xs (a (B, C, H, W) tensor or a list of (C, H_b, W_b)) -> per image
         (the best beam's tokens up to and including its eos, their log-probabilities or None)"""
         res = self.model.beam_search(xs, beams, max_len, return_logp=return_logp, length_alpha=length_alpha,
-                                     **({} if rules is None else {"rules": rules, "close": close}))
+                                     **({} if rules is None else {"rules": rules, "close": close}),
+                                     **({} if repeat_guard is None else {"repeat_guard": repeat_guard}))
         lengths = res.lengths[:, 0].tolist()
         rows = [res.tokens[b, 0, :n].tolist() for b, n in enumerate(lengths)]
         logp = [res.logp[b, 0, :n].tolist() for b, n in enumerate(lengths)] if return_logp else [None] * len(rows)
@@ -249,7 +254,9 @@ class TeXOCRWrapper:
         max_len, so every row ends balanced and finished; with a prefix too deep to close in max_len it closes as far as it gets.
         repeat_guard=(max_period, max_repeats) (build extension; default: the wrapper's own setting; False: none): the repeat guard
         (OCRModel.generate_ragged(repeat_guard=)) -- no row ends in max_repeats + 1 consecutive copies of a block of at most max_period
-        tokens; texocr_amd.guard.hits flags the rows of an unguarded decode that looped.  Not with decode='beam' or close=True."""
+        tokens; texocr_amd.guard.hits flags the rows of an unguarded decode that looped.  With decode='beam' only on a wrapper built with
+        guard_beam=True: the ban then binds inside the beam selection (OCRModel.beam_search(repeat_guard=)), also beside close=True.  Not with
+        close=True in the other decodes."""
         rules = self._rules(balanced, decode)
         ckw = {**self._close(close, rules), **self._guard(repeat_guard, decode)}
         rule = self._trim_rule(trim, trim_level, trim_margin)
