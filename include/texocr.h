@@ -428,7 +428,8 @@ int txo_ingest_u8_view(txo_engine* e, const uint8_t* pix_dev, const int64_t* off
  * from a counter-based RNG keyed by (`seed`; row of the batch, position): reproducible, independent of the decode path and of
  * how the engine splits the batch into row ranges; a different stream than torch.multinomial.  The draw, exactly: Philox4x32-10 with
  * counter (row, position, 0, 0) and key (seed low 32 bits, seed high 32 bits); u = ((c0 >> 8) + 0.5f) / 2^24 in float32; the kept
- * set is the `topk` largest logits, ties at the k-th value kept lowest index first; the token is the first kept entry, in index
+ * set is the `topk` largest logits, ties at the k-th value kept lowest index first ("largest" and "tie" by the order of the float bits:
+ * a logit of -0.0 ranks below +0.0 and does not tie with it); the token is the first kept entry, in index
  * order, at which the running sum of exp((logit - max) / temp) reaches u times their total (tests/sampler_ref.py restates it).
  * mode 1 with a vocabulary beyond TXO_Q_SAMPLE_VOCAB_MAX: TXO_E_INVALID. */
 int txo_set_sampling(txo_engine* e, int32_t mode, int32_t topk, float temp, uint64_t seed);
