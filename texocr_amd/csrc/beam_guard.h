@@ -303,10 +303,31 @@ __global__ __launch_bounds__(256) void beam_select_guard_kernel(BeamArgs a, Beam
     if (tid == 0) beam_arrive(a, t, allfin);
 }
 
-inline void launch_beam_guard(hipStream_t s, const BeamArgs& ba, const BeamRuleArgs& ra, const BeamCloseArgs& ca, const BeamGuardArgs& ga, bool logp) {
-    const size_t lds = beam_guard_lds_bytes(ba.k, ba.V, ga.p, ga.r);
-    if (logp) hipLaunchKernelGGL(beam_select_guard_kernel<true>, dim3(ba.images), dim3(256), lds, s, ba, ra, ca, ga);
-    else hipLaunchKernelGGL(beam_select_guard_kernel<false>, dim3(ba.images), dim3(256), lds, s, ba, ra, ca, ga);
+// The one launch of a selection step, whatever its form (here: the first place where every form's kernel is declared): one workgroup per
+// image of the range; a form reads the arguments its kernel takes and no others.
+enum class BeamForm { plain, rules, close, guard };
+inline void launch_beam_select(hipStream_t s, const BeamArgs& ba, const BeamRuleArgs& ra, const BeamCloseArgs& ca, const BeamGuardArgs& ga, BeamForm form, bool logp) {
+    const dim3 grid(ba.images), block(256);
+    switch (form) {
+    case BeamForm::plain:
+        if (logp) hipLaunchKernelGGL(beam_select_kernel<true>, grid, block, 0, s, ba);
+        else hipLaunchKernelGGL(beam_select_kernel<false>, grid, block, 0, s, ba);
+        break;
+    case BeamForm::rules:
+        if (logp) hipLaunchKernelGGL(beam_select_rules_kernel<true>, grid, block, 0, s, ba, ra);
+        else hipLaunchKernelGGL(beam_select_rules_kernel<false>, grid, block, 0, s, ba, ra);
+        break;
+    case BeamForm::close:
+        if (logp) hipLaunchKernelGGL(beam_select_close_kernel<true>, grid, block, 0, s, ba, ra, ca);
+        else hipLaunchKernelGGL(beam_select_close_kernel<false>, grid, block, 0, s, ba, ra, ca);
+        break;
+    case BeamForm::guard: {
+        const size_t lds = beam_guard_lds_bytes(ba.k, ba.V, ga.p, ga.r);
+        if (logp) hipLaunchKernelGGL(beam_select_guard_kernel<true>, grid, block, lds, s, ba, ra, ca, ga);
+        else hipLaunchKernelGGL(beam_select_guard_kernel<false>, grid, block, lds, s, ba, ra, ca, ga);
+        break;
+    }
+    }
 }
 
 }  // namespace txo

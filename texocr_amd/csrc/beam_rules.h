@@ -37,24 +37,6 @@ __device__ inline int2 beam_rule_next(const BeamRuleArgs& ra, int V, int2 sd, in
     const int r = ra.rules[(size_t)sd.x * V + v];
     return make_int2(rule_next(r), rule_depth_after(r, sd.y, ra.depth_max));
 }
-// history slots of the new beam (the parent's, plus the parent's own slot for position t), as beam_select_kernel copies them
-__device__ inline void beam_copy_path(const BeamArgs& a, int img, int r, int j, int t, int tid) {
-    const short* src = a.path_cur + (size_t)(img * a.k + j) * a.path_stride;
-    short* dst = a.path_nxt + (size_t)(img * a.k + r) * a.path_stride;
-    for (int p = tid; p < t; p += 256) dst[p] = src[p];
-    if (tid == 0) dst[t] = (short)(img * a.k + j);
-}
-// one thread of the image's workgroup: the range's arrival word, done flag and position, as beam_select_kernel keeps them
-__device__ inline void beam_arrive(const BeamArgs& a, int t, int allfin) {
-    const unsigned add = 1u + ((a.eos >= 0 && allfin) ? (1u << 16) : 0u);
-    const unsigned old = atomicAdd(&a.st->arrive, add);
-    if ((old & 0xffffu) == (unsigned)(a.images - 1)) {
-        a.done_flag[t] = (int)((old + add) >> 16) >= a.images ? 1 : 0;
-        a.st->arrive = 0u;
-        a.st->t = t + 1;
-    }
-}
-
 // One workgroup per image, 256 threads, like beam_select_kernel; LOGP as there.
 template <bool LOGP>
 __global__ __launch_bounds__(256) void beam_select_rules_kernel(BeamArgs a, BeamRuleArgs ra) {
@@ -488,6 +470,12 @@ __global__ __launch_bounds__(64) void beam_finish_rules_kernel(BeamFinishArgs a,
         if (lp) lp[t] = a.logp_hist[h];
         cur = a.parent_hist[h];
     }
+}
+
+// the tail of a beam call: with `state` (a constrained search) the slots' states follow their beams into the final order
+inline void launch_beam_finish(hipStream_t s, int images, const BeamFinishArgs& fa, int2* state) {
+    if (state) hipLaunchKernelGGL(beam_finish_rules_kernel, dim3(images), dim3(64), 0, s, fa, state);
+    else hipLaunchKernelGGL(beam_finish_kernel, dim3(images), dim3(64), 0, s, fa);
 }
 
 }  // namespace txo

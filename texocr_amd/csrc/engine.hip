@@ -1707,19 +1707,13 @@ struct Engine : EngineBase {
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
-            if (bm->guard_p > 0) {   // guarded beam search (beam_guard.h): one kernel, with or without the rules and the budget
-                const BeamRuleArgs ra{bm->ruled ? rules_dev : nullptr, bm->ruled ? rules_S : 0, bm->ruled ? rules_dmax : 0, bm->ruled ? brule_state + r0 : nullptr};
-                const BeamCloseArgs ca{bm->closing ? close_dev : nullptr, bm->positions};
-                launch_beam_guard(s, ba, ra, ca, BeamGuardArgs{bm->guard_p, bm->guard_r}, bm->logp);
-            } else if (bm->ruled) {   // constrained beam search: the table, and the range's slice of the slots' states (range-local, like every pointer of ba)
-                const BeamRuleArgs ra{rules_dev, rules_S, rules_dmax, brule_state + r0};
-                const BeamCloseArgs ca{close_dev, bm->positions};
-                if (bm->closing && bm->logp) hipLaunchKernelGGL(beam_select_close_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra, ca);
-                else if (bm->closing) hipLaunchKernelGGL(beam_select_close_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra, ca);
-                else if (bm->logp) hipLaunchKernelGGL(beam_select_rules_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
-                else hipLaunchKernelGGL(beam_select_rules_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba, ra);
-            } else if (bm->logp) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(nb / bm->k), dim3(256), 0, s, ba);
-            else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(nb / bm->k), dim3(256), 0, s, ba);
+            // every form of the selection through one launch (beam_guard.h: launch_beam_select).  ra: the table and the range's slice of the
+            // slots' states (range-local, like every pointer of ba), nulls without rules; ca: the distance table, null unless closing.  A
+            // guarded search is one kernel with or without the rules and the budget; the plain form reads none of ra / ca / the guard's pair
+            const BeamRuleArgs ra{bm->ruled ? rules_dev : nullptr, bm->ruled ? rules_S : 0, bm->ruled ? rules_dmax : 0, bm->ruled ? brule_state + r0 : nullptr};
+            const BeamCloseArgs ca{bm->closing ? close_dev : nullptr, bm->positions};
+            const BeamForm form = bm->guard_p > 0 ? BeamForm::guard : !bm->ruled ? BeamForm::plain : bm->closing ? BeamForm::close : BeamForm::rules;
+            launch_beam_select(s, ba, ra, ca, BeamGuardArgs{bm->guard_p, bm->guard_r}, form, bm->logp);
         } else if (ses.guarded()) launch_guard_step(s, nb, sa, sample_mode != 0);   // (with or without rules; never closing: generate refuses)
         else if (ses.closing) launch_rules_close_step(s, nb, sa, sample_mode != 0);
         else if (ses.ruled) launch_rules_step(s, nb, sa, sample_mode != 0);
@@ -2451,8 +2445,7 @@ struct Engine : EngineBase {
             const txo_beam_out& o = *sink.out;
             BeamFinishArgs fa{bparent, btok, want_logp ? blogp : nullptr, Bmax, bscore, steps, beams, eos, o.length_alpha,
                               o.tokens, o.logp, o.scores, o.lengths, max_len};
-            if (ruled) hipLaunchKernelGGL(beam_finish_rules_kernel, dim3(B), dim3(64), 0, s, fa, brule_state);   // ... and the states into that order
-            else hipLaunchKernelGGL(beam_finish_kernel, dim3(B), dim3(64), 0, s, fa);
+            launch_beam_finish(s, B, fa, ruled ? brule_state : nullptr);   // ... and, under rules, the states into that order
         } else {
             // backtrack every beam into tok_buf rows, then hand out the best beam (slot 0: selection order is by score)
             hipLaunchKernelGGL(beam_backtrack_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, bparent, btok, Bmax, steps, rows,

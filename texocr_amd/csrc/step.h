@@ -516,6 +516,24 @@ struct BeamArgs {
     int row0;                             // this row range's first row in the batch: every pointer above is the RANGE's (slots in `path` are range-local,
                                           // like the range's K/V base), only the back-pointers name rows of the whole batch (beam_backtrack_kernel)
 };
+// history slots of the new beam: the parent's, plus the parent's own slot for position t.  For the selection kernels of beam_rules.h and
+// beam_guard.h; beam_select_kernel below spells both helpers out, because calling them moved its compiled text.
+__device__ inline void beam_copy_path(const BeamArgs& a, int img, int r, int j, int t, int tid) {
+    const short* src = a.path_cur + (size_t)(img * a.k + j) * a.path_stride;
+    short* dst = a.path_nxt + (size_t)(img * a.k + r) * a.path_stride;
+    for (int p = tid; p < t; p += 256) dst[p] = src[p];
+    if (tid == 0) dst[t] = (short)(img * a.k + j);
+}
+// one thread of the image's workgroup: the range's arrival word, done flag and position
+__device__ inline void beam_arrive(const BeamArgs& a, int t, int allfin) {
+    const unsigned add = 1u + ((a.eos >= 0 && allfin) ? (1u << 16) : 0u);
+    const unsigned old = atomicAdd(&a.st->arrive, add);
+    if ((old & 0xffffu) == (unsigned)(a.images - 1)) {
+        a.done_flag[t] = (int)((old + add) >> 16) >= a.images ? 1 : 0;
+        a.st->arrive = 0u;
+        a.st->t = t + 1;
+    }
+}
 
 // LOGP: also record logp_hist[t][slot] = the float that was added to the parent's score for the selected candidate, logits[j][v] - lse[j]
 // (exactly 0.0f where the parent was already finished), so that a beam's increments summed left to right in float give its score bit
