@@ -560,6 +560,41 @@ int txo_set_repeat_guard(txo_engine* e, int32_t max_period, int32_t max_repeats)
  * beyond the 56 KB of LDS the guarded selection may use (the message names the vocabulary). */
 int txo_set_guard_beam(txo_engine* e, int32_t on);
 
+/* Alternatives per token, a BUILD EXTENSION: the k best ids of every logits row a pick is made from, and their log-probabilities.  An engine
+ * knob like txo_set_repeat_guard: k = 0 switches them off (the default), 1 <= k <= 8 on; the setting stays until it is changed and binds
+ * txo_generate, txo_generate_logp, their _from_enc forms, txo_generate_prefix* and txo_generate_ragged*.
+ * For the f32 logits row x[0 .. V-1] of a pick:
+ *   ids[0 .. k-1]  the indices of the k largest entries in descending value, the LOWER INDEX FIRST among equals (a stable descending sort),
+ *                  so ids[0] is the greedy pick;
+ *   logp[j]        x[ids[j]] - logsumexp(x): natural log, temperature 1, the whole vocabulary -- the quantity logp_out reports.
+ * Always the RAW row: not the sampler's top-k / temperature distribution, and not masked by token rules, the closing decode or the repeat
+ * guard.  Under a sampled, constrained or guarded decode the committed token may therefore be missing from its own alternatives: that is how
+ * a caller sees that a rule forced it.  In a greedy decode logp[0] is bit for bit the float logp_out holds, and ids[0] the token.  A
+ * non-finite row has unspecified alternatives with ids in [0, V); other rows are untouched.
+ * The columns are the tokens' own: column t, or t + 1 - prefix_len[b] in a prompted decode; a forced prefix token has none.  Wherever
+ * tokens_out / logp_out hold pad / 0.0 -- behind a row's first eos under TXO_STOP_ROW, in columns a longer-prefix row never reached -- the
+ * alternatives hold pad / 0.0.
+ * While set, every txo_generate* runs its loop with one launch per stage (TXO_Q_LAST_PERSISTENT reads 0, TXO_Q_LAST_ALTS reads k) with one
+ * more kernel in front of the pick (texocr_amd/csrc/step_alts.h), and otherwise as ever: greedy and sampled, captured steps, row ranges,
+ * TXO_STOP_ROW with live-row compaction, ragged batches, prefix, rules, closing, guard.  txo_decode_step keeps none.
+ * Refused with TXO_E_INVALID: k outside [0, 8] or beyond cfg.vocab; by txo_generate*, behind every other refusal of the entry, max_len beyond
+ * cfg.max_len (the sliding window's tail does not run the loop that keeps them); by txo_generate_beam / txo_beam_search /
+ * txo_beam_search_ragged while they are set.
+ * txo_last_alternatives copies [B][cols][k] int32 ids and float log-probabilities (either may be NULL) of the LAST txo_generate* to device
+ * memory, on `stream`: TXO_E_INVALID if that call ran without alternatives or failed, or if B / cols exceed its rows / its *n_steps. */
+int txo_set_alternatives(txo_engine* e, int32_t k);
+int txo_last_alternatives(txo_engine* e, int32_t* ids_out_dev, float* logp_out_dev, int32_t B, int32_t cols, void* stream);
+
+/* txo_decode_score / txo_score with the k best of every scored row, 1 <= k <= 8 and k <= cfg.vocab (TXO_E_INVALID otherwise; independent of
+ * txo_set_alternatives): alt_ids_out_dev int32 [B][L-1][k], alt_logp_out_dev float [B][L-1][k], neither NULL, by the rule above on the row
+ * the fused kernel forms -- the logits are still never stored.  alt_ids[..][0] is top1 and alt_logp[..][0] is top1_logp bit for bit; logp_out,
+ * top1_out and top1_logp_out are bit for bit what the call without alternatives writes. */
+int txo_decode_score_alts(txo_engine* e, const int64_t* tokens_dev, int32_t L, float* logp_out_dev, int64_t* top1_out_dev, float* top1_logp_out_dev,
+                          int32_t k, int32_t* alt_ids_out_dev, float* alt_logp_out_dev, void* stream);
+int txo_score_alts(txo_engine* e, const float* img_dev, int32_t B, int32_t C, int32_t H, int32_t W, const int64_t* tokens_dev, const uint8_t* mask_dev,
+                   int32_t L, float* logp_out_dev, int64_t* top1_out_dev, float* top1_logp_out_dev, int32_t k, int32_t* alt_ids_out_dev,
+                   float* alt_logp_out_dev, void* stream);
+
 /* Timing hooks for bench.py: average duration (ms) of the decode-step cross-attention launches and of
  * the encoder launches recorded with HIP events on the stream the kernels run on, since profiling was last
  * enabled (txo_profile_enable(e, 1) also clears the previous samples); *count = number of launches averaged.  kind: 0 = cross-attention decode kernel,
@@ -590,6 +625,7 @@ int txo_profile_read(txo_engine* e, int32_t kind, double* avg_ms, int64_t* count
                                     * 0 where the engine declined it (no latent form, per-row stop, a positional table beyond the beam slot table) */
 #define TXO_Q_LAST_GUARDED 9       /* 1 if the last txo_generate* picked under a repeat guard (txo_set_repeat_guard), 0 otherwise; with txo_set_guard_beam on,
                                     * also set by the beam entries: 1 behind a guarded beam search, 0 behind one without a guard */
+#define TXO_Q_LAST_ALTS 10         /* the k of the last txo_generate* (txo_set_alternatives), 0 where it kept no alternatives */
 int txo_engine_query(txo_engine* e, int32_t what, int64_t* out);
 
 const char* txo_last_error(void);

@@ -18,7 +18,7 @@ TXO_E_INVALID, TXO_E_STATE, TXO_E_HIP = -1, -2, -3
 TXO_FIT_TAPS = 65        # include/texocr.h: the K_out row length of txo_ingest_fit_coeffs
 # txo_engine_query codes (include/texocr.h: TXO_Q_*; tests/test_abi_cpu.py holds the two lists together)
 (Q_LAST_PERSISTENT, Q_PERSIST_FALLBACKS, Q_LAST_ROW_RANGES, Q_LAST_LATENT, Q_RELOAD_KNOBS, Q_LAST_COMPACTIONS,
- Q_SAMPLE_VOCAB_MAX, Q_LAST_RAGGED, Q_LAST_LATENT_SELF, Q_LAST_GUARDED) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+ Q_SAMPLE_VOCAB_MAX, Q_LAST_RAGGED, Q_LAST_LATENT_SELF, Q_LAST_GUARDED, Q_LAST_ALTS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
 
 class TxoConfig(C.Structure):
@@ -84,6 +84,10 @@ SYMBOLS = {
     "txo_rules_close_dist": (C.c_int, [_P, C.c_void_p, _I, _I]),
     "txo_set_repeat_guard": (C.c_int, [_P, _I, _I]),
     "txo_set_guard_beam": (C.c_int, [_P, _I]),
+    "txo_set_alternatives": (C.c_int, [_P, _I]),
+    "txo_last_alternatives": (C.c_int, [_P, C.c_void_p, _FP, _I, _I, _P]),
+    "txo_decode_score_alts": (C.c_int, [_P, _I64P, _I, _FP, _I64P, _FP, _I, C.c_void_p, _FP, _P]),
+    "txo_score_alts": (C.c_int, [_P, _FP, _I, _I, _I, _I, _I64P, C.c_void_p, _I, _FP, _I64P, _FP, _I, C.c_void_p, _FP, _P]),
     "txo_set_ragged_forward": (C.c_int, [_P, _I]),
     "txo_set_ragged_hybrid": (C.c_int, [_P, _I]),
     "txo_profile_enable": (C.c_int, [_P, _I]),

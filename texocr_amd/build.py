@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libtexocr_hip.so")
 SOURCES = ["engine.hip"]
-HEADERS = ["common.h", "prefill.h", "attn_probs.h", "score.h", "conv.h", "gemm_big.h", "gemm_pp.h", "gemm_split.h", "rows.h", "enc_attn.h", "dec_gemm.h", "dec_attn.h", "lat_attn.h", "step.h", "step_prefix.h", "step_rules.h", "step_guard.h", "beam_rules.h", "beam_guard.h", "rules_close.h", "ingest.h", "ingest_fit.h", "ingest_trim.h", "persist.h", "knobs.h", "lanes.h", "session.h", "stamps.h", "ingest_req.h"]
+HEADERS = ["common.h", "prefill.h", "attn_probs.h", "score.h", "conv.h", "gemm_big.h", "gemm_pp.h", "gemm_split.h", "rows.h", "enc_attn.h", "dec_gemm.h", "dec_attn.h", "lat_attn.h", "step.h", "step_prefix.h", "step_rules.h", "step_guard.h", "step_alts.h", "kbest.h", "beam_rules.h", "beam_guard.h", "rules_close.h", "ingest.h", "ingest_fit.h", "ingest_trim.h", "persist.h", "knobs.h", "lanes.h", "session.h", "stamps.h", "ingest_req.h"]
 
 
 # Mandatory flags (never replaced by the environment):
@@ -70,7 +70,7 @@ def build(force: bool = False, verbose: bool = True, out: str = "") -> str:
 
 
 def build_example(verbose: bool = True, name: str = "generate_tiny") -> str:
-    """examples/generate_tiny (or `name`: ingest_tiny, ingest_fit_tiny, ingest_trim_tiny, rules_tiny, beam_rules_tiny, rules_close_tiny, guard_tiny, beam_guard_tiny): a torch-free C host program on the C ABI (plain gcc; HIP runtime API for device memory)."""
+    """examples/generate_tiny (or `name`: ingest_tiny, ingest_fit_tiny, ingest_trim_tiny, rules_tiny, beam_rules_tiny, rules_close_tiny, guard_tiny, beam_guard_tiny, alts_tiny): a torch-free C host program on the C ABI (plain gcc; HIP runtime API for device memory)."""
     root = os.path.dirname(HERE)
     src, out = os.path.join(root, "examples", name + ".c"), os.path.join(root, "examples", name)
     if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(src), os.path.getmtime(OUT)):

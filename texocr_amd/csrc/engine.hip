@@ -53,6 +53,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #include "beam_rules.h"    // (the constrained beam selection: step.h's beam kernels with that automaton; last again)
 #include "rules_close.h"   // (host only: the closing decode's distance table)
 #include "beam_guard.h"    // (the repeat guard inside the beam selection: beam_rules.h with step_guard.h's ban; last again)
+#include "step_alts.h"     // (the k best of every row in front of the pick: step.h's streaming with kbest.h's lists; last again)
 #include "knobs.h"    // host helpers from here on (they use fail() / HIP_TRY)
 #include "lanes.h"
 #include "session.h"
@@ -121,6 +122,15 @@ struct EngineBase {
     // txo_set_repeat_guard (step_guard.h): while set (max_period > 0), every generate from BOS or a prefix decodes on the launch path with the
     // *_guard_step kernels; last_guarded: the last txo_generate* ran them (TXO_Q_LAST_GUARDED)
     int guard_p = 0, guard_r = 0; bool last_guarded = false;
+    // txo_set_alternatives (step_alts.h): while set (k > 0), every generate from BOS or a prefix decodes on the launch path with
+    // alts_step_kernel in front of its pick.  last_alts: the k of the last txo_generate* (TXO_Q_LAST_ALTS), alts_B x alts_cols what
+    // txo_last_alternatives may read of it
+    int alts_k = 0, last_alts = 0, alts_B = 0, alts_cols = 0;
+    virtual int last_alternatives(int32_t* ids_out, float* logp_out, int B, int cols, hipStream_t s) = 0;
+    virtual int decode_score_alts(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, int k, int32_t* alt_ids_out,
+                                  float* alt_logp_out, hipStream_t s) = 0;
+    virtual int score_alts(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
+                           int64_t* top1_out, float* top1_logp_out, int k, int32_t* alt_ids_out, float* alt_logp_out, hipStream_t s) = 0;
     // txo_ingest_u8 / _fit / _view behind their checks (ingest_req.h: ingest_plan): descriptors up in one staged copy, then one launch -- or,
     // where an image is downscaled, the horizontal pass of those that need one and the fused vertical pass + ingest
     virtual int ingest(const IngestPlan& p, const IngestReq& q, hipStream_t s) = 0;
@@ -250,6 +260,9 @@ struct Engine : EngineBase {
     // tokens' log-probabilities [Bmax][Tmax] -- engine-owned, so that a captured step can carry them
     int64_t* ftab = nullptr; int* flen = nullptr; float* fplogp = nullptr;
     int prefix_cols = 0;                   // StepArgs::out_cols of the running prompted decode
+    // alternatives (step_alts.h): [Bmax][Tmax][k] ids and log-probabilities of the running / last decode, k = ses.alts / last_alts (room for
+    // ALTS_MAX) -- engine-owned, so that a captured step can carry them; allocated at the first use
+    int32_t* alt_ids = nullptr; float* alt_logp = nullptr;
     // constrained decode (step_rules.h): the packed table [RULES_MAX_STATES][V], every row's (state, depth) [Bmax] and the state behind every
     // position [Bmax][Tmax] -- engine-owned, so that a captured step can carry them
     int* rules_dev = nullptr; int2* rule_state = nullptr; int2* rule_hist = nullptr;
@@ -1192,6 +1205,7 @@ struct Engine : EngineBase {
         // results of THIS call, also when it is refused (txo_generate_ragged / _logp: only once the batch is accepted, generate_common)
         if (q.prefix || !ragged) { last_compactions = 0; last_ragged = false; }
         last_guarded = false;
+        last_alts = 0; alts_B = alts_cols = 0;
         if (ragged) { if (int r = ragged_refusals()) return r; }
         Decode d{q};
         if (int r = q.prefix ? check_prefix(q, &d.m, &d.M) : check_length(q.max_len, ragged)) return r;
@@ -1203,6 +1217,15 @@ struct Engine : EngineBase {
                                            "conflict (txo_set_repeat_guard(e, 0, 0) switches the guard off)");
             if (sample_mode && !sample_in_regs(V) && (size_t)V * sizeof(float) + guard_map_bytes(V) > 65536)
                 return fail(TXO_E_INVALID, "repeat guard: the vocabulary does not fit the guarded sampler's LDS (vocab * 4 bytes + vocab / 8 bytes per workgroup, 64 KB)");
+        }
+        if (alts_k > 0) {                                          // ... and the alternatives' last
+            if (q.max_len > Tmax)
+                return fail(TXO_E_INVALID, "alternatives: max_len exceeds the decoder's max_length (the sliding window's tail does not run the loop that keeps "
+                                           "them; txo_set_alternatives(e, 0) switches them off)");
+            if (!alt_ids) {
+                if (int r = dalloc(&alt_ids, (size_t)Bmax * Tmax * ALTS_MAX)) return r;
+                if (int r = dalloc(&alt_logp, (size_t)Bmax * Tmax * ALTS_MAX)) return r;
+            }
         }
         if (q.prefix) {   // the lengths to the device, through the pinned staging of the ragged sizes (behind ragged_batch's own copy)
             std::vector<int32_t> len((size_t)q.src.B, q.P);
@@ -1704,6 +1727,10 @@ struct Engine : EngineBase {
             if (ses.closing) { sa.close_tab = close_dev; sa.rule_close = rule_close + r0; }
         }
         sa.guard_p = ses.guard_p; sa.guard_r = ses.guard_r;
+        // alternatives: the raw row's k best in front of whatever pick follows, on the same stream (never a beam step: beam_search refuses)
+        if (ses.alts > 0 && !bm)
+            hipLaunchKernelGGL(alts_step_kernel, dim3(nb), dim3(64), 0, s, sa,
+                               AltsArgs{alt_ids + r0 * Tmax * ses.alts, alt_logp + r0 * Tmax * ses.alts, ses.alts, Tmax});
         if (bm) {
             BeamArgs ba{llog, V, bm->k, nb / bm->k, cur_tok + r0, bscore + r0, bfin + r0, bm->path_cur + r0 * Tmax, bm->path_nxt + r0 * Tmax, Tmax,
                         bparent + r0, btok + r0, Bmax, bm->logp ? blogp + r0 : nullptr, st + li, done_flag + (size_t)li * Tmax, eos, (int)r0};
@@ -1729,7 +1756,7 @@ struct Engine : EngineBase {
     // logp: the step also writes its log-probabilities, into the engine-owned logp_buf (part of the key: it is another StepArgs)
     int lane_graph(int li, int eos, bool logp) {
         const auto& ln = lanes[li];
-        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode, logp, rules_S * 256 + rules_dmax + (ses.closing ? 4096 : 0));   // (S * 256 + depth cap < 4096)
+        const LaneSet::GraphKey key = ses.graph_key(ln, eos, sample_mode, logp, rules_S * 256 + rules_dmax + (ses.closing ? 4096 : 0));   // (ses.alts is in it)   // (S * 256 + depth cap < 4096)
         if (lanes.cached(li, key)) return 0;
         hipStream_t cs = lanes.cap_stream;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -1801,37 +1828,52 @@ struct Engine : EngineBase {
 
     // AutoRegressiveDecoder.forward without autograd (decoder.py:124-145): tokens [B][L]; columns 0..L-2 are fed through the
     // multi-position forward, column p + 1 is the target of position p; per-position scores from the fused kernel of score.h
+    // per-position scores [B][L-1] (each may be null), and with k > 0 the k best ids / log-probabilities of every row [B][L-1][k] (score.h: the
+    // k-best form of the fused kernel; txo_decode_score_alts / txo_score_alts)
+    struct ScoreOut { float* logp; int64_t* top1; float* top1_logp; int k = 0; int32_t* alt_ids = nullptr; float* alt_logp = nullptr; };
     int decode_score(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
+        return decode_score_to(tokens, L, ScoreOut{logp_out, top1_out, top1_logp_out}, s);
+    }
+    int decode_score_alts(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, int k, int32_t* alt_ids_out,
+                          float* alt_logp_out, hipStream_t s) override {
+        return decode_score_to(tokens, L, ScoreOut{logp_out, top1_out, top1_logp_out, k, alt_ids_out, alt_logp_out}, s);
+    }
+    int decode_score_to(const int64_t* tokens, int L, const ScoreOut& so, hipStream_t s) {
         if (!ses.open) return fail(TXO_E_STATE, "txo_decode_begin has not been called");
         if (lanes.n != 1) return fail(TXO_E_STATE, "decode_score needs a session started by txo_decode_begin");
         if (ses.images != ses.rows) return fail(TXO_E_STATE, "decode_score is not available inside a beam-search session");
         if (ses.ragged && !rag_fwd) return refuse_ragged_forward("txo_decode_score");
-        return score_pass(tokens, L, logp_out, top1_out, top1_logp_out, s);
+        return score_pass(tokens, L, so, s);
     }
     // (the session is open, has one row per image and one row range: decode_score checked it, or txo_score / txo_score_ragged just opened it)
-    int score_pass(const int64_t* tokens, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out, hipStream_t s) {
+    int score_pass(const int64_t* tokens, int L, const ScoreOut& so, hipStream_t s) {
         lanes[0].stream = s;
-        const ScoreOut so{logp_out, top1_out, top1_logp_out};
         return prefill(tokens, L, L - 1, nullptr, nullptr, s, &so);
     }
 
     // OCRModel.forward's path (ocr_model.py:38-44) in one call: encode into the engine's own buffer, open the session, mask, score
     int score(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
               int64_t* top1_out, float* top1_logp_out, hipStream_t s) override {
+        return score_to(img, B, C, H, W, tokens, mask, L, ScoreOut{logp_out, top1_out, top1_logp_out}, s);
+    }
+    int score_alts(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, float* logp_out,
+                   int64_t* top1_out, float* top1_logp_out, int k, int32_t* alt_ids_out, float* alt_logp_out, hipStream_t s) override {
+        return score_to(img, B, C, H, W, tokens, mask, L, ScoreOut{logp_out, top1_out, top1_logp_out, k, alt_ids_out, alt_logp_out}, s);
+    }
+    int score_to(const float* img, int B, int C, int H, int W, const int64_t* tokens, const unsigned char* mask, int L, const ScoreOut& so, hipStream_t s) {
         if (ses.open && ses.ragged && !rag_fwd) return refuse_ragged_forward("txo_score (a ragged batch session is open)");
         if (int r = encode(img, B, C, H, W, eenc, s)) return r;
         if (int r = begin_session(eenc, B, 1 + (H / 16) * (W / 16), cfg.eos, s, true)) return r;
-        return score_open_session(tokens, mask, L, logp_out, top1_out, top1_logp_out, s);
+        return score_open_session(tokens, mask, L, so, s);
     }
     // the tail txo_score and txo_score_ragged share: the [B][L] mask's first L - 1 columns as the key mask, the scores, the mask cleared
-    int score_open_session(const int64_t* tokens, const unsigned char* mask, int L, float* logp_out, int64_t* top1_out, float* top1_logp_out,
-                           hipStream_t s) {
+    int score_open_session(const int64_t* tokens, const unsigned char* mask, int L, const ScoreOut& so, hipStream_t s) {
         if (mask) {
             const int n = ses.rows * Tmax;
             hipLaunchKernelGGL(set_key_mask_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, kmask, ses.rows, L, L - 1, Tmax);
             ses.kmask_on = true;
         }
-        const int rc = score_pass(tokens, L, logp_out, top1_out, top1_logp_out, s);
+        const int rc = score_pass(tokens, L, so, s);
         ses.kmask_on = false;
         return rc;
     }
@@ -1842,14 +1884,13 @@ struct Engine : EngineBase {
         if (int r = ragged_batch(B, C, Hc, Wc, sizes, s, &ib)) return r;
         if (int r = encode_batch(ib, img, eenc, s)) return r;
         if (int r = begin_session(eenc, B, ib.N, cfg.eos, s, true, KeyCounts{rag_ntok})) return r;
-        return score_open_session(tokens, mask, L, logp_out, top1_out, top1_logp_out, s);
+        return score_open_session(tokens, mask, L, ScoreOut{logp_out, top1_out, top1_logp_out}, s);
     }
 
     // ---- multi-position decoder forward (prefill.h): Transformer.forward over t positions at once, filling the self K/V cache ----
     // tokens [B][tok_stride] (the first t of each row); logits_out [B][t][V] or null; last_logits [B][V] or null (final LN + logits of
     // position t-1 only, on the single-position launch); score: per-position scores [B][t] against the targets tokens[b][p + 1]
     // (tok_stride > t then) or null.  Runs in the encoder's workspace, image chunks of as many rows as fit.
-    struct ScoreOut { float* logp; int64_t* top1; float* top1_logp; };
     template <typename TO>
     void launch_attn_mq(hipStream_t s, bool causal, const T* q, const T* k, const T* v, TO* out, int nb, int nq, int nk, int kv_rows,
                         const unsigned char* km = nullptr, const int* lens = nullptr) {
@@ -1933,10 +1974,17 @@ struct Engine : EngineBase {
                 launch_ln<2, T>(s, ey, nullptr, ez, decn_g, decn_b, M);
                 gemm_plain(s, ez, wlog, M, V, D, EpiStore<float>{logits_out + (size_t)b0 * t * V, V, blog});
             }
-            if (score && (score->logp || score->top1 || score->top1_logp)) {   // decoder.py:141-145 without the logits: score.h
+            if (score && (score->logp || score->top1 || score->top1_logp || score->k > 0)) {   // decoder.py:141-145 without the logits: score.h
                 launch_ln<2, T>(s, ey, nullptr, ez, decn_g, decn_b, M);
                 const int nw = score_waves<T>(D);
                 const size_t o = (size_t)b0 * t;
+                if (score->k > 0)
+                    hipLaunchKernelGGL((score_rows_alts_kernel<T>), dim3((M + nw * SC_ROWS - 1) / (nw * SC_ROWS)), dim3(64 * nw),
+                                       (size_t)nw * SC_ROWS * D * sizeof(T), s, ez, wlog, blog, tokens + (size_t)b0 * tok_stride, tok_stride, t, M, D, V,
+                                       score->logp ? score->logp + o : nullptr, score->top1 ? score->top1 + o : nullptr,
+                                       score->top1_logp ? score->top1_logp + o : nullptr, score->k, score->alt_ids + o * score->k,
+                                       score->alt_logp + o * score->k);
+                else
                 hipLaunchKernelGGL((score_rows_kernel<T>), dim3((M + nw * SC_ROWS - 1) / (nw * SC_ROWS)), dim3(64 * nw),
                                    (size_t)nw * SC_ROWS * D * sizeof(T), s, ez, wlog, blog, tokens + (size_t)b0 * tok_stride, tok_stride, t, M, D, V,
                                    score->logp ? score->logp + o : nullptr, score->top1 ? score->top1 + o : nullptr,
@@ -1970,6 +2018,7 @@ struct Engine : EngineBase {
         if (ses.forced) return false;                                 // so does a prompted decode (persist.h starts at BOS and forces nothing)
         if (ses.ruled) return false;                                  // and a constrained one (persist.h picks without rules)
         if (ses.guarded()) return false;                              // and a guarded one (persist.h keeps no ban set)
+        if (ses.alts > 0) return false;                               // and one that keeps alternatives (persist.h picks without them)
         if (cfg.dec_exp != 4 || cfg.dec_layers > PS_MAXLD) return false;
         const bool exists = (D == 256 && cfg.dec_heads == 8) || (D == 768 && cfg.dec_heads == 12 && sizeof(T) == 2);
         if (!exists) return false;
@@ -2087,6 +2136,8 @@ struct Engine : EngineBase {
         ses.ruled = false;                                        // ... without rules: they bind the generate family only
         ses.closing = false;
         ses.guard_p = ses.guard_r = 0;                            // ... nor a repeat guard
+        ses.alts = 0;                                             // ... and keeps no alternatives
+        if (last_alts > 0 && rc == 0) { alts_B = d.src.B; alts_cols = std::min(steps, Tmax); }   // what txo_last_alternatives may read
         rules_rows = (rules_on && rc == 0) ? d.src.B : 0;         // what txo_last_rule_state may read
         if (last_ragged) ses.open = false;                        // nothing ragged outlives the call (stepping on one: txo_decode_begin_ragged)
         if (rc) return rc;
@@ -2142,6 +2193,7 @@ struct Engine : EngineBase {
         ses.closing = closing();
         ses.guard_p = guard_p; ses.guard_r = guard_r;
         last_guarded = guard_p > 0;
+        ses.alts = last_alts = alts_k;
         if (d.prompted()) {   // the prefix into the engine's table (lengths are in flen: generate), no forced token scored yet
             hipLaunchKernelGGL(prefix_table_kernel, dim3((B * Tmax + 255) / 256), dim3(256), 0, s, ftab, Tmax, q.prefix, q.P, flen, B, V);
             HIP_TRY(hipMemsetAsync(fplogp, 0, sizeof(float) * (size_t)B * Tmax, s));
@@ -2213,6 +2265,10 @@ struct Engine : EngineBase {
         lanes.split(ses.rows, want, s);
         last_ranges = lanes.n;
         reset_lanes(s, eos, d.prompted() ? d.m : 0);
+        if (ses.alts > 0) {   // pad / 0.0 in every column no step will write
+            const size_t n = (size_t)B * Tmax * ses.alts;
+            hipLaunchKernelGGL(alts_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, alt_ids, alt_logp, n, cfg.pad);
+        }
         if (ses.ruled)   // every row's automaton at its start, run over the prefix columns the multi-position pass consumes
             hipLaunchKernelGGL(rules_start_kernel, dim3((B + 255) / 256), dim3(256), 0, s, rule_state, B, rules_dev, V, rules_S, rules_dmax, ftab, Tmax,
                                d.prompted() ? d.m : 0);
@@ -2296,6 +2352,10 @@ struct Engine : EngineBase {
         if (d.prompted())   // pad / 0.0 where a row did not get to (or is finished, per-row stop); the forced tokens' log-probabilities to the caller
             hipLaunchKernelGGL(prefix_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, q.tokens, q.logp, max_len, n_cols, B, poll.steps, q.eos,
                                cfg.pad, stop_mode == 1 ? 1 : 0, ftab, Tmax, flen, d.m, fplogp, q.prefix_logp, q.P);
+        // the alternatives follow the tokens: pad / 0.0 where a row did not get to or is finished (step_alts.h)
+        if (ses.alts > 0 && (d.prompted() || (stop_mode == 1 && q.eos >= 0)))
+            hipLaunchKernelGGL(alts_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, alt_ids, alt_logp, ses.alts, Tmax, q.tokens, max_len, n_cols, B,
+                               poll.steps, q.eos, cfg.bos, cfg.pad, stop_mode == 1 ? 1 : 0, ftab, Tmax, d.prompted() ? flen : nullptr);
         // the rules' states behind the last RETURNED position of every row (the loop may have run ahead of the eos break; a prompted row stops
         // counting at its last returned column).  Under the per-row stop a finished row froze its state itself.
         if (ses.ruled && !ses.row_stop && poll.steps >= 1)
@@ -2383,6 +2443,8 @@ struct Engine : EngineBase {
             return fail(TXO_E_INVALID, "beam search: the vocabulary does not fit the guarded selection's LDS (beams * (vocab / 8 bytes + ((max_repeats + 1) * max_period - 1) * 4 bytes) "
                                        "per workgroup, 56 KB; the vocabulary has " + std::to_string(V) + " entries)");
         if (guard_beam) last_guarded = guard_p > 0;               // (off: a beam entry leaves TXO_Q_LAST_GUARDED as it was, as it always did)
+        if (alts_k > 0)
+            return fail(TXO_E_INVALID, "beam search: alternatives are not available (txo_set_alternatives(e, 0) switches them off)");
         brule_B = brule_k = 0;
         const int rc = beam_impl(src, beams, max_len, eos, sink, n_steps, s);
         if (rules_on && rc == 0) { brule_B = src.B; brule_k = beams; }   // what txo_last_beam_rule_state may read
@@ -2509,6 +2571,19 @@ struct Engine : EngineBase {
                                        std::to_string(picks));
         return 0;
     }
+    int last_alternatives(int32_t* ids_out, float* logp_out, int B, int cols, hipStream_t s) override {
+        if (last_alts < 1 || alts_B < 1)
+            return fail(TXO_E_INVALID, "txo_last_alternatives: the last txo_generate* ran without alternatives (txo_set_alternatives)");
+        if (B < 1 || B > alts_B || cols < 1 || cols > alts_cols)
+            return fail(TXO_E_INVALID, "txo_last_alternatives: B must be in [1, " + std::to_string(alts_B) + "] and cols in [1, " + std::to_string(alts_cols) +
+                                       "], the rows and columns of the last alternatives decode");
+        const size_t k = (size_t)last_alts;
+        if (ids_out)
+            HIP_TRY(hipMemcpy2DAsync(ids_out, sizeof(int32_t) * cols * k, alt_ids, sizeof(int32_t) * Tmax * k, sizeof(int32_t) * cols * k, B, hipMemcpyDeviceToDevice, s));
+        if (logp_out)
+            HIP_TRY(hipMemcpy2DAsync(logp_out, sizeof(float) * cols * k, alt_logp, sizeof(float) * Tmax * k, sizeof(float) * cols * k, B, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
     int last_rule_state(int32_t* out, int B, hipStream_t s) override {
         if (!rules_on) return fail(TXO_E_STATE, "txo_last_rule_state: no token rules are set");
         if (rules_rows < 1) return fail(TXO_E_STATE, "txo_last_rule_state: no generate has run since the token rules were set");
@@ -2542,6 +2617,7 @@ struct Engine : EngineBase {
         else if (what == TXO_Q_LAST_RAGGED) *out = last_ragged ? 1 : 0;
         else if (what == TXO_Q_LAST_LATENT_SELF) *out = (!last_persist && ses.latent && ses.lat_self) ? 1 : 0;
         else if (what == TXO_Q_LAST_GUARDED) *out = last_guarded ? 1 : 0;
+        else if (what == TXO_Q_LAST_ALTS) *out = last_alts;
         else if (what == TXO_Q_SAMPLE_VOCAB_MAX) *out = std::max<int64_t>(64 * SR_PER, (int64_t)(sample_lds_max / sizeof(float)));
         else return fail(TXO_E_INVALID, "unknown query");
         return 0;
@@ -2783,6 +2859,32 @@ int txo_score(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, 
     return e->impl->score(img, B, C, H, W, tokens, mask, L, logp_out, top1_out, top1_logp_out, (hipStream_t)stream);
 }
 
+// k and the two outputs of the *_alts scoring entries
+static int check_score_alts(txo_engine* e, int32_t k, const int32_t* ids, const float* lp) {
+    if (k < 1 || k > txo::ALTS_MAX)
+        return fail(TXO_E_INVALID, "alternatives: k is " + std::to_string(k) + "; it must be in [1, " + std::to_string(txo::ALTS_MAX) + "]");
+    if (k > e->impl->cfg.vocab)
+        return fail(TXO_E_INVALID, "alternatives: k is " + std::to_string(k) + " and the vocabulary has " + std::to_string(e->impl->cfg.vocab) + " entries");
+    if (!ids || !lp) return fail(TXO_E_INVALID, "alternatives: alt_ids_out_dev and alt_logp_out_dev must not be NULL");
+    return 0;
+}
+
+int txo_decode_score_alts(txo_engine* e, const int64_t* tokens, int32_t L, float* logp_out, int64_t* top1_out, float* top1_logp_out, int32_t k,
+                          int32_t* alt_ids_out, float* alt_logp_out, void* stream) {
+    if (!e || !tokens) return fail(TXO_E_INVALID, "null argument");
+    if (L < 2 || L > e->impl->cfg.max_len + 1) return fail(TXO_E_INVALID, "score: L must be in [2, max_len + 1]");
+    if (int r = check_score_alts(e, k, alt_ids_out, alt_logp_out)) return r;
+    return e->impl->decode_score_alts(tokens, L, logp_out, top1_out, top1_logp_out, k, alt_ids_out, alt_logp_out, (hipStream_t)stream);
+}
+
+int txo_score_alts(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t H, int32_t W, const int64_t* tokens, const uint8_t* mask, int32_t L,
+                   float* logp_out, int64_t* top1_out, float* top1_logp_out, int32_t k, int32_t* alt_ids_out, float* alt_logp_out, void* stream) {
+    if (!e || !img || !tokens) return fail(TXO_E_INVALID, "null argument");
+    if (L < 2 || L > e->impl->cfg.max_len + 1) return fail(TXO_E_INVALID, "score: L must be in [2, max_len + 1]");
+    if (int r = check_score_alts(e, k, alt_ids_out, alt_logp_out)) return r;
+    return e->impl->score_alts(img, B, C, H, W, tokens, mask, L, logp_out, top1_out, top1_logp_out, k, alt_ids_out, alt_logp_out, (hipStream_t)stream);
+}
+
 int txo_score_ragged(txo_engine* e, const float* img, int32_t B, int32_t C, int32_t Hc, int32_t Wc, const int32_t* sizes, const int64_t* tokens,
                      const uint8_t* mask, int32_t L, float* logp_out, int64_t* top1_out, float* top1_logp_out, void* stream) {
     if (!e || !img || !sizes || !tokens) return fail(TXO_E_INVALID, "null argument");
@@ -2959,6 +3061,26 @@ int txo_set_repeat_guard(txo_engine* e, int32_t max_period, int32_t max_repeats)
                                    std::to_string(max_period + 1) + " (the guard may ban max_period tokens at a pick)");
     e->impl->guard_p = max_period; e->impl->guard_r = max_repeats;
     return 0;
+}
+
+int txo_set_alternatives(txo_engine* e, int32_t k) {
+    if (k == 0) {
+        if (!e) return fail(TXO_E_INVALID, "null engine");
+        e->impl->alts_k = 0;
+        return 0;
+    }
+    if (k < 1 || k > txo::ALTS_MAX)
+        return fail(TXO_E_INVALID, "alternatives: k is " + std::to_string(k) + "; it must be in [1, " + std::to_string(txo::ALTS_MAX) + "] (0 switches them off)");
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    if (k > e->impl->cfg.vocab)
+        return fail(TXO_E_INVALID, "alternatives: k is " + std::to_string(k) + " and the vocabulary has " + std::to_string(e->impl->cfg.vocab) + " entries");
+    e->impl->alts_k = k;
+    return 0;
+}
+
+int txo_last_alternatives(txo_engine* e, int32_t* ids_out, float* logp_out, int32_t B, int32_t cols, void* stream) {
+    if (!e) return fail(TXO_E_INVALID, "null engine");
+    return e->impl->last_alternatives(ids_out, logp_out, B, cols, (hipStream_t)stream);
 }
 
 int txo_rules_close_dist(txo_engine* e, int32_t* out_host, int32_t S, int32_t D) {

@@ -11,7 +11,7 @@ struct LaneSet {
     // captured steps, by what they were built for: built in ONE place, Session::graph_key (session.h: the range, eos, and every field of the
     // session a step's launches depend on).  Per-row stop replays a step per row count of the shrinking range (multiples of 16): a handful of
     // entries per range, built once and kept across generates.  exec = the entry the current decode replays.
-    using GraphKey = std::array<int, 7>;
+    using GraphKey = std::array<int, 8>;
     struct Lane {
         int b0 = 0, nb = 0;
         hipStream_t stream = nullptr;      // lane 0 runs on the caller's stream unless the tuned pair owns it

@@ -23,6 +23,7 @@
 // peak memory at 256 x 256 rows.  A wlog tile shared through LDS by the workgroup's waves would cut the stream fourfold.
 #pragma once
 #include "common.h"
+#include "kbest.h"
 
 namespace txo {
 
@@ -37,10 +38,15 @@ template <typename T> inline int score_waves(int D) {
 
 // z [M][D]; W [V][D]; tokens [images][tok_stride], row m = (b, p) with b = m / t: its target is tokens[b][p + 1].
 // Outputs are indexed by m; each may be null.
-template <typename T>
-__global__ __launch_bounds__(256) void score_rows_kernel(const T* __restrict__ z, const T* __restrict__ W, const float* __restrict__ bias,
-                                                         const int64_t* __restrict__ tokens, int tok_stride, int t, int M, int D, int V,
-                                                         float* __restrict__ logp, int64_t* __restrict__ top1, float* __restrict__ top1_logp) {
+// ALTS (the k-best form, score_rows_alts_kernel below): every lane also keeps the KBEST_MAX best of the logits it owns (kbest.h; it meets them
+// in increasing index), and the 4 lane groups of a row are merged in k rounds of the top-1 merge's own exchange -- the same order, the same
+// tie rule, no atomics -- so alt_ids[..][0] is top1 and alt_logp[..][0] the float top1_logp holds; alt_logp[j] = logit - lse like it.
+// alt_ids / alt_logp [M][k].  The <false> form reads none of the three and is the kernel as it was (profiles/alts_resource_usage.txt).
+template <typename T, bool ALTS>
+__device__ __forceinline__ void score_rows_body(const T* __restrict__ z, const T* __restrict__ W, const float* __restrict__ bias,
+                                                const int64_t* __restrict__ tokens, int tok_stride, int t, int M, int D, int V,
+                                                float* __restrict__ logp, int64_t* __restrict__ top1, float* __restrict__ top1_logp,
+                                                int k, int32_t* __restrict__ alt_ids, float* __restrict__ alt_logp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sc_lds[];
     constexpr int PER16 = Elem<T>::PER16, KCHUNK = Elem<T>::KCHUNK;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -69,6 +75,8 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const T* __restrict__ z
     }
     float m_run = SC_MASKED, l_run = 0.f, best = SC_MASKED, tl = 0.f;
     int bi = 0;
+    KBest kb;
+    if constexpr (ALTS) kb.clear(SC_MASKED);
     const int KC = D / KCHUNK;
     const unsigned char* zrow = zs + lc * rowbytes;
     for (int v0 = 0; v0 < V; v0 += 16 * SC_VT) {
@@ -98,6 +106,7 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const T* __restrict__ z
                     x = acc[j][r] + bias[v];
                     if (x > best) { best = x; bi = v; }       // entries in increasing order: the first of equals stays
                     if (v == tgt) tl = x;
+                    if constexpr (ALTS) kb.push(x, v);
                 }
                 acc[j][r] = x;
                 mx = fmaxf(mx, x);
@@ -129,6 +138,37 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const T* __restrict__ z
         if (top1) top1[m] = bi;
         if (top1_logp) top1_logp[m] = best - lse;
     }
+    if constexpr (ALTS) {
+        const float lse = m_all + logf(l_all);
+        for (int r = 0; r < k; ++r) {
+            float b = kb.val[0]; int i = kb.idx[0];
+            auto take = [&](float ov, int oi) { if (ov > b || (ov == b && oi < i)) { b = ov; i = oi; } };
+            const float o16 = xor16(b); const int i16 = xor16(i);
+            take(o16, i16);
+            const float o32 = xor32(b); const int i32 = xor32(i);
+            take(o32, i32);
+            if (i == kb.idx[0] && i != 0x7fffffff) kb.pop(SC_MASKED);         // (one lane of the four holds entry i)
+            if (lg == 0 && r0 + lc < M) {
+                const size_t o = (size_t)(r0 + lc) * k + r;
+                alt_ids[o] = (unsigned)i < (unsigned)V ? i : 0;               // (a non-finite row: unspecified, inside the vocabulary)
+                alt_logp[o] = b - lse;
+            }
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void score_rows_kernel(const T* __restrict__ z, const T* __restrict__ W, const float* __restrict__ bias,
+                                                         const int64_t* __restrict__ tokens, int tok_stride, int t, int M, int D, int V,
+                                                         float* __restrict__ logp, int64_t* __restrict__ top1, float* __restrict__ top1_logp) {
+    score_rows_body<T, false>(z, W, bias, tokens, tok_stride, t, M, D, V, logp, top1, top1_logp, 0, nullptr, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void score_rows_alts_kernel(const T* __restrict__ z, const T* __restrict__ W, const float* __restrict__ bias,
+                                                              const int64_t* __restrict__ tokens, int tok_stride, int t, int M, int D, int V,
+                                                              float* __restrict__ logp, int64_t* __restrict__ top1, float* __restrict__ top1_logp,
+                                                              int k, int32_t* __restrict__ alt_ids, float* __restrict__ alt_logp) {
+    score_rows_body<T, true>(z, W, bias, tokens, tok_stride, t, M, D, V, logp, top1, top1_logp, k, alt_ids, alt_logp);
 }
 
 // kmask [rows][tmax] from a caller's mask [rows][stride] of which the first `cols` columns are positions (txo_score: stride L,

@@ -18,12 +18,13 @@ struct Session {
     bool closing = false;                 // ... and under the closing budget (txo_set_rules_close; implies ruled)
     int guard_p = 0, guard_r = 0;         // a guarded decode: the steps pick under the repeat guard (step_guard.h; launch path only), 0: none
     bool guarded() const { return guard_p > 0; }
+    int alts = 0;                         // the steps keep the k best of every row in front of the pick (step_alts.h; launch path only), 0: off
     // what a captured step was built for (lanes.h): every field a step's launches depend on (strides and row count are baked into them)
     // rules: what a constrained step bakes of the rule set (states * 256 + depth cap, + 4096 for a closing decode's kernels; the tables
     // themselves stay in the engine's buffers; + 8192 * (17 * max_period + max_repeats) for a guarded decode's)
     LaneSet::GraphKey graph_key(const LaneSet::Lane& ln, int eos, int sample_mode, bool logp, int rules = 0) const {
         return {ln.b0, ln.nb, keys, eos, rows, images,
-                (int)latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)ragged + 32 * (int)logp + 64 * (int)forced + 128 * ((ruled ? rules : 0) + 8192 * (17 * guard_p + guard_r))};
+                (int)latent + 2 * (int)lat_self + 4 * (int)row_stop + 8 * sample_mode + 16 * (int)ragged + 32 * (int)logp + 64 * (int)forced + 128 * ((ruled ? rules : 0) + 8192 * (17 * guard_p + guard_r)), alts};
     }
 };
 struct KeyCounts { const int* dev = nullptr; const int32_t* host = nullptr; };   // a ragged session's key count per image: a device array or the caller's host array (staged)

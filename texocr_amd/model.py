@@ -100,6 +100,7 @@ class HipEngine:
         self.loaded = False
         self.token_rules = None                      # (a new handle has no token rules: a set installed by hand goes with the old one)
         self.repeat_guard = None                     # (... and no repeat guard)
+        self.alts = 0                                # (... and keeps no alternatives)
         if getattr(self, "_ragged_hybrid", False):   # (a reload of the weights makes a new handle: the switch follows the engine object)
             _lib.check(self.lib.txo_set_ragged_hybrid(h, 1))
         if getattr(self, "_rules_beam", False):
@@ -333,6 +334,19 @@ class HipEngine:
         """(B, 2) int32: the (state, depth) of every row behind the last constrained generate, beside its tokens (B, n)"""
         return torch.ops.texocr.last_rule_state(tokens if tokens.ndim == 2 else tokens[None, :], self.id)
 
+    def set_alternatives(self, k: int) -> None:
+        """txo_set_alternatives: k in [1, 8] (checked on the host first, ops.check_alts: the same refusals), or 0 = off.  While set, every
+        generate from BOS or a prefix keeps the k best ids / log-probabilities of every row it picks from, on the launch path; beam search raises."""
+        self._ensure()
+        torch.ops.texocr.set_alternatives(self.id, ops.check_alts(k, self.dims.vocab) if k else 0)
+
+    def last_alternatives(self, tokens: torch.Tensor) -> "Alts":
+        """Alts (B, n, k) of the last generate, beside its tokens (B, n)"""
+        return Alts(*torch.ops.texocr.last_alternatives(tokens if tokens.ndim == 2 else tokens[None, :], self.id, int(getattr(self, "alts", 0))))
+
+    def decode_score_alts(self, tokens: torch.Tensor, k: int):
+        return torch.ops.texocr.decode_score_alts(tokens, self.id, int(k))
+
     def set_repeat_guard(self, repeat_guard) -> None:
         """txo_set_repeat_guard: (max_period, max_repeats) (checked on the host first, texocr_amd.guard.check: the same refusals), or None =
         off.  While set, every generate from BOS or a prefix picks under the guard, on the launch path; close=True raises there, and beam search raises unless guard_beam is on."""
@@ -342,14 +356,15 @@ class HipEngine:
 
     @contextlib.contextmanager
     def modes(self, sample: Optional[Tuple[float, Optional[int]]] = None, stop: str = "global", decode: Optional[str] = None, rules=None,
-              close: bool = False, repeat_guard=None):
+              close: bool = False, repeat_guard=None, alts: int = 0):
         """The engine's global switches around the calls of one generate: sampling with sample = (temp, seed) -- a seed of None is
         drawn from torch's generator; decode='greedy' overrides it --, per-row stop, and token rules (rules=: a TokenRules installed for the
         scope; the set that was installed before, or none, is back behind every exit).  Nothing else in this module turns sampling or the
         per-row stop on, and both are off again behind every exit.  Yields (temp, seed) as set, or None.
         close=True (only with rules=, ValueError otherwise): the closing decode (txo_set_rules_close) for the scope, off again behind it.
         repeat_guard=(max_period, max_repeats): the repeat guard (txo_set_repeat_guard) for the scope; the one set before, or none, is back
-        behind every exit."""
+        behind every exit.
+        alts=k: alternatives per token (txo_set_alternatives) for the scope; the k set before, or 0, is back behind every exit."""
         _check_modes(stop, decode or "greedy")
         if close not in (False, True, 0, 1):
             raise ValueError("close must be False or True")
@@ -361,7 +376,10 @@ class HipEngine:
             sample = (sample[0], int(torch.randint(0, 2**62, (1,)).item()))
         before = getattr(self, "token_rules", None)                # what ops.set_token_rules recorded: (table, depth_max) or None
         guard_before = getattr(self, "repeat_guard", None)         # what ops.set_repeat_guard recorded: (P, R) or None
+        alts_before = getattr(self, "alts", 0)                     # what ops.set_alternatives recorded
         try:
+            if alts:
+                self.set_alternatives(alts)
             if repeat_guard is not None:
                 self.set_repeat_guard(repeat_guard)
             if rules is not None:
@@ -374,6 +392,8 @@ class HipEngine:
                 self.set_stop_mode("row")
             yield sample
         finally:
+            if alts:
+                torch.ops.texocr.set_alternatives(self.id, alts_before)
             if repeat_guard is not None:
                 torch.ops.texocr.set_repeat_guard(self.id, *(guard_before or (0, 0)))
             if sample is not None:
@@ -601,6 +621,29 @@ def _session(eng, enc: torch.Tensor, n_tokens: Optional[torch.Tensor]):
             yield
 
 
+class Alts(NamedTuple):
+    """Alternatives per token (build extension): ids (B, n, k) int32 and logp (B, n, k) float32.  ids[b, t] are the k largest entries of the
+    logits row token t of row b was picked from, in descending value, the lower id first among equals (a stable descending sort: ids[..., 0]
+    is the greedy pick); logp = log_softmax(row)[ids], temperature 1 over the whole vocabulary.  Always the RAW model's row: not the
+    sampler's top-k / temperature distribution, not masked by rules=, close=True or repeat_guard= -- under a sampled, constrained or guarded
+    decode the committed token may be missing from its own alternatives, which is how a caller sees that a rule forced it.  Where tokens /
+    logp hold pad / 0.0 (behind a row's eos under stop='row', columns a longer-prefix row never reached) so do ids / logp."""
+    ids: torch.Tensor
+    logp: torch.Tensor
+
+
+def _squeeze0(o):
+    return Alts(o.ids.squeeze(0), o.logp.squeeze(0)) if isinstance(o, Alts) else o.squeeze(0)
+
+
+def _append_alts(eng, out, k: int):
+    """a generate's result with the Alts of the call behind it (k = 0: the result as it is)"""
+    if not k:
+        return out
+    out = out if isinstance(out, tuple) else (out,)
+    return (*out, eng.last_alternatives(out[0]))
+
+
 class Score(NamedTuple):
     """What AutoRegressiveDecoder.score / OCRModel.score return (position p of row b scores the target trg[b, p + 1]):
     logp (B, L-1) log-probability of the target; top1 (B, L-1) arg-max of the logits; top1_logp (B, L-1) its log-probability;
@@ -779,13 +822,20 @@ class AutoRegressiveDecoder(nn.Module):
 
     @torch.no_grad()
     def score(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, enc: Optional[torch.Tensor] = None,
-              n_tokens: Optional[torch.Tensor] = None) -> Score:
-        """The quantity forward() trains on, for inference (decoder.py:124-145 without autograd): x (B, L) int64 target sequences
+              n_tokens: Optional[torch.Tensor] = None, alts: int = 0):
+        """alts=k (build extension, 1..8): -> (Score, Alts), the k best ids / log-probabilities of every scored row (B, L-1, k) from the same
+        fused kernel (the logits are still never stored); Alts.ids[..., 0] is Score.top1 and Alts.logp[..., 0] Score.top1_logp bit for bit, and
+        every Score field is bit for bit what the call without alts= returns.  Not with n_tokens= (ValueError).
+        The quantity forward() trains on, for inference (decoder.py:124-145 without autograd): x (B, L) int64 target sequences
         (bos first), x[:, :-1] is fed in one causal pass and x[:, 1:] are the targets.  mask (B, L) bool, False = padding (None: no
         padding).  The logits are never materialised (csrc/score.h).  Unlike the reference's loss, `loss` averages over the valid
         positions only (F.cross_entropy there has no ignore_index); without padding the two are the same number.
         n_tokens= (build extension): enc / n_tokens as VisionEncoder.forward_ragged returns them; row b scores against image b's own rows."""
         _need_enc(enc)
+        if alts:
+            ops.check_alts(alts, self._engine.dims.vocab)
+            if n_tokens is not None:
+                raise ValueError("alts= is not available with n_tokens= (alternatives are not kept on a ragged scoring pass)")
         if n_tokens is not None:
             n_tokens = _check_n_tokens(n_tokens, enc)
         _check_x(x, "(B, L)")
@@ -799,6 +849,9 @@ class AutoRegressiveDecoder(nn.Module):
         _check_token_ids(x, eng.dims.vocab)
         m = torch.ones_like(x, dtype=torch.bool) if mask is None else mask.to(device=x.device, dtype=torch.bool)
         with _session(eng, enc, n_tokens), eng.key_mask(m[:, :-1]):   # (the last column is a target only, never a key)
+            if alts:
+                logp, top1, top1_logp, ids, alp = eng.decode_score_alts(x, alts)
+                return score_summary(logp, top1, top1_logp, x, m), Alts(ids, alp)
             logp, top1, top1_logp = eng.decode_score(x)
         return score_summary(logp, top1, top1_logp, x, m)
 
@@ -856,10 +909,15 @@ class AutoRegressiveDecoder(nn.Module):
         close = kwargs.pop("close", False)                         # build extension, with rules=: the closing decode (OCRModel.generate)
         # build extension: (max_period, max_repeats), the repeat guard (OCRModel.generate).  Needs the engine's own loop, like rules=
         repeat_guard = kwargs.pop("repeat_guard", None)
-        rstate = None
+        # build extension: k in [1, 8], an Alts (B, n, k) of the k best ids / log-probabilities behind every token, appended to the result directly
+        # before rule_state where there is one and last otherwise.  Needs the engine's own loop inside the positional table, like rules=
+        return_alts = kwargs.pop("return_alts", 0)
+        rstate = alts = None
         if kwargs:
             raise ValueError(f"unsupported arguments: {sorted(kwargs)}")
         _need_enc(enc)
+        if return_alts:
+            ops.check_alts(return_alts, self._engine.dims.vocab)
         if mask is not None and mask.ndim == 1:
             mask = mask[None, :]
         padded = mask is not None and not bool(mask.all())
@@ -888,9 +946,11 @@ class AutoRegressiveDecoder(nn.Module):
             prompted = True
             if return_logits:
                 raise ValueError("return_logits is not available with prefix_len (a prompted decode keeps no logits)")
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard) as sample:
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard, alts=return_alts) as sample:
             if prompted:
                 out = eng.generate_prefix(None, st.to(enc.device), max_len, eos_tok, prefix_len=prefix_len, enc=enc, return_logp=return_logp)
+                if return_alts:
+                    alts = eng.last_alternatives(out[0] if return_logp else out)
                 if rules is not None:
                     rstate = eng.last_rule_state(out[0] if return_logp else out)
                 # stop='row': the engine has padded with its own pad id, by each row's own prefix; a caller's pad= is put in its place -- every
@@ -899,10 +959,12 @@ class AutoRegressiveDecoder(nn.Module):
                     toks = out[0] if return_logp else out
                     toks = _pad_after_eos(toks, _inside_lengths(st, prefix_len, -1).to(toks.device), eos_tok, int(pad))
                     out = (toks, *out[1:]) if return_logp else toks
+                if return_alts:
+                    out = (*out, alts) if return_logp else (out, alts)
                 if rules is not None:
-                    out = (*out, rstate) if return_logp else (out, rstate)
-                if return_logp or rules is not None:
-                    return tuple(o.squeeze(0) for o in out) if squeeze else out
+                    out = (*out, rstate) if (return_logp or return_alts) else (out, rstate)
+                if return_logp or return_alts or rules is not None:
+                    return tuple(_squeeze0(o) for o in out) if squeeze else out
                 return out.squeeze(0) if squeeze else out
             # beyond the positional table the engine slides the window with its multi-position forward, which needs a vocabulary
             # that is a multiple of 8 and a table that fits its workspace -- else the general stepwise loop below
@@ -914,12 +976,16 @@ class AutoRegressiveDecoder(nn.Module):
             if repeat_guard is not None and not engine_loop:
                 raise ValueError("repeat_guard= needs the engine's own loop: a start the prompted decode or a BOS start can take (no padding mask; "
                                  "beyond decoder.max_len a vocabulary that is a multiple of 8 and max_length <= max_batch * max_tokens)")
+            if return_alts and not engine_loop:
+                raise ValueError("return_alts= needs the engine's own loop: a start the prompted decode or a BOS start can take (no padding mask)")
             if padded:
                 if return_logits or return_logp:
                     raise ValueError("return_logits / return_logp are not available with a padding mask")
                 out = self._generate_stepwise(st, eos_tok, max_len, enc, sample, mask=mask)
             elif T0 == 1 and bool((st == eng.dims.bos).all()) and (window_ok or return_logits):
                 out = eng.generate(None, max_len, eos_tok, enc=enc, return_logits=return_logits, return_logp=return_logp)
+                if return_alts:
+                    alts = eng.last_alternatives(out[0] if (return_logits or return_logp) else out)
                 if rules is not None:
                     rstate = eng.last_rule_state(out[0] if (return_logits or return_logp) else out)
             elif return_logits:
@@ -938,10 +1004,12 @@ class AutoRegressiveDecoder(nn.Module):
                 out = (_pad_after_eos(out[0], st.to(out[0].device), eos_tok, p_id), *out[1:])
             else:
                 out = _pad_after_eos(out, st.to(out.device), eos_tok, p_id)
+        if return_alts:
+            out = (*out, alts) if (return_logits or return_logp) else (out, alts)
         if rules is not None:
-            out = (*out, rstate) if (return_logits or return_logp) else (out, rstate)
-        if return_logits or return_logp or rules is not None:
-            return tuple(o.squeeze(0) for o in out) if squeeze else out
+            out = (*out, rstate) if (return_logits or return_logp or return_alts) else (out, rstate)
+        if return_logits or return_logp or return_alts or rules is not None:
+            return tuple(_squeeze0(o) for o in out) if squeeze else out
         return out.squeeze(0) if squeeze else out
 
     def _generate_stepwise(self, st, eos_tok, max_len, enc, sample, mask=None):
@@ -1091,8 +1159,15 @@ class OCRModel(nn.Module):
     def generate(self, src: torch.Tensor, max_len: int, temp: float = 0.3, *, decode: str = "greedy",
                  generator: Optional[torch.Generator] = None, seed: Optional[int] = None, return_logits: bool = False,
                  beam: int = 0, return_beams: bool = False, stop: str = "global", return_logp: bool = False,
-                 prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None, close: bool = False, repeat_guard=None):
-        """repeat_guard=(max_period, max_repeats) (build extension; both in [1, 16]): the repeat guard, for this call.  No row may end in
+                 prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None, close: bool = False, repeat_guard=None,
+                 return_alts: int = 0):
+        """return_alts=k (build extension; k in [1, 8]): which tokens the model would have taken instead.  An Alts (ids, logp), each (B, n, k),
+        is appended to the result, directly before rule_state where there is one and last otherwise: the k best ids of the raw logits row
+        behind every token and their log-probabilities (see Alts: raw, not the sampler's distribution, not masked by rules= / close= /
+        repeat_guard=, so a forced token may be missing from its own alternatives).  In a greedy decode ids[..., 0] are the tokens and
+        logp[..., 0] is return_logp's logp bit for bit.  With prefix=: the columns are the tokens' own.  The decode runs on the launch path.
+        Refused (ValueError): k outside [1, 8] or beyond the vocabulary, with beam=, max_len > decoder.max_len.
+        repeat_guard=(max_period, max_repeats) (build extension; both in [1, 16]): the repeat guard, for this call.  No row may end in
         max_repeats + 1 consecutive copies of a block of at most max_period tokens: the token that would complete such a run is masked in
         the selection like a rule-disallowed one (texocr_amd.guard.banned is the rule; the history is the prefix's tokens behind its start
         token, then the row's picks).  eos is never banned, a prefix token never masked; logp and logits stay those of the raw logits.  With
@@ -1123,9 +1198,13 @@ class OCRModel(nn.Module):
         _check_modes(stop)
         if prefix is not None:
             return self._generate_prefix(src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules,
-                                         close, repeat_guard)
+                                         close, repeat_guard, return_alts)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
+        if return_alts:
+            ops.check_alts(return_alts, self._engine.dims.vocab)
+            if beam:
+                raise ValueError("return_alts is not available with beam search (beam=k): alternatives are kept by the greedy / sampled decode only")
         if beam and return_logp:
             raise ValueError("return_logp is not available with beam search (beam=k): it returns beam scores (return_beams=True)")
         if beam:                                           # build extension (BASELINE config 5); engine max_batch >= B * beam
@@ -1140,8 +1219,9 @@ class OCRModel(nn.Module):
         if decode == "greedy" and self.bos_token == self._engine.dims.bos:
             # (max_len > decoder.max_len: txo_generate slides the window like the reference, decoder.py:99-100)
             # (stop='row' with return_logits: the engine does not compact -- a finished row's logits would be missing -- and only pads)
-            with self._engine.modes(stop=stop, rules=rules, close=close, repeat_guard=repeat_guard):
+            with self._engine.modes(stop=stop, rules=rules, close=close, repeat_guard=repeat_guard, alts=return_alts):
                 out = self._engine.generate(src, max_len, self.eos_token, return_logits=return_logits, return_logp=return_logp)
+                out = _append_alts(self._engine, out, return_alts)
                 if rules is None:
                     return out
                 out = out if isinstance(out, tuple) else (out,)
@@ -1152,12 +1232,17 @@ class OCRModel(nn.Module):
                                      decode=decode, generator=generator, seed=seed, enc=enc, return_logits=return_logits,
                                      stop=stop, pad=self.trg_pad_idx, return_logp=return_logp,
                                      **({} if rules is None and not close else {"rules": rules, "close": close}),
-                                     **({} if repeat_guard is None else {"repeat_guard": repeat_guard}))
+                                     **({} if repeat_guard is None else {"repeat_guard": repeat_guard}),
+                                     **({} if not return_alts else {"return_alts": return_alts}))
 
     def _generate_prefix(self, src, max_len, temp, decode, generator, seed, return_logits, beam, stop, return_logp, prefix, prefix_len, rules=None,
-                         close=False, repeat_guard=None):
+                         close=False, repeat_guard=None, return_alts=0):
         """generate(prefix=) / generate_ragged(prefix=): src a (B, C, H, W) tensor or a sequence of images.  Every refusal comes before
         the engine is touched."""
+        if return_alts:
+            ops.check_alts(return_alts, self._engine.dims.vocab)
+            if beam:
+                raise ValueError("return_alts is not available with beam search (beam=k): alternatives are kept by the greedy / sampled decode only")
         if beam:
             raise ValueError("prefix= is not available with beam search (beam=k)")
         if return_logits:
@@ -1174,8 +1259,9 @@ class OCRModel(nn.Module):
         if seed is None and generator is not None:
             seed = generator.initial_seed()
         dev = src[0].device if isinstance(src, (list, tuple)) else src.device           # (a tensor or a PackedImages says it itself)
-        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard):
+        with eng.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard, alts=return_alts):
             out = eng.generate_prefix(src, prefix.to(dev), max_len, self.eos_token, prefix_len=prefix_len, return_logp=return_logp)
+            out = _append_alts(eng, out, return_alts)
             if rules is None:
                 return out
             out = out if isinstance(out, tuple) else (out,)
@@ -1206,7 +1292,7 @@ class OCRModel(nn.Module):
 
     @torch.no_grad()
     def beam_search(self, src, beams: int, max_len: int, *, return_logp: bool = False, length_alpha: float = 0.0, rules=None,
-                    close: bool = False, repeat_guard=None) -> Beams:
+                    close: bool = False, repeat_guard=None, return_alts: int = 0) -> Beams:
         """Build extension: the k = beams best sequences of every image, with score, length and (return_logp=True) the log-probability of
         every token -> Beams.  src is a (B, C, H, W) tensor, or a sequence of (C, H_b, W_b) tensors of different sizes: those go
         through ONE ragged encode and ONE decode, and the beams of image b are what beam_search(src[b][None]) returns, over the batch's n.
@@ -1225,6 +1311,8 @@ class OCRModel(nn.Module):
         candidate counts as -inf like a rule-disallowed one, eos is never banned, scores and logp stay sums of the raw log-probabilities.
         Beside rules= (rules_beam on as well) a candidate must be allowed and unbanned; a beam that has no such token drops its ban at that
         pick (the yield rule), so with close=True every live beam still ends finished."""
+        if return_alts:
+            raise ValueError("return_alts is not available in beam_search: alternatives are kept by generate()'s greedy / sampled decode only")
         if isinstance(src, torch.Tensor):
             if src.ndim != 4:
                 raise ValueError("beam search needs src of shape (B, C, H, W), or a sequence of (C, H_b, W_b) images")
@@ -1241,8 +1329,9 @@ class OCRModel(nn.Module):
     @torch.no_grad()
     def generate_ragged(self, images, max_len: int, temp: float = 0.3, *, decode: str = "greedy", seed: Optional[int] = None,
                         stop: str = "global", return_logp: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len=None, rules=None,
-                        close: bool = False, repeat_guard=None):
-        """Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
+                        close: bool = False, repeat_guard=None, return_alts: int = 0):
+        """return_alts=k: as generate() takes it (an Alts appended, before rule_state); refused with max_len > decoder.max_len.
+        Build extension: generate() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call -> (B, n_steps).
         Row b is what generate(images[b][None]) returns, over the batch's n_steps (the eos rules are generate()'s; a sampled draw
         is keyed by the row of the batch).  max_len may exceed decoder.max_len: the window slides as in generate(), under the engine's
         two preconditions (a vocabulary that is a multiple of 8, max_length <= max_batch * max_tokens; ValueError before anything is
@@ -1250,24 +1339,30 @@ class OCRModel(nn.Module):
         repeat_guard=: as generate() takes them (rules=: rule_state (B, 2) is the result's last element)."""
         if prefix is not None:
             return self._generate_prefix(images, max_len, temp, decode, None, seed, False, 0, stop, return_logp, prefix, prefix_len, rules, close,
-                                         repeat_guard)
+                                         repeat_guard, return_alts)
         if prefix_len is not None:
             raise ValueError("prefix_len needs prefix")
-        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard):
+        if return_alts:
+            ops.check_alts(return_alts, self._engine.dims.vocab)
+        with self._engine.modes(sample=(temp, seed), stop=stop, decode=decode, rules=rules, close=close, repeat_guard=repeat_guard, alts=return_alts):
             out = self._engine.generate_ragged(images, max_len, self.eos_token, return_logp=return_logp)
+            out = _append_alts(self._engine, out, return_alts)
             if rules is None:
                 return out
             out = out if isinstance(out, tuple) else (out,)
             return (*out, self._engine.last_rule_state(out[0]))
 
     @torch.no_grad()
-    def score(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:
+    def score(self, src: torch.Tensor, trg: torch.Tensor, mask: Optional[torch.Tensor] = None, alts: int = 0):
         """Teacher-forced scoring of trg (B, L) against the images src -- what forward(src, trg) computes (ocr_model.py:38-44),
         without autograd and per token: see AutoRegressiveDecoder.score.  mask defaults to trg != trg_pad_idx (make_trg_mask).
-        The confidence of a generate() result: score(src, cat([bos], tokens))."""
+        The confidence of a generate() result: score(src, cat([bos], tokens)).
+        alts=k (build extension, 1..8): -> (Score, Alts), the k best ids / log-probabilities of every scored row (AutoRegressiveDecoder.score)."""
+        if alts:
+            ops.check_alts(alts, self._engine.dims.vocab)
         if mask is None:
             mask = trg != self.trg_pad_idx
-        return self.decoder.score(trg, mask=mask, enc=self.encoder(src))
+        return self.decoder.score(trg, mask=mask, enc=self.encoder(src), **({"alts": alts} if alts else {}))
 
     def _ragged_trg(self, images, trg: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
         """the checks score_ragged / align_ragged share, before the engine is touched -> the mask (default trg != trg_pad_idx)"""
@@ -1284,9 +1379,12 @@ class OCRModel(nn.Module):
         return mask
 
     @torch.no_grad()
-    def score_ragged(self, images, trg: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Score:
-        """Build extension: score() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call (txo_score_ragged): row b
+    def score_ragged(self, images, trg: torch.Tensor, mask: Optional[torch.Tensor] = None, alts: int = 0) -> Score:
+        """alts=: refused (ValueError) -- alternatives are not kept on a ragged scoring pass.
+        Build extension: score() over a sequence of (C, H_b, W_b) images of different sizes in ONE engine call (txo_score_ragged): row b
         is what score(images[b][None], trg[b:b+1], mask[b:b+1]) returns; loss and token_acc run over the whole batch's valid positions."""
+        if alts:
+            raise ValueError("alts= is not available in score_ragged: alternatives are not kept on a ragged scoring pass (use score())")
         mask = self._ragged_trg(images, trg, mask)
         _check_x(trg, "(B, L)")
         _check_token_ids(trg, self._engine.dims.vocab)

@@ -25,6 +25,9 @@ traced (``torch.compile`` / ``FakeTensorMode``) without a GPU.  The reference ca
   texocr::set_guard_beam    (build extension, opt-in) the repeat guard inside the beam selection: the beam entries accept a guard
   texocr::set_repeat_guard  (build extension, opt-in) the repeat guard: a row of the generate family may not end in max_repeats + 1 copies of a
                             block of at most max_period tokens (texocr_amd/guard.py is the rule in numpy)
+  texocr::set_alternatives / last_alternatives / decode_score_alts / score_alts
+                            (build extension, opt-in) the k best ids and log-probabilities of every logits row: beside the tokens of the
+                            generate family (csrc/step_alts.h), and beside the teacher-forced scores (csrc/score.h), no (B, T, V) tensor
   texocr::set_rules_close   (build extension, opt-in) the closing decode: a constrained decode or beam search only picks tokens from which
                             eos can still be reached in the positions left (``rules_close_dist`` reads the engine's distance table)
   texocr::encode_ragged / decode_begin_ragged / generate_ragged / score_ragged
@@ -269,6 +272,83 @@ def _(tokens, engine):
     B, L = tokens.shape
     return (tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1), dtype=torch.int64),
             tokens.new_empty((B, L - 1), dtype=torch.float32))
+
+
+ALTS_MAX = 8       # include/texocr.h: txo_set_alternatives
+
+
+def check_alts(k, vocab: Optional[int] = None) -> int:
+    """k of an alternatives request, as the engine checks it (the same refusals, before the engine is touched)"""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"alternatives: k must be an int in [1, {ALTS_MAX}], got {k!r}")
+    if k < 1 or k > ALTS_MAX:
+        raise ValueError(f"alternatives: k is {k}; it must be in [1, {ALTS_MAX}]")
+    if vocab is not None and k > vocab:
+        raise ValueError(f"alternatives: k is {k} and the vocabulary has {vocab} entries")
+    return k
+
+
+@custom_op("texocr::decode_score_alts", mutates_args=())
+def decode_score_alts(tokens: torch.Tensor, engine: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_score with the k best of every scored row (txo_decode_score_alts) -> (logp, top1, top1_logp, alt_ids (B, L-1, k) int32,
+    alt_logp (B, L-1, k) float32): descending value, the lower id first among equals; alt_ids[..., 0] is top1 and alt_logp[..., 0] top1_logp,
+    and the first three are bit for bit decode_score's."""
+    e = _eng(engine)
+    B = session(e, "decode_score_alts").rows
+    tokens = _i64_dev(tokens, "tokens", e, B, 2, "(B, L) matching the session started by texocr::decode_begin")
+    L = int(tokens.shape[1])
+    if L < 2 or L - 1 > e.dims.max_len:
+        raise ValueError(f"tokens must have 2 <= L <= max_len + 1 = {e.dims.max_len + 1} columns, got {L}")
+    logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    top1 = torch.empty((B, L - 1), device=tokens.device, dtype=torch.int64)
+    top1_logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    ids = torch.empty((B, L - 1, max(int(k), 0)), device=tokens.device, dtype=torch.int32)
+    alp = torch.empty((B, L - 1, max(int(k), 0)), device=tokens.device, dtype=torch.float32)
+    _call(e, "txo_decode_score_alts", tokens.data_ptr(), L, logp.data_ptr(), top1.data_ptr(), top1_logp.data_ptr(), int(k), ids.data_ptr(), alp.data_ptr())
+    return logp, top1, top1_logp, ids, alp
+
+
+@decode_score_alts.register_fake
+def _(tokens, engine, k):
+    B, L = tokens.shape
+    return (tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1), dtype=torch.int64),
+            tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1, k), dtype=torch.int32),
+            tokens.new_empty((B, L - 1, k), dtype=torch.float32))
+
+
+@custom_op("texocr::score_alts", mutates_args=())
+def score_alts(img: torch.Tensor, tokens: torch.Tensor, mask: Optional[torch.Tensor], engine: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """txo_score_alts: images (B, C, H, W), tokens (B, L) int64, mask (B, L) bool / uint8 (False = padding) or None: encode, open the session
+    and score in one call -> decode_score_alts's five tensors.  The session stays open on the engine's own encoder rows."""
+    e = _eng(engine, ready=True)
+    img = _img_arg(img, e)
+    B = int(img.shape[0])
+    tokens = _i64_dev(tokens, "tokens", e, B, 2, "(B, L), one row per image")
+    L = int(tokens.shape[1])
+    if L < 2 or L - 1 > e.dims.max_len:
+        raise ValueError(f"tokens must have 2 <= L <= max_len + 1 = {e.dims.max_len + 1} columns, got {L}")
+    m8 = None
+    if mask is not None:
+        if tuple(mask.shape) != (B, L):
+            raise ValueError("mask must have the shape of tokens")
+        m8 = mask.to(device=tokens.device, dtype=torch.uint8).contiguous()
+    logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    top1 = torch.empty((B, L - 1), device=tokens.device, dtype=torch.int64)
+    top1_logp = torch.empty((B, L - 1), device=tokens.device, dtype=torch.float32)
+    ids = torch.empty((B, L - 1, max(int(k), 0)), device=tokens.device, dtype=torch.int32)
+    alp = torch.empty((B, L - 1, max(int(k), 0)), device=tokens.device, dtype=torch.float32)
+    _call(e, "txo_score_alts", img.data_ptr(), B, int(img.shape[1]), int(img.shape[2]), int(img.shape[3]), tokens.data_ptr(),
+          None if m8 is None else m8.data_ptr(), L, logp.data_ptr(), top1.data_ptr(), top1_logp.data_ptr(), int(k), ids.data_ptr(), alp.data_ptr(),
+          leaves=(B, img, 1 + (int(img.shape[2]) // 16) * (int(img.shape[3]) // 16)))
+    return logp, top1, top1_logp, ids, alp
+
+
+@score_alts.register_fake
+def _(img, tokens, mask, engine, k):
+    B, L = tokens.shape
+    return (tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1), dtype=torch.int64),
+            tokens.new_empty((B, L - 1), dtype=torch.float32), tokens.new_empty((B, L - 1, k), dtype=torch.int32),
+            tokens.new_empty((B, L - 1, k), dtype=torch.float32))
 
 
 def _session_keys(e, ses: Session) -> int:
@@ -842,6 +922,45 @@ def set_repeat_guard(engine: int, max_period: int, max_repeats: int) -> None:
 @set_repeat_guard.register_fake
 def _(engine, max_period, max_repeats):
     return None
+
+
+# ---- alternatives per token (txo_set_alternatives): the k best ids / log-probabilities of every row the generate family picks from ----
+@custom_op("texocr::set_alternatives", mutates_args=())
+def set_alternatives(engine: int, k: int) -> None:
+    """txo_set_alternatives: k in [1, 8], 0: off (the default).  The engine names what it refuses (ValueError).  ``engine.alts`` records k."""
+    e = _eng(engine)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.txo_set_alternatives(e.handle, int(k)))
+    e.alts = int(k)
+
+
+@set_alternatives.register_fake
+def _(engine, k):
+    return None
+
+
+@custom_op("texocr::last_alternatives", mutates_args=())
+def last_alternatives(tokens: torch.Tensor, engine: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """txo_last_alternatives: the alternatives of the last generate beside its `tokens` (B, n) -> (ids (B, n, k) int32, logp (B, n, k) float32);
+    k is what that generate ran with (the engine refuses if it ran without)."""
+    e = _eng(engine)
+    if not tokens.is_cuda or tokens.ndim != 2 or tokens.device.index != e.device:
+        raise ValueError("last_alternatives: tokens must be the (B, n) GPU tensor the generate returned")
+    B, n = int(tokens.shape[0]), int(tokens.shape[1])
+    ids = torch.empty((B, n, int(k)), device=tokens.device, dtype=torch.int32)
+    lp = torch.empty((B, n, int(k)), device=tokens.device, dtype=torch.float32)
+    with torch.cuda.device(e.device):
+        out = C.c_int64(0)
+        _lib.check(e.lib.txo_engine_query(e.handle, _lib.Q_LAST_ALTS, C.byref(out)))
+    if out.value != int(k):
+        raise ValueError(f"last_alternatives: the last generate kept {out.value} alternatives per token, not {int(k)}")
+    _call(e, "txo_last_alternatives", ids.data_ptr(), lp.data_ptr(), B, n)
+    return ids, lp
+
+
+@last_alternatives.register_fake
+def _(tokens, engine, k):
+    return (tokens.new_empty((*tokens.shape, k), dtype=torch.int32), tokens.new_empty((*tokens.shape, k), dtype=torch.float32))
 
 
 # ---- repeat guard inside beam search (txo_set_guard_beam): the opt-in that lets the beam entries run under a repeat guard --------------------

@@ -63,6 +63,23 @@ def align_inputs(rows: Sequence[List[int]], bos: int, pad: int) -> Tuple[torch.T
     return trg, mask
 
 
+def pair_alts(tokenizer, ids, logp, n: int) -> List[List[Tuple[str, float]]]:
+    """One row's alternatives for the caller: ids / logp (n_cols, k) as lists -> one list per kept token (the first n) of k (piece, logp) pairs,
+    piece the tokenizer's string for the id (tokenizer.decode_list)"""
+    return [list(zip(tokenizer.decode_list(ids[t]), [float(v) for v in logp[t]])) for t in range(n)]
+
+
+def _split_result(res, return_logp: bool, ruled: bool, return_alts: int):
+    """a generate's result -> (tokens, logp or None, Alts or None): the rule states dropped, the alternatives taken off the end"""
+    res = res if isinstance(res, tuple) else (res,)
+    if ruled:
+        res = res[:-1]
+    alts = None
+    if return_alts:
+        alts, res = res[-1], res[:-1]
+    return res[0], (res[1] if return_logp else None), alts
+
+
 class TeXOCRWrapper:
     def __init__(self, config: dict, dtype: str = "fp32", max_batch: int = 1, ragged_hybrid: bool = False, balanced: bool = False,
                  rules_beam: bool = False, close: bool = False, repeat_guard=None, guard_beam: bool = False):
@@ -126,6 +143,15 @@ class TeXOCRWrapper:
         if decode == "beam" and not self.model.guard_beam:
             raise ValueError("repeat_guard is not available with decode='beam' (the repeat guard binds generate() only)")
         return {"repeat_guard": g}
+
+    def _alts(self, return_alts, decode: str) -> dict:
+        """the return_alts= of a call as keyword arguments"""
+        if not return_alts:
+            return {}
+        if decode == "beam":
+            raise ValueError("return_alts is not available with decode='beam' (alternatives are kept by the greedy / sampled decode only)")
+        from . import ops
+        return {"return_alts": ops.check_alts(return_alts)}
 
     def _tensor(self, img) -> torch.Tensor:
         x = preprocess_image(img, self.dims.patch)
@@ -216,8 +242,12 @@ class TeXOCRWrapper:
               seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
               length_alpha: float = 0.0, prefix: Optional[Sequence] = None, ingest: str = "host", fit: str = "none",
               trim: str = "none", trim_level: int = 127, trim_margin: int = 2, balanced: Optional[bool] = None,
-              close: Optional[bool] = None, repeat_guard=None) -> List[tuple]:
-        """Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
+              close: Optional[bool] = None, repeat_guard=None, return_alts: int = 0) -> List[tuple]:
+        """return_alts=k (build extension; k in [1, 8]; not with decode='beam'): the last element of every result is one list per kept token
+        of k (piece, logp) pairs -- the k best tokens of the raw logits row behind that token as the tokenizer's strings, with their
+        log-probabilities (OCRModel.generate(return_alts=); raw: a token a rule, the guard or the sampler committed may be missing from its
+        own list), cut where the tokens are cut.
+        Build extension: __call__ over a list of PIL images of any sizes -> [(tokens, latex)] in order.
         Every image is preprocessed as __call__ does; chunks of the model's max_batch go through ONE ragged generate each with the
         per-row stop, and every row is cut at its eos.  max_len is capped at the positional table (a ragged decode does not slide the
         window).  A sampled draw is keyed by (seed + chunk index, row of its chunk, position): with an explicit seed the result is
@@ -258,7 +288,7 @@ class TeXOCRWrapper:
         guard_beam=True: the ban then binds inside the beam selection (OCRModel.beam_search(repeat_guard=)), also beside close=True.  Not with
         close=True in the other decodes."""
         rules = self._rules(balanced, decode)
-        ckw = {**self._close(close, rules), **self._guard(repeat_guard, decode)}
+        ckw = {**self._close(close, rules), **self._guard(repeat_guard, decode), **self._alts(return_alts, decode)}
         rule = self._trim_rule(trim, trim_level, trim_margin)
         eng = self.model._engine
         max_len = min(int(max_len), self.dims.max_len)
@@ -279,11 +309,11 @@ class TeXOCRWrapper:
                 kw = {} if pre is None else dict(prefix=pre[c0:c0 + step].cuda(), prefix_len=plen[c0:c0 + step])
                 toks = self.model.generate_ragged(chunk, max_len, temp=temp, decode=decode, seed=chunk_seed, stop="row",
                                                   return_logp=return_logp, **kw, **({} if rules is None else {"rules": rules}), **ckw)
-                if rules is not None:
-                    toks = toks[:-1] if return_logp else toks[0]                       # (without the rule states)
-                toks, logp = toks[:2] if return_logp else (toks, None)
+                toks, logp, alts = _split_result(toks, return_logp, rules is not None, return_alts)   # (without the rule states)
                 full = [cut_at_eos(row, self.model.eos_token) for row in toks.tolist()]
                 logp = logp.tolist() if return_logp else None
+                if return_alts:
+                    alts = (alts.ids.tolist(), alts.logp.tolist())
             maps = None
             if return_align:
                 trg, mask = align_inputs(full, self.model.bos_token, self.model.trg_pad_idx)
@@ -292,14 +322,18 @@ class TeXOCRWrapper:
                 row = row[:-1]                                                        # ocr_model.py:104 (drops the last token)
                 latex = process_output(self.tokenizer.decode(row if prows is None else prows[c0 + b] + row))
                 item = (row, latex, logp[b][:len(row)]) if return_logp else (row, latex)
-                out.append((*item, maps[b][:len(row)]) if return_align else item)
+                item = (*item, maps[b][:len(row)]) if return_align else item
+                out.append((*item, pair_alts(self.tokenizer, alts[0][b], alts[1][b], len(row))) if return_alts else item)
         return out
 
     def __call__(self, img, max_len: int = 350, temp: float = 0.3, decode: str = "sample",
                  seed: Optional[int] = None, return_logp: bool = False, return_align: bool = False, beams: int = 5,
                  length_alpha: float = 0.0, prefix=None, ingest: str = "host", fit: str = "none", trim: str = "none", trim_level: int = 127,
-                 trim_margin: int = 2, balanced: Optional[bool] = None, close: Optional[bool] = None, repeat_guard=None) -> tuple:
-        """-> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
+                 trim_margin: int = 2, balanced: Optional[bool] = None, close: Optional[bool] = None, repeat_guard=None,
+                 return_alts: int = 0) -> tuple:
+        """return_alts=k: the last element of the result is one list per kept token of k (piece, logp) pairs (see batch); max_len is then
+        capped at the positional table (the sliding window keeps no alternatives).
+        -> (tokens, latex); return_logp=True: (tokens, latex, logp), logp[i] the log-probability of tokens[i] (OCRModel.generate);
         return_align=True appends maps (len(tokens), H/16, W/16) float32 on the host: maps[i] is where in the (padded) image tokens[i]
         came from -- the head-mean cross attention of the last decoder layer (OCRModel.align), from one teacher-forced pass over
         [bos] + tokens behind the generate.  Not available once the output outgrew the positional table (the window has slid).
@@ -314,7 +348,9 @@ class TeXOCRWrapper:
         balanced=True: the decode picks under the tokenizer's brace rule (see batch).  close=True: as a closing decode (see batch).
         repeat_guard=(max_period, max_repeats): under the repeat guard (see batch)."""
         rules = self._rules(balanced, decode)
-        ckw = {**self._close(close, rules), **self._guard(repeat_guard, decode)}
+        ckw = {**self._close(close, rules), **self._guard(repeat_guard, decode), **self._alts(return_alts, decode)}
+        if return_alts:
+            max_len = min(int(max_len), self.dims.max_len)
         x = self._images([img], ingest, fit, self._trim_rule(trim, trim_level, trim_margin))
         x = x.box if ingest == "device" else x[0][None]
         prow: List[int] = []
@@ -332,9 +368,7 @@ class TeXOCRWrapper:
             # slides its window exactly as the reference does (decoder.py:99-100), at window-length engine steps per token
             toks = self.model.generate(x, max_len=max_len, temp=temp, decode=decode, seed=seed, return_logp=return_logp, **gen_kw,
                                        **({} if rules is None else {"rules": rules}), **ckw)
-            if rules is not None:
-                toks = toks[:-1] if return_logp else toks[0]                           # (without the rule states)
-            toks, logp = toks[:2] if return_logp else (toks, None)
+            toks, logp, alts = _split_result(toks, return_logp, rules is not None, return_alts)   # (without the rule states)
         out_tokens = toks.squeeze(0).tolist()[:-1]                                   # ocr_model.py:104 (drops the EOS)
         latex = process_output(self.tokenizer.decode(prow + out_tokens))             # :105-108
         out = (out_tokens, latex, logp.squeeze(0)[:len(out_tokens)].tolist()) if return_logp else (out_tokens, latex)
@@ -345,4 +379,6 @@ class TeXOCRWrapper:
             bos = torch.full((1, 1), self.model.bos_token, dtype=torch.int64, device=toks.device)
             maps = self.model.align(x, torch.cat((bos, toks), dim=1), mask=torch.ones((1, toks.shape[1] + 1), dtype=torch.bool)).maps
             out = (*out, maps[0, :len(out_tokens)].cpu())
+        if return_alts:
+            out = (*out, pair_alts(self.tokenizer, alts.ids[0].tolist(), alts.logp[0].tolist(), len(out_tokens)))
         return out
